@@ -13,10 +13,11 @@ bytes broadcast through torch.distributed, mw_tiles_create_rank everywhere).  to
 the barriers and the max-over-ranks of the timing; `--gather` adds the library's own gather of the last step of every
 batch to rank 0 (ncclSend/ncclRecv on a side stream behind an event), overlapped with the next batch.
 
-The default run (no --workload; what the driver runs) times the 1024^2 headline and then, at N = 1, BASELINE configs[3] (4096^2, 64 steps
-in 32-step enqueues) and configs[4] (the pond, 1M vertices x 8 waves) -- each with its own parity gate, `roofline` and bounded
-`cpu_baseline` -- under "configs": {"ocean4096": {...}, "pond": {...}} of the same line (--workload ocean1024 = the headline alone).
-Every K-step timed region is repeated until at least --min-timed-ms (50 ms) of timed work exist, whatever K the driver passes.
+The default run (no --workload; what the driver runs) times the 1024^2 headline alone: exactly K timed steps (one K-step region;
+--repeats / --min-timed-ms ask for more), `ms_per_step` = that region / K.  --workload all adds, at N = 1, BASELINE configs[3]
+(4096^2, 64 steps in 32-step enqueues), configs[4] (the pond, 1M vertices x 8 waves) and the renderer -- each with its own step count,
+parity gate, `roofline` and bounded `cpu_baseline` -- under "configs": {"ocean4096": {...}, "pond": {...}, ...} of the same line.
+--dump-outputs DIR writes the last timed step's outputs (vertices, normals, whitecap) as .npy files for output-for-output comparisons.
 
 Extra objects on the same line:
   roofline      dominant kernel (k_pass2) ALGORITHMIC bytes / its mean launch duration measured live with hipEvents on the
@@ -60,8 +61,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=4000)
     ap.add_argument("--warmup", type=int, default=64)
-    ap.add_argument("--workload", default="all", choices=["all", "ocean1024", "ocean4096", "ocean2048", "ocean512", "ocean256", "pond", "renderer1024", "direct"],
-                    help="all (default) = the ocean1024 headline + at N = 1 BASELINE configs[3] (ocean4096) and [4] (pond) under `configs`")
+    ap.add_argument("--workload", default="ocean1024", choices=["all", "ocean1024", "ocean4096", "ocean2048", "ocean512", "ocean256", "pond", "renderer1024", "direct"],
+                    help="ocean1024 (default) = the headline alone; all = the headline + at N = 1 BASELINE configs[3] (ocean4096), [4] (pond) and "
+                         "the renderer under `configs` (each with its own fixed step count, not --steps)")
     ap.add_argument("--direct-n", type=int, default=1000,
                     help="direct: grid size of the non-FFT FFTMesh case (50 = the Inspector default S/FFTMesh.cs:13, 100, 1000)")
     ap.add_argument("--batch", type=int, default=32, help="time-steps per enqueue (FFTMesh steps are independent in t); renderer1024: consecutive "
@@ -69,11 +71,15 @@ def parse():
     ap.add_argument("--preheat-ms", type=float, default=150.0,
                     help="untimed: keep the device busy with the workload this long before the W warm-up steps, so the "
                          "timed region starts at steady clocks (the first ~5 ms after idle run ~25 %% slower)")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="the K-step timed region is run this many times (each between its own barrier + synchronize pairs); "
-                         "`value` / `ms_per_step` are the MEDIAN region, min / max are printed beside it")
-    ap.add_argument("--min-timed-ms", type=float, default=50.0,
-                    help="the K-step region is repeated at least until this much timed work exists (R = max(--repeats, ceil(this / region)))")
+                         "`value` / `ms_per_step` are the MEDIAN region, min / max are printed beside it.  Default 1: K timed steps in all")
+    ap.add_argument("--min-timed-ms", type=float, default=0.0,
+                    help="> 0: an untimed pilot region sizes R, and the K-step region is repeated at least until this much timed work "
+                         "exists (R = max(--repeats, ceil(this / region))).  Default 0: no pilot, --repeats regions")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (the arrays a caller of the timed path receives) "
+                         "as DIR/<name>.npy in float32, at most 64 MB in all (a fixed seeded sample of rows beyond that); ocean workloads")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-latency", action="store_true",
@@ -195,6 +201,43 @@ def d2h(ptr, shape, dtype=np.float32):
     rc = _hip.hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), out.nbytes, 2)
     assert rc == 0, f"hipMemcpy D2H failed ({rc})"
     return out
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000 - 4096     # --dump-outputs: at most 64 MB in all, .npy headers included
+
+
+def dump_outputs(dirpath, arrays, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """Write `arrays` (name -> array; every array has the same number of rows) as dirpath/<name>.npy in float32.  When they hold more
+    than max_bytes in all, the same fixed, seeded sample of rows of every array is written instead, sorted, and its row indices as
+    sample_rows.npy (float64).  Returns what was written: {"dir", "files": {name: shape}, "sampled_rows": int | None, "of_rows"}."""
+    arrays = {k: np.ascontiguousarray(v, np.float32) for k, v in arrays.items()}
+    (n,) = {v.shape[0] for v in arrays.values()}
+    total = sum(v.nbytes for v in arrays.values())
+    sampled = None
+    if total > max_bytes:
+        keep = int(max_bytes // (total // n + 8))            # + 8 B per row: the float64 index
+        rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+        sampled = keep
+    os.makedirs(dirpath, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirpath, k + ".npy"), v)
+    return {"dir": dirpath, "files": {k: list(v.shape) for k, v in arrays.items()}, "sampled_rows": sampled, "of_rows": n}
+
+
+def dump_last_step(dirpath, nb, NN, tile_ptrs=None, bufs=None):
+    """--dump-outputs of an FFTMesh workload: step nb - 1 of the latest enqueue (the last timed step) as a caller of the timed path receives
+    it -- vertices [NN, 3], normals [NN, 3], whitecap [NN] -- from the handle's device buffers (dv, dn, dw: [B, NN, 3], [B, NN, 3], [B, NN])
+    or from a tile's output pointers (mw_tiles_outputs: the same layouts with max_steps rows)."""
+    k = nb - 1
+    if tile_ptrs is not None:
+        pv, pn, pw = tile_ptrs
+        got = {"vertices": d2h(pv + k * NN * 12, (NN, 3)), "normals": d2h(pn + k * NN * 12, (NN, 3)), "whitecap": d2h(pw + k * NN * 4, (NN,))}
+    else:
+        dv, dn, dw = bufs
+        got = {"vertices": dv[k].cpu().numpy(), "normals": dn[k].cpu().numpy(), "whitecap": dw[k].cpu().numpy()}
+    return dump_outputs(dirpath, got)
 
 
 def batch_plan(K, max_batch):
@@ -376,6 +419,8 @@ def setup(a):
 
 def main():
     a = parse()
+    if a.dump_outputs and a.workload in ("pond", "renderer1024", "direct"):
+        raise SystemExit(f"--dump-outputs is implemented for the ocean workloads, not {a.workload}")
     e = setup(a)
     extra = (a.workload == "all")
     if a.workload == "pond":
@@ -402,7 +447,8 @@ def main():
                                    ("renderer1024_frame", lambda aa: renderer(aa, e, extra=True),
                                     dict(steps=400, warmup=50, batch=1, tiles=1, no_cpu_baseline=True))):
                 aa = copy.copy(a)
-                for k, v in over.items():
+                # their own step counts, at least 50 ms of timed work each, and no output dump (that is the headline's)
+                for k, v in dict(over, repeats=5, min_timed_ms=50.0, dump_outputs=None).items():
                     setattr(aa, k, v)
                 t0 = time.perf_counter()
                 try:
@@ -598,15 +644,32 @@ def ocean(a, e, N, extra=False):
     plan(sizes, lo)      # the timed plan's calls exist before the first region
     barrier()   # rank 0 may have spent seconds in the parity gate: line the ranks up BEFORE warming the clocks
     preheat_ms = preheat(lambda: run([B], 0), torch, a.preheat_ms)
+    # the warm-up between a pair of timing events: the first such pair of a process slows the region it sits in (measured: +0.2 to
+    # +0.9 % on a single 20000-step region), so it is paid here and not in the one timed region
+    warm_evs = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if not use_tiles else None
+    if warm_evs:
+        warm_evs[0].record(stream)
     run(warm_sizes, 0)
+    if warm_evs:
+        warm_evs[1].record(stream)
     sync()
+
+    ev_pairs = []
 
     def wall_region(gather=False):
         """EXACTLY the K steps between barrier + synchronize pairs, by the wall clock (the contract's figure).  Nothing but the
-        enqueues sits inside: no event records (they are a stream operation each, ~5 us of host time before the first launch)."""
+        enqueues sits inside the clock: the first event record (a stream operation, ~5 us of host time) goes before it starts, the
+        second behind the last enqueue, while the device is still busy.  The events time the same region on the launch stream."""
         barrier()
+        evs = None
+        if not use_tiles and not gather:
+            evs = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            evs[0].record(stream)
         t0 = time.perf_counter()
         run(sizes, lo, gather=gather)
+        if evs is not None:
+            evs[1].record(stream)
+            ev_pairs.append(evs)
         if not use_tiles:
             while not stream.query():   # spin until the stream drains: a blocking synchronize adds its wake-up latency (tens of
                 pass                    # microseconds) to a region that is a fraction of a millisecond at the driver's K = 20
@@ -617,32 +680,29 @@ def ocean(a, e, N, extra=False):
         return par.max_over_ranks(el, dist, red_dev)      # the job took as long as its slowest rank
     local_regions, local_gather = [], []
 
-    def event_region():
-        """The same K steps by HIP events on the launch stream (what the device spent; launch latency of the first enqueue and the
-        host's wake-up are outside)."""
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        barrier()
-        ev0.record(stream)
-        run(sizes, lo)
-        ev1.record(stream)
-        sync()
-        el = ev0.elapsed_time(ev1) * 1e-3
-        barrier()
-        return par.max_over_ranks(el, dist, red_dev) if dist is not None else el
-
-    # R: at least --repeats regions and at least --min-timed-ms of timed work in total (VERDICT r4 item 9: at the driver's K = 20 a
-    # region is 0.27 ms -- five of them were 1.4 ms of evidence).  The pilot region sizes R and is not counted; every rank uses
+    # R: --repeats regions (default 1: the run times exactly K steps).  With --min-timed-ms > 0 also at least that much timed work in
+    # total (at K = 20 a region is 0.27 ms); a pilot region then sizes R and is not counted; every rank uses
     # rank 0's figure (wall_region already returns the max over ranks, identical everywhere).
-    pilot = wall_region()
-    R = scaled_repeats(pilot, a.repeats, a.min_timed_ms)
-    regions = [wall_region() for _ in range(R)]
-    while sum(regions) * 1e3 < a.min_timed_ms and len(regions) < 4000:      # regions faster than the pilot: keep going until the total is there
-        regions.append(wall_region())
+    if a.min_timed_ms > 0:
+        pilot = wall_region()
+        R = scaled_repeats(pilot, a.repeats, a.min_timed_ms)
+        regions = [wall_region() for _ in range(R)]
+        while sum(regions) * 1e3 < a.min_timed_ms and len(regions) < 4000:      # regions faster than the pilot: keep going until the total is there
+            regions.append(wall_region())
+        del local_regions[0]            # the pilot
+        del ev_pairs[:1]
+    else:
+        regions = [wall_region() for _ in range(max(1, a.repeats))]
     R = len(regions)
     el = float(np.median(regions))
-    del local_regions[0]            # the pilot
-    R_ev = min(R, 64)
-    ev_regions = [event_region() for _ in range(R_ev)] if not use_tiles else None
+    dumped = None
+    if a.dump_outputs and not extra and rank == (world - 1 if shard_steps else 0):      # the rank that ran the job's last step
+        dumped = dump_last_step(a.dump_outputs, sizes[-1], NN, (tiles.outputs(0) if use_tiles else None), (dv, dn, dw) if not use_tiles else None)
+        dumped["t"] = par.step_times(lo, hi)[-1] if hi > lo else None
+    ev_regions = [ev0.elapsed_time(ev1) * 1e-3 for ev0, ev1 in ev_pairs[:64]]
+    if dist is not None and ev_regions:
+        ev_regions = [par.max_over_ranks(x, dist, red_dev) for x in ev_regions]
+    R_ev = len(ev_regions)
     el_events = float(np.median(ev_regions)) if ev_regions else None
     # ---- kernel-level timing with HIP events on the launch stream (rank 0) ----------------------------
     prof = tiles_ocean = None
@@ -766,9 +826,9 @@ def ocean(a, e, N, extra=False):
         "event_region_ms": [round(x * 1e3, 5) for x in ev_regions[:8]] if ev_regions else None,
         "event_region_ms_stats": {k: (round(v * 1e3, 5) if k != "n" else v) for k, v in pcts(ev_regions).items()} if ev_regions else None,
         "wall_over_events": (el / el_events) if el_events else None,
-        "timing": f"median of {R} runs of the K-step region (>= --repeats {a.repeats} and >= {a.min_timed_ms:g} ms of timed work in total), each "
-                  f"between barrier + torch.cuda.synchronize() pairs (wall clock, max over ranks); event_* = the same region by HIP events on "
-                  f"the launch stream, {R_ev} separate runs",
+        "timing": f"median of {R} run(s) of the K-step region (--repeats {a.repeats}, --min-timed-ms {a.min_timed_ms:g}), each "
+                  f"between barrier + torch.cuda.synchronize() pairs (wall clock, max over ranks); event_* = the same regions by HIP events on "
+                  f"the launch stream ({R_ev} of them)",
         "config": {"workload": f"SURVEY 8d config {2 if N == 1024 else 4 if N == 4096 else '2 at another N'}, literally: "
                                f"FFTMesh-semantics ocean {N}x{N}, height+choppy+normals+Jacobian whitecap, "
                                f"unit_width {p.unit_width:g}, length {p.length:g}, wind ({p.wind_x:g}, {p.wind_y:g}), "
@@ -791,6 +851,8 @@ def ocean(a, e, N, extra=False):
         "roofline": roofline,
         "parity": parity,
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     # ---- the same K steps again with the per-batch gather to rank 0 overlapped (default at N > 1), under the watchdog ----
     el_gather = gather_regions = None
     do_gather = use_tiles and (a.gather or world > 1) and not a.no_gather
@@ -1123,8 +1185,11 @@ def renderer(a, e, extra=False):
         el = time.perf_counter() - t0
         barrier()
         return par.max_over_ranks(el, dist, e.red_dev)
-    pilot = wall_region()
-    R = scaled_repeats(pilot, a.repeats, a.min_timed_ms)
+    if a.min_timed_ms > 0:      # a pilot region sizes R (not counted); default: --repeats regions, K timed frames each
+        pilot = wall_region()
+        R = scaled_repeats(pilot, a.repeats, a.min_timed_ms)
+    else:
+        R = max(1, a.repeats)
     regions = [wall_region() for _ in range(R)]
     el = float(np.median(regions))
 
@@ -1320,8 +1385,11 @@ def pond(a, e, extra=False):
         el = time.perf_counter() - t0
         barrier()
         return par.max_over_ranks(el, dist, e.red_dev)
-    pilot = wall_region()
-    R = scaled_repeats(pilot, a.repeats, a.min_timed_ms)
+    if a.min_timed_ms > 0:      # a pilot region sizes R (not counted); default: --repeats regions, K timed steps each
+        pilot = wall_region()
+        R = scaled_repeats(pilot, a.repeats, a.min_timed_ms)
+    else:
+        R = max(1, a.repeats)
     regions = [wall_region() for _ in range(R)]
     while sum(regions) * 1e3 < a.min_timed_ms and len(regions) < 4000:
         regions.append(wall_region())

@@ -117,3 +117,26 @@ def test_phase_guard_prints_the_checkpointed_line_when_a_multi_gpu_phase_hangs_o
     exits.clear()
     g.abandon("nothing measured yet")                # rank 0 without a line to print: a failure exit code
     assert exits == [3]
+
+
+def test_dump_outputs_writes_float32_and_samples_large_outputs_the_same_way_every_time(tmp_path):
+    """--dump-outputs: small outputs are written whole in float32; above the byte cap every array keeps the same fixed, seeded sample of
+    rows (sorted), the row indices are written beside them, and the files stay under the cap."""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    v, w = rng.standard_normal((1000, 3)), rng.standard_normal(1000).astype(np.float32)
+    r = bench.dump_outputs(str(tmp_path / "whole"), {"vertices": v, "whitecap": w})
+    assert r["sampled_rows"] is None and r["files"] == {"vertices": [1000, 3], "whitecap": [1000]}
+    got = np.load(tmp_path / "whole" / "vertices.npy")
+    assert got.dtype == np.float32 and (got == v.astype(np.float32)).all()
+    cap = 4000
+    r1 = bench.dump_outputs(str(tmp_path / "s1"), {"vertices": v, "whitecap": w}, max_bytes=cap)
+    r2 = bench.dump_outputs(str(tmp_path / "s2"), {"vertices": v, "whitecap": w}, max_bytes=cap)
+    assert r1 == dict(r2, dir=r1["dir"]) and 0 < r1["sampled_rows"] < 1000 and r1["of_rows"] == 1000
+    rows = np.load(tmp_path / "s1" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and (np.diff(rows) > 0).all() and (rows == np.load(tmp_path / "s2" / "sample_rows.npy")).all()
+    idx = rows.astype(np.int64)
+    assert (np.load(tmp_path / "s1" / "vertices.npy") == v[idx].astype(np.float32)).all()
+    assert (np.load(tmp_path / "s1" / "whitecap.npy") == w[idx]).all()
+    payload = sum(np.load(tmp_path / "s1" / f).nbytes for f in os.listdir(tmp_path / "s1"))
+    assert payload <= cap

@@ -697,9 +697,9 @@ def test_bench_two_rank_control_flow_on_one_device():
     """The N > 1 control flow of bench.py as the driver launches it (torch.distributed.run, 2 processes), on the 1-GPU box:
     gloo carries barriers / reductions, both ranks drive cuda:0 (an RCCL communicator cannot hold one device twice, so the
     tile API agrees on its fallback and says so).  Rank 0 alone prints; value is the whole-job aggregate over MAX-of-ranks time."""
-    d = _run_bench(["--steps", "64", "--warmup", "32", "--no-cpu-baseline", "--preheat-ms", "20"],      # the default workload: N > 1 carries the headline only
+    d = _run_bench(["--steps", "64", "--warmup", "32", "--no-cpu-baseline", "--preheat-ms", "20", "--min-timed-ms", "50"],      # the default workload: N > 1 carries the headline only
                    {"MW_BENCH_BACKEND": "gloo", "MW_BENCH_SAME_DEVICE": "1"}, nproc=2)
-    assert d["configs"] is None
+    assert d.get("configs") is None
     NN = 1024 * 1024
     assert d["n_gpus"] == 2 and d["steps"] == 64 and d["scaling"] == "weak" and d["config"]["tiles"] == 2
     assert d["config"]["steps_per_enqueue"] == 32 and d["config"]["enqueues_per_region"] == 2 and d["config"]["enqueues_timed"] == 2 * d["repeats"] and d["config"]["pass1_time_group"] == 8
@@ -741,14 +741,18 @@ def test_bench_renderer_frames_sharded_over_two_ranks():
 
 
 def test_bench_times_what_it_prints_and_gates_the_tile_path():
-    """The driver's command line (--steps 20 --warmup 5): ONE 20-step enqueue, pass-1 time group 5, roofline from 20-step
-    launches, literal config-2 parameters, frame-at-a-time figures present; and the tile-API path keeps the parity gate."""
+    """The driver's command line (--steps 20 --warmup 5): ONE 20-step enqueue timed once (exactly K timed steps, ms_per_step = that region / K),
+    pass-1 time group 5, roofline from 20-step launches, literal config-2 parameters, frame-at-a-time figures present; and the tile-API path
+    keeps the parity gate."""
     d = _run_bench(["--workload", "ocean1024", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"], {})
     c = d["config"]
-    assert d["repeats"] >= 5 and d["timed_ms_total"] >= 50.0 and d["region_ms_stats"]["n"] == d["repeats"]     # >= --min-timed-ms of timed work whatever K
+    assert d["repeats"] == 1 and d["region_ms_stats"]["n"] == 1 and c["enqueues_timed"] == 1                 # K timed steps, no more
+    assert abs(d["timed_ms_total"] - d["ms_per_step"] * 20) < 1e-9 * d["timed_ms_total"]
+    r = _run_bench(["--workload", "ocean1024", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-latency", "--min-timed-ms", "50"], {})
+    assert r["repeats"] >= 5 and r["timed_ms_total"] >= 50.0 and r["region_ms_stats"]["n"] == r["repeats"]     # >= --min-timed-ms of timed work on request
     st = d["roofline"]["launch_us_stats"]
     assert st["p10"] <= st["median"] <= st["p90"] and abs(st["mean"] - d["roofline"]["launch_us"]) < 1e-3 * st["mean"]
-    assert c["steps_per_enqueue"] == 20 and c["enqueues_per_region"] == 1 and c["enqueues_timed"] >= 5 and c["enqueue_sizes_timed"] == [20] and c["pass1_time_group"] == 5
+    assert c["steps_per_enqueue"] == 20 and c["enqueues_per_region"] == 1 and c["enqueue_sizes_timed"] == [20] and c["pass1_time_group"] == 5
     assert d["roofline"]["steps_per_launch"] == 20 and d["roofline"]["bytes_per_launch"] == 52 * 1024 * 1024 * 20
     assert "amplitude 0.41" in c["workload"] and d["parity"].startswith("ok")
     assert abs(d["event_ms_per_step"] - d["ms_per_step"]) < 0.25 * d["ms_per_step"]
@@ -759,10 +763,36 @@ def test_bench_times_what_it_prints_and_gates_the_tile_path():
     assert t["config"]["api"].startswith("mw_tiles_") and "through mw_tiles_" in t["parity"]
 
 
-def test_default_bench_line_carries_every_single_gpu_baseline_config():
-    """the driver's command line prints ONE line whose headline is the 1024^2 config and whose `configs` object holds
+def test_bench_dump_outputs_is_the_last_timed_step(mw, tmp_path):
+    """--dump-outputs DIR: the last timed step (t = K / 60) as the timed path hands it out -- vertices, normals, whitecap of the seed-1 ocean in
+    float32 -- identical from run to run with the same arguments, and the oracle's step of the same spectrum."""
+    import os
+    from oracle import oracle as O
+    args = ["--workload", "ocean1024", "--steps", "21", "--warmup", "5", "--no-cpu-baseline", "--no-latency", "--no-parity", "--preheat-ms", "20"]
+    d1 = _run_bench(args + ["--dump-outputs", str(tmp_path / "a")], {})
+    _run_bench(args + ["--dump-outputs", str(tmp_path / "b")], {})
+    NN = 1024 * 1024
+    assert d1["dumped_outputs"]["files"] == {"vertices": [NN, 3], "normals": [NN, 3], "whitecap": [NN]} and d1["dumped_outputs"]["sampled_rows"] is None
+    assert abs(d1["dumped_outputs"]["t"] - 21 / 60.0) < 1e-12
+    got = {}
+    for name in ("vertices", "normals", "whitecap"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and (a == b).all(), name
+        got[name] = a
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 * 1000 * 1000
+    p = workloads.fftmesh_config2(1024)
+    with mw.Ocean(resolution=p.N, unit_width=p.unit_width, length=p.length, wind=(p.wind_x, p.wind_y), amplitude=p.amplitude,
+                  choppiness=p.choppiness, gravity=p.gravity, seed=1, device=0) as o:
+        h0, h0c = o.get_spectrum()
+    vf, nf, cf, hds = O.eval_fft_f64(p, h0, h0c, float(np.float32(21 / 60.0)), return_hds=True)
+    workloads.assert_parity(got["vertices"], got["normals"], got["whitecap"][:, None], vf, nf, cf[:, :1], O.rest_mesh(p)[0],
+                            np.abs(hds).max(), tag="bench --dump-outputs", hds=hds)
+
+
+def test_workload_all_line_carries_every_single_gpu_baseline_config():
+    """--workload all prints ONE line whose headline is the 1024^2 config and whose `configs` object holds
     BASELINE configs[3] (4096^2) and configs[4] (the pond), each with its own parity gate, roofline object and bounded CPU baseline."""
-    d = _run_bench(["--steps", "20", "--warmup", "5"], {}, timeout=900)
+    d = _run_bench(["--workload", "all", "--steps", "20", "--warmup", "5"], {}, timeout=900)
     assert d["config"]["grid"] == 1024 and d["parity"].startswith("ok") and d["cpu_baseline"]["value"] > 0
     o, p = d["configs"]["ocean4096"], d["configs"]["pond"]
     assert "error" not in o and "error" not in p, (o.get("error"), p.get("error"))

@@ -1,6 +1,7 @@
 """One OceanRenderer GenerateTexture() at resolution 64 .. 512 (512^2 .. 4096^2 textures), device-resident: us per frame and fraction of the 120-B figure."""
-import sys, time
-sys.path[:0] = ["/root/repo", "/root/repo/mistral-water_amd", "/root/repo/tests"]
+import os, sys, time
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "mistral-water_amd"), os.path.join(REPO, "tests")]
 import torch; torch.cuda.init()
 import ctypes as C
 import mistral_water as mw

@@ -1,7 +1,8 @@
 """OceanRenderer frames per enqueue (mw_ocean_generate_texture_steps_device): us per frame against n, device-resident.
 usage: [MW_LIB=variants/X.so] python tools/renderer_steps_probe.py [resolution ...]"""
-import sys, time
-sys.path[:0] = ["/root/repo", "/root/repo/mistral-water_amd", "/root/repo/tests"]
+import os, sys, time
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "mistral-water_amd"), os.path.join(REPO, "tests")]
 import torch; torch.cuda.init()
 import ctypes as C
 import numpy as np
