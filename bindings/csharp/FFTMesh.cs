@@ -109,6 +109,15 @@ public class FFTMesh : MonoBehaviour
         mesh.colors = colors;
     }
 
+    /// Not in the reference: the displaced mesh's surface at horizontal points, xz = {x0, z0, x1, z1, ...} in the mesh's object space;
+    /// result (8 floats per point) = position xyz, normal xyz, whitecap, residual.  world = true: xz lies on the displaced surface (the
+    /// buoyancy question "how high is the water here?"); false: xz is a rest-plane position (NaN off the mesh).  Surface of the latest Update().
+    public void SampleSurface(float[] xz, float[] result, bool world = true)
+    {
+        if (result.Length < xz.Length * 4) throw new ArgumentException("result needs 8 floats per point");
+        Native.Check(Native.mw_ocean_query_surface(ocean, -1, world ? Native.QueryWorld : Native.QueryRest, xz, xz.Length / 2, 0, result));
+    }
+
     /// Evaluate the ocean Unity itself generated: pass the reference's own htilde0 draws (verttilde / vertConj).
     public void SetSpectrum(Vector2[] h0, Vector2[] h0conj)
     {

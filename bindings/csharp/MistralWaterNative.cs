@@ -22,6 +22,7 @@ public static class MistralWaterNative
     public enum Semantics { FFTMesh = 0, OceanRenderer = 1 }
     public enum PondMode { Wave = 0, Gerstner = 1, GerstnerLevelOne = 2 }
     public const uint OutWhiteScalar = 0u, OutColorRgba = 1u;
+    public const int QueryRest = 0, QueryWorld = 1;
 
     [StructLayout(LayoutKind.Sequential)]   // mw_params: 56 bytes
     public struct Params
@@ -111,6 +112,9 @@ public static class MistralWaterNative
     [DllImport(Lib)] public static extern Status mw_ocean_frame_textures(IntPtr ocean, int frame, out IntPtr dHeight, out IntPtr dDispXZ, out IntPtr dNormal, out IntPtr dWhite);
     [DllImport(Lib)] public static extern Status mw_ocean_displace_mesh(IntPtr ocean, [Out] Vector3[] vertices, [Out] Vector3[] normals, [Out] float[] colors);
     [DllImport(Lib)] public static extern Status mw_ocean_displace_mesh_device(IntPtr ocean, IntPtr dVertices, IntPtr dNormals, IntPtr dColors);
+    // surface queries: xz [n][2] -> result [n][8] = (px, py, pz, nx, ny, nz, white, residual); frame -1 = latest
+    [DllImport(Lib)] public static extern Status mw_ocean_query_surface(IntPtr ocean, int frame, int mode, float[] xz, long n, int iterations, [Out] float[] result);
+    [DllImport(Lib)] public static extern Status mw_ocean_query_surface_device(IntPtr ocean, int frame, int mode, IntPtr dXz, long n, int iterations, IntPtr dResult);
 
     // ---- page-locked output arrays ------------------------------------------------------------------------------
     [DllImport(Lib)] public static extern Status mw_host_register(IntPtr ptr, UIntPtr bytes);

@@ -156,6 +156,15 @@ public class OceanRenderer : MonoBehaviour
         t.Apply(false, false);
     }
 
+    /// Not in the reference: the displaced mesh's surface at horizontal points, xz = {x0, z0, x1, z1, ...} in the mesh's object space;
+    /// result (8 floats per point) = position xyz, normal xyz, whitecap, residual.  world = true: xz lies on the displaced surface (the
+    /// buoyancy question "how high is the water here?"); false: xz is a rest-plane position (NaN off the mesh).  Surface of the latest GenerateTexture().
+    public void SampleSurface(float[] xz, float[] result, bool world = true)
+    {
+        if (result.Length < xz.Length * 4) throw new ArgumentException("result needs 8 floats per point");
+        Native.Check(Native.mw_ocean_query_surface(ocean, -1, world ? Native.QueryWorld : Native.QueryRest, xz, xz.Length / 2, 0, result));
+    }
+
     /// Checkpoint of the animation: initialTexture, the phase texture and the length the normal pass uses.  The last one differs
     /// from `length` after a length change: the reference sets normalMat._Length once in SetParams (S/OceanRenderer.cs:163).
     public void SaveState(Vector2[] h0, Vector2[] h0conj, float[] phase, out float normalLength)

@@ -240,6 +240,44 @@ mw_status mw_ocean_generate_texture_steps_rgba(mw_ocean* o, const float* delta_t
 mw_status mw_ocean_displace_mesh(mw_ocean* o, float* vertices_xyz, float* normals_xyz, float* colors);
 mw_status mw_ocean_displace_mesh_device(mw_ocean* o, void* d_vertices_xyz, void* d_normals_xyz, void* d_colors);
 
+/* ---- surface queries: how high is the water here? ---------------------------------------------------------------
+ * The surface of a frame is the displaced triangle mesh the library hands out:
+ *   vertices  FFTMesh: what the latest mw_ocean_evaluate / mw_ocean_update returned (vertices, normals, colour R);
+ *             OceanRenderer: what mw_ocean_displace_mesh returns for the selected frame (resolution^2 vertices);
+ *   triangles the index buffer of mw_ocean_rest_mesh (S/FFTMesh.cs:101-139, S/OceanRenderer.cs:172-207): rest-grid cell (i, j)
+ *             is split along its (i, j+1)-(i+1, j) diagonal;
+ *   inside a triangle position, normal and whitecap are interpolated barycentrically in REST-plane coordinates; the normal
+ *             is normalised afterwards.
+ * A query is a horizontal point (x, z) in the object space of the vertex outputs; out is [n][8] floats per point:
+ *   px, py, pz, nx, ny, nz, white, residual.
+ *   MW_QUERY_REST:  (x, z) is a rest-plane position; the result is the displaced surface point the mesh carries there.
+ *                   Rest positions outside the mesh footprint give NaN in every field (the status is still MW_OK).  residual = 0.
+ *   MW_QUERY_WORLD: (x, z) is a position on the DISPLACED surface (buoyancy).  The rest point u with displaced(u).xz = (x, z) is
+ *                   found by the iteration u <- (x, z) - D(u), D the horizontal displacement; the map is affine within a triangle,
+ *                   so at every visited point one exact 2 x 2 solve in its triangle finishes the job when its solution lies inside
+ *                   that triangle.  Otherwise the step is preconditioned by the inverse of the triangle's map (a Newton step of the
+ *                   piecewise-affine map, at most 4 cells; the plain step in folded triangles), which keeps converging near the
+ *                   fold limit where the plain iteration stalls.  `iterations` bounds the walk: 0 = the default, 8; at most 64.
+ *                   residual = |displaced(u*).xz - (x, z)|: ~0 where the answer was found; where the mesh folds over itself
+ *                   (strong choppiness: no unique answer) or (x, z) is off the displaced footprint, the visited point of smallest
+ *                   residual is returned -- a point on the mesh -- with that residual.  Non-finite (x, z) give NaN.
+ * frame: -1 = the latest frame (FFTMesh: latest mw_ocean_evaluate / update; OceanRenderer: what mw_ocean_displace_mesh samples);
+ *        0..k-1 = frame of the latest OceanRenderer steps call, as mw_ocean_frame_textures (its textures must have stayed in the handle).
+ * MW_ESTATE before the first frame; MW_EINVAL for a NULL array with n > 0, n < 0 or n > 2^32 - 256 (one launch), a bad mode,
+ * iterations outside [0,64], a frame out of range, frame != -1 on an FFTMesh handle, or a batched handle (mw_ocean_create_batch).
+ * n == 0 does nothing.  The query reads the frame and changes nothing of the handle's state.  OceanRenderer queries first run the
+ * vertex stage of the frame into a buffer of the handle, reused by the next query in the order of the handle's stream (as every
+ * entry point's staging is); mw_ocean_set_stream drains the previous stream before a switch, so queries on either side of a
+ * switch cannot overlap.                                                                                                    */
+#define MW_QUERY_REST 0
+#define MW_QUERY_WORLD 1
+/* xz [n][2], out [n][8]: host arrays, synchronous */
+mw_status mw_ocean_query_surface(mw_ocean* o, int32_t frame, int32_t mode, const float* xz, int64_t n, int32_t iterations,
+                                 float* out);
+/* device arrays (d_xz 8-byte, d_out 16-byte aligned), asynchronous on the handle's stream */
+mw_status mw_ocean_query_surface_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xz, int64_t n,
+                                        int32_t iterations, void* d_out);
+
 /* ---- independent tiles on several devices (BASELINE configs[2]) ------------------------------------
  * Tiles are independent units in both semantics: tile k is the ocean of `params` with seed params->seed + k on its own
  * device, compute stream and output buffers; there is no data-path collective.  FFTMesh tiles advance up to max_steps

@@ -25,6 +25,8 @@
 #include "direct_kernels.h"
 #include "gerstner_kernels.h"
 #include "pond_kernels.h"
+#include "surface_query.h"
+static_assert(MW_SQ_REST == MW_QUERY_REST && MW_SQ_WORLD == MW_QUERY_WORLD, "surface_query.h and the ABI name the modes alike");
 
 #ifndef MW_LATENCY_PLAN
 #define MW_LATENCY_PLAN 1  // single-step enqueues at 512^2 / 1024^2 (mw_frame_plan_n): k_pass1<.., FS> + k_pass2_frame (launch_pass*_n)
@@ -687,6 +689,9 @@ struct mw_ocean {
     cf *E = nullptr, *Cj0 = nullptr;
     int e_cap = 0;  // steps the exchange buffer holds
     float *s_vert = nullptr, *s_norm = nullptr, *s_white = nullptr;  // 1-step scratch for the host API
+    bool s_have = false;  // s_vert / s_norm / s_white hold a frame: the "latest frame" of mw_ocean_query_surface
+    int s_wstride = 4;    // ... and the whitecap stride its writer used: 4 (RGBA colours, the host API) or 1 (the profiling hook)
+    float* q_mesh = nullptr;  // OceanRenderer surface queries: the vertex stage of the queried frame, [res^2][3 + 3 + 1], allocated on first use
     void* scratch = nullptr;  // grow-only device staging of the host-pointer entry points (rest mesh, RGBA targets, ...):
     size_t scratch_cap = 0;   // allocated once at the largest size asked for, not per call
     DirectState direct;
@@ -990,7 +995,7 @@ void mw_ocean_destroy(mw_ocean* o) {
     hipSetDevice(o->device);
     if (hipStreamSynchronize(o->stream) != hipSuccess) (void)hipGetLastError();  // a dead caller stream has nothing pending
     hipFree(o->h0); hipFree(o->h0c); hipFree(o->PQt); hipFree(o->Om); hipFree(o->dPQ_i0); hipFree(o->dPQ_j0);
-    hipFree(o->TW); hipFree(o->TW2); hipFree(o->Wpre); hipFree(o->p1_jobs); hipFree(o->E); hipFree(o->Cj0); hipFree(o->s_vert); hipFree(o->s_norm); hipFree(o->s_white); hipFree(o->scratch);
+    hipFree(o->TW); hipFree(o->TW2); hipFree(o->Wpre); hipFree(o->p1_jobs); hipFree(o->E); hipFree(o->Cj0); hipFree(o->s_vert); hipFree(o->s_norm); hipFree(o->s_white); hipFree(o->q_mesh); hipFree(o->scratch);
     direct_free(o->direct);
     or_free(o->orr);
     if (o->own_stream) hipStreamDestroy(o->own_stream);
@@ -1342,6 +1347,8 @@ mw_status mw_ocean_evaluate(mw_ocean* o, float t, float* vertices_xyz, float* no
     if (o->sem != MW_SEM_FFTMESH) return fail(MW_ESTATE, "mw_ocean_evaluate: FFTMesh semantics only");
     mw_status s = mw_ocean_evaluate_device(o, &t, 1, o->s_vert, o->s_norm, o->s_white, MW_OUT_COLOR_RGBA);
     if (s != MW_OK) return s;
+    o->s_have = true;
+    o->s_wstride = 4;
     const size_t NN = (size_t)o->N * o->N;
     if (vertices_xyz) HIP_TRY(hipMemcpyAsync(vertices_xyz, o->s_vert, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
     if (normals_xyz) HIP_TRY(hipMemcpyAsync(normals_xyz, o->s_norm, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
@@ -1564,6 +1571,95 @@ mw_status mw_ocean_displace_mesh(mw_ocean* o, float* vertices_xyz, float* normal
     return MW_OK;
 }
 
+// ---- surface queries (csrc/surface_query.h) -------------------------------------------------------------------
+// Validates the call and names the vertex arrays of the queried frame.  OceanRenderer: the material's vertex stage of that frame
+// (k_or_displace_mesh, so the vertices are those of mw_ocean_displace_mesh bit for bit) runs into the handle's q_mesh first.
+static mw_status query_prepare(mw_ocean* o, int32_t frame, int32_t mode, const void* xz, int64_t n, int32_t iterations, const void* out,
+                               const char* who, SqMesh* m) {
+    if (!o) return fail(MW_EINVAL, std::string(who) + ": NULL handle");
+    if (n < 0) return fail(MW_EINVAL, std::string(who) + ": n < 0");
+    if (n > 0 && (!xz || !out)) return fail(MW_EINVAL, std::string(who) + ": NULL array");
+    if (mode != MW_QUERY_REST && mode != MW_QUERY_WORLD) return fail(MW_EINVAL, std::string(who) + ": mode must be MW_QUERY_REST or MW_QUERY_WORLD");
+    if (iterations < 0 || iterations > MW_SQ_MAX_ITERS) return fail(MW_EINVAL, std::string(who) + ": iterations must be in [0,64]");
+    // one launch: gridDim.x * blockDim.x must fit in 32 bits
+    if (n > (int64_t)UINT32_MAX - 255) return fail(MW_EINVAL, std::string(who) + ": n > 2^32 - 256 (one launch)");
+    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
+        return fail(MW_EINVAL, std::string(who) + ": a batched handle (mw_ocean_create_batch) has no single surface");
+    if (o->sem == MW_SEM_FFTMESH && frame != -1) return fail(MW_EINVAL, std::string(who) + ": FFTMesh handles keep one frame (frame = -1)");
+    if (o->sem == MW_SEM_OCEANRENDERER && (frame < -1 || (frame >= 0 && frame >= o->orr.frames_last)))
+        return fail(MW_EINVAL, std::string(who) + ": frame out of range (-1, or a frame of the latest steps call)");
+    if (!(o->p.unit_width > 0.f)) return fail(MW_EINVAL, std::string(who) + ": the mesh needs unit_width > 0");
+    m->unit_width = o->p.unit_width;
+    if (o->sem == MW_SEM_FFTMESH) {
+        if (!o->s_have) return fail(MW_ESTATE, std::string(who) + ": no frame yet (mw_ocean_evaluate / mw_ocean_update first)");
+        m->vert = o->s_vert; m->norm = o->s_norm; m->white = o->s_white; m->R = o->N; m->wstride = o->s_wstride;
+        return MW_OK;
+    }
+    OrState& r = o->orr;
+    const float *h, *nrm, *wh;
+    const cf* d;
+    if (frame == -1) {
+        if (!r.have_frame) return fail(MW_ESTATE, std::string(who) + ": no GenerateTexture() yet");
+        h = r.out_height; d = r.out_disp_cf; nrm = r.out_normal; wh = r.out_white;
+    } else if (r.frames_last == 1) {  // a one-frame steps call ran the lone-frame plan: its frame is the handle's latest (mw_ocean_frame_textures)
+        if (!(r.fr_have[0] && r.fr_have[1] && r.fr_have[2] && r.fr_have[3]))
+            return fail(MW_ESTATE, std::string(who) + ": the steps call sent this frame's textures to caller buffers");
+        h = r.out_height; d = r.out_disp_cf; nrm = r.out_normal; wh = r.out_white;
+    } else {
+        if (!(r.fr_have[0] && r.fr_have[1] && r.fr_have[2] && r.fr_have[3]))
+            return fail(MW_ESTATE, std::string(who) + ": the steps call sent this frame's textures to caller buffers");
+        const size_t off = (size_t)frame * r.M * r.M;
+        h = r.fr_height + off; d = r.fr_disp + off; nrm = r.fr_normal + 3 * off; wh = r.fr_white + off;
+    }
+    const int res = o->p.resolution, nv = res * res;
+    if (n == 0) return MW_OK;
+    if (!o->q_mesh) {
+        mw_status s = dmalloc(&o->q_mesh, (size_t)nv * 7);
+        if (s != MW_OK) return s;
+    }
+    float *qv = o->q_mesh, *qn = qv + (size_t)nv * 3, *qw = qn + (size_t)nv * 3;
+    k_or_displace_mesh<<<dim3((unsigned)((nv + 255) / 256), 1), dim3(256), 0, o->stream>>>(r.M, res, o->p.unit_width, h, d, nrm, wh, qv, qn, qw);
+    HIP_TRY(hipGetLastError());
+    m->vert = qv; m->norm = qn; m->white = qw; m->R = res; m->wstride = 1;
+    return MW_OK;
+}
+static mw_status query_launch(mw_ocean* o, const SqMesh& m, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
+    const int iters = iterations == 0 ? MW_SQ_DEFAULT_ITERS : iterations;
+    k_query_surface<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, mode, iters, static_cast<const float2*>(d_xz), n,
+                                                                                   static_cast<float4*>(d_out));
+    HIP_TRY(hipGetLastError());
+    return MW_OK;
+}
+
+mw_status mw_ocean_query_surface_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xz, int64_t n, int32_t iterations,
+                                        void* d_out) {
+    const char* who = "mw_ocean_query_surface_device";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (n > 0 && ((reinterpret_cast<uintptr_t>(d_xz) & 7) || (reinterpret_cast<uintptr_t>(d_out) & 15)))
+        return fail(MW_EINVAL, std::string(who) + ": d_xz must be 8-byte and d_out 16-byte aligned");
+    SqMesh m{};
+    mw_status s = query_prepare(o, frame, mode, d_xz, n, iterations, d_out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    return query_launch(o, m, mode, d_xz, n, iterations, d_out);
+}
+
+mw_status mw_ocean_query_surface(mw_ocean* o, int32_t frame, int32_t mode, const float* xz, int64_t n, int32_t iterations, float* out) {
+    const char* who = "mw_ocean_query_surface";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    SqMesh m{};
+    mw_status s = query_prepare(o, frame, mode, xz, n, iterations, out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    const size_t bin = align256((size_t)n * 2 * sizeof(float)), bout = (size_t)n * 8 * sizeof(float);
+    void* buf = nullptr;
+    if ((s = scratch_reserve(o, bin + bout, &buf)) != MW_OK) return s;
+    char* base = static_cast<char*>(buf);
+    HIP_TRY(hipMemcpyAsync(base, xz, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, o->stream));
+    if ((s = query_launch(o, m, mode, base, n, iterations, base + bin)) != MW_OK) return s;
+    HIP_TRY(hipMemcpyAsync(out, base + bin, bout, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    return MW_OK;
+}
+
 // per-launch durations -> (mean, median, p10, p90, min, max), milliseconds
 static void launch_stats(std::vector<float>& v, float* out6) {
     std::sort(v.begin(), v.end());
@@ -1658,6 +1754,7 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
         }
         hipEvent_t ev[4];
         for (auto& e : ev) hipEventCreate(&e);
+        o->s_have = false;  // the launches below overwrite the host-API frame (whitecap scalar, stride 1)
         hipError_t he = hipSuccess;
         for (int w = 0; w < 5 && he == hipSuccess; w++)
             he = direct_evaluate(o->direct, consts_of(o), o->h0, o->h0c, 1.0f, o->s_vert, o->s_norm, o->s_white, 1, o->stream);
@@ -1678,6 +1775,8 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
         }
         for (auto& e : ev) hipEventDestroy(e);
         if (he != hipSuccess) return fail(MW_EDEVICE, std::string("direct-sum profile: ") + hipGetErrorString(he));
+        o->s_have = true;  // the chirp-z / direct kernels above wrote the host-API frame: it is the latest frame now
+        o->s_wstride = 1;
         for (int k = 0; k < 2; k++) {
             ms_out[k] = (float)(acc[k] / iters);
             if (names_out) names_out[k] = dnames[k];
@@ -1690,7 +1789,7 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
     if (s != MW_OK) return s;
     const size_t NN = (size_t)o->N * o->N;
     float *dv = nullptr, *dn = nullptr, *dw = nullptr;
-    if (nsteps == 1) { dv = o->s_vert; dn = o->s_norm; dw = o->s_white; }
+    if (nsteps == 1) { dv = o->s_vert; dn = o->s_norm; dw = o->s_white; o->s_have = false; }  // overwritten below, whitecap stride 1
     else {
         if ((s = dmalloc(&dv, NN * 3 * nsteps)) != MW_OK || (s = dmalloc(&dn, NN * 3 * nsteps)) != MW_OK ||
             (s = dmalloc(&dw, NN * nsteps)) != MW_OK) { hipFree(dv); hipFree(dn); hipFree(dw); return s; }
@@ -1742,6 +1841,7 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
     }
     for (auto& e : ev) hipEventDestroy(e);
     if (nsteps != 1) { hipFree(dv); hipFree(dn); hipFree(dw); }
+    else if (s == MW_OK) { o->s_have = true; o->s_wstride = 1; }  // the host-API frame is the profiled step (t = 1) now
     *nkernels = 2;
     return s;
 }
@@ -1786,6 +1886,8 @@ mw_status mw_debug_evaluate_hds(mw_ocean* o, float t, float* vertices_xyz, float
         if (s != MW_OK) return s;
         dh = o->direct.hds;
     }
+    o->s_have = true;
+    o->s_wstride = 4;
     if (vertices_xyz) HIP_TRY(hipMemcpyAsync(vertices_xyz, o->s_vert, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
     if (normals_xyz) HIP_TRY(hipMemcpyAsync(normals_xyz, o->s_norm, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
     if (colors_rgba) HIP_TRY(hipMemcpyAsync(colors_rgba, o->s_white, NN * 4 * sizeof(float), hipMemcpyDeviceToHost, o->stream));

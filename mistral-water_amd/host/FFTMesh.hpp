@@ -31,6 +31,17 @@ inline void check(mw_status s) {
     if (s != MW_OK) throw std::runtime_error(std::string("mistral_water: ") + mw_last_error());
 }
 
+// one answer of mw_ocean_query_surface: the displaced mesh's surface point, its normal, whitecap and the horizontal residual
+struct SurfaceSample { Vector3 position, normal; float white = 0.f, residual = 0.f; };
+static_assert(sizeof(SurfaceSample) == 32, "[n][8] floats of mw_ocean_query_surface");
+// xz: horizontal points {x, z} (Vector2 x = x, y = z); world = true: points on the displaced surface (buoyancy), false: rest positions
+inline void query_surface(mw_ocean* o, int32_t frame, const std::vector<Vector2>& xz, std::vector<SurfaceSample>& out, bool world,
+                          int32_t iterations) {
+    out.resize(xz.size());
+    check(mw_ocean_query_surface(o, frame, world ? MW_QUERY_WORLD : MW_QUERY_REST, xz.empty() ? nullptr : &xz[0].x, (int64_t)xz.size(),
+                                 iterations, out.empty() ? nullptr : &out[0].position.x));
+}
+
 class FFTMesh {
 public:
     // ---- public Inspector fields, S/FFTMesh.cs:9-23 -------------------------------------------------
@@ -66,6 +77,10 @@ public:
     void EvaluateWaves(float t) {  // S/FFTMesh.cs:224-280
         check(mw_ocean_set_choppiness(ocean_, choppiness));
         check(mw_ocean_evaluate(ocean_, t, &mesh.vertices[0].x, &mesh.normals[0].x, &mesh.colors[0].r));
+    }
+    // Not in the reference: the surface of the latest EvaluateWaves() at horizontal points (include/mistral_water.h, surface queries)
+    void QuerySurface(const std::vector<Vector2>& xz, std::vector<SurfaceSample>& out, bool world = true, int32_t iterations = 0) {
+        query_surface(ocean_, -1, xz, out, world, iterations);
     }
     float timer() const { return timer_; }
     mw_ocean* handle() { return ocean_; }
@@ -149,6 +164,11 @@ public:
         const size_t nn = (size_t)resolution * resolution;
         vertices.resize(nn); normals.resize(nn); foam.resize(nn);
         check(mw_ocean_displace_mesh(ocean_, &vertices[0].x, &normals[0].x, foam.data()));
+    }
+    // Not in the reference: the surface DisplaceMesh() describes (frame -1) or frame k of the latest steps call, at horizontal points
+    void QuerySurface(const std::vector<Vector2>& xz, std::vector<SurfaceSample>& out, bool world = true, int32_t frame = -1,
+                      int32_t iterations = 0) {
+        query_surface(ocean_, frame, xz, out, world, iterations);
     }
 
 private:

@@ -13,6 +13,9 @@ int main() {
         double hmax = 0;
         for (auto& v : m.mesh.vertices) hmax = hmax > (v.y < 0 ? -v.y : v.y) ? hmax : (v.y < 0 ? -v.y : v.y);
         std::printf("FFTMesh 256^2: timer = %.9g, max|height| = %.9g, colour[0] = %.9g\n", m.timer(), hmax, m.mesh.colors[0].r);
+        std::vector<SurfaceSample> here;
+        m.QuerySurface({{0.f, 0.f}, {10.5f, -3.25f}}, here);  // how high is the water at these two points of the displaced surface?
+        std::printf("FFTMesh 256^2: water height at (0, 0) = %.6g (residual %.2g)\n", here[0].position.y, here[0].residual);
         OceanRenderer r;
         r.resolution = 16; r.length = 60.f; r.amplitude = 0.41f; r.choppiness = 0.46f; r.mult = 1.5f; r.wind = {14.45f, 12.f};
         r.Awake();
@@ -22,6 +25,8 @@ int main() {
         std::vector<Vector3> dv, dn;
         std::vector<float> foam;
         r.DisplaceMesh(dv, dn, foam);
+        r.QuerySurface({{1.f, 2.f}}, here);
+        std::printf("OceanRenderer: water height at (1, 2) = %.6g\n", here[0].position.y);
         std::printf("OceanRenderer 128^2: height.r[0] = %.5f, bump.a[0] = %.1f, vertex[0].y = %.5f\n", H[0], B[3], dv[0].y);
         PondMaterial pond;
         std::vector<Vector3> grid(1000), moved, nrm;

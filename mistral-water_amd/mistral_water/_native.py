@@ -20,6 +20,7 @@ HOOKS_HEADER_PATH = os.path.join(REPO_DIR, "include", "mistral_water_hooks.h")
 MW_OK, MW_EINVAL, MW_ENOTPOW2, MW_ENOTCOMMENSURATE, MW_ENOMEM, MW_EDEVICE, MW_ESTATE = range(7)
 MW_SEM_FFTMESH, MW_SEM_OCEANRENDERER = 0, 1
 MW_OUT_WHITE_SCALAR, MW_OUT_COLOR_RGBA = 0, 1
+MW_QUERY_REST, MW_QUERY_WORLD = 0, 1
 STATUS_NAMES = {0: "MW_OK", 1: "MW_EINVAL", 2: "MW_ENOTPOW2", 3: "MW_ENOTCOMMENSURATE", 4: "MW_ENOMEM",
                 5: "MW_EDEVICE", 6: "MW_ESTATE"}
 
@@ -195,6 +196,8 @@ def lib():
         "mw_ocean_generate_texture_rgba_device": (C.c_int, [vp, C.c_float, vp, vp, vp, vp]),
         "mw_ocean_displace_mesh": (C.c_int, [vp, f32p, f32p, f32p]),
         "mw_ocean_displace_mesh_device": (C.c_int, [vp, vp, vp, vp]),
+        "mw_ocean_query_surface": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, C.c_int32, f32p]),
+        "mw_ocean_query_surface_device": (C.c_int, [vp, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int32, vp]),
         "mw_ocean_profile_kernels": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
         "mw_ocean_profile_kernels_stats": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
         "mw_gerstner_displace": (C.c_int, [f32p, C.c_int64, f32p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
@@ -241,7 +244,8 @@ ABI_SYMBOLS = [
     "mw_ocean_evaluate_device", "mw_ocean_max_batch", "mw_ocean_generate_texture",
     "mw_ocean_generate_texture_device", "mw_ocean_generate_texture_steps_device", "mw_ocean_generate_texture_steps_rgba_device",
     "mw_ocean_generate_texture_steps", "mw_ocean_generate_texture_steps_rgba", "mw_ocean_max_frames", "mw_ocean_advance_phase", "mw_ocean_frame_textures", "mw_host_register", "mw_host_unregister", "mw_ocean_generate_texture_rgba", "mw_ocean_generate_texture_rgba_device",
-    "mw_ocean_displace_mesh", "mw_ocean_displace_mesh_device", "mw_gerstner_displace",
+    "mw_ocean_displace_mesh", "mw_ocean_displace_mesh_device", "mw_ocean_query_surface", "mw_ocean_query_surface_device",
+    "mw_gerstner_displace",
     "mw_gerstner_displace_device", "mw_gerstner_displace_steps_device", "mw_gerstner_max_steps", "mw_pond_displace", "mw_pond_displace_device",
 ]
 #: measurement and test hooks (include/mistral_water_hooks.h): exported, but not part of the drop-in boundary

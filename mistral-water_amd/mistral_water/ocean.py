@@ -282,6 +282,26 @@ class Ocean:
         nat.check(nat.lib().mw_ocean_displace_mesh(self._h, _p(v), _p(nr), _p(c)))
         return v, nr, c
 
+    # -- surface queries (mw_ocean_query_surface) ----------------------------------------------
+    _QUERY_MODES = {"rest": nat.MW_QUERY_REST, "world": nat.MW_QUERY_WORLD}
+
+    def query_surface(self, xz, mode: str = "world", frame: int = -1, iterations: int = 0):
+        """Height, normal and whitecap of the displaced mesh at horizontal points xz [n, 2] -> [n, 8] float32 rows
+        (px, py, pz, nx, ny, nz, white, residual).  mode "world": xz is a point on the displaced surface (buoyancy);
+        "rest": a rest-plane position (NaN off the mesh).  frame -1 = the latest frame; k = frame k of the latest
+        OceanRenderer steps call.  iterations 0 = the library default (8), at most 64."""
+        xz = np.ascontiguousarray(xz, np.float32).reshape(-1, 2)
+        out = np.empty((xz.shape[0], 8), np.float32)
+        nat.check(nat.lib().mw_ocean_query_surface(self._h, int(frame), self._QUERY_MODES[mode], _p(xz), xz.shape[0],
+                                                    int(iterations), _p(out)))
+        return out
+
+    def query_surface_device(self, d_xz: int, n: int, d_out: int, mode: str = "world", frame: int = -1, iterations: int = 0):
+        """Device-pointer form: d_xz [n][2] (8-byte aligned), d_out [n][8] (16-byte aligned) float32; asynchronous on the
+        handle's stream (synchronize() or the stream before reading d_out)."""
+        nat.check(nat.lib().mw_ocean_query_surface_device(self._h, int(frame), self._QUERY_MODES[mode], C.c_void_p(d_xz), int(n),
+                                                           int(iterations), C.c_void_p(d_out)))
+
 
 class _Mesh:
     """The handful of UnityEngine.Mesh members the reference assigns (S/FFTMesh.cs:134-138,277-279)."""
@@ -337,6 +357,10 @@ class FFTMesh:
         self._ocean.set_choppiness(self.choppiness)  # :244-245 read the live field
         v, n, c = self._ocean.evaluate(t)
         self.mesh.vertices, self.mesh.normals, self.mesh.colors = v, n, c  # :277-279
+
+    def SampleSurface(self, xz, world: bool = True, iterations: int = 0):
+        """Not in the reference: the mesh's surface at horizontal points xz [n, 2] of the latest EvaluateWaves (Ocean.query_surface)."""
+        return self._ocean.query_surface(xz, mode="world" if world else "rest", iterations=iterations)
 
     @property
     def timer(self):
@@ -399,6 +423,11 @@ class OceanRenderer:
         H, D, Nn, W = self._ocean.generate_texture_steps(deltaTimes)
         self.heightTexture, self.displacementTexture, self.normalTexture, self.whiteTexture = H[-1], D[-1], Nn[-1], W[-1]
         return H, D, Nn, W
+
+    def SampleSurface(self, xz, world: bool = True, frame: int = -1, iterations: int = 0):
+        """Not in the reference: the displaced mesh's surface at horizontal points xz [n, 2] (Ocean.query_surface); frame -1 = what
+        the latest GenerateTexture() shows, k = frame k of the latest GenerateTextures()."""
+        return self._ocean.query_surface(xz, mode="world" if world else "rest", frame=frame, iterations=iterations)
 
     @property
     def ocean(self) -> Ocean:
