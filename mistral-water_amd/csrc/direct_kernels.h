@@ -179,15 +179,12 @@ __global__ void k_direct_white(int N, const cf* hds, const float* normals, float
 // kernel's transform / the post-chirp are requested before the first input load, so that ONE memory latency covers them all (M <= 512 only: at
 // M = 2048 the 64 extra registers of the early loads cost a wave per SIMD, N = 1000 98 -> 122 us).  Same table
 // values, same expressions: the same bits (tests/test_zz_frame_plan.py, every direct-path parity test).
-#ifndef MW_CZT_PRELOAD
-#define MW_CZT_PRELOAD 1
-#endif
 #ifndef MW_CZT_STAGE_MAX_M
 #define MW_CZT_STAGE_MAX_M 512  // larger transforms keep their tables in global memory (their LDS decides how many workgroups share a CU)
 #endif
 template <int M, int P>
 struct CztTw {
-    static constexpr bool STAGE = MW_CZT_PRELOAD && M <= MW_CZT_STAGE_MAX_M && TwGeom<M, P>::IN_LDS;
+    static constexpr bool STAGE = M <= MW_CZT_STAGE_MAX_M && TwGeom<M, P>::IN_LDS;
     static constexpr int HALF = STAGE ? ((TwGeom<M, P>::LDS_ALL + 1) & ~1) : 0;  // cf entries per direction, 16-B aligned
     static constexpr int CF = 2 * HALF;                                          // in front of the line buffers
 };
@@ -230,10 +227,7 @@ __device__ __forceinline__ void czt_line_core(const CztArgs& A, int u, cf* buf, 
     // A line's buffer is written and read by the line's own T threads only: where those sit in ONE wave (T <= 64: M <= 512) its exchanges
     // need that wave's LDS operations in order and no workgroup barrier (the lines drift apart: a dozen barriers less on the dependent
     // chain of a small-grid step).  The first barrier stays a workgroup barrier: it publishes the staged tables.
-#ifndef MW_CZT_WAVE_SYNC
-#define MW_CZT_WAVE_SYNC 1
-#endif
-    constexpr bool WS = MW_CZT_WAVE_SYNC && T <= 64 && 64 % T == 0;
+    constexpr bool WS = T <= 64 && 64 % T == 0;
     auto line_sync = [&]() {
         if (WS) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
         else __syncthreads();

@@ -40,18 +40,12 @@ struct StepTimes {
 #endif
 template <int N> struct Exch { static constexpr int CW = (N >= MW_CW2_MIN_N) ? 2 : 4; };
 
-#ifndef MW_FAST_SINCOS
-#define MW_FAST_SINCOS 1  // hardware v_sin/v_cos after an exact reduction (1.8e-7 abs; +1 % at 1024^2, -4 % OceanRenderer frame time)
-#endif
-MW_HD void mw_sincos(float x, float* s, float* c) {
-    if (MW_FAST_SINCOS) sincos_fast_f32(x, s, c); else sincos_f32(x, s, c);
-}
+// hardware v_sin/v_cos after an exact reduction (1.8e-7 abs; +1 % at 1024^2, -4 % OceanRenderer frame time)
+MW_HD void mw_sincos(float x, float* s, float* c) { sincos_fast_f32(x, s, c); }
 // hardware sine/cosine after an exact reduction (1.8e-7 absolute on the device): the VALU-bound pond kernels
 MW_HD void mw_sincos_fast(float x, float* s, float* c) { sincos_fast_f32(x, s, c); }
-// streaming (write-once) stores: MW_NT_STORES marks them non-temporal so that they do not displace reusable lines
-#ifndef MW_NT_STORES
-#define MW_NT_STORES 1  // measured: pass 1 -10 % (exchange-buffer stores), pass 2 -3 % (results)
-#endif
+// streaming (write-once) stores, non-temporal so that they do not displace reusable lines (measured: pass 1 -10 % with the
+// exchange-buffer stores, pass 2 -3 % with the results)
 // Results (vertices, normals, whitecap): non-temporal from 512^2 up (512^2 +5 % step, 1024^2 +2 %, and with the round-2
 // kernels 2048^2 +3 %, 4096^2 +2 % in pass 2); slower at 256^2, where everything is cache-resident (-8 % pass 2).
 #ifndef MW_NT_RESULTS_MIN_N
@@ -67,14 +61,14 @@ MW_HD constexpr bool mw_nt_exchange(int N) { return N >= MW_NT_EXCHANGE_MIN_N; }
 template <bool NT = true>
 MW_HD void mw_store_stream(float* p, float v) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    if (MW_NT_STORES && NT) { __builtin_nontemporal_store(v, p); return; }
+    if (NT) { __builtin_nontemporal_store(v, p); return; }
 #endif
     *p = v;
 }
 template <bool NT = true>
 MW_HD void mw_store_stream(cf* p, cf v) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    if (MW_NT_STORES && NT) {
+    if (NT) {
         typedef float f2v __attribute__((ext_vector_type(2)));
         f2v t; t.x = v.x; t.y = v.y;
         __builtin_nontemporal_store(t, reinterpret_cast<f2v*>(p));
@@ -89,7 +83,7 @@ MW_HD void mw_store_stream(cf* p, cf v) {
 template <bool NT = true>
 MW_HD void mw_store_stream(f4* p, f4 v) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    if (MW_NT_STORES && NT) {
+    if (NT) {
         typedef float f4v __attribute__((ext_vector_type(4)));
         f4v t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
         __builtin_nontemporal_store(t, reinterpret_cast<f4v*>(p));
@@ -98,20 +92,8 @@ MW_HD void mw_store_stream(f4* p, f4 v) {
 #endif
     *p = v;
 }
-#ifndef MW_NT_LOADS
-#define MW_NT_LOADS 0
-#endif
-// MW_NT_LOADS: 1 = every exchange-buffer load non-temporal (-9 % at 1024^2), 2 = only the loads flagged `last_use`
-MW_HD cf mw_load_stream(const cf* p, bool last_use = false) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (MW_NT_LOADS == 1 || (MW_NT_LOADS == 2 && last_use)) {
-        typedef float f2v __attribute__((ext_vector_type(2)));
-        const f2v t = __builtin_nontemporal_load(reinterpret_cast<const f2v*>(p));
-        return mk(t.x, t.y);
-    }
-#endif
-    return *p;
-}
+// exchange-buffer loads: plain (non-temporal loads measured -9 % at 1024^2)
+MW_HD cf mw_load_stream(const cf* p) { return *p; }
 template <bool WAVE_UNIFORM>
 MW_HD int wave_uniform(int v) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -247,12 +229,6 @@ MW_HD void prep_element(int N, float length, float gravity, int i, int j, const 
 // correction column cz(i,0) * D'(i,0) through the very same code path and writes it
 // to Cj0, which pass 2 adds to element j = 0 of every row.  The i = 0 correction is one element per
 // column: thread u == 0 carries it in `dl0` (zero for every other thread, so no branch).
-#ifndef MW_NOISE_LDS
-#define MW_NOISE_LDS 1
-#endif
-#ifndef MW_DBUF
-#define MW_DBUF 0  // ping-pong exchange sets: measured no gain at 2x the LDS
-#endif
 struct P1Args {
     const f4* PQt;     // [j][i] (P,Q) * pre
     const f4* dPQ_i0;  // [j]    (dP,dQ) * pre on the row i = 0
@@ -264,8 +240,8 @@ struct P1Args {
     OceanConsts c;
     int tgroup;        // > 0: 1-D grid, `tgroup` time-steps of one column job kept on one XCD (p1_block_map)
     int nsteps;
-    int field_split = 0;  // single-step enqueues, ONE field per workgroup: 1 = grid (column jobs, 3); 2 = 1-D grid over `jobs`
-    const int* jobs = nullptr;  // field_split == 2: workgroup id -> (field << 16 | column job), -1 = none (p1_frame_jobs)
+    bool field_split = false;   // single-step enqueues, ONE field per workgroup: 1-D grid over `jobs`
+    const int* jobs = nullptr;  // field_split: workgroup id -> (field << 16 | column job), -1 = none (p1_frame_jobs)
     int njobs = 0;
 };
 
@@ -294,9 +270,7 @@ struct P1Geom {
     static constexpr int BUFSTRIDE = FftGeom<N, P>::LBUF + (XLay<N, P>::EXACT ? XLay<N, P>::PAD_RD4 : MW_BUF_PAD);
     static constexpr int TW_LDS = (TwGeom<N, P>::LDS_ALL + 1) & ~1;  // cf units, 16-B aligned
     static constexpr int SETSTRIDE = CW * BUFSTRIDE;
-    // 2: ping-pong exchange buffers, one barrier per exchange (when both sets fit a 100 KiB budget)
-    static constexpr int NBUF = (MW_DBUF && (TW_LDS + 2 * SETSTRIDE) * 8 <= 100 * 1024) ? 2 : 1;
-    static constexpr int LDS_BYTES = (TW_LDS + NBUF * SETSTRIDE) * (int)sizeof(cf);
+    static constexpr int LDS_BYTES = (TW_LDS + SETSTRIDE) * (int)sizeof(cf);
     static constexpr int GRID_X = N / CW + 1;
     static_assert(NTHREADS <= 1024, "workgroup too large: use P = 16 for this N");
 };
@@ -511,11 +485,10 @@ struct P2Geom {
     static constexpr int BUFSTRIDE = P2Buf<N, P>::BUFSTRIDE;
     static constexpr int TW_LDS = (TwGeom<N, P>::LDS_ALL + 1) & ~1;
     static constexpr int SETSTRIDE = NGROUPS * BUFSTRIDE;
-    static constexpr int NBUF = (!HS && MW_DBUF && (TW_LDS + 2 * SETSTRIDE) * 8 <= 100 * 1024) ? 2 : 1;
     // the whitecap noise term |0.3 n.xz| waits in LDS (R2*N floats) from the slope field to the epilogue instead of
     // in P registers per thread: that is what lets pass 2 fit 80 VGPRs without scratch spills
-    static constexpr bool NOISE_REG = HS || !MW_NOISE_LDS;
-    static constexpr int NOISE_OFF = TW_LDS + NBUF * SETSTRIDE;  // cf units
+    static constexpr bool NOISE_REG = HS;
+    static constexpr int NOISE_OFF = TW_LDS + SETSTRIDE;  // cf units
     static constexpr int NOISE_CF = NOISE_REG ? 0 : R2 * N / 2;
 #ifndef MW_P2_LDS_EXTRA
 #define MW_P2_LDS_EXTRA 0  // occupancy experiments: bytes of unused LDS per pass-2 workgroup
@@ -524,7 +497,7 @@ struct P2Geom {
     static_assert(NTHREADS <= 1024, "workgroup too large");
 };
 
-template <int P, bool NOISE_REG_ = !MW_NOISE_LDS>
+template <int P, bool NOISE_REG_ = false>
 struct P2State {
     static constexpr bool NOISE_REG = NOISE_REG_;
     float noise[NOISE_REG_ ? P : 1];  // |0.3 n.xz| per slot (S/FFTMesh.cs:269-270) when it is not parked in LDS
@@ -558,8 +531,6 @@ MW_HD void p2_load_map(int tid, int* r1, int* u1) {
 // mode 2); 2 = the assembly on top of part 1 -- the height-row loads, the kz T1 term and the conjugation of the mirrored
 // slots.  The sequential-halo kernel issues part 1 of all its virtual threads, then part 2 + stage 0 one virtual thread at a
 // time: the height rows' registers are then live for one virtual thread only.
-// nyq != nullptr: the Nyquist-column term is returned there instead of being added to x[0] (a prefetch must not consume any
-// of its loads: the add's s_waitcnt would wait for all of them, vmcnt being in-order); the caller adds it when it uses x.
 // keep (KeepT1, mode 2 of the half-stored slope field): the height fetch (f = 0) leaves the RAW values of its mirrored slots q >= P/2
 // there -- element (a, N - j) of the height rows, before the conjugation --, and the slope assembly (f = 2, PART 0 / 2) takes them from
 // there instead of fetching the same exchange-buffer words a second time (4 B per grid point that had left the L2 by then).
@@ -569,7 +540,7 @@ struct KeepT1 {
                                   ((N / 2) % FftGeom<N, P>::T == 0);
 };
 template <int N, int P, int R2, int PART = 0>
-MW_HD void p2_fetch(const P2Args& A, int ab, int step, int tid, int f, cf (&x)[P], cf* nyq = nullptr, cf* keep = nullptr) {
+MW_HD void p2_fetch(const P2Args& A, int ab, int step, int tid, int f, cf (&x)[P], cf* keep = nullptr) {
     constexpr int T = FftGeom<N, P>::T;
     int r1, u1;
     p2_load_map<N, P, R2>(tid, &r1, &u1);
@@ -596,16 +567,16 @@ MW_HD void p2_fetch(const P2Args& A, int ab, int step, int tid, int f, cf (&x)[P
             // the edge slot's two candidates differ per lane: select the (non-negative) offset, not the data
             const size_t ub = edge ? 0 : chunk;  // uniform part
             const unsigned off = all_mir ? voffm : (edge ? (u1 > 0 ? voffm - (unsigned)chunk : voff + (unsigned)chunk) : voff);
-            cf v = (PART == 2) ? x[q] : mw_load_stream(&(all_mir ? Ef - ub : Ef + ub)[off], f != 0);
+            cf v = (PART == 2) ? x[q] : mw_load_stream(&(all_mir ? Ef - ub : Ef + ub)[off]);
             if (PART == 1) { x[q] = v; continue; }
             if (f == 0 && keep && (all_mir || edge)) keep[q - P / 2] = v;  // T q >= N/2  <=>  q >= P/2
             if (mw_split_slopes(N) == 1 && f == 2) {  // T3(a,j) = G'(a,j) + kz(j) T1'(a,j)
-                const cf t = mw_load_stream(&(all_mir ? E0 - ub : E0 + ub)[off], true);
+                const cf t = mw_load_stream(&(all_mir ? E0 - ub : E0 + ub)[off]);
                 const float kz = wave_k_fast(N, kscale, u1 + T * q);
                 v = mk(__builtin_fmaf(kz, t.x, v.x), __builtin_fmaf(kz, t.y, v.y));
             }
             if (mw_split_slopes(N) == 2 && f == 2 && (all_mir || edge)) {  // T3(a,j) = conj(T3(a,m) - 2 kz(m) T1(a,m)), kz(m) = -kz(j)
-                const cf t = keep ? keep[q - P / 2] : mw_load_stream(&(all_mir ? E0 - ub : E0 + ub)[off], true);
+                const cf t = keep ? keep[q - P / 2] : mw_load_stream(&(all_mir ? E0 - ub : E0 + ub)[off]);
                 const float k2 = 2.0f * wave_k_fast(N, kscale, u1 + T * q);
                 const float c = mir ? k2 : 0.f;  // the edge slot's lane u1 == 0 is j = N/2: plain
                 v = mk(__builtin_fmaf(c, t.x, v.x), __builtin_fmaf(c, t.y, v.y));
@@ -613,10 +584,7 @@ MW_HD void p2_fetch(const P2Args& A, int ab, int step, int tid, int f, cf (&x)[P
             x[q] = mir ? cconj(v) : v;
             if (PART == 2 && MW_SLOPE_FENCE_Q && q % MW_SLOPE_FENCE_Q == MW_SLOPE_FENCE_Q - 1) mw_sched_fence();  // cap the height-row loads in flight
         }
-        if (PART != 1 && f != 0) {  // Nyquist column j = 0
-            if (nyq) *nyq = (u1 == 0) ? A.Cj0[((size_t)step * 3 + f) * N + row] : mk(0.f, 0.f);
-            else if (u1 == 0) x[0] = x[0] + A.Cj0[((size_t)step * 3 + f) * N + row];
-        }
+        if (PART != 1 && f != 0 && u1 == 0) x[0] = x[0] + A.Cj0[((size_t)step * 3 + f) * N + row];  // Nyquist column j = 0
         return;
     }
 #pragma unroll
@@ -634,7 +602,7 @@ MW_HD void p2_fetch(const P2Args& A, int ab, int step, int tid, int f, cf (&x)[P
             x[q] = cconj(v);
         } else {
             const unsigned off = (unsigned)(((j / CW) * N + r1) * CW + (j % CW));
-            cf v = (T % CW == 0) ? mw_load_stream(&(Ef + (size_t)(T / CW) * q * N * CW)[voff], f != 0) : Ef[off];
+            cf v = (T % CW == 0) ? mw_load_stream(&(Ef + (size_t)(T / CW) * q * N * CW)[voff]) : Ef[off];
             if (mw_split_slopes(N) == 1 && f == 2) {
                 const cf t = mw_load_stream(&(A.E + ((size_t)step * 3 + 0) * N * N + (size_t)ab * R2 * CW)[off]);
                 const float kz = wave_k_fast(N, 2.0f * MW_PI_F / A.c.length, j);
@@ -643,10 +611,7 @@ MW_HD void p2_fetch(const P2Args& A, int ab, int step, int tid, int f, cf (&x)[P
             x[q] = v;
         }
     }
-    if (f != 0) {  // Nyquist column j = 0
-        if (nyq) *nyq = (u1 == 0) ? A.Cj0[((size_t)step * 3 + f) * N + row] : mk(0.f, 0.f);
-        else if (u1 == 0) x[0] = x[0] + A.Cj0[((size_t)step * 3 + f) * N + row];
-    }
+    if (f != 0 && u1 == 0) x[0] = x[0] + A.Cj0[((size_t)step * 3 + f) * N + row];  // Nyquist column j = 0
 }
 template <int N, int P, int R2>
 MW_HD void p2_stage0(int tid, cf (&x)[P], cf* lds) {
@@ -656,7 +621,7 @@ MW_HD void p2_stage0(int tid, cf (&x)[P], cf* lds) {
 }
 template <int N, int P, int R2>
 MW_HD void p2_load(const P2Args& A, int ab, int step, int tid, int f, cf (&x)[P], cf* lds, cf* keep = nullptr) {
-    p2_fetch<N, P, R2>(A, ab, step, tid, f, x, nullptr, keep);
+    p2_fetch<N, P, R2>(A, ab, step, tid, f, x, keep);
     p2_stage0<N, P, R2>(tid, x, lds);
 }
 // the slope field can be loaded in two parts (p2_fetch) when the fast half-field path applies
@@ -916,7 +881,7 @@ MW_HD void p2_hs_finish_slopes(const P2Args& A, const Twiddles& tw, int ab, int 
 
 // halo row a0+R2 of the displacement field, loaded by group 0 in the row-major mapping (thread u: j = u + T q)
 template <int N, int P, int R2>
-MW_HD void p2_hs_halo_fetch(const P2Args& A, int ab, int step, int u, cf (&x)[P], cf* nyq = nullptr) {
+MW_HD void p2_hs_halo_fetch(const P2Args& A, int ab, int step, int u, cf (&x)[P]) {
     constexpr int T = FftGeom<N, P>::T;
     const int row = ab * R2 + R2;
     constexpr int CW = Exch<N>::CW;
@@ -924,8 +889,7 @@ MW_HD void p2_hs_halo_fetch(const P2Args& A, int ab, int step, int u, cf (&x)[P]
     const unsigned voff = (unsigned)((u / CW) * N * CW + (u % CW));
 #pragma unroll
     for (int q = 0; q < P; q++) x[q] = (Ef + (size_t)(T / CW) * q * N * CW)[voff];
-    if (nyq) *nyq = (u == 0) ? A.Cj0[((size_t)step * 3 + 1) * N + row] : mk(0.f, 0.f);
-    else if (u == 0) x[0] = x[0] + A.Cj0[((size_t)step * 3 + 1) * N + row];  // Nyquist column j = 0
+    if (u == 0) x[0] = x[0] + A.Cj0[((size_t)step * 3 + 1) * N + row];  // Nyquist column j = 0
 }
 // transformed halo row -> plain hds row in buffer 0
 template <int N, int P, int R2>
@@ -947,9 +911,6 @@ MW_HD void p2_hs_halo_publish(int ab, int u, const cf (&x)[P], cf* buf0) {
 // publish hds and the slope groups store the normals and leave the whitecap's noise term in their row buffers; one barrier; then
 // the HEIGHT groups store the vertices (h from their registers, hds from the published rows) while the displacement groups form
 // 1 - J and store the whitecap.  Every value is formed by the expressions of the batched plan: the same bits.
-#ifndef MW_FRAME_NT_RESULTS
-#define MW_FRAME_NT_RESULTS 1
-#endif
 #ifndef MW_FRAME_R2
 #define MW_FRAME_R2 4  // rows per workgroup of k_pass2_frame at 1024^2 (2: 16.9 against 15.6 us)
 #endif
@@ -1005,9 +966,9 @@ MW_HD void p2_frame_normals(const P2Args& A, int ab, int step, int tl, const cf 
         const float sx = sg * x[q].x, sz = sg * x[q].y;
         const float inv = mw_rsqrt(__builtin_fmaf(sz, sz, __builtin_fmaf(sx, sx, 1.0f)));
         const float nx = sx * inv, ny = inv, nz = sz * inv;
-        mw_store_stream<MW_FRAME_NT_RESULTS != 0>(&nq[noff + 0], nx);
-        mw_store_stream<MW_FRAME_NT_RESULTS != 0>(&nq[noff + 1], ny);
-        mw_store_stream<MW_FRAME_NT_RESULTS != 0>(&nq[noff + 2], nz);
+        mw_store_stream(&nq[noff + 0], nx);
+        mw_store_stream(&nq[noff + 1], ny);
+        mw_store_stream(&nq[noff + 2], nz);
         const float n0 = smul(fabsf(nx), 0.3f), n1 = smul(fabsf(nz), 0.3f);
         nrow[b] = ssqrt(sadd(smul(n0, n0), smul(n1, n1)));  // :269
     }
@@ -1026,9 +987,9 @@ MW_HD void p2_frame_vertices(const P2Args& A, int ab, int step, int tl, const cf
         const int b = u + T * q;
         const cf d = drow[b];
         float* vq = vblk + (size_t)T * q * 3;                                              // uniform
-        mw_store_stream<MW_FRAME_NT_RESULTS != 0>(&vq[voff + 0], ssub(rx, smul(d.x, A.c.choppiness)));                                // :245
-        mw_store_stream<MW_FRAME_NT_RESULTS != 0>(&vq[voff + 1], post_sign(a, b) * x[q].x);                                           // :243
-        mw_store_stream<MW_FRAME_NT_RESULTS != 0>(&vq[voff + 2], ssub(rest_coord(N, A.c.unit_width, b), smul(d.y, A.c.choppiness)));  // :244
+        mw_store_stream(&vq[voff + 0], ssub(rx, smul(d.x, A.c.choppiness)));                                // :245
+        mw_store_stream(&vq[voff + 1], post_sign(a, b) * x[q].x);                                           // :243
+        mw_store_stream(&vq[voff + 2], ssub(rest_coord(N, A.c.unit_width, b), smul(d.y, A.c.choppiness)));  // :244
     }
 }
 // displacement groups: 1 - J from the published rows (nxt: row a + 1, the halo row's buffer for the block's last row), then the whitecap
@@ -1049,7 +1010,7 @@ MW_HD void p2_frame_white(const P2Args& A, int ab, int step, int tl, const cf* s
         P2RowView<P> v;
         v.d[q] = nb.row[b];
         const float omj = p2_one_minus_jacobian<N, P, R2>(a, b, q, v, nxt, nb);
-        p2_store_white<MW_FRAME_NT_RESULTS != 0>(wblk + (size_t)T * q * A.white_stride, woff, A.white_stride, omj, nrow[b]);
+        p2_store_white<true>(wblk + (size_t)T * q * A.white_stride, woff, A.white_stride, omj, nrow[b]);
     }
 }
 
@@ -1075,12 +1036,6 @@ MW_HD void p2_frame_white(const P2Args& A, int ab, int step, int tl, const cf* s
 #ifndef MW_PT2_4096
 #define MW_PT2_4096 16
 #endif
-#ifndef MW_HS_2048
-#define MW_HS_2048 1  // 2048^2: sequential halo, 4 rows, 2 virtual threads per lane, two 4-wave workgroups per CU: +10 % over 4 rows + halo group
-#endif
-#ifndef MW_HS_4096
-#define MW_HS_4096 1  // sequential-halo pass 2 (P2Geom<..., true>): 4096^2 +9 % over 2 rows + halo group
-#endif
 #ifndef MW_R2_2048
 #define MW_R2_2048 4
 #endif
@@ -1102,24 +1057,11 @@ MW_HD void p2_frame_white(const P2Args& A, int ab, int step, int tl, const cf* s
 #ifndef MW_PT2_1024
 #define MW_PT2_1024 16
 #endif
-#ifndef MW_HS_1024
-#define MW_HS_1024 1
-#endif
 #ifndef MW_VT_1024
 #define MW_VT_1024 2
 #endif
 #ifndef MW_VT1_4096
 #define MW_VT1_4096 1
-#endif
-// software prefetch level of k_pass2_hs (0 none, 1 displacement rows during the height field, 2 + slope rows during displacement)
-#ifndef MW_PF_4096
-#define MW_PF_4096 0  // displacement rows prefetched during the height field: -1.5 % at 4096^2 in round 2; with KeepT1 (round 4) the plan
-#endif                // without it is 1 % ahead (265.0 vs 267.9 us per step), and 2048^2 / 1024^2 were always slower with it
-#ifndef MW_PF_2048
-#define MW_PF_2048 0
-#endif
-#ifndef MW_PF_1024
-#define MW_PF_1024 0
 #endif
 #ifndef MW_VT1_2048
 #define MW_VT1_2048 1
@@ -1131,12 +1073,12 @@ template <int N> struct Plan {
     static constexpr int P = (N >= 2048) ? 16 : MW_PT_OR;  // OceanRenderer passes
     static constexpr int P1 = (N >= 2048) ? 16 : MW_PT1;  // 5 x N/8 threads would exceed 1024 at N = 2048
     static constexpr int P2 = (N >= 4096) ? MW_PT2_4096 : (N == 2048 ? MW_PT2_2048 : (N == 1024 ? MW_PT2_1024 : MW_PT2));
-    static constexpr bool HS = (N >= 4096) ? (MW_HS_4096 != 0) : (N == 2048 ? (MW_HS_2048 != 0) : (N == 1024 ? (MW_HS_1024 != 0) : false));
+    // the sequential-halo pass 2 (k_pass2_hs) from 1024^2 up: 2048^2 +10 %, 4096^2 +9 % over R2 rows + halo group
+    static constexpr bool HS = N >= 1024;
     static constexpr int R2 = (N >= 4096) ? MW_R2_4096 : (N == 2048 ? MW_R2_2048 : (N == 1024 ? MW_R2_1024 : ((N <= MW_R2_SMALL_N) ? 8 : 4)));
     // virtual threads per lane of the sequential-halo kernel (k_pass2_hs): 2 = 8 fat waves with a 256-VGPR budget
     static constexpr int VT = (N >= 4096) ? MW_VT_4096 : (N == 2048 ? MW_VT_2048 : MW_VT_1024);
     static constexpr int VT1 = (N >= 4096) ? MW_VT1_4096 : (N == 2048 ? MW_VT1_2048 : 1);  // the same for pass 1
-    static constexpr int PF = (N >= 4096) ? MW_PF_4096 : (N == 2048 ? MW_PF_2048 : MW_PF_1024);
 };
 
 }  // namespace mw

@@ -3,7 +3,6 @@
 // Streaming kernel, 24 B/vertex algorithmic (read position 12 B + write displaced position 12 B).
 #pragma once
 #include "fftmesh_kernels.h"
-#include "mw_switches.h"
 
 #define MW_GERSTNER_MAX_WAVES 16
 
@@ -95,7 +94,7 @@ __global__ __launch_bounds__(256) void k_gerstner(const float* __restrict__ pos,
 // of a sincos.  The positions are read once per launch; per step only the 12-B result leaves.
 #define MW_GERSTNER_PHASES 256  // nsteps * nwaves per launch (2 KiB of kernel arguments)
 #ifndef MW_POND_STEPS_PER_WG
-#define MW_POND_STEPS_PER_WG 8  // time values per workgroup of k_gerstner_steps (switch MW_POND_STEPS_PER_WG overrides: A/B)
+#define MW_POND_STEPS_PER_WG 8  // time values per workgroup of k_gerstner_steps
 #endif
 struct GerstnerPhases {
     float cb[MW_GERSTNER_PHASES], sb[MW_GERSTNER_PHASES];  // [step * nwaves + i]
@@ -130,26 +129,11 @@ MW_HD void gerstner_step_vertex(const GerstnerWaves& wv, const GerstnerPhases& p
 // and go, issued in address order, instead of one long-lived workgroup walking all 32 slabs -- on this memory system fresh
 // workgroups beat long-lived ones for every store stream (profiles/r03_hbm_probe.txt); 8 steps per workgroup measured best (the
 // position part, 8 sincos per vertex, is then re-formed 4 times per launch: +13 % VALU, still well under the store time).
-#ifndef MW_POND_LOADS_FIRST
-#define MW_POND_LOADS_FIRST 1
-#endif
 template <int NW>
 __global__ __launch_bounds__(256) void k_gerstner_steps(const float* __restrict__ pos, float* __restrict__ out, int64_t nverts,
                                                         GerstnerWaves wv, GerstnerPhases ph, int nsteps, float amplitude,
-                                                        float frequency, float steepness, int steps_per_wg, int xcd_blocks) {
-    // xcd_blocks > 0 (round 5): 1-D grid; the step groups of ONE vertex chunk sit in consecutive slots of ONE XCD (the dispatcher
-    // places workgroup b on XCD b % 8), so the first of them pulls the chunk's 12 KiB of positions into that XCD's L2 and the others
-    // hit there: the positions cross HBM once per launch instead of once per step group (13.5 -> 12.4 B per vertex-step) while the
-    // workgroups stay short-lived.  xcd_blocks = the number of vertex chunks per trip (what gridDim.x was in the 2-D form).
-    int vb = (int)blockIdx.x, sg = (int)blockIdx.y, nvb = (int)gridDim.x;
-    if (xcd_blocks > 0) {
-        const int ngroups = (nsteps + steps_per_wg - 1) / steps_per_wg;
-        const int xcd = (int)blockIdx.x % 8, slot = (int)blockIdx.x / 8;
-        sg = slot % ngroups;
-        vb = (slot / ngroups) * 8 + xcd;
-        nvb = xcd_blocks;
-        if (vb >= nvb) return;
-    }
+                                                        float frequency, float steepness, int steps_per_wg) {
+    const int vb = (int)blockIdx.x, sg = (int)blockIdx.y, nvb = (int)gridDim.x;
     const int step_lo = sg * steps_per_wg, step_hi = step_lo + steps_per_wg < nsteps ? step_lo + steps_per_wg : nsteps;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t v0 = ((int64_t)vb * 4 + wave) * 256; v0 < nverts; v0 += (int64_t)nvb * 1024) {  // wave-uniform chunk of 256 vertices
@@ -162,13 +146,10 @@ __global__ __launch_bounds__(256) void k_gerstner_steps(const float* __restrict_
             ok[k] = vid < nverts;
             const float* p = pos + 3 * (ok[k] ? vid : v0);
             v[3 * k] = p[0]; v[3 * k + 1] = p[1]; v[3 * k + 2] = p[2];
-            if (!MW_POND_LOADS_FIRST) gerstner_position_part<NW>(wv, frequency, v[3 * k], v[3 * k + 2], sa[k], ca[k]);
         }
-        if (MW_POND_LOADS_FIRST) {
-            mw_sched_fence();
+        mw_sched_fence();
 #pragma unroll
-            for (int k = 0; k < 4; k++) gerstner_position_part<NW>(wv, frequency, v[3 * k], v[3 * k + 2], sa[k], ca[k]);
-        }
+        for (int k = 0; k < 4; k++) gerstner_position_part<NW>(wv, frequency, v[3 * k], v[3 * k + 2], sa[k], ca[k]);
         for (int step = step_lo; step < step_hi; step++) {
             float* dst = out + (size_t)step * nverts * 3 + 3 * v0;
 #pragma unroll
@@ -212,17 +193,10 @@ static inline hipError_t gerstner_launch_steps(const float* d_pos, int64_t nvert
     int64_t blocks = (nverts + 1023) / 1024;  // 1024 vertices per 256-thread workgroup and trip
     if (blocks < 1) blocks = 1;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    const int spw_env = sw(SW_POND_STEPS_PER_WG);
-    const int spw = spw_env > 0 ? (spw_env < nsteps ? spw_env : nsteps) : (MW_POND_STEPS_PER_WG < nsteps ? MW_POND_STEPS_PER_WG : nsteps);
-    // switch MW_POND_XCD = 1: the step groups of a vertex chunk on one XCD.  Measured round 5 (profiles/r05_ab_notes.md): 4.25e11 against 4.48e11
-    // vertices/s for the 2-D grid -- the positions' second to fourth read is 1.1 of 13.5 B per vertex-step and not what the launch waits for: off
-    const int xcd_env = sw(SW_POND_XCD);
-    const int ngroups = (nsteps + spw - 1) / spw;
-    const bool xcd = xcd_env != 0 && ngroups > 1;
-    const dim3 grid = xcd ? dim3((unsigned)(((blocks + 7) / 8) * 8 * ngroups)) : dim3((unsigned)blocks, (unsigned)ngroups);
-    const int xb = xcd ? (int)blocks : 0;
-    if (nwaves == 4) k_gerstner_steps<4><<<grid, dim3(256), 0, st>>>(d_pos, d_out, nverts, wv, ph, nsteps, amplitude, frequency, steepness, spw, xb);
-    else k_gerstner_steps<8><<<grid, dim3(256), 0, st>>>(d_pos, d_out, nverts, wv, ph, nsteps, amplitude, frequency, steepness, spw, xb);
+    const int spw = MW_POND_STEPS_PER_WG < nsteps ? MW_POND_STEPS_PER_WG : nsteps;
+    const dim3 grid((unsigned)blocks, (unsigned)((nsteps + spw - 1) / spw));
+    if (nwaves == 4) k_gerstner_steps<4><<<grid, dim3(256), 0, st>>>(d_pos, d_out, nverts, wv, ph, nsteps, amplitude, frequency, steepness, spw);
+    else k_gerstner_steps<8><<<grid, dim3(256), 0, st>>>(d_pos, d_out, nverts, wv, ph, nsteps, amplitude, frequency, steepness, spw);
     return hipGetLastError();
 }
 #endif

@@ -28,12 +28,6 @@
 #include "surface_query.h"
 static_assert(MW_SQ_REST == MW_QUERY_REST && MW_SQ_WORLD == MW_QUERY_WORLD, "surface_query.h and the ABI name the modes alike");
 
-#ifndef MW_LATENCY_PLAN
-#define MW_LATENCY_PLAN 1  // single-step enqueues at 512^2 / 1024^2 (mw_frame_plan_n): k_pass1<.., FS> + k_pass2_frame (launch_pass*_n)
-#endif
-#ifndef MW_LATENCY_PF
-#define MW_LATENCY_PF 2  // prefetch level of the frame plan's pass 2 (k_pass2_hs<.., VT = 1, PF>)
-#endif
 #ifndef MW_WAVES_P1
 #define MW_WAVES_P1 6  // min waves per SIMD the register allocator must leave room for (measured best)
 #endif
@@ -133,9 +127,8 @@ __device__ long long g_stamps[2][64][16][32];  // [kernel][block slot][wave][sta
 #define MW_STAMP_HWID_END(K) do { } while (0)
 #endif
 
-// LDS layout of both pass kernels: [twiddle tables, if small] [NBUF sets of exchange buffers].  With
-// NBUF == 2 the sets are used ping-pong (every store goes to the set the previous load did NOT read), so
-// one barrier per exchange suffices; with NBUF == 1 a second (WAR) barrier follows every load.
+// LDS layout of both pass kernels: [twiddle tables, if small] [one set of exchange buffers]; a second (WAR) barrier follows
+// every load.
 // VT = virtual threads per lane (see k_pass2_hs): the phase functions are written for 4*T virtual threads (4 spectrum
 // columns x T); a workgroup of 4*T/VT lanes runs virtual threads tid, tid + NT, ... of every phase back to back.
 // issue priority (s_setprio, 0..3) of the row groups by field once the loads are out: the slope groups -- the longest fetch, then the
@@ -161,13 +154,7 @@ __device__ __forceinline__ void mw_setprio(int p) {  // the builtin wants a lite
         default: __builtin_amdgcn_s_setprio(3); break;
     }
 }
-#ifndef MW_P1_FRAME_WAVE_SYNC
-#define MW_P1_FRAME_WAVE_SYNC 1  // single-step plan: a column's exchanges stay inside its own wave up to the last one
-#endif
-#ifndef MW_P1_FRAME_PRIO
-#define MW_P1_FRAME_PRIO 0       // single-step plan: issue priority by field (1: f = 0 highest; 2: f = 1 highest; 3: f = 2 highest)
-#endif
-// FS = the single-step (frame-at-a-time) instantiation: one FIELD per workgroup (A.field_split says which grid decodes it)
+// FS = the single-step (frame-at-a-time) instantiation: one FIELD per workgroup, a 1-D grid over A.jobs
 template <int N, int P, int VT, bool FS = false>
 __global__ __launch_bounds__((P1Geom<N, P>::NTHREADS / VT))
 __attribute__((amdgpu_waves_per_eu(VT > 1 ? P1Geom<N, P>::NTHREADS / VT / 256 : (P == 8 ? MW_WAVES_P1 : 4)))) void k_pass1(P1Args A, StepTimes times) {
@@ -178,29 +165,24 @@ __attribute__((amdgpu_waves_per_eu(VT > 1 ? P1Geom<N, P>::NTHREADS / VT / 256 : 
     static_assert(G::NTHREADS % VT == 0 && (VT == 1 || NT % T == 0), "a lane's virtual threads must belong to whole columns");
     const int tid = threadIdx.x;
     int jb = blockIdx.x, step = blockIdx.y;
-    // Frame-at-a-time plan (A.field_split, single-step enqueues): grid (column jobs, 3) -- one FIELD per workgroup instead of
-    // the three one after the other, each workgroup re-forming the (cheap) animated spectrum.  A step is 257 workgroups at
+    // Frame-at-a-time plan (A.field_split, single-step enqueues): one FIELD per workgroup instead of the three one after the
+    // other, each workgroup re-forming the (cheap) animated spectrum.  A step is 257 workgroups at
     // 1024^2 where the device has 1024 slots, so its latency is that of ONE workgroup: a third of the work each cuts it
     // accordingly.  The arithmetic of a field does not depend on which workgroup runs it: same bits as the batched plan.
     int f_lo = 0, f_hi = 3;
     if constexpr (FS) {
-        if (A.field_split == 2) {  // 1-D grid over the list of active (column job, field) pairs (p1_frame_jobs)
-            const int job = A.jobs[blockIdx.x];
-            if (job < 0) return;
-            jb = job & 0xffff;
-            f_lo = job >> 16;
-        } else {
-            f_lo = (int)blockIdx.y;
-        }
+        const int job = A.jobs[blockIdx.x];  // 1-D grid over the list of active (column job, field) pairs (p1_frame_jobs)
+        if (job < 0) return;
+        jb = job & 0xffff;
+        f_lo = job >> 16;
         f_hi = f_lo + 1;
         step = 0;
         if (!p1_field_active(N, jb, f_lo, G::CW)) return;  // block-uniform, before any barrier
-        if (MW_P1_FRAME_PRIO) mw_setprio(3 - (f_lo + 4 - MW_P1_FRAME_PRIO) % 3);
     } else if (A.tgroup > 0 && !p1_block_map((int)blockIdx.x, G::GRID_X, A.nsteps, A.tgroup, &jb, &step)) return;
     // Up to its last exchange a column's buffer is written and read by the column's own T threads: where those are one wave (the
     // single-step plan at T == 64) the exchanges need that wave's LDS operations in order and no workgroup barrier -- the four columns
     // drift apart; the last exchange feeds the column-interleaved final pass and keeps the barrier.
-    constexpr bool WS = FS && MW_P1_FRAME_WAVE_SYNC && VT == 1 && T == 64;
+    constexpr bool WS = FS && VT == 1 && T == 64;
     auto col_sync = [&](bool whole_group) {
         if (WS && !whole_group) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
         else __syncthreads();
@@ -208,14 +190,13 @@ __attribute__((amdgpu_waves_per_eu(VT > 1 ? P1Geom<N, P>::NTHREADS / VT / 256 : 
     (void)col_sync;
     const float t = times.t[step];
     TwStage<N, P, NT> tws;
-    if (TwGeom<N, P>::LDS_ALL) tws.load(lds, A.TW, tid);  // in LDS behind the spectrum requests, visible after the first barrier
+    if (TwGeom<N, P>::LDS_ALL) tws.load(A.TW, tid);  // in LDS behind the spectrum requests, visible after the first barrier
     const Twiddles tw = TwGeom<N, P>::view(A.TW, lds);
     cf* set0 = lds + G::TW_LDS;
-    int cur = 0;  // set the next store goes to
     P1State<P> st[VT];
     cf x[VT][P];
 #define MW_VT(h) for (int h = 0; h < VT; h++)
-#define MW_BUF(h) (set0 + cur * G::SETSTRIDE + ((tid + (h) * NT) / T) * G::BUFSTRIDE)
+#define MW_BUF(h) (set0 + ((tid + (h) * NT) / T) * G::BUFSTRIDE)
 #define MW_U(h) ((tid + (h) * NT) % T)
     MW_STAMP(0, 0);
     MW_STAMP_RT(0, 30);
@@ -230,7 +211,7 @@ __attribute__((amdgpu_waves_per_eu(VT > 1 ? P1Geom<N, P>::NTHREADS / VT / 256 : 
         if (!p1_field_active(N, jb, f, G::CW)) continue;  // block-uniform: height needs columns j <= N/2 only
 #pragma unroll
         MW_VT(h) p1_build<N, P>(A, jb, tid + h * NT, f, st[h], x[h]);
-        if (G::NBUF == 1 && f) __syncthreads();
+        if (f) __syncthreads();
         MW_STAMP(0, 2 + 8 * f);
 #pragma unroll
         MW_VT(h) stage0_store<N, P, +1>(x[h], MW_U(h), MW_BUF(h));
@@ -241,7 +222,7 @@ __attribute__((amdgpu_waves_per_eu(VT > 1 ? P1Geom<N, P>::NTHREADS / VT / 256 : 
 #pragma unroll
             MW_VT(h) load_slots<N, P>(x[h], MW_U(h), MW_BUF(h), s - 1);
             if (s == 1) MW_STAMP(0, 4 + 8 * f);
-            if (G::NBUF == 1) col_sync(false); else cur ^= 1;
+            col_sync(false);
             if (s == 1) MW_STAMP(0, 5 + 8 * f);
 #pragma unroll
             MW_VT(h) stage_store<N, P, +1>(x[h], MW_U(h), MW_BUF(h), tw, s);
@@ -250,8 +231,7 @@ __attribute__((amdgpu_waves_per_eu(VT > 1 ? P1Geom<N, P>::NTHREADS / VT / 256 : 
         }
         MW_STAMP(0, 7 + 8 * f);
 #pragma unroll
-        MW_VT(h) p1_finish<N, P>(A, tw, jb, step, tid + h * NT, f, x[h], set0 + cur * G::SETSTRIDE);
-        if (G::NBUF == 2) cur ^= 1;
+        MW_VT(h) p1_finish<N, P>(A, tw, jb, step, tid + h * NT, f, x[h], set0);
         MW_STAMP(0, 8 + 8 * f);
     }
     MW_STAMP(0, 26);
@@ -286,59 +266,42 @@ __global__ __launch_bounds__((P2Geom<N, P, R2>::NTHREADS)) __attribute__((amdgpu
     const int ab = p2_row_block<N / R2>((int)blockIdx.x);
     const int g = tid / T;
     TwStage<N, P, G::NTHREADS> tws;
-    if (TwGeom<N, P>::LDS_ALL) tws.load(lds, A.TW, tid);
+    if (TwGeom<N, P>::LDS_ALL) tws.load(A.TW, tid);
     const Twiddles tw = TwGeom<N, P>::view(A.TW, lds);
     cf* set0 = lds + G::TW_LDS;
     float* noise_lds = reinterpret_cast<float*>(lds + G::NOISE_OFF);
-    int cur = 0;
     P2State<P> st;
     cf x[P];
-#ifdef MW_P2_PREFETCH
-    cf xn[P];
-    if (p2_active<N, P, R2>(ab, tid, p2_field(0))) p2_fetch<N, P, R2>(A, ab, step, tid, p2_field(0), xn);
-#endif
     MW_STAMP(1, 0);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         const int f = p2_field(k);
         const bool active = p2_active<N, P, R2>(ab, tid, f);
-        if (G::NBUF == 1 && k) __syncthreads();
+        if (k) __syncthreads();
         MW_STAMP(1, 1 + 8 * k);
-#ifdef MW_P2_PREFETCH
-        if (active) {
-#pragma unroll
-            for (int q = 0; q < P; q++) x[q] = xn[q];
-            p2_stage0<N, P, R2>(tid, x, set0 + cur * G::SETSTRIDE);
-        }
-        if (k < 2 && p2_active<N, P, R2>(ab, tid, p2_field(k + 1)))  // next field's rows fly during this field's passes
-            p2_fetch<N, P, R2>(A, ab, step, tid, p2_field(k + 1), xn);
-#else
-        if (active) p2_load<N, P, R2>(A, ab, step, tid, f, x, set0 + cur * G::SETSTRIDE);
-#endif
+        if (active) p2_load<N, P, R2>(A, ab, step, tid, f, x, set0);
         if (k == 0 && TwGeom<N, P>::LDS_ALL) tws.store(lds, tid);  // published by the barrier below
         MW_STAMP(1, 2 + 8 * k);
         __syncthreads();
 #pragma unroll
         for (int s = 1; s < FftGeom<N, P>::S; s++) {
-            constexpr bool LIR = LastStays<N, P>::value && G::NBUF == 1;
-            const bool in_regs = LIR && s == FftGeom<N, P>::S - 1;  // the last pass writes nothing to LDS: no barrier on either side of it
-            if (active) p2_mid_load<N, P, R2>(tid, s, x, set0 + cur * G::SETSTRIDE);
-            if (!in_regs) { if (G::NBUF == 1) __syncthreads(); else cur ^= 1; }
-            if (active) p2_mid_store<N, P, R2>(tw, tid, s, x, set0 + cur * G::SETSTRIDE);
+            const bool in_regs = LastStays<N, P>::value && s == FftGeom<N, P>::S - 1;  // the last pass writes nothing to LDS: no barrier on either side of it
+            if (active) p2_mid_load<N, P, R2>(tid, s, x, set0);
+            if (!in_regs) __syncthreads();
+            if (active) p2_mid_store<N, P, R2>(tw, tid, s, x, set0);
             if (!in_regs) __syncthreads();
         }
         MW_STAMP(1, 6 + 8 * k);
-        if (active) p2_finish<N, P, R2>(A, tw, ab, step, tid, f, x, st, set0 + cur * G::SETSTRIDE, noise_lds);
-        if (G::NBUF == 2) cur ^= 1;
+        if (active) p2_finish<N, P, R2>(A, tw, ab, step, tid, f, x, st, set0, noise_lds);
         MW_STAMP(1, 7 + 8 * k);
     }
-    if (G::NBUF == 1) __syncthreads();
-    MW_STAMP(1, 25);
-    if (p2_active<N, P, R2>(ab, tid, 1)) p2_publish_hds<N, P, R2>(tid, st, set0 + cur * G::SETSTRIDE);
     __syncthreads();
-    if constexpr (DUMP) p2_dump_hds<N, P, R2>(A, ab, step, tid, G::NTHREADS, set0 + cur * G::SETSTRIDE);  // test hook
+    MW_STAMP(1, 25);
+    if (p2_active<N, P, R2>(ab, tid, 1)) p2_publish_hds<N, P, R2>(tid, st, set0);
+    __syncthreads();
+    if constexpr (DUMP) p2_dump_hds<N, P, R2>(A, ab, step, tid, G::NTHREADS, set0);  // test hook
     MW_STAMP(1, 26);
-    if (g < R2) p2_epilogue<N, P, R2>(A, ab, step, tid, st, set0 + cur * G::SETSTRIDE, noise_lds);
+    if (g < R2) p2_epilogue<N, P, R2>(A, ab, step, tid, st, set0, noise_lds);
     MW_STAMP(1, 27);
 }
 
@@ -351,26 +314,13 @@ __global__ __launch_bounds__((P2Geom<N, P, R2>::NTHREADS)) __attribute__((amdgpu
 // waves instead of 16: each lane owns 2 x 16 points, the register budget doubles to 256 (the 16-wave form spilled 29
 // dwords = 14 B of scratch traffic per grid point at its 128), the two independent rows of a lane give the scheduler two
 // instruction streams to interleave, and every barrier joins half as many waves.
-//
-// mw_fresh (opt-in, -DMW_FRESH): every phase derives its lane indices from an opaque copy of the thread index, so that the
-// compiler cannot hoist the index arithmetic of all phases to the top of the kernel; it removes the spills of the 16-wave
-// form but the asm statements are scheduling barriers and the kernel gets 10-15 % slower: off.
-__device__ __forceinline__ int mw_fresh(int v) {
-#ifdef MW_FRESH
-    asm volatile("" : "+v"(v));
-#endif
-    return v;
-}
-#ifndef MW_HS_JAC_FROM_LDS
-#define MW_HS_JAC_FROM_LDS 99  // points per thread from which the Jacobian re-reads its own row from LDS (d[] dead): off
-#endif
 // minimum waves per SIMD the register allocator must leave room for: as many workgroups per CU as the LDS admits (at most 2)
 constexpr int hs_min_waves(int nthreads, int lds_bytes) {
     const int wgs = (2 * lds_bytes <= 160 * 1024) ? 2 : 1;
     const int w = nthreads / 64 * wgs / 4;
     return w < 1 ? 1 : (w > 8 ? 8 : w);
 }
-template <int N, int P, int R2, int VT, bool DUMP = false, int PF = 0>
+template <int N, int P, int R2, int VT, bool DUMP = false>
 __global__ __launch_bounds__((P2Geom<N, P, R2, true>::NTHREADS / VT))
 __attribute__((amdgpu_waves_per_eu(hs_min_waves(P2Geom<N, P, R2, true>::NTHREADS / VT, P2Geom<N, P, R2, true>::LDS_BYTES)))) void k_pass2_hs(P2Args A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -380,118 +330,50 @@ __attribute__((amdgpu_waves_per_eu(hs_min_waves(P2Geom<N, P, R2, true>::NTHREADS
     static_assert(G::NTHREADS % VT == 0 && NT % T == 0, "a lane's virtual threads must belong to distinct whole row groups");
     static_assert(T % 64 == 0, "row groups must be whole waves: the row group of a lane is treated as wave-uniform (512^2 at 16 points fails parity)");
     const int tid0 = threadIdx.x, step = blockIdx.y;
-#ifdef MW_HS_NO_XCD_MAP
-    const int ab = blockIdx.x;
-#else
     const int ab = p2_row_block<N / R2>((int)blockIdx.x);  // neighbouring row blocks (halo rows, shared 128-B lines) on one XCD
-#endif
     const int g0 = wave_uniform<true>(tid0 / T);  // row group of virtual thread 0; virtual thread h is in group g0 + h * NT / T
     TwStage<N, P, NT> tws;
-    if (TwGeom<N, P>::LDS_ALL) tws.load(lds, A.TW, tid0);
+    if (TwGeom<N, P>::LDS_ALL) tws.load(A.TW, tid0);
     const Twiddles tw = TwGeom<N, P>::view(A.TW, lds);
     cf* set0 = lds + G::TW_LDS;
     P2StateHS<P> st[VT];
     cf x[VT][P];
-#ifndef MW_HS_HALO_EARLY
-#define MW_HS_HALO_EARLY 1
-#endif
-#ifndef MW_HS_HALO_EARLY_2048
-#define MW_HS_HALO_EARLY_2048 1  // fits (251 VGPRs) since the radix-8 final pass forms its twiddles by powers (MW_TF_POWERS_MIN_RL)
-#endif
-#ifndef MW_HS_HALO_EARLY_4096
-#define MW_HS_HALO_EARLY_4096 0  // 4096^2 prefetches the displacement rows during the height field instead (PF = 1): the two together spill
-#endif
-    // PF = 2 (the frame-at-a-time plan, one wave per row): EVERY exchange-buffer load of the workgroup -- height, displacement, the
-    // stored half of the slope field, the halo row -- is requested before the first transform.  A single-step launch is one
-    // workgroup per CU: nothing else hides a load.  Measured (profiles/r04_ab_notes.md): pass 2 of a lone step 19.5 -> 18.4 us.
-    constexpr bool HALO_EARLY =
-        ((N == 2048 ? (MW_HS_HALO_EARLY_2048 != 0) : (N >= 4096 ? (MW_HS_HALO_EARLY_4096 != 0) : (MW_HS_HALO_EARLY != 0))) && VT >= 2) || PF == 2;
+    // The halo row's lines are the next row block's own lines: fetched while that block (same XCD, same phase) loads
+    // them too, they are L2 hits; fetched two phases later they have left the L2 and cost a second 128-B fill per
+    // 32-B piece (measured +6 B per grid point).  Needs 2P spare VGPRs across the displacement transform: VT >= 2.
+    // Not at 4096^2, where it measured slower (profiles/r03_ab_notes.md).
+    constexpr bool HALO_EARLY = N <= 2048 && VT >= 2;
     cf xh[HALO_EARLY ? P : 1];  // halo row data parked in registers across the displacement transform
     const int tid = tid0;  // MW_STAMP
     MW_STAMP(1, 0);
 #define MW_VT(h) for (int h = 0; h < VT; h++)
-#define MW_VTID(h) (mw_fresh(tid0) + (h) * NT)
-    // PF = 1 (software prefetch; the 4096^2 plan of rounds 2-3, an A/B option since round 4: MW_PF_4096): the displacement field's exchange-buffer rows are
-    // requested while the height field -- whose phase holds nothing but x -- is transformed, into a second register set.
-    // Three things make the loads really asynchronous: the height field's own loads are issued first (scheduling fence;
-    // vmcnt is in-order), the Nyquist-column term is added at use (p2_fetch's nyq), and no pass of the transform reads
-    // global memory (TwGeom::PW_CF).  Measured: pass 2 -1.5 % at 4096^2 (round 2; with KeepT1 the plan without it is 1 % ahead), +1 % at 1024^2 and 2048^2.  Prefetching the
-    // slope rows during the displacement transform as well (all of them: 17 spilled dwords; one virtual thread's: 243
-    // VGPRs) made the kernel 4-11 % slower: removed.
-    static_assert(PF == 0 || PF == 1 || PF == 2, "prefetch level");
-    static_assert(PF != 2 || P2SlopeParts<N, P>::value, "PF = 2 parks the stored half of the slope field");
+#define MW_VTID(h) (tid0 + (h) * NT)
     constexpr bool SPARTS = P2SlopeParts<N, P>::value;
-    // EARLY_SLOPES (experiment, off; profiles/r03_ab_notes.md): the slope field's stored half requested BEFORE the vertex stores
-    // -- gfx950 counts stores in vmcnt, in order with loads -- and parked in x while the Jacobians are formed.  Measured: 4096^2
-    // pass 2 7 % SLOWER (6173 -> 6629 us per 32 steps, 5 spilled dwords), 1024^2 40 % slower (256 VGPRs: one wave per SIMD):
-    // the drain of the stores is not what the slope loads wait for.
-#ifndef MW_EARLY_SLOPES_MIN_N
-#define MW_EARLY_SLOPES_MIN_N 8192
-#endif
-    constexpr bool EARLY_SLOPES = SPARTS && N >= MW_EARLY_SLOPES_MIN_N;
-    cf xn[PF ? VT : 1][PF ? P : 1], xn_nyq[PF ? VT : 1], xh_nyq = mk(0.f, 0.f);
-    cf xs[PF == 2 ? VT : 1][PF == 2 ? P : 1];  // PF = 2: the stored half of the slope field, parked from the start
     constexpr bool KEEP = KeepT1<N, P>::value && P2SlopeParts<N, P>::value;
     cf t1m[KEEP ? VT : 1][KEEP ? P / 2 : 1];   // raw mirrored height-row values, from the height fetch to the slope assembly (KeepT1)
-    (void)xn; (void)xn_nyq; (void)xs; (void)t1m;
+    (void)t1m;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         const int f = p2_hs_field(k);
-        if (k != 0 || MW_TW_STAGE != 2) __syncthreads();  // the previous phase's LDS reads are done (k = 0: nothing to wait for -- the twiddle tables
-                                                          // go to LDS behind the first requests below and are published by the barrier after stage 0)
+        if (k != 0) __syncthreads();  // the previous phase's LDS reads are done (k = 0: nothing to wait for -- the twiddle tables
+                                      // go to LDS behind the first requests below and are published by the barrier after stage 0)
         MW_STAMP(1, 1 + 8 * k);
-        if (PF >= 1 && k == 1) {  // compile-time: k is unrolled
-            if constexpr (PF != 0) {
+        if (f == 2 && SPARTS) {  // the slope half of every virtual thread in flight, then height rows + stage 0 one at a time
 #pragma unroll
-                MW_VT(h) {
-#pragma unroll
-                    for (int q = 0; q < P; q++) x[h][q] = xn[h][q];
-                    int r1, u1;
-                    p2_load_map<N, P, R2>(MW_VTID(h), &r1, &u1);
-                    if (u1 == 0) x[h][0] = x[h][0] + xn_nyq[h];
-                }
-            }
-        } else if (f == 2 && SPARTS) {  // the slope half of every virtual thread in flight, then height rows + stage 0 one at a time
-            if constexpr (PF == 2) {
-#pragma unroll
-                MW_VT(h)
-#pragma unroll
-                for (int q = 0; q < P; q++) x[h][q] = xs[h][q];
-            } else if constexpr (!EARLY_SLOPES) {
-#pragma unroll
-                MW_VT(h) p2_fetch<N, P, R2, 1>(A, ab, step, MW_VTID(h), f, x[h]);
-            }
+            MW_VT(h) p2_fetch<N, P, R2, 1>(A, ab, step, MW_VTID(h), f, x[h]);
         } else {
 #pragma unroll
-            MW_VT(h) p2_fetch<N, P, R2>(A, ab, step, MW_VTID(h), f, x[h], nullptr, (KEEP && f == 0) ? t1m[h] : nullptr);
+            MW_VT(h) p2_fetch<N, P, R2>(A, ab, step, MW_VTID(h), f, x[h], (KEEP && f == 0) ? t1m[h] : nullptr);
         }
-        if constexpr (PF != 0) {
-            if (k == 0) {
-                mw_sched_fence();
-#pragma unroll
-                MW_VT(h) p2_fetch<N, P, R2>(A, ab, step, MW_VTID(h), p2_hs_field(1), xn[h], &xn_nyq[h]);
-                if constexpr (PF == 2) {
-#pragma unroll
-                    MW_VT(h) p2_fetch<N, P, R2, 1>(A, ab, step, MW_VTID(h), 2, xs[h]);
-                }
-            }
-        }
-        // The halo row's lines are the next row block's own lines: fetched while that block (same XCD, same phase) loads
-        // them too, they are L2 hits; fetched two phases later they have left the L2 and cost a second 128-B fill per
-        // 32-B piece (measured +6 B per grid point).  Needs 2P spare VGPRs across the displacement transform: VT >= 2.
         if constexpr (HALO_EARLY)
-            if (k == (PF >= 1 ? 0 : 1) && g0 == 0 && ab * R2 + R2 < N)
-                p2_hs_halo_fetch<N, P, R2>(A, ab, step, mw_fresh(tid0) % T, xh, PF >= 1 ? &xh_nyq : nullptr);
+            if (k == 1 && g0 == 0 && ab * R2 + R2 < N) p2_hs_halo_fetch<N, P, R2>(A, ab, step, tid0 % T, xh);
         if (k == 0 && TwGeom<N, P>::LDS_ALL) tws.store(lds, tid0);
         if (f == 2 && SPARTS) {
 #pragma unroll
             MW_VT(h) {
-                p2_fetch<N, P, R2, 2>(A, ab, step, MW_VTID(h), f, x[h], nullptr, KEEP ? t1m[h] : nullptr);
+                p2_fetch<N, P, R2, 2>(A, ab, step, MW_VTID(h), f, x[h], KEEP ? t1m[h] : nullptr);
                 p2_stage0<N, P, R2>(MW_VTID(h), x[h], set0);
-#ifndef MW_SLOPE_STAGE_FENCE
-#define MW_SLOPE_STAGE_FENCE 1
-#endif
-                if (MW_SLOPE_STAGE_FENCE) mw_sched_fence();
+                mw_sched_fence();
             }
         } else {
 #pragma unroll
@@ -521,11 +403,6 @@ __attribute__((amdgpu_waves_per_eu(hs_min_waves(P2Geom<N, P, R2, true>::NTHREADS
         MW_STAMP(1, 7 + 8 * k);
         if (f != 1) continue;
         // ---- displacement done: vertices, halo row, Jacobian ----
-        if constexpr (EARLY_SLOPES) {
-#pragma unroll
-            MW_VT(h) p2_fetch<N, P, R2, 1>(A, ab, step, MW_VTID(h), 2, x[h]);
-            mw_sched_fence();
-        }
 #pragma unroll
         MW_VT(h) p2_vertices<N, P, R2>(A, ab, step, MW_VTID(h), st[h]);
         MW_STAMP(1, 24);
@@ -541,23 +418,17 @@ __attribute__((amdgpu_waves_per_eu(hs_min_waves(P2Geom<N, P, R2, true>::NTHREADS
 #pragma unroll
         MW_VT(h) {
             const int g = g0 + h * (NT / T);
-            if (g != R2 - 1) {
-                if (P >= MW_HS_JAC_FROM_LDS)
-                    p2_hs_jacobian_lds<N, P, R2>(ab, MW_VTID(h), st[h], set0 + g * G::BUFSTRIDE, set0 + (g + 1) * G::BUFSTRIDE);
-                else
-                    p2_hs_jacobian<N, P, R2>(ab, MW_VTID(h), st[h], set0 + g * G::BUFSTRIDE, set0 + (g + 1) * G::BUFSTRIDE);
-            }
+            if (g != R2 - 1) p2_hs_jacobian<N, P, R2>(ab, MW_VTID(h), st[h], set0 + g * G::BUFSTRIDE, set0 + (g + 1) * G::BUFSTRIDE);
         }
         __syncthreads();  // group 0 no longer reads its own row
         MW_STAMP(1, 25);
         if (has_halo) {  // group 0 = virtual thread 0 of the lanes below T
-            const int u = mw_fresh(tid0) % T;
+            const int u = tid0 % T;
             cf xq[P];  // the halo row in registers of its own: the allocator no longer ties it to x[0] (248 -> 219 VGPRs at 1024^2)
             if (g0 == 0) {
                 if constexpr (HALO_EARLY) {
 #pragma unroll
                     for (int q = 0; q < P; q++) xq[q] = xh[q];
-                    if (PF >= 1 && u == 0) xq[0] = xq[0] + xh_nyq;
                 } else {
                     p2_hs_halo_fetch<N, P, R2>(A, ab, step, u, xq);
                 }
@@ -592,9 +463,6 @@ __attribute__((amdgpu_waves_per_eu(hs_min_waves(P2Geom<N, P, R2, true>::NTHREADS
 // Pass 2 of a single-step enqueue (the frame-at-a-time plan, P2FrameGeom in fftmesh_kernels.h): 3 R2 + 1 row groups transform the
 // three fields of the block's rows and the halo row at the same time; the latency of the workgroup -- which IS the latency of the
 // step, 256 workgroups on 256 CUs -- is one transform instead of four.
-#ifndef MW_FRAME_WAVE_SYNC
-#define MW_FRAME_WAVE_SYNC 1  // the middle passes of a row stay inside its own wave: no workgroup barrier between them
-#endif
 template <int N, int P, int R2>
 __global__ __launch_bounds__((P2FrameGeom<N, P, R2>::NTHREADS)) void k_pass2_frame(P2Args A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -616,7 +484,7 @@ __global__ __launch_bounds__((P2FrameGeom<N, P, R2>::NTHREADS)) void k_pass2_fra
     MW_STAMP(1, 0);
     MW_STAMP_RT(1, 30);
     TwStage<N, P, G::NTHREADS> tws;
-    if (TwGeom<N, P>::LDS_ALL) tws.load(lds, A.TW, tid);  // requested first (vmcnt is in order), written to LDS behind the row requests
+    if (TwGeom<N, P>::LDS_ALL) tws.load(A.TW, tid);  // requested first (vmcnt is in order), written to LDS behind the row requests
     if (row) p2_fetch<N, P, R2>(A, ab, step, tl, fg, x);
     else if (halo) p2_hs_halo_fetch<N, P, R2>(A, ab, step, tl, x);
     if (TwGeom<N, P>::LDS_ALL) tws.store(lds, tid);
@@ -629,7 +497,7 @@ __global__ __launch_bounds__((P2FrameGeom<N, P, R2>::NTHREADS)) void k_pass2_fra
     // wave's own LDS operations in order, nothing else -- the row groups drift apart, and the first to finish starts its stores while
     // the others still transform.
     static_assert((T == 64 || T == 32) && G::FT % 64 == 0, "a wave holds whole row groups of one field");
-    constexpr bool WSYNC = MW_FRAME_WAVE_SYNC && XLay<N, P>::EXACT;  // (the padded layouts' middle passes run row-interleaved: barriers)
+    constexpr bool WSYNC = XLay<N, P>::EXACT;  // the middle passes of a row stay inside its own wave (the padded layouts' run row-interleaved: barriers)
     auto row_sync = [&]() {
         if constexpr (WSYNC) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
         else __syncthreads();
@@ -677,7 +545,7 @@ struct mw_ocean {
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
     int p1_tgroup = 8;  // time-steps of one pass-1 column job grouped on one XCD (p1_block_map): -25 % pass-1 time;
-                        // env MW_P1_TGROUP overrides (0 = plain 2-D grid)
+                        // switch MW_P1_TGROUP overrides (0 = plain 2-D grid)
     float timer = 0.f;
     // FFTMesh state
     cf *h0 = nullptr, *h0c = nullptr;
@@ -756,7 +624,7 @@ static mw_status upload_twiddles(mw_ocean* o) {
     HIP_TRY(hipMemcpy(o->TW, tab.data(), sizeof(cf) * tab.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(o->TW2, tab2.data(), sizeof(cf) * tab2.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(o->Wpre, Wpre.data(), sizeof(cf) * 2 * N, hipMemcpyHostToDevice));
-    if (mw_frame_plan_n(N) && MW_LATENCY_PLAN) {
+    if (mw_frame_plan_n(N)) {
         const std::vector<int> jobs = p1_frame_jobs(N, N >= MW_CW2_MIN_N ? 2 : 4);
         if ((st = dmalloc(&o->p1_jobs, jobs.size())) != MW_OK) return st;
         HIP_TRY(hipMemcpy(o->p1_jobs, jobs.data(), sizeof(int) * jobs.size(), hipMemcpyHostToDevice));
@@ -775,15 +643,6 @@ static OceanConsts consts_of(const mw_ocean* o) {
     return c;
 }
 
-// the frame-at-a-time plan (single-step enqueues at 1024^2): compiled in by MW_LATENCY_PLAN, switched at run time by the
-// switch of the same name (mw_switches.h; 0 = the batched plan for every enqueue; A/B without a rebuild)
-static bool latency_plan_on() { return MW_LATENCY_PLAN && sw(SW_LATENCY_PLAN) != 0; }
-
-// MW_FRAME_KERNEL=0: pass 2 of a single step by the sequential-halo kernel with one wave per row (round 3's frame plan) instead of
-// k_pass2_frame; MW_P1_FRAME_XCD=0: its pass 1 on the plain (column jobs, 3) grid.  Run-time A/B switches, same bits either way.
-static bool frame_kernel_on() { return sw(SW_FRAME_KERNEL) != 0; }
-static bool p1_frame_xcd_on() { return sw(SW_P1_FRAME_XCD) != 0; }
-
 // ---- kernel dispatch over N ----------------------------------------------------------------------
 template <int N>
 static hipError_t launch_pass1_n(const P1Args& A, const StepTimes& tm, int nsteps, hipStream_t st) {
@@ -794,13 +653,12 @@ static hipError_t launch_pass1_n(const P1Args& A, const StepTimes& tm, int nstep
         if (e != hipSuccess) return e;
     }
     constexpr int NT = P1Geom<N, P>::NTHREADS / VT, LB = P1Geom<N, P>::LDS_BYTES, GX = P1Geom<N, P>::GRID_X;
-    if constexpr (mw_frame_plan_n(N) && MW_LATENCY_PLAN) {
+    if constexpr (mw_frame_plan_n(N)) {
         if (A.field_split) {
             static AttrOnce attrf;
             hipError_t e = attrf.set(reinterpret_cast<const void*>(&k_pass1<N, P, VT, true>), LB);
             if (e != hipSuccess) return e;
-            if (A.field_split == 2) k_pass1<N, P, VT, true><<<dim3(A.njobs), dim3(NT), LB, st>>>(A, tm);
-            else k_pass1<N, P, VT, true><<<dim3(GX, 3), dim3(NT), LB, st>>>(A, tm);
+            k_pass1<N, P, VT, true><<<dim3(A.njobs), dim3(NT), LB, st>>>(A, tm);
             return hipGetLastError();
         }
     }
@@ -814,45 +672,34 @@ template <int N, bool DUMP>
 static hipError_t launch_pass2_n(const P2Args& A, int nsteps, hipStream_t st) {
     constexpr int P = Plan<N>::P2, R2 = Plan<N>::R2;
     constexpr bool HS = Plan<N>::HS;
-    constexpr int VT = HS ? Plan<N>::VT : 1, PF = HS ? Plan<N>::PF : 0;
+    constexpr int VT = HS ? Plan<N>::VT : 1;
     constexpr int NT = P2Geom<N, P, R2, HS>::NTHREADS / VT, LB = P2Geom<N, P, R2, HS>::LDS_BYTES;
     static AttrOnce attr;
     {
         const void* fn;
-        if constexpr (HS) fn = reinterpret_cast<const void*>(&k_pass2_hs<N, P, R2, VT, DUMP, PF>);
+        if constexpr (HS) fn = reinterpret_cast<const void*>(&k_pass2_hs<N, P, R2, VT, DUMP>);
         else fn = reinterpret_cast<const void*>(&k_pass2<N, P, R2, DUMP>);
         hipError_t e = attr.set(fn, LB);
         if (e != hipSuccess) return e;
     }
-    // Frame-at-a-time plan (FFTMesh.Update, S/FFTMesh.cs:60-73: ONE step per call; 512^2 and 1024^2): a step cannot fill the device,
-    // its latency is that of one workgroup.  k_pass2_frame transforms the three fields of a row block side by side; MW_FRAME_KERNEL=0
-    // selects round 3's form at 1024^2 -- the sequential-halo kernel with one virtual thread per lane (one wave per row, every load up
-    // front) -- and the batched kernel at 512^2.  The arithmetic of a row does not depend on which kernel runs it: same bits.
-    if constexpr (mw_frame_plan_n(N) && !DUMP && MW_LATENCY_PLAN) {
-        if (nsteps == 1 && latency_plan_on()) {
-            constexpr int RF = mw_frame_r2(N);
-            if constexpr (P2FrameGeom<N, P, RF>::OK) {
-                if (frame_kernel_on()) {
-                    static AttrOnce attrf;
-                    constexpr int LBF = P2FrameGeom<N, P, RF>::LDS_BYTES;
-                    hipError_t e = attrf.set(reinterpret_cast<const void*>(&k_pass2_frame<N, P, RF>), LBF);
-                    if (e != hipSuccess) return e;
-                    k_pass2_frame<N, P, RF><<<dim3(N / RF, 1), dim3(P2FrameGeom<N, P, RF>::NTHREADS), LBF, st>>>(A);
-                    return hipGetLastError();
-                }
-            }
-            if constexpr (HS && VT == 2) {
-                static AttrOnce attr1;
-                constexpr int PFL = MW_LATENCY_PF;  // 2: every load of the workgroup requested up front
-                hipError_t e = attr1.set(reinterpret_cast<const void*>(&k_pass2_hs<N, P, R2, 1, false, PFL>), LB);
+    // Frame-at-a-time plan (FFTMesh.Update, S/FFTMesh.cs:60-73: ONE step per call; 256^2 to 1024^2): a step cannot fill the device,
+    // its latency is that of one workgroup.  k_pass2_frame transforms the three fields of a row block side by side.  The arithmetic
+    // of a row does not depend on which kernel runs it: same bits as the batched plan.
+    if constexpr (mw_frame_plan_n(N) && !DUMP) {
+        constexpr int RF = mw_frame_r2(N);
+        if constexpr (P2FrameGeom<N, P, RF>::OK) {
+            if (nsteps == 1) {
+                static AttrOnce attrf;
+                constexpr int LBF = P2FrameGeom<N, P, RF>::LDS_BYTES;
+                hipError_t e = attrf.set(reinterpret_cast<const void*>(&k_pass2_frame<N, P, RF>), LBF);
                 if (e != hipSuccess) return e;
-                k_pass2_hs<N, P, R2, 1, false, PFL><<<dim3(N / R2, 1), dim3(P2Geom<N, P, R2, true>::NTHREADS), LB, st>>>(A);
+                k_pass2_frame<N, P, RF><<<dim3(N / RF, 1), dim3(P2FrameGeom<N, P, RF>::NTHREADS), LBF, st>>>(A);
                 return hipGetLastError();
             }
         }
     }
     if constexpr (HS)
-        k_pass2_hs<N, P, R2, VT, DUMP, PF><<<dim3(N / R2, nsteps), dim3(NT), LB, st>>>(A);
+        k_pass2_hs<N, P, R2, VT, DUMP><<<dim3(N / R2, nsteps), dim3(NT), LB, st>>>(A);
     else
         k_pass2<N, P, R2, DUMP><<<dim3(N / R2, nsteps), dim3(NT), LB, st>>>(A);
     return hipGetLastError();
@@ -884,8 +731,8 @@ static mw_status launch_pass1(mw_ocean* o, const StepTimes& tm, int nsteps, hipS
     A.c = consts_of(o);
     A.nsteps = nsteps;
     A.tgroup = p1_time_group(o, nsteps);
-    A.field_split = (latency_plan_on() && nsteps == 1 && mw_frame_plan_n(o->N)) ? ((p1_frame_xcd_on() && o->p1_jobs) ? 2 : 1) : 0;
-    if (A.field_split == 2) { A.jobs = o->p1_jobs; A.njobs = o->p1_njobs; }
+    A.field_split = nsteps == 1 && mw_frame_plan_n(o->N);
+    if (A.field_split) { A.jobs = o->p1_jobs; A.njobs = o->p1_njobs; }
     hipError_t e = hipSuccess;
     MW_DISPATCH_N(o->N, e = launch_pass1_n<NN>(A, tm, nsteps, st));
     if (e != hipSuccess) return fail(MW_EDEVICE, std::string("pass1 launch: ") + hipGetErrorString(e));

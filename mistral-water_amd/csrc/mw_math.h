@@ -393,11 +393,8 @@ struct TwGeom {
     // The powers pass reads ONE twiddle per thread, w_k = TS[POW_STAGE][k (P+1) + 1], k < P^POW_STAGE: those P^s values are
     // gathered into LDS behind the staged prefix (2 KiB at N = 4096), so that no pass of a transform touches global memory
     // -- a global load in the middle of a transform would make its s_waitcnt (vmcnt is in-order) wait for every
-    // exchange-buffer load prefetched before it (k_pass2_hs, PF).
-#ifndef MW_POW_LDS
-#define MW_POW_LDS 1
-#endif
-    static constexpr int PW_CF = (MW_POW_LDS && POW_STAGE != 0) ? mw_ipow(P, POW_STAGE) : 0;
+    // exchange-buffer load issued before it.
+    static constexpr int PW_CF = POW_STAGE != 0 ? mw_ipow(P, POW_STAGE) : 0;
     static constexpr int LDS_ALL = LDS_CF + PW_CF;  // cf entries a kernel stages (stage_twiddles)
     // sub-table at offset `off`: the LDS copy when it was staged, else global memory
     static MW_HD const cf* pick(const cf* glob, const cf* lds, int off) { return off < LDS_CF ? lds + off : glob + off; }
@@ -423,10 +420,7 @@ struct TwGeom {
 // behind the requests of their first input rows and in front of their first barrier, so that the tables ride under the same memory latency
 // as the data.  Up to here it was a copy loop `for (i = tid; i < LDS_CF; i += NT) lds[i] = tw[i]`, which compiles to load -> s_waitcnt
 // vmcnt(0) -> ds_write per iteration: three to five L2 round trips ONE AFTER THE OTHER at the head of every workgroup, in front of a barrier
-// in front of its first data request (k_pass2_hs<1024>: five of them, 128 lanes for 528 entries).  MW_TW_STAGE=0 keeps that loop (A/B).
-#ifndef MW_TW_STAGE
-#define MW_TW_STAGE 2  // 2: loads at the top, LDS writes behind the first data requests; 1: loads then writes at the top; 0: the copy loop
-#endif
+// in front of its first data request (k_pass2_hs<1024>: five of them, 128 lanes for 528 entries).
 #if defined(__HIPCC__)
 // WITH_PW = false: a kernel that keeps the table in every pass (stage_regs<.., ALLOW_POW = false>: the OceanRenderer passes) and whose LDS
 // layout has no room for the base twiddles of a powers pass
@@ -434,33 +428,25 @@ template <int N, int P, int NT, bool WITH_PW = true>
 struct TwStage {
     using TG = TwGeom<N, P>;
     static constexpr int PW = WITH_PW ? TG::PW_CF : 0;
-    static constexpr int IT = MW_TW_STAGE ? (TG::LDS_CF + NT - 1) / NT : 0, ITP = MW_TW_STAGE ? (PW + NT - 1) / NT : 0;
+    static constexpr int IT = (TG::LDS_CF + NT - 1) / NT, ITP = (PW + NT - 1) / NT;
     cf r[IT > 0 ? IT : 1], rp[ITP > 0 ? ITP : 1];
-    __device__ __forceinline__ void store_now(cf* dst, int tid) const {
+    // at the top of the kernel
+    __device__ __forceinline__ void load(const cf* __restrict__ src, int tid) {
+#pragma unroll
+        for (int k = 0; k < IT; k++) { const int i = tid + k * NT; r[k] = (IT * NT == TG::LDS_CF || i < TG::LDS_CF) ? src[i] : mk(0.f, 0.f); }
+#pragma unroll
+        for (int k = 0; k < ITP; k++) {  // base twiddles of the powers pass: entry 1 of every (P+1)-entry row
+            const int i = tid + k * NT;
+            rp[k] = (ITP * NT == PW || i < PW) ? src[TG::off_ts(TG::POW_STAGE) + i * (P + 1) + 1] : mk(0.f, 0.f);
+        }
+    }
+    // behind the kernel's first data requests, in front of its first barrier
+    __device__ __forceinline__ void store(cf* dst, int tid) const {
 #pragma unroll
         for (int k = 0; k < IT; k++) { const int i = tid + k * NT; if (IT * NT == TG::LDS_CF || i < TG::LDS_CF) dst[i] = r[k]; }
 #pragma unroll
         for (int k = 0; k < ITP; k++) { const int i = tid + k * NT; if (ITP * NT == PW || i < PW) dst[TG::LDS_CF + i] = rp[k]; }
     }
-    // at the top of the kernel
-    __device__ __forceinline__ void load(cf* dst, const cf* __restrict__ src, int tid) {
-        if (MW_TW_STAGE == 0) {
-            for (int i = tid; i < TG::LDS_CF; i += NT) dst[i] = src[i];
-            if (PW)  // base twiddles of the powers pass: entry 1 of every (P+1)-entry row
-                for (int i = tid; i < PW; i += NT) dst[TG::LDS_CF + i] = src[TG::off_ts(TG::POW_STAGE) + i * (P + 1) + 1];
-            return;
-        }
-#pragma unroll
-        for (int k = 0; k < IT; k++) { const int i = tid + k * NT; r[k] = (IT * NT == TG::LDS_CF || i < TG::LDS_CF) ? src[i] : mk(0.f, 0.f); }
-#pragma unroll
-        for (int k = 0; k < ITP; k++) {
-            const int i = tid + k * NT;
-            rp[k] = (ITP * NT == PW || i < PW) ? src[TG::off_ts(TG::POW_STAGE) + i * (P + 1) + 1] : mk(0.f, 0.f);
-        }
-        if (MW_TW_STAGE == 1) store_now(dst, tid);
-    }
-    // behind the kernel's first data requests, in front of its first barrier
-    __device__ __forceinline__ void store(cf* dst, int tid) const { if (MW_TW_STAGE == 2) store_now(dst, tid); }
 };
 #endif
 
@@ -520,29 +506,7 @@ MW_HD void stage_regs(cf (&x)[P], int u, const Twiddles& tw, int s) {
     const int p = 1 << (LogP<P>::v * s);
     const int k = u & (p - 1);
     const cf* __restrict__ row = tw.TS[s] + k * (P + 1);
-#ifdef MW_TW_POWERS
-    constexpr bool POWERS = true;  // experiment: every pass by powers (+1 % step time at 1024^2: 24 VALU for 6 saved reads)
-#else
     const bool POWERS = (ALLOW_POW && TwGeom<N, P>::POW_STAGE != 0 && s == TwGeom<N, P>::POW_STAGE);  // folds: s is unrolled
-#endif
-#if defined(MW_TW_SHUFFLE) && defined(__HIP_DEVICE_COMPILE__)
-    // A/B experiment (BASELINE.json's "wavefront shuffle for the twiddle rows", profiles/r02_twiddle_shuffle_ab.json): the
-    // first radix-8 pass needs e^{SGN 2 pi i r k / 64}, r k < 64: ONE 64-entry row held across the wave (lane l keeps entry l
-    // in two VGPRs) and fetched by ds_bpermute -- two 32-bit permutes per complex twiddle instead of one ds_read_b64 of the
-    // LDS table.  Both go through the LDS crossbar; the permute form issues twice as many DS instructions.
-    if (P == 8 && s == 1) {
-        const int lane = (int)__lane_id();
-        float ws, wc;
-        sincospif((float)lane * (1.0f / 32.0f), &ws, &wc);
-        ws = SGN > 0 ? ws : -ws;
-#pragma unroll
-        for (int r = 1; r < P; r++) {
-            const int src = (r * k) & 63;
-            const cf w = mk(__shfl(wc, src), __shfl(ws, src));
-            x[r] = cmul(x[r], w);
-        }
-    } else
-#endif
     if (POWERS) {  // one table read per thread, the other P-2 twiddles as its powers (product tree <= log2 P deep)
         cf w[P];
         w[1] = tw.PW ? tw.PW[k] : row[1];
@@ -621,8 +585,8 @@ template <int N, int P>
 struct LastStays { static constexpr bool value = LastInRegs<N, P>::value || LastInWave<N, P>::value; };
 // THE predicate "radix-P pass s leaves its results in registers": the phase functions (p2_mid_store / p2_last_load, p1_finish, the halo and
 // chirp-z transforms) and the kernels' barrier elision all ask this one function, so a caller cannot skip the LDS write and still read
-// the exchange afterwards.  A kernel that keeps its barriers anyway (ping-pong buffers, MW_DBUF) stays correct: the phase
-// functions alone decide where the data is.
+// the exchange afterwards.  A kernel that keeps its barriers anyway stays correct: the phase functions alone decide where the
+// data is.
 template <int N, int P>
 MW_HD constexpr bool mw_pass_in_regs(int s) { return LastStays<N, P>::value && s == FftGeom<N, P>::S - 1; }
 template <int N, int P, int SGN, bool ALLOW_POW = true>
@@ -732,11 +696,7 @@ inline std::vector<cf> build_twiddle_table_host(int N, int P, int sgn) {
 // differently shaped loops (or_p1_animate: point by point in the lone frame, eight points at a time in the batched forms) produced spectra
 // that differed in the last bit -- a batched OceanRenderer handle was no longer bit-identical to its single handles.  Same policy as cmul /
 // MW_FFT_STRICT: the rounding is fixed in the source.
-#ifndef MW_ANIMATE_EXPLICIT
-#define MW_ANIMATE_EXPLICIT 1  // 0: the plain expression of rounds 1-4 (A/B of the speed only: its bits depend on the inlining context)
-#endif
 MW_HD cf animate(float px, float py, float qx, float qy, float c, float s) {
-    if (!MW_ANIMATE_EXPLICIT) return mk(px * c - py * s + qx * c + qy * s, px * s + py * c - qx * s + qy * c);
     const float re = __builtin_fmaf(px, c, __builtin_fmaf(-py, s, __builtin_fmaf(qx, c, smul(qy, s))));
     const float im = __builtin_fmaf(px, s, __builtin_fmaf(py, c, __builtin_fmaf(-qx, s, smul(qy, c))));
     return mk(re, im);

@@ -105,9 +105,6 @@ __global__ void k_or_prep(int M, const f4* initT, f4* PQT) {
 #ifndef MW_OR_P1_LONE_CHUNK
 #define MW_OR_P1_LONE_CHUNK 4  // points whose loads the lone frame's spectrum workgroup requests together (1 / 2 / 4 / 8: 1024^2 34.4 / 34.1 / 34.0 /
 #endif                         // 34.7 us per frame, 512^2 19.9 / 19.0 / 18.9 / 18.9; the three-transform plan keeps point by point)
-#ifndef MW_OR_P2_LONE_SPLIT
-#define MW_OR_P2_LONE_SPLIT 1  // lone frame, packed plan: pass 2 with one field per workgroup
-#endif
 #ifndef MW_OR_PACKED_MAX_M
 #define MW_OR_PACKED_MAX_M 4096  // textures from this size up keep the three-transform plan
 #endif
@@ -130,7 +127,7 @@ __global__ __launch_bounds__((OrP1Geom<N, P>::NTHREADS)) void k_or_pass1_packed(
     }
     const int w = tid / T, u = tid % T;
     TwStage<N, P, G::NTHREADS, false> tws;
-    tws.load(lds, A.TW, tid);
+    tws.load(A.TW, tid);
     const Twiddles tw = TwGeom<N, P>::view(A.TW, lds);
     cf* set0 = lds + G::TW_LDS;
     cf h[P], hh[P], x[P];
@@ -172,7 +169,7 @@ __global__ __launch_bounds__((OrP1Geom<N, P>::NTHREADS)) void k_or_pass1(OrP1Arg
     }
     const int w = tid / T, u = tid % T;
     TwStage<N, P, G::NTHREADS, false> tws;
-    tws.load(lds, A.TW, tid);
+    tws.load(A.TW, tid);
     const Twiddles tw = TwGeom<N, P>::view(A.TW, lds);
     cf* set0 = lds + G::TW_LDS;
     cf h[P], x[P];
@@ -210,7 +207,7 @@ __global__ __launch_bounds__((OrP1Geom<N, P>::NTHREADS)) void k_or_pass1_steps(O
     OrP1Args A = S.a;
     const int w = tid / T, u = tid % T;
     TwStage<N, P, G::NTHREADS, false> tws;
-    tws.load(lds, A.TW, tid);
+    tws.load(A.TW, tid);
     const Twiddles tw = TwGeom<N, P>::view(A.TW, lds);
     cf* set0 = lds + G::TW_LDS;
     float om[P], ph[P];
@@ -287,7 +284,7 @@ __global__ __launch_bounds__((OrP2Geom<N, P>::NTHREADS)) void k_or_pass2(OrP2Arg
         if (A.disp_a) A.disp_a += toff;
     }
     TwStage<N, P, G::NTHREADS, false> tws;
-    tws.load(lds, A.TW, tid);
+    tws.load(A.TW, tid);
     const Twiddles tw = TwGeom<N, P>::view(A.TW, lds);
     cf* set0 = lds + G::TW_LDS;
     cf x[P];
@@ -325,7 +322,7 @@ __global__ __launch_bounds__((OrP2Geom<N, P>::NTHREADS)) void k_or_pass2_packed(
         A.E += 2 * toff; A.height += toff; A.disp += toff; A.disp_g += toff;
     }
     TwStage<N, P, G::NTHREADS, false> tws;
-    tws.load(lds, A.TW, tid);
+    tws.load(A.TW, tid);
     const Twiddles tw = TwGeom<N, P>::view(A.TW, lds);
     cf* set0 = lds + G::TW_LDS;
     cf x[P];
@@ -352,35 +349,24 @@ __global__ __launch_bounds__((OrP2Geom<N, P>::NTHREADS)) void k_or_pass2_packed(
 
 // F/OceanNormal.shader + F/WhiteCap.shader in one launch: WhiteCap reads _Bump at its own texel only (:38), so the thread
 // that produced the normal goes straight on to the whitecap (its own global write is visible to itself).
-#ifndef MW_OR_NW_BANDS
-#define MW_OR_NW_BANDS 1  // one band of texel rows per XCD (0: rows round-robin over the XCDs, A/B)
-#endif
-#ifndef MW_OR_NW_LDS_TURN
-#define MW_OR_NW_LDS_TURN 1  // a wave's normals turned through LDS so that every store instruction writes 1 KiB contiguous (0: straight from the lane)
-#endif
-#ifndef MW_OR_NW_QUAD
-#define MW_OR_NW_QUAD 1  // four texels of a row per thread from 16-byte loads (0: one texel per thread, A/B)
-#endif
 template <bool NT>
 __global__ __launch_bounds__(256) void k_or_normal_white(OrConsts c, const float* height, const cf* disp, const float* disp_g,
                                                          float* normal, float* white) {
     // XCD-aware: block b runs on XCD b % 8; give each XCD one contiguous band of texel rows, so that the +-1 and +-8 row
     // neighbours are hits in ITS L2 (round-robin rows made every XCD fetch its own copy: 29.5 B/texel for 16 needed)
-    const unsigned blk = MW_OR_NW_BANDS ? or_xcd_band(blockIdx.x, gridDim.x) : blockIdx.x;
+    const unsigned blk = or_xcd_band(blockIdx.x, gridDim.x);
     int idx = blk * blockDim.x + threadIdx.x;
     {   // tile blockIdx.y of a batched handle
         const size_t toff = (size_t)blockIdx.y * c.M * c.M;
         height += toff; disp += toff; disp_g += toff; normal += 3 * toff; white += toff;
     }
-#if MW_OR_NW_QUAD
-    const int Q = c.M / 4;  // thread idx: texels 4 (idx % Q) .. + 3 of row idx / Q
+    const int Q = c.M / 4;  // thread idx: texels 4 (idx % Q) .. + 3 of row idx / Q, from 16-byte loads
     if (idx >= c.M * Q) return;  // whole waves (M^2 / 4 is a multiple of 64)
     float n[4][3], w[4];
     or_normal_white_quad_compute(c, 4 * (idx % Q), idx / Q, height, disp, disp_g, n, w);
     f4 o;
     o.x = w[0]; o.y = w[1]; o.z = w[2]; o.w = w[3];
     mw_store_stream<NT>(reinterpret_cast<f4*>(white) + idx, o);  // 64 lanes x 16 B = 1 KiB contiguous
-#if MW_OR_NW_LDS_TURN
     // The normals: a lane owns 48 contiguous bytes (4 texels x 3), a wave 3 KiB (thread idx <-> texels 4 idx .. 4 idx + 3 of the row-major texture).
     // Stored straight from the lane every instruction writes 16-byte pieces 48 bytes apart -- a third of every line, left to the L2 to merge, and
     // slow with the non-temporal hint.  Turned through LDS inside the wave (as wave_store_3f4 does for the pond's vertices) every store
@@ -398,20 +384,8 @@ __global__ __launch_bounds__(256) void k_or_normal_white(OrConsts c, const float
     f4* dst = reinterpret_cast<f4*>(normal) + (size_t)3 * (idx - lane);
 #pragma unroll
     for (int j = 0; j < 3; j++) mw_store_stream<NT>(&dst[j * 64 + lane], wt[j * 64 + lane]);
-#else
-    float* np_ = normal + (size_t)12 * idx;
-    o.x = n[0][0]; o.y = n[0][1]; o.z = n[0][2]; o.w = n[1][0]; mw_store_stream<NT>(reinterpret_cast<f4*>(np_), o);
-    o.x = n[1][1]; o.y = n[1][2]; o.z = n[2][0]; o.w = n[2][1]; mw_store_stream<NT>(reinterpret_cast<f4*>(np_ + 4), o);
-    o.x = n[2][2]; o.y = n[3][0]; o.z = n[3][1]; o.w = n[3][2]; mw_store_stream<NT>(reinterpret_cast<f4*>(np_ + 8), o);
-#endif
-#else
-    if (idx >= c.M * c.M) return;
-    float nxz[2];
-    or_normal_element<NT>(c, idx % c.M, idx / c.M, height, disp, disp_g, normal, nxz);
-    or_white_element<NT>(c, idx % c.M, idx / c.M, disp, normal, white, nxz);
-#endif
 }
-static inline unsigned or_nw_blocks(size_t MM) { return (unsigned)((MM / (MW_OR_NW_QUAD ? 4 : 1) + 255) / 256); }
+static inline unsigned or_nw_blocks(size_t MM) { return (unsigned)((MM / 4 + 255) / 256); }
 
 __global__ void k_or_pack_rgba(int M, const float* height, const float* height_g, const cf* disp, const float* disp_g,
                                const float* disp_a, const float* normal, const float* white, f4* H, f4* D, f4* Nn, f4* W) {
@@ -532,7 +506,7 @@ static hipError_t or_launch_passes(OrState& s, float dt, hipStream_t st, hipEven
         k_or_pass1_packed<N, P><<<dim3(N / 4, all_fields ? 1 : 2, s.tiles), dim3(NT1), LB1, st>>>(A1);
         if (ev) hipEventRecord(ev[1], st);
         std::swap(s.phaseT, s.phaseT2);
-        k_or_pass2_packed<N, P><<<dim3(N / 4, (all_fields || !MW_OR_P2_LONE_SPLIT) ? 1 : 2, s.tiles), dim3(NT2), LB2, st>>>(A2);
+        k_or_pass2_packed<N, P><<<dim3(N / 4, all_fields ? 1 : 2, s.tiles), dim3(NT2), LB2, st>>>(A2);  // lone frame: one field per workgroup
         if (ev) hipEventRecord(ev[2], st);
         return hipGetLastError();
     }
@@ -632,9 +606,6 @@ static inline mw_status or_frames_reserve(OrState& s, int n, const bool (&need)[
 #ifndef MW_OR_FRAME_GROUPS_PACKED
 #define MW_OR_FRAME_GROUPS_PACKED 2  // the packed plan has two workgroups per column job and group already (one per field): 1 / 2 / 3 / 4 groups measured
 #endif                               // 18.9 / 18.6 / 19.8 / 19.3 us per frame at 32 frames per enqueue
-#ifndef MW_OR_STEPS_KEEP
-#define MW_OR_STEPS_KEEP 1
-#endif
 #ifndef MW_OR_STEPS_CHUNK
 #define MW_OR_STEPS_CHUNK 8  // frames per pass-2 / normal-pass launch pair at 1024^2 (scaled with the texture area)
 #endif
@@ -643,19 +614,14 @@ static inline int or_steps_chunk(int M) {
     return c < 1 ? 1 : (c > MW_OR_MAX_FRAMES ? MW_OR_MAX_FRAMES : (int)c);
 }
 static inline int or_steps_chunks(int M, int n) { const int c = or_steps_chunk(M); return (n + c - 1) / c; }
-#ifndef MW_OR_STEPS_NW_NT
-#define MW_OR_STEPS_NW_NT 1  // normal / whitecap textures of a steps call leave with non-temporal stores
-#endif
 #ifndef MW_OR_STEPS_MAX_N
 #define MW_OR_STEPS_MAX_N 2048  // above: the 1024-thread P = 16 workgroup has 128 VGPRs per lane, no room for a chain in registers
-#endif
-#ifndef MW_OR_STEPS_KEEP_PACKED
-#define MW_OR_STEPS_KEEP_PACKED 1  // packed plan: (h0, h0c) AND (P, Q) of a workgroup's points stay in registers over its frames
 #endif
 template <int N, bool PACKED>
 static hipError_t or_launch_steps(OrState& s, const float* dt, int n, const OrP2Args& A2, float* f_n, float* f_w, hipStream_t st, hipEvent_t* ev = nullptr) {
     constexpr int P = Plan<N>::P, NF = PACKED ? 2 : 3;
-    constexpr bool KEEP = (PACKED ? MW_OR_STEPS_KEEP_PACKED : MW_OR_STEPS_KEEP) != 0 && P <= 8;  // P = 16: no registers to spare
+    // KEEP: (h0, h0c) -- and in the packed plan (P, Q) -- of a workgroup's points stay in registers over its frames (P = 16: no registers to spare)
+    constexpr bool KEEP = P <= 8;
     static AttrOnce attr1, attr2;
     {
         hipError_t e;
@@ -678,7 +644,7 @@ static hipError_t or_launch_steps(OrState& s, const float* dt, int n, const OrP2
         if constexpr (PACKED) k_or_pass2_packed<N, P><<<dim3(N / 4, 1, cn), dim3(NT2), LB2, st>>>(B2);
         else k_or_pass2<N, P><<<dim3(N / 4, 2, cn), dim3(NT2), LB2, st>>>(B2);
         if (ev) hipEventRecord(ev[2 + 3 * j], st);
-        k_or_normal_white<MW_OR_STEPS_NW_NT != 0><<<dim3(or_nw_blocks(MM), cn), dim3(256), 0, st>>>(s.c, B2.height, B2.disp, B2.disp_g, f_n + 3 * off, f_w + off);
+        k_or_normal_white<true><<<dim3(or_nw_blocks(MM), cn), dim3(256), 0, st>>>(s.c, B2.height, B2.disp, B2.disp_g, f_n + 3 * off, f_w + off);
         if (ev) hipEventRecord(ev[3 + 3 * j], st);
     };
     // Pass 2 and the normal / whitecap pass alternate over chunks of frames: the height / displacement textures a chunk writes (16 B per texel

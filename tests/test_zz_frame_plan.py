@@ -1,12 +1,11 @@
 """GPU tier, run last: the frame-at-a-time plan of the 1024^2 FFT path (FFTMesh.Update drives ONE step per call,
 S/FFTMesh.cs:60-73) against the batched plan, bit for bit.
 
-A single-step enqueue at 256^2 / 512^2 / 1024^2 is two launches of their own (csrc/mistral_water.hip, MW_LATENCY_PLAN): pass 1 with one FIELD
-per workgroup over the list of active (column job, field) pairs, a column job's fields on one XCD (k_pass1<.., FS>,
+A single-step enqueue at 256^2 / 512^2 / 1024^2 is two launches of their own (csrc/mistral_water.hip, mw_frame_plan_n): pass 1 with one
+FIELD per workgroup over the list of active (column job, field) pairs, a column job's fields on one XCD (k_pass1<.., FS>,
 p1_frame_jobs); pass 2 with the three fields of a row block and the halo row transformed side by side by 13 row groups that
 meet through LDS (k_pass2_frame).  Neither changes the arithmetic of a row or a column, so every output of a step must be
-the same bit pattern whichever plan produced it.  the switches MW_FRAME_KERNEL = 0 / MW_P1_FRAME_XCD = 0 (mw_debug_set_switch) select round 3's forms of the two
-launches (run-time A/B switches): the same bits again."""
+the same bit pattern whichever plan produced it."""
 import os
 import subprocess
 import sys
@@ -61,29 +60,6 @@ def test_single_step_plan_equals_batched_plan_bit_for_bit_small_grids(mw, N):
     2-row workgroups of 7 row groups there."""
     _frames_against_batch(mw, workloads.fftmesh_params(N), 7, 12, True)
     _frames_against_batch(mw, workloads.fftmesh_config2(N), 2, 5, True)
-
-
-_FRAME_CHILD = r'''
-import sys
-sys.path[:0] = [%(repo)r, %(repo)r + "/mistral-water_amd", %(repo)r + "/tests"]
-import torch; torch.cuda.init()
-import mistral_water as mw, workloads
-import test_zz_frame_plan as T
-mw.set_switch("MW_FRAME_KERNEL", %(frame_kernel)s); mw.set_switch("MW_P1_FRAME_XCD", %(p1_xcd)s)
-T._frames_against_batch(mw, workloads.fftmesh_params(1024), 5, 4, True)
-T._frames_against_batch(mw, workloads.fftmesh_params(512), 5, 4, True)
-T._frames_against_batch(mw, workloads.fftmesh_params(256), 5, 4, True)
-print("FRAME_OK")
-'''
-
-
-@pytest.mark.parametrize("frame_kernel,p1_xcd", [("0", "1"), ("1", "0"), ("0", "0")])
-def test_single_step_plan_switches_select_the_same_bits(frame_kernel, p1_xcd):
-    """The run-time A/B switches of the two single-step launches (csrc/mw_switches.h, set through the test hook), each combination in a
-    child process of its own."""
-    r = subprocess.run([sys.executable, "-c", _FRAME_CHILD % {"repo": REPO, "frame_kernel": frame_kernel, "p1_xcd": p1_xcd}],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "FRAME_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
 
 
 def test_cpp_host_mirror_runs_and_agrees_with_the_python_mirror(mw):
