@@ -118,6 +118,17 @@ public class FFTMesh : MonoBehaviour
         Native.Check(Native.mw_ocean_query_surface(ocean, -1, world ? Native.QueryWorld : Native.QueryRest, xz, xz.Length / 2, 0, result));
     }
 
+    /// Not in the reference: the water's velocity at horizontal points xz (x0, z0, x1, z1, ...), located exactly as SampleSurface locates
+    /// them; result = (vx, vy, vz, residual) per point, the velocity PER SECOND of Update's deltaTime (the library's value is per unit of
+    /// the time argument, which Update advances by deltaTime / tDivision).  Drag needs the water's velocity relative to the hull.
+    public void SampleVelocity(float[] xz, float[] result, bool world = true)
+    {
+        if (result.Length < xz.Length * 2) throw new ArgumentException("result needs 4 floats per point");
+        Native.Check(Native.mw_ocean_query_velocity(ocean, -1, world ? Native.QueryWorld : Native.QueryRest, xz, xz.Length / 2, 0, result));
+        for (int k = 0; k < xz.Length / 2; k++)
+            for (int c = 0; c < 3; c++) result[4 * k + c] /= tDivision;
+    }
+
     /// Evaluate the ocean Unity itself generated: pass the reference's own htilde0 draws (verttilde / vertConj).
     public void SetSpectrum(Vector2[] h0, Vector2[] h0conj)
     {

@@ -115,6 +115,11 @@ public static class MistralWaterNative
     // surface queries: xz [n][2] -> result [n][8] = (px, py, pz, nx, ny, nz, white, residual); frame -1 = latest
     [DllImport(Lib)] public static extern Status mw_ocean_query_surface(IntPtr ocean, int frame, int mode, float[] xz, long n, int iterations, [Out] float[] result);
     [DllImport(Lib)] public static extern Status mw_ocean_query_surface_device(IntPtr ocean, int frame, int mode, IntPtr dXz, long n, int iterations, IntPtr dResult);
+    // surface velocity: per vertex [R*R][3], or at xz [n][2] -> result [n][4] = (vx, vy, vz, residual); FFTMesh per unit of t, OceanRenderer per second
+    [DllImport(Lib)] public static extern Status mw_ocean_velocity(IntPtr ocean, int frame, [Out] Vector3[] velocity);
+    [DllImport(Lib)] public static extern Status mw_ocean_velocity_device(IntPtr ocean, int frame, IntPtr dVelocity);
+    [DllImport(Lib)] public static extern Status mw_ocean_query_velocity(IntPtr ocean, int frame, int mode, float[] xz, long n, int iterations, [Out] float[] result);
+    [DllImport(Lib)] public static extern Status mw_ocean_query_velocity_device(IntPtr ocean, int frame, int mode, IntPtr dXz, long n, int iterations, IntPtr dResult);
 
     // ---- page-locked output arrays ------------------------------------------------------------------------------
     [DllImport(Lib)] public static extern Status mw_host_register(IntPtr ptr, UIntPtr bytes);

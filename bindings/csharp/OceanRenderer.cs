@@ -165,6 +165,14 @@ public class OceanRenderer : MonoBehaviour
         Native.Check(Native.mw_ocean_query_surface(ocean, -1, world ? Native.QueryWorld : Native.QueryRest, xz, xz.Length / 2, 0, result));
     }
 
+    /// Not in the reference: the water's velocity at horizontal points xz, located exactly as SampleSurface locates them; result =
+    /// (vx, vy, vz, residual) per point, per second of Update's deltaTime (mult included), at the current phase.
+    public void SampleVelocity(float[] xz, float[] result, bool world = true)
+    {
+        if (result.Length < xz.Length * 2) throw new ArgumentException("result needs 4 floats per point");
+        Native.Check(Native.mw_ocean_query_velocity(ocean, -1, world ? Native.QueryWorld : Native.QueryRest, xz, xz.Length / 2, 0, result));
+    }
+
     /// Checkpoint of the animation: initialTexture, the phase texture and the length the normal pass uses.  The last one differs
     /// from `length` after a length change: the reference sets normalMat._Length once in SetParams (S/OceanRenderer.cs:163).
     public void SaveState(Vector2[] h0, Vector2[] h0conj, float[] phase, out float normalLength)

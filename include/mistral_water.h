@@ -278,6 +278,40 @@ mw_status mw_ocean_query_surface(mw_ocean* o, int32_t frame, int32_t mode, const
 mw_status mw_ocean_query_surface_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xz, int64_t n,
                                         int32_t iterations, void* d_out);
 
+/* ---- surface velocity: how fast does the water move here? -------------------------------------------------------
+ * The time derivative of the vertices mw_ocean_query_surface reads, computed exactly from the spectrum (every output is linear in
+ * it, and d/dt of h0 e^{iwt} + h0c e^{-iwt} is the same sum over (i w h0, -i w h0c)), not by differencing two frames:
+ *   FFTMesh        velocity = (-choppiness dDx/dt, dh/dt, -choppiness dDz/dt) of vertex (x - chop Dx, h, z - chop Dz) at the t and
+ *                  choppiness of the latest mw_ocean_evaluate / mw_ocean_update frame (or of the profiling hook's frame).  UNITS: per
+ *                  unit of the time argument t.  mw_ocean_update advances t by delta_time / t_division, so the velocity per second
+ *                  of delta_time is this value / t_division.  frame must be -1.
+ *   OceanRenderer  velocity = d/dt of rest + (_Anim.r, _Height.r, _Anim.b) / 8, the vertex stage of mw_ocean_displace_mesh, sampled
+ *                  the same way (resolution^2 vertices) at the handle's CURRENT phase.  UNITS: per second of delta_time: the phase
+ *                  advances by omega * delta_time * mult, so the spectrum is weighted by omega * mult.  The handle keeps only its latest phase, so frame is -1
+ *                  or the last frame of the latest steps call while no later call (a single frame, mw_ocean_advance_phase,
+ *                  mw_ocean_set_phase, ...) has moved the phase; any other frame is MW_EINVAL.  After mw_ocean_advance_phase /
+ *                  mw_ocean_set_phase the current phase is the new one, ahead of the latest textures.
+ * mw_ocean_velocity: velocity_xyz [R*R*3], R = grid size (FFTMesh) or resolution (OceanRenderer), vertex layout of the outputs.
+ * mw_ocean_query_velocity: the point located EXACTLY as mw_ocean_query_surface locates it (same arguments, same modes, same walk;
+ *   residuals bit-identical), out [n][4] = vx, vy, vz, residual: the velocity of the water particle at the located rest point u*,
+ *   the vertex velocities of u*'s triangle interpolated with the weights of the position.  A rest-mode query at a vertex returns
+ *   that vertex's velocity bit for bit.  NaN where mw_ocean_query_surface gives NaN.
+ * mw_ocean_query_velocity returns MW_ESTATE while the spectrum or phase has moved on since the latest frame (mw_ocean_set_spectrum,
+ *   mw_ocean_reinit_spectrum, mw_ocean_set_phase, mw_ocean_advance_phase without a frame after them): the located surface and the
+ *   velocity would belong to different instants.  mw_ocean_velocity answers for the current spectrum and phase.
+ * Errors as mw_ocean_query_surface: MW_ESTATE before the first frame; MW_EINVAL for a batched handle, a bad mode or frame, iterations
+ * outside [0,64], a NULL array, n out of range (mw_tiles_* handles: use the tile's own handle, single oceans only).
+ * No velocity call changes the handle's state (timer, phase, latest frame, frame textures); the weighted spectrum is built on first use
+ * into buffers of the handle, rebuilt after mw_ocean_set_spectrum / mw_ocean_reinit_spectrum, and freed by mw_ocean_destroy.       */
+mw_status mw_ocean_velocity(mw_ocean* o, int32_t frame, float* velocity_xyz); /* host, synchronous */
+mw_status mw_ocean_velocity_device(mw_ocean* o, int32_t frame, void* d_velocity_xyz); /* device array, async on the handle's stream */
+/* xz [n][2], out [n][4]: host arrays, synchronous */
+mw_status mw_ocean_query_velocity(mw_ocean* o, int32_t frame, int32_t mode, const float* xz, int64_t n, int32_t iterations,
+                                  float* out);
+/* device arrays (d_xz 8-byte, d_out 16-byte aligned), asynchronous on the handle's stream */
+mw_status mw_ocean_query_velocity_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xz, int64_t n,
+                                         int32_t iterations, void* d_out);
+
 /* ---- independent tiles on several devices (BASELINE configs[2]) ------------------------------------
  * Tiles are independent units in both semantics: tile k is the ocean of `params` with seed params->seed + k on its own
  * device, compute stream and output buffers; there is no data-path collective.  FFTMesh tiles advance up to max_steps

@@ -26,6 +26,7 @@
 #include "gerstner_kernels.h"
 #include "pond_kernels.h"
 #include "surface_query.h"
+#include "velocity_kernels.h"
 static_assert(MW_SQ_REST == MW_QUERY_REST && MW_SQ_WORLD == MW_QUERY_WORLD, "surface_query.h and the ABI name the modes alike");
 
 #ifndef MW_WAVES_P1
@@ -559,6 +560,10 @@ struct mw_ocean {
     float *s_vert = nullptr, *s_norm = nullptr, *s_white = nullptr;  // 1-step scratch for the host API
     bool s_have = false;  // s_vert / s_norm / s_white hold a frame: the "latest frame" of mw_ocean_query_surface
     int s_wstride = 4;    // ... and the whitecap stride its writer used: 4 (RGBA colours, the host API) or 1 (the profiling hook)
+    float s_t = 0.f, s_chop = 0.f;  // ... and the time and choppiness it was evaluated with (mw_ocean_velocity differentiates there)
+    int or_steps_tail = -1;  // OceanRenderer: the last frame of the latest steps call while the phase is still that frame's, else -1
+    bool frame_behind = false;  // the spectrum or the phase changed after the latest frame was made (mw_ocean_query_velocity refuses)
+    VelState vel;            // mw_ocean_velocity: the weighted spectrum and the velocity buffers (velocity_kernels.h)
     float* q_mesh = nullptr;  // OceanRenderer surface queries: the vertex stage of the queried frame, [res^2][3 + 3 + 1], allocated on first use
     void* scratch = nullptr;  // grow-only device staging of the host-pointer entry points (rest mesh, RGBA targets, ...):
     size_t scratch_cap = 0;   // allocated once at the largest size asked for, not per call
@@ -724,11 +729,14 @@ static int p1_time_group(const mw_ocean* o, int nsteps) {
         if (nsteps % g == 0) return g;
     return 0;
 }
-static mw_status launch_pass1(mw_ocean* o, const StepTimes& tm, int nsteps, hipStream_t st) {
+// vel: pass 1 of the velocity (mw_ocean_velocity) -- the prep tables of the weighted spectrum and the consts the frame was made with
+static mw_status launch_pass1(mw_ocean* o, const StepTimes& tm, int nsteps, hipStream_t st, const VelState* vel = nullptr,
+                              const OceanConsts* c = nullptr) {
     P1Args A;
     A.PQt = o->PQt; A.dPQ_i0 = o->dPQ_i0; A.dPQ_j0 = o->dPQ_j0; A.Om = o->Om; A.TW = o->TW;
+    if (vel) { A.PQt = vel->PQt; A.dPQ_i0 = vel->dPQ_i0; A.dPQ_j0 = vel->dPQ_j0; A.Om = vel->Om; }
     A.E = o->E; A.Cj0 = o->Cj0;
-    A.c = consts_of(o);
+    A.c = c ? *c : consts_of(o);
     A.nsteps = nsteps;
     A.tgroup = p1_time_group(o, nsteps);
     A.field_split = nsteps == 1 && mw_frame_plan_n(o->N);
@@ -738,11 +746,12 @@ static mw_status launch_pass1(mw_ocean* o, const StepTimes& tm, int nsteps, hipS
     if (e != hipSuccess) return fail(MW_EDEVICE, std::string("pass1 launch: ") + hipGetErrorString(e));
     return MW_OK;
 }
-static mw_status launch_pass2(mw_ocean* o, int nsteps, float* dv, float* dn, float* dw, int white_stride, cf* hds_dump = nullptr) {
+static mw_status launch_pass2(mw_ocean* o, int nsteps, float* dv, float* dn, float* dw, int white_stride, cf* hds_dump = nullptr,
+                              const OceanConsts* c = nullptr) {
     P2Args A;
     A.E = o->E; A.Cj0 = o->Cj0; A.TW = o->TW2; A.vertices = dv; A.normals = dn; A.white = dw; A.white_stride = white_stride;
     A.hds_dump = hds_dump;
-    A.c = consts_of(o);
+    A.c = c ? *c : consts_of(o);
     hipError_t e = hipSuccess;
     if (hds_dump) { MW_DISPATCH_N(o->N, (e = launch_pass2_n<NN, true>(A, nsteps, o->stream))); }
     else { MW_DISPATCH_N(o->N, (e = launch_pass2_n<NN, false>(A, nsteps, o->stream))); }
@@ -843,6 +852,7 @@ void mw_ocean_destroy(mw_ocean* o) {
     if (hipStreamSynchronize(o->stream) != hipSuccess) (void)hipGetLastError();  // a dead caller stream has nothing pending
     hipFree(o->h0); hipFree(o->h0c); hipFree(o->PQt); hipFree(o->Om); hipFree(o->dPQ_i0); hipFree(o->dPQ_j0);
     hipFree(o->TW); hipFree(o->TW2); hipFree(o->Wpre); hipFree(o->p1_jobs); hipFree(o->E); hipFree(o->Cj0); hipFree(o->s_vert); hipFree(o->s_norm); hipFree(o->s_white); hipFree(o->q_mesh); hipFree(o->scratch);
+    vel_free(o->vel);
     direct_free(o->direct);
     or_free(o->orr);
     if (o->own_stream) hipStreamDestroy(o->own_stream);
@@ -989,6 +999,9 @@ mw_status mw_ocean_reset_timer(mw_ocean* o) {
 mw_status mw_ocean_set_spectrum(mw_ocean* o, const float* h0_xy, const float* h0conj_xy) {
     if (!o || !h0_xy || !h0conj_xy) return fail(MW_EINVAL, "mw_ocean_set_spectrum: NULL argument");
     HIP_TRY(hipSetDevice(o->device));
+    o->vel.ready = false;  // the velocity spectrum is derived from this one
+    o->or_steps_tail = -1;  // OceanRenderer: the phase restarts
+    o->frame_behind = true;
     const int tiles = (o->sem == MW_SEM_OCEANRENDERER) ? o->orr.tiles : 1;
     const size_t bytes = sizeof(cf) * (size_t)o->N * o->N * tiles;
     if (o->sem == MW_SEM_OCEANRENDERER) {  // initialTexture.rg / .ba, texel (px,py) at py*M + px, tile-major
@@ -1040,6 +1053,8 @@ mw_status mw_ocean_reinit_spectrum(mw_ocean* o, float length, float wind_x, floa
     if (!o) return fail(MW_EINVAL, "NULL handle");
     if (!(length > 0.f)) return fail(MW_EINVAL, "mw_ocean_reinit_spectrum: length must be positive");
     HIP_TRY(hipSetDevice(o->device));
+    o->vel.ready = false;  // new spectrum and dispersion
+    o->frame_behind = true;
     if (o->sem == MW_SEM_OCEANRENDERER) {  // S/OceanRenderer.cs:98-109: RenderInitial() again, phase textures untouched
         mw_status s = or_reinit(o->orr, length, wind_x, wind_y, amplitude, seed, o->stream);
         if (s != MW_OK) return fail(s, or_last_error());
@@ -1114,6 +1129,8 @@ static mw_status phase_copy(mw_ocean* o, float* host_out, const float* host_in, 
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(host_out, tmp, bytes, hipMemcpyDeviceToHost, o->stream));
     } else {
+        o->or_steps_tail = -1;
+        o->frame_behind = true;
         HIP_TRY(hipMemcpyAsync(tmp, host_in, bytes, hipMemcpyHostToDevice, o->stream));
         k_or_phase_transpose<<<grid, block, 0, o->stream>>>(o->N, tmp, o->orr.phaseT);
         HIP_TRY(hipGetLastError());
@@ -1196,6 +1213,8 @@ mw_status mw_ocean_evaluate(mw_ocean* o, float t, float* vertices_xyz, float* no
     if (s != MW_OK) return s;
     o->s_have = true;
     o->s_wstride = 4;
+    o->s_t = t;
+    o->s_chop = o->p.choppiness; o->frame_behind = false;
     const size_t NN = (size_t)o->N * o->N;
     if (vertices_xyz) HIP_TRY(hipMemcpyAsync(vertices_xyz, o->s_vert, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
     if (normals_xyz) HIP_TRY(hipMemcpyAsync(normals_xyz, o->s_norm, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
@@ -1216,6 +1235,8 @@ mw_status mw_ocean_generate_texture_device(mw_ocean* o, float delta_time, void* 
     if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture: OceanRenderer semantics only");
     HIP_TRY(hipSetDevice(o->device));
     o->orr.choppiness = o->p.choppiness;
+    o->or_steps_tail = -1;
+    o->frame_behind = false;
     mw_status s = or_generate(o->orr, delta_time, (float*)d_height, (float*)d_disp_xz, (float*)d_normal_xyz, (float*)d_white,
                               o->stream);
     if (s != MW_OK) return fail(s, or_last_error());
@@ -1253,6 +1274,8 @@ mw_status mw_ocean_generate_texture_steps_device(mw_ocean* o, const float* delta
     if (s != MW_OK) return fail(s, or_last_error());
     o->orr.fr_have[0] = !d_height; o->orr.fr_have[1] = !d_disp_xz; o->orr.fr_have[2] = !d_normal_xyz; o->orr.fr_have[3] = !d_white;
     o->orr.frames_last = nframes;
+    o->or_steps_tail = nframes - 1;
+    o->frame_behind = false;
     return MW_OK;
 }
 // host forms of the steps calls: the frames stay in the handle's frame buffers, then leave over PCIe into the caller's [nframes][...] arrays
@@ -1303,6 +1326,8 @@ mw_status mw_ocean_advance_phase(mw_ocean* o, const float* delta_time, int32_t n
     if (nframes < 0) return fail(MW_EINVAL, "mw_ocean_advance_phase: nframes < 0");
     if (nframes == 0) return MW_OK;
     HIP_TRY(hipSetDevice(o->device));
+    o->or_steps_tail = -1;
+    o->frame_behind = true;
     mw_status s = or_advance_phase(o->orr, delta_time, nframes, o->stream);
     if (s != MW_OK) return fail(s, or_last_error());
     return MW_OK;
@@ -1342,6 +1367,8 @@ mw_status mw_ocean_generate_texture_steps_rgba_device(mw_ocean* o, const float* 
     if (s != MW_OK) return fail(s, or_last_error());
     for (int k = 0; k < 4; k++) o->orr.fr_have[k] = true;
     o->orr.frames_last = nframes;
+    o->or_steps_tail = nframes - 1;
+    o->frame_behind = false;
     return MW_OK;
 }
 
@@ -1362,6 +1389,8 @@ mw_status mw_ocean_generate_texture_rgba_device(mw_ocean* o, float delta_time, v
     if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture_rgba: OceanRenderer semantics only");
     HIP_TRY(hipSetDevice(o->device));
     o->orr.choppiness = o->p.choppiness;
+    o->or_steps_tail = -1;
+    o->frame_behind = false;
     mw_status s = or_generate_rgba(o->orr, delta_time, (f4*)d_height_rgba, (f4*)d_disp_rgba, (f4*)d_normal_rgba,
                                    (f4*)d_white_rgba, o->stream);
     if (s != MW_OK) return fail(s, or_last_error());
@@ -1507,6 +1536,145 @@ mw_status mw_ocean_query_surface(mw_ocean* o, int32_t frame, int32_t mode, const
     return MW_OK;
 }
 
+// ---- surface velocity (csrc/velocity_kernels.h) --------------------------------------------------------------------
+// The frame a velocity call differentiates: FFTMesh the latest frame (frame -1); OceanRenderer the current phase, which is the latest
+// frame's (-1) or the last frame of the latest steps call while no other call has moved the phase since.  Argument errors first, as
+// query_prepare orders them.
+static mw_status velocity_check(mw_ocean* o, int32_t frame, const char* who) {
+    if (!o) return fail(MW_EINVAL, std::string(who) + ": NULL handle");
+    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
+        return fail(MW_EINVAL, std::string(who) + ": a batched handle (mw_ocean_create_batch) has no single surface");
+    if (o->sem == MW_SEM_FFTMESH && frame != -1) return fail(MW_EINVAL, std::string(who) + ": FFTMesh handles keep one frame (frame = -1)");
+    if (o->sem == MW_SEM_OCEANRENDERER && frame != -1 && !(frame >= 0 && frame == o->or_steps_tail))
+        return fail(MW_EINVAL, std::string(who) + ": the handle keeps only the latest phase: frame must be -1 or the last frame of the latest "
+                                                  "steps call");
+    if (o->sem == MW_SEM_FFTMESH && !o->s_have) return fail(MW_ESTATE, std::string(who) + ": no frame yet (mw_ocean_evaluate / mw_ocean_update first)");
+    if (o->sem == MW_SEM_OCEANRENDERER && !o->orr.have_frame) return fail(MW_ESTATE, std::string(who) + ": no GenerateTexture() yet");
+    return MW_OK;
+}
+// the velocity of every vertex into d_vel [R*R][3], on the handle's stream; writes only the handle's velocity buffers
+static mw_status velocity_run(mw_ocean* o, float* d_vel) {
+    VelState& v = o->vel;
+    if (o->sem == MW_SEM_OCEANRENDERER) {
+        mw_status s = or_velocity(o->orr, v, o->p.resolution, d_vel, o->stream);
+        return s == MW_OK ? MW_OK : fail(s, or_last_error());
+    }
+    const int N = o->N;
+    const size_t NN = (size_t)N * N;
+    mw_status s = MW_OK;
+    if (!v.white) {  // the last buffer allocated: a failure half-way frees them all, and the next call starts again
+        if ((s = dmalloc(&v.h0, NN)) != MW_OK || (s = dmalloc(&v.h0c, NN)) != MW_OK || (s = dmalloc(&v.norm, 3 * NN)) != MW_OK ||
+            (o->use_fft && ((s = dmalloc(&v.PQt, NN)) != MW_OK || (s = dmalloc(&v.Om, NN)) != MW_OK ||
+                            (s = dmalloc(&v.dPQ_i0, (size_t)N)) != MW_OK || (s = dmalloc(&v.dPQ_j0, (size_t)N)) != MW_OK)) ||
+            (s = dmalloc(&v.white, NN)) != MW_OK) {
+            vel_free(v);
+            return s;
+        }
+    }
+    const unsigned nb = (unsigned)((NN + 255) / 256);
+    if (!v.ready) {  // (i w h0, -i w h0c) and, on the FFT path, its prep tables: once per spectrum
+        hipLaunchKernelGGL(k_velocity_spectrum, dim3(nb), dim3(256), 0, o->stream, N, o->p.length, o->p.gravity, o->h0, o->h0c, v.h0, v.h0c);
+        if (o->use_fft)
+            hipLaunchKernelGGL(k_prep, dim3(nb), dim3(256), 0, o->stream, N, o->p.length, o->p.gravity, v.h0, v.h0c, o->Wpre, v.PQt,
+                               v.dPQ_i0, v.dPQ_j0, v.Om);
+        HIP_TRY(hipGetLastError());
+        v.ready = true;
+    }
+    OceanConsts C = consts_of(o);
+    C.choppiness = o->s_chop;  // the frame's choppiness (mw_ocean_set_choppiness may have changed it since)
+    if (!o->use_fft) {
+        if (direct_evaluate(o->direct, C, v.h0, v.h0c, o->s_t, d_vel, v.norm, v.white, 1, o->stream) != hipSuccess)
+            return fail(MW_EDEVICE, "velocity: direct-sum kernels failed to launch");
+        hipLaunchKernelGGL(k_velocity_from_hds, dim3(nb), dim3(256), 0, o->stream, N, C.choppiness, o->direct.hds, d_vel);
+        HIP_TRY(hipGetLastError());
+        return MW_OK;
+    }
+    if ((s = ensure_exchange(o, 1)) != MW_OK) return s;
+    StepTimes tm;
+    tm.t[0] = o->s_t;
+    if ((s = launch_pass1(o, tm, 1, o->stream, &v, &C)) != MW_OK) return s;
+    C.unit_width = 0.f;  // rest coordinate +-0: the vertex the epilogue writes is (-chop Dx, h, -chop Dz) of the weighted spectrum
+    return launch_pass2(o, 1, d_vel, v.norm, v.white, 1, nullptr, &C);
+}
+static mw_status velocity_stage(mw_ocean* o) {
+    const int R = o->sem == MW_SEM_OCEANRENDERER ? o->p.resolution : o->N;
+    return o->vel.vert ? MW_OK : dmalloc(&o->vel.vert, (size_t)R * R * 3);
+}
+
+mw_status mw_ocean_velocity_device(mw_ocean* o, int32_t frame, void* d_velocity_xyz) {
+    const char* who = "mw_ocean_velocity_device";
+    mw_status s = velocity_check(o, frame, who);
+    if (s != MW_OK) return s;
+    if (!d_velocity_xyz) return fail(MW_EINVAL, std::string(who) + ": NULL array");
+    HIP_TRY(hipSetDevice(o->device));
+    return velocity_run(o, static_cast<float*>(d_velocity_xyz));
+}
+
+mw_status mw_ocean_velocity(mw_ocean* o, int32_t frame, float* velocity_xyz) {
+    const char* who = "mw_ocean_velocity";
+    mw_status s = velocity_check(o, frame, who);
+    if (s != MW_OK) return s;
+    if (!velocity_xyz) return fail(MW_EINVAL, std::string(who) + ": NULL array");
+    HIP_TRY(hipSetDevice(o->device));
+    if ((s = velocity_stage(o)) != MW_OK || (s = velocity_run(o, o->vel.vert)) != MW_OK) return s;
+    const int R = o->sem == MW_SEM_OCEANRENDERER ? o->p.resolution : o->N;
+    HIP_TRY(hipMemcpyAsync(velocity_xyz, o->vel.vert, (size_t)R * R * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    return MW_OK;
+}
+
+// velocity queries: the surface query's validation and mesh (query_prepare), the per-vertex velocity into the handle's buffer, one lane
+// per point locating exactly as k_query_surface does (sq_locate)
+// The located surface is the latest frame's; the velocity is that of the handle's current spectrum and phase.  Once either moved on
+// without a new frame (mw_ocean_set_spectrum / reinit_spectrum / set_phase / advance_phase) the two would belong to different
+// instants: MW_ESTATE until the next frame.
+static mw_status query_velocity_prepare(mw_ocean* o, int32_t frame, int32_t mode, const void* xz, int64_t n, int32_t iterations, const void* out,
+                                        const char* who, SqMesh* m) {
+    mw_status s = query_prepare(o, frame, mode, xz, n, iterations, out, who, m);
+    if (s == MW_OK) s = velocity_check(o, frame, who);
+    if (s == MW_OK && o->frame_behind)
+        return fail(MW_ESTATE, std::string(who) + ": the spectrum or phase changed after the latest frame: the surface and the velocity would "
+                                                  "belong to different instants (make a frame first)");
+    return s;
+}
+static mw_status query_velocity_launch(mw_ocean* o, const SqMesh& m, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
+    mw_status s;
+    if ((s = velocity_stage(o)) != MW_OK || (s = velocity_run(o, o->vel.vert)) != MW_OK) return s;
+    const int iters = iterations == 0 ? MW_SQ_DEFAULT_ITERS : iterations;
+    k_query_velocity<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, o->vel.vert, mode, iters, static_cast<const float2*>(d_xz), n,
+                                                                                    static_cast<float4*>(d_out));
+    HIP_TRY(hipGetLastError());
+    return MW_OK;
+}
+
+mw_status mw_ocean_query_velocity_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
+    const char* who = "mw_ocean_query_velocity_device";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (n > 0 && ((reinterpret_cast<uintptr_t>(d_xz) & 7) || (reinterpret_cast<uintptr_t>(d_out) & 15)))
+        return fail(MW_EINVAL, std::string(who) + ": d_xz must be 8-byte and d_out 16-byte aligned");
+    SqMesh m{};
+    mw_status s = query_velocity_prepare(o, frame, mode, d_xz, n, iterations, d_out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    return query_velocity_launch(o, m, mode, d_xz, n, iterations, d_out);
+}
+
+mw_status mw_ocean_query_velocity(mw_ocean* o, int32_t frame, int32_t mode, const float* xz, int64_t n, int32_t iterations, float* out) {
+    const char* who = "mw_ocean_query_velocity";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    SqMesh m{};
+    mw_status s = query_velocity_prepare(o, frame, mode, xz, n, iterations, out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    const size_t bin = align256((size_t)n * 2 * sizeof(float)), bout = (size_t)n * 4 * sizeof(float);
+    void* buf = nullptr;
+    if ((s = scratch_reserve(o, bin + bout, &buf)) != MW_OK) return s;
+    char* base = static_cast<char*>(buf);
+    HIP_TRY(hipMemcpyAsync(base, xz, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, o->stream));
+    if ((s = query_velocity_launch(o, m, mode, base, n, iterations, base + bin)) != MW_OK) return s;
+    HIP_TRY(hipMemcpyAsync(out, base + bin, bout, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    return MW_OK;
+}
+
 // per-launch durations -> (mean, median, p10, p90, min, max), milliseconds
 static void launch_stats(std::vector<float>& v, float* out6) {
     std::sort(v.begin(), v.end());
@@ -1545,6 +1713,8 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
         float dts[MW_OR_MAX_FRAMES];
         for (int k = 0; k < MW_OR_MAX_FRAMES; k++) dts[k] = 1.0f / 60.0f;
         o->orr.choppiness = o->p.choppiness;
+        o->or_steps_tail = -1;
+        o->frame_behind = false;
         auto call = [&](hipEvent_t* ev) {
             return nsteps == 1 ? or_generate(o->orr, dts[0], nullptr, nullptr, nullptr, nullptr, o->stream, ev)
                                : or_generate_steps(o->orr, dts, nsteps, nullptr, nullptr, nullptr, nullptr, o->stream, ev);
@@ -1624,6 +1794,8 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
         if (he != hipSuccess) return fail(MW_EDEVICE, std::string("direct-sum profile: ") + hipGetErrorString(he));
         o->s_have = true;  // the chirp-z / direct kernels above wrote the host-API frame: it is the latest frame now
         o->s_wstride = 1;
+        o->s_t = 1.0f + (float)(iters - 1) / 60.f;
+        o->s_chop = o->p.choppiness; o->frame_behind = false;
         for (int k = 0; k < 2; k++) {
             ms_out[k] = (float)(acc[k] / iters);
             if (names_out) names_out[k] = dnames[k];
@@ -1688,7 +1860,7 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
     }
     for (auto& e : ev) hipEventDestroy(e);
     if (nsteps != 1) { hipFree(dv); hipFree(dn); hipFree(dw); }
-    else if (s == MW_OK) { o->s_have = true; o->s_wstride = 1; }  // the host-API frame is the profiled step (t = 1) now
+    else if (s == MW_OK) { o->s_have = true; o->s_wstride = 1; o->s_t = 1.0f; o->s_chop = o->p.choppiness; o->frame_behind = false; }  // the host-API frame is the profiled step (t = 1) now
     *nkernels = 2;
     return s;
 }
@@ -1735,6 +1907,8 @@ mw_status mw_debug_evaluate_hds(mw_ocean* o, float t, float* vertices_xyz, float
     }
     o->s_have = true;
     o->s_wstride = 4;
+    o->s_t = t;
+    o->s_chop = o->p.choppiness; o->frame_behind = false;
     if (vertices_xyz) HIP_TRY(hipMemcpyAsync(vertices_xyz, o->s_vert, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
     if (normals_xyz) HIP_TRY(hipMemcpyAsync(normals_xyz, o->s_norm, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
     if (colors_rgba) HIP_TRY(hipMemcpyAsync(colors_rgba, o->s_white, NN * 4 * sizeof(float), hipMemcpyDeviceToHost, o->stream));

@@ -104,8 +104,12 @@ MW_HD bool sq_inside(bool upper, float sa, float sb) {
     return !upper ? (sa >= -t && sb >= -t && sa + sb <= 1.f + t) : (sa <= 1.f + t && sb <= 1.f + t && sa + sb >= 1.f - t);
 }
 
-// one query: out = (px, py, pz, nx, ny, nz, white, residual)
-MW_HD void sq_query_point(const SqMesh& m, int mode, float qx, float qz, int iters, float out[8]) {
+// The rest point a query resolves to: rest mode one lookup, world mode the walk.  Where the query has an answer, `found` receives the
+// corners v and barycentric weights w of its triangle; where it has none -- a rest point off the footprint, a non-finite world point --
+// `miss` runs instead.  The surface query (sq_query_point) and the velocity query (sq_velocity_point) both locate here, so they resolve
+// every point identically.
+template <typename Miss, typename Found>
+MW_HD void sq_locate(const SqMesh& m, int mode, float qx, float qz, int iters, Miss miss, Found found) {
     const int R = m.R;
     const float lo = fminf(rest_coord(R, m.unit_width, 0), rest_coord(R, m.unit_width, R - 1));
     const float hi = fmaxf(rest_coord(R, m.unit_width, 0), rest_coord(R, m.unit_width, R - 1));
@@ -113,7 +117,7 @@ MW_HD void sq_query_point(const SqMesh& m, int mode, float qx, float qz, int ite
     // rest mode: the point must lie on the footprint; world mode: a finite point (the walk stays on the footprint by clamping)
     const bool ok = rest ? (qx >= lo && qx <= hi && qz >= lo && qz <= hi) : (fabsf(qx) <= 3.4e38f && fabsf(qz) <= 3.4e38f);
     if (!ok) {
-        for (int k = 0; k < 8; k++) out[k] = NAN;
+        miss();
         return;
     }
     float ux = fminf(fmaxf(qx, lo), hi), uz = fminf(fmaxf(qz, lo), hi);
@@ -165,23 +169,54 @@ MW_HD void sq_query_point(const SqMesh& m, int mode, float qx, float qz, int ite
             tu = sq_upper(ta, tb);
         }
     }
-    // the surface at the chosen rest point: gathered once
     int v[3];
     float w[3];
     sq_triangle(R, ci, cj, up, fa, fb, v, w);
-    float p[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f}, wh = 0.f;
-    for (int k = 0; k < 3; k++) {
-        for (int c = 0; c < 3; c++) {
-            p[c] += w[k] * m.vert[3 * v[k] + c];
-            n[c] += w[k] * m.norm[3 * v[k] + c];
+    found(v, w);
+}
+
+// one query: out = (px, py, pz, nx, ny, nz, white, residual)
+MW_HD void sq_query_point(const SqMesh& m, int mode, float qx, float qz, int iters, float out[8]) {
+    sq_locate(m, mode, qx, qz, iters, [&] { for (int k = 0; k < 8; k++) out[k] = NAN; }, [&](const int v[3], const float w[3]) {
+        const bool rest = mode == MW_SQ_REST;
+        // the surface at the chosen rest point: gathered once
+        float p[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f}, wh = 0.f;
+        for (int k = 0; k < 3; k++) {
+            for (int c = 0; c < 3; c++) {
+                p[c] += w[k] * m.vert[3 * v[k] + c];
+                n[c] += w[k] * m.norm[3 * v[k] + c];
+            }
+            wh += w[k] * m.white[(size_t)m.wstride * v[k]];
         }
-        wh += w[k] * m.white[(size_t)m.wstride * v[k]];
+        const float inv = 1.f / sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+        out[0] = p[0]; out[1] = p[1]; out[2] = p[2];
+        out[3] = n[0] * inv; out[4] = n[1] * inv; out[5] = n[2] * inv;
+        out[6] = wh;
+        out[7] = rest ? 0.f : sqrtf((p[0] - qx) * (p[0] - qx) + (p[2] - qz) * (p[2] - qz));
+    });
+}
+
+// |displaced(u*).xz - (x, z)| of a located point: the horizontal position accumulated as sq_query_point accumulates it
+MW_HD float sq_residual(const SqMesh& m, const int v[3], const float w[3], float qx, float qz) {
+    float px = 0.f, pz = 0.f;
+    for (int k = 0; k < 3; k++) {
+        px += w[k] * m.vert[3 * v[k]];
+        pz += w[k] * m.vert[3 * v[k] + 2];
     }
-    const float inv = 1.f / sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-    out[0] = p[0]; out[1] = p[1]; out[2] = p[2];
-    out[3] = n[0] * inv; out[4] = n[1] * inv; out[5] = n[2] * inv;
-    out[6] = wh;
-    out[7] = rest ? 0.f : sqrtf((p[0] - qx) * (p[0] - qx) + (p[2] - qz) * (p[2] - qz));
+    return sqrtf((px - qx) * (px - qx) + (pz - qz) * (pz - qz));
+}
+
+// one velocity query (mw_ocean_query_velocity): the point located exactly as sq_query_point locates it, the velocity of the water
+// particle there -- the per-vertex velocities vel [R*R][3] interpolated with the weights of the position -- and the same residual.
+// out = (vx, vy, vz, residual)
+MW_HD void sq_velocity_point(const SqMesh& m, const float* vel, int mode, float qx, float qz, int iters, float out[4]) {
+    sq_locate(m, mode, qx, qz, iters, [&] { for (int k = 0; k < 4; k++) out[k] = NAN; }, [&](const int v[3], const float w[3]) {
+        float u[3] = {0.f, 0.f, 0.f};
+        for (int k = 0; k < 3; k++)
+            for (int c = 0; c < 3; c++) u[c] += w[k] * vel[3 * v[k] + c];
+        out[0] = u[0]; out[1] = u[1]; out[2] = u[2];
+        out[3] = mode == MW_SQ_REST ? 0.f : sq_residual(m, v, w, qx, qz);
+    });
 }
 
 #if defined(__HIPCC__)
@@ -196,6 +231,16 @@ __global__ __launch_bounds__(256) void k_query_surface(SqMesh m, int mode, int i
     sq_query_point(m, mode, q.x, q.y, iters, r);
     out[2 * k] = make_float4(r[0], r[1], r[2], r[3]);
     out[2 * k + 1] = make_float4(r[4], r[5], r[6], r[7]);
+}
+// One lane per query, as k_query_surface: the same walk, one final gather of the three corners' velocities, one 16-byte store.
+__global__ __launch_bounds__(256) void k_query_velocity(SqMesh m, const float* __restrict__ vel, int mode, int iters,
+                                                        const float2* __restrict__ xz, int64_t n, float4* __restrict__ out) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const float2 q = xz[k];
+    float r[4];
+    sq_velocity_point(m, vel, mode, q.x, q.y, iters, r);
+    out[k] = make_float4(r[0], r[1], r[2], r[3]);
 }
 #endif
 

@@ -42,6 +42,16 @@ inline void query_surface(mw_ocean* o, int32_t frame, const std::vector<Vector2>
                                  iterations, out.empty() ? nullptr : &out[0].position.x));
 }
 
+// one answer of mw_ocean_query_velocity: the water's velocity at the point mw_ocean_query_surface locates, and the same residual
+struct VelocitySample { Vector3 velocity; float residual = 0.f; };
+static_assert(sizeof(VelocitySample) == 16, "[n][4] floats of mw_ocean_query_velocity");
+inline void query_velocity(mw_ocean* o, int32_t frame, const std::vector<Vector2>& xz, std::vector<VelocitySample>& out, bool world,
+                           int32_t iterations) {
+    out.resize(xz.size());
+    check(mw_ocean_query_velocity(o, frame, world ? MW_QUERY_WORLD : MW_QUERY_REST, xz.empty() ? nullptr : &xz[0].x, (int64_t)xz.size(),
+                                  iterations, out.empty() ? nullptr : &out[0].velocity.x));
+}
+
 class FFTMesh {
 public:
     // ---- public Inspector fields, S/FFTMesh.cs:9-23 -------------------------------------------------
@@ -81,6 +91,18 @@ public:
     // Not in the reference: the surface of the latest EvaluateWaves() at horizontal points (include/mistral_water.h, surface queries)
     void QuerySurface(const std::vector<Vector2>& xz, std::vector<SurfaceSample>& out, bool world = true, int32_t iterations = 0) {
         query_surface(ocean_, -1, xz, out, world, iterations);
+    }
+    // Not in the reference: the velocity of every vertex of the latest frame, per second of Update's deltaTime (the library's value is
+    // per unit of t, and Update advances t by deltaTime / tDivision)
+    void Velocity(std::vector<Vector3>& out) {
+        out.resize((size_t)resolution * resolution);
+        check(mw_ocean_velocity(ocean_, -1, &out[0].x));
+        for (auto& v : out) { v.x /= tDivision; v.y /= tDivision; v.z /= tDivision; }
+    }
+    // ... and at horizontal points, located as QuerySurface locates them (per second, as Velocity)
+    void QueryVelocity(const std::vector<Vector2>& xz, std::vector<VelocitySample>& out, bool world = true, int32_t iterations = 0) {
+        query_velocity(ocean_, -1, xz, out, world, iterations);
+        for (auto& s : out) { s.velocity.x /= tDivision; s.velocity.y /= tDivision; s.velocity.z /= tDivision; }
     }
     float timer() const { return timer_; }
     mw_ocean* handle() { return ocean_; }
@@ -169,6 +191,14 @@ public:
     void QuerySurface(const std::vector<Vector2>& xz, std::vector<SurfaceSample>& out, bool world = true, int32_t frame = -1,
                       int32_t iterations = 0) {
         query_surface(ocean_, frame, xz, out, world, iterations);
+    }
+    // Not in the reference: the water's velocity per second of delta_time at the handle's current phase (frame -1)
+    void Velocity(std::vector<Vector3>& out) {
+        out.resize((size_t)resolution * resolution);
+        check(mw_ocean_velocity(ocean_, -1, &out[0].x));
+    }
+    void QueryVelocity(const std::vector<Vector2>& xz, std::vector<VelocitySample>& out, bool world = true, int32_t iterations = 0) {
+        query_velocity(ocean_, -1, xz, out, world, iterations);
     }
 
 private:

@@ -16,6 +16,9 @@ int main() {
         std::vector<SurfaceSample> here;
         m.QuerySurface({{0.f, 0.f}, {10.5f, -3.25f}}, here);  // how high is the water at these two points of the displaced surface?
         std::printf("FFTMesh 256^2: water height at (0, 0) = %.6g (residual %.2g)\n", here[0].position.y, here[0].residual);
+        std::vector<VelocitySample> flow;
+        m.QueryVelocity({{0.f, 0.f}}, flow);  // and how fast does it move there (per second)?
+        std::printf("FFTMesh 256^2: water velocity at (0, 0) = (%.6g, %.6g, %.6g)\n", flow[0].velocity.x, flow[0].velocity.y, flow[0].velocity.z);
         OceanRenderer r;
         r.resolution = 16; r.length = 60.f; r.amplitude = 0.41f; r.choppiness = 0.46f; r.mult = 1.5f; r.wind = {14.45f, 12.f};
         r.Awake();

@@ -198,6 +198,10 @@ def lib():
         "mw_ocean_displace_mesh_device": (C.c_int, [vp, vp, vp, vp]),
         "mw_ocean_query_surface": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, C.c_int32, f32p]),
         "mw_ocean_query_surface_device": (C.c_int, [vp, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int32, vp]),
+        "mw_ocean_velocity": (C.c_int, [vp, C.c_int32, f32p]),
+        "mw_ocean_velocity_device": (C.c_int, [vp, C.c_int32, vp]),
+        "mw_ocean_query_velocity": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, C.c_int32, f32p]),
+        "mw_ocean_query_velocity_device": (C.c_int, [vp, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int32, vp]),
         "mw_ocean_profile_kernels": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
         "mw_ocean_profile_kernels_stats": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
         "mw_gerstner_displace": (C.c_int, [f32p, C.c_int64, f32p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
@@ -245,6 +249,7 @@ ABI_SYMBOLS = [
     "mw_ocean_generate_texture_device", "mw_ocean_generate_texture_steps_device", "mw_ocean_generate_texture_steps_rgba_device",
     "mw_ocean_generate_texture_steps", "mw_ocean_generate_texture_steps_rgba", "mw_ocean_max_frames", "mw_ocean_advance_phase", "mw_ocean_frame_textures", "mw_host_register", "mw_host_unregister", "mw_ocean_generate_texture_rgba", "mw_ocean_generate_texture_rgba_device",
     "mw_ocean_displace_mesh", "mw_ocean_displace_mesh_device", "mw_ocean_query_surface", "mw_ocean_query_surface_device",
+    "mw_ocean_velocity", "mw_ocean_velocity_device", "mw_ocean_query_velocity", "mw_ocean_query_velocity_device",
     "mw_gerstner_displace",
     "mw_gerstner_displace_device", "mw_gerstner_displace_steps_device", "mw_gerstner_max_steps", "mw_pond_displace", "mw_pond_displace_device",
 ]

@@ -302,6 +302,36 @@ class Ocean:
         nat.check(nat.lib().mw_ocean_query_surface_device(self._h, int(frame), self._QUERY_MODES[mode], C.c_void_p(d_xz), int(n),
                                                            int(iterations), C.c_void_p(d_out)))
 
+    # -- surface velocity (mw_ocean_velocity) --------------------------------------------------
+    def _velocity_vertices(self):
+        return self.N * self.N if self.semantics == nat.MW_SEM_FFTMESH else self.mesh_resolution * self.mesh_resolution
+
+    def velocity(self, frame: int = -1):
+        """Time derivative of the vertices of the frame query_surface reads -> [n, 3] float32, computed from the spectrum.
+        FFTMesh: per unit of the time argument t (divide by t_division for per second of Update's deltaTime);
+        OceanRenderer: per second of delta_time, at the handle's current phase (frame -1, or the last frame of the latest steps call)."""
+        out = np.empty((self._velocity_vertices(), 3), np.float32)
+        nat.check(nat.lib().mw_ocean_velocity(self._h, int(frame), _p(out)))
+        return out
+
+    def velocity_device(self, d_velocity: int, frame: int = -1):
+        """Device-pointer form: d_velocity [n][3] float32; asynchronous on the handle's stream."""
+        nat.check(nat.lib().mw_ocean_velocity_device(self._h, int(frame), C.c_void_p(d_velocity)))
+
+    def query_velocity(self, xz, mode: str = "world", frame: int = -1, iterations: int = 0):
+        """Velocity of the water at horizontal points xz [n, 2], located exactly as query_surface locates them -> [n, 4] float32
+        rows (vx, vy, vz, residual); units as velocity()."""
+        xz = np.ascontiguousarray(xz, np.float32).reshape(-1, 2)
+        out = np.empty((xz.shape[0], 4), np.float32)
+        nat.check(nat.lib().mw_ocean_query_velocity(self._h, int(frame), self._QUERY_MODES[mode], _p(xz), xz.shape[0],
+                                                     int(iterations), _p(out)))
+        return out
+
+    def query_velocity_device(self, d_xz: int, n: int, d_out: int, mode: str = "world", frame: int = -1, iterations: int = 0):
+        """Device-pointer form: d_xz [n][2] (8-byte aligned), d_out [n][4] (16-byte aligned) float32; asynchronous."""
+        nat.check(nat.lib().mw_ocean_query_velocity_device(self._h, int(frame), self._QUERY_MODES[mode], C.c_void_p(d_xz), int(n),
+                                                            int(iterations), C.c_void_p(d_out)))
+
 
 class _Mesh:
     """The handful of UnityEngine.Mesh members the reference assigns (S/FFTMesh.cs:134-138,277-279)."""
