@@ -129,6 +129,20 @@ public class FFTMesh : MonoBehaviour
             for (int c = 0; c < 3; c++) result[4 * k + c] /= tDivision;
     }
 
+    /// Not in the reference: buoyancy and drag on bodies sharing one hull mesh, from the surface of the latest Update()
+    /// (mw_ocean_hull_forces).  result (8 floats per body) = force xyz, wetted area, torque xyz about the centre of mass, residual, in
+    /// the ocean's object space (unscaled ocean transform assumed: ocean.TransformDirection maps them to world space).  The water
+    /// velocity the drag uses is per second of Update's deltaTime (the library's value per unit of t, over tDivision).  Drag 0 computes no velocity.
+    public void HullForces(Mesh hull, Rigidbody[] bodies, float[] result, float density = 1000f, float linearDrag = 0f, float quadraticDrag = 0f)
+    {
+        if (result.Length < bodies.Length * 8) throw new ArgumentException("result needs 8 floats per body");
+        float[] hullXyz, packed;
+        int[] triangles;
+        Native.PackHull(transform, hull, bodies, out hullXyz, out triangles, out packed);
+        float[] coeffs = { density, -Physics.gravity.y, linearDrag, quadraticDrag, 1f / tDivision };
+        Native.Check(Native.mw_ocean_hull_forces(ocean, -1, hullXyz, hullXyz.Length / 3, triangles, triangles.Length / 3, packed, bodies.Length, coeffs, 0, result));
+    }
+
     /// Evaluate the ocean Unity itself generated: pass the reference's own htilde0 draws (verttilde / vertConj).
     public void SetSpectrum(Vector2[] h0, Vector2[] h0conj)
     {

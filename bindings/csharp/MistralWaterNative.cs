@@ -23,6 +23,7 @@ public static class MistralWaterNative
     public enum PondMode { Wave = 0, Gerstner = 1, GerstnerLevelOne = 2 }
     public const uint OutWhiteScalar = 0u, OutColorRgba = 1u;
     public const int QueryRest = 0, QueryWorld = 1;
+    public const int HullNCoeffs = 5;
 
     [StructLayout(LayoutKind.Sequential)]   // mw_params: 56 bytes
     public struct Params
@@ -120,6 +121,10 @@ public static class MistralWaterNative
     [DllImport(Lib)] public static extern Status mw_ocean_velocity_device(IntPtr ocean, int frame, IntPtr dVelocity);
     [DllImport(Lib)] public static extern Status mw_ocean_query_velocity(IntPtr ocean, int frame, int mode, float[] xz, long n, int iterations, [Out] float[] result);
     [DllImport(Lib)] public static extern Status mw_ocean_query_velocity_device(IntPtr ocean, int frame, int mode, IntPtr dXz, long n, int iterations, IntPtr dResult);
+    // hull forces: hullXyz [nverts][3], triangles [ntris][3], bodies [nbodies][16] (p _ q v _ w _), coeffs [HullNCoeffs] (density, gravity,
+    // linearDrag, quadraticDrag, velocityScale) -> result [nbodies][8] = (Fx, Fy, Fz, wettedArea, tx, ty, tz, residual)
+    [DllImport(Lib)] public static extern Status mw_ocean_hull_forces(IntPtr ocean, int frame, float[] hullXyz, int nverts, int[] triangles, int ntris, float[] bodies, int nbodies, float[] coeffs, int iterations, [Out] float[] result);
+    [DllImport(Lib)] public static extern Status mw_ocean_hull_forces_device(IntPtr ocean, int frame, IntPtr dHullXyz, int nverts, IntPtr dTriangles, int ntris, IntPtr dBodies, int nbodies, float[] coeffs, int iterations, IntPtr dResult);
 
     // ---- page-locked output arrays ------------------------------------------------------------------------------
     [DllImport(Lib)] public static extern Status mw_host_register(IntPtr ptr, UIntPtr bytes);
@@ -158,6 +163,38 @@ public static class MistralWaterNative
     public static void Check(Status s)
     {
         if (s != Status.OK) throw new InvalidOperationException("libmistral_water: " + s + ": " + LastError());
+    }
+
+    /// Packs the arrays of mw_ocean_hull_forces for bodies that share one hull mesh (one prefab): the mesh's vertices about the
+    /// first body's centre of mass, scaled by its lossyScale (worldCenterOfMass = TransformPoint(centerOfMass)), its triangles, and
+    /// per body (p _ q v _ w _) in the OCEAN'S OBJECT SPACE -- the space of the ocean's vertex outputs -- with p the body's centre of
+    /// mass, so the torque the call returns is about it.  The ocean's transform is assumed unscaled (rotation and translation only);
+    /// forces and torques map back to world space with ocean.TransformDirection.
+    public static void PackHull(Transform ocean, Mesh hull, Rigidbody[] bodies, out float[] hullXyz, out int[] triangles, out float[] packed)
+    {
+        Vector3[] v = hull.vertices;
+        Vector3 s = bodies.Length > 0 ? bodies[0].transform.lossyScale : Vector3.one;
+        Vector3 c = bodies.Length > 0 ? bodies[0].centerOfMass : Vector3.zero;
+        hullXyz = new float[v.Length * 3];
+        for (int k = 0; k < v.Length; k++)
+        {
+            hullXyz[3 * k] = (v[k].x - c.x) * s.x; hullXyz[3 * k + 1] = (v[k].y - c.y) * s.y; hullXyz[3 * k + 2] = (v[k].z - c.z) * s.z;
+        }
+        triangles = hull.triangles;
+        packed = new float[bodies.Length * 16];
+        Quaternion inv = Quaternion.Inverse(ocean.rotation);
+        for (int b = 0; b < bodies.Length; b++)
+        {
+            Rigidbody r = bodies[b];
+            Vector3 p = ocean.InverseTransformPoint(r.worldCenterOfMass);
+            Quaternion q = inv * r.rotation;
+            Vector3 vel = ocean.InverseTransformDirection(r.velocity), w = ocean.InverseTransformDirection(r.angularVelocity);
+            int o = 16 * b;
+            packed[o] = p.x; packed[o + 1] = p.y; packed[o + 2] = p.z;
+            packed[o + 4] = q.x; packed[o + 5] = q.y; packed[o + 6] = q.z; packed[o + 7] = q.w;
+            packed[o + 8] = vel.x; packed[o + 9] = vel.y; packed[o + 10] = vel.z;
+            packed[o + 12] = w.x; packed[o + 13] = w.y; packed[o + 14] = w.z;
+        }
     }
 
     /// Page-locks a managed array for as long as the returned handle lives (mw_host_register): the per-frame copy of the

@@ -173,6 +173,20 @@ public class OceanRenderer : MonoBehaviour
         Native.Check(Native.mw_ocean_query_velocity(ocean, -1, world ? Native.QueryWorld : Native.QueryRest, xz, xz.Length / 2, 0, result));
     }
 
+    /// Not in the reference: buoyancy and drag on bodies sharing one hull mesh, from the surface of the latest GenerateTexture()
+    /// (mw_ocean_hull_forces).  result (8 floats per body) = force xyz, wetted area, torque xyz about the centre of mass, residual, in
+    /// the ocean's object space (unscaled ocean transform assumed: ocean.TransformDirection maps them to world space).  The water
+    /// velocity the drag uses is per second of Update's deltaTime (mult included).  Drag 0 computes no velocity.
+    public void HullForces(Mesh hull, Rigidbody[] bodies, float[] result, float density = 1000f, float linearDrag = 0f, float quadraticDrag = 0f)
+    {
+        if (result.Length < bodies.Length * 8) throw new ArgumentException("result needs 8 floats per body");
+        float[] hullXyz, packed;
+        int[] triangles;
+        Native.PackHull(transform, hull, bodies, out hullXyz, out triangles, out packed);
+        float[] coeffs = { density, -Physics.gravity.y, linearDrag, quadraticDrag, 1f };
+        Native.Check(Native.mw_ocean_hull_forces(ocean, -1, hullXyz, hullXyz.Length / 3, triangles, triangles.Length / 3, packed, bodies.Length, coeffs, 0, result));
+    }
+
     /// Checkpoint of the animation: initialTexture, the phase texture and the length the normal pass uses.  The last one differs
     /// from `length` after a length change: the reference sets normalMat._Length once in SetParams (S/OceanRenderer.cs:163).
     public void SaveState(Vector2[] h0, Vector2[] h0conj, float[] phase, out float normalLength)

@@ -312,6 +312,52 @@ mw_status mw_ocean_query_velocity(mw_ocean* o, int32_t frame, int32_t mode, cons
 mw_status mw_ocean_query_velocity_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xz, int64_t n,
                                          int32_t iterations, void* d_out);
 
+/* ---- hull forces: buoyancy and drag on floating bodies -----------------------------------------------------------
+ * The force and torque the water exerts on nbodies instances of one hull, from the displaced surface mw_ocean_query_surface reads
+ * and, with drag on, the velocity mw_ocean_query_velocity reads.  No rigid-body integration: the caller applies the result.
+ * Hull: one triangle mesh in body space, hull_xyz [nverts][3], triangles [ntris][3] (int32), shared by all bodies.  (b - a) x (c - a)
+ *   points OUT of the hull (the numeric convention of Unity's RecalculateNormals: a Unity mesh passes as it is).  The mesh need not
+ *   be closed, but the buoyancy is exactly Archimedes (rho g V_submerged through the centre of buoyancy, on flat water) only for a
+ *   closed mesh.
+ * Bodies: bodies [nbodies][16] floats (64 B per body; 16-byte aligned in the device form) = px py pz _ | qx qy qz qw | vx vy vz _ |
+ *   wx wy wz _: the reference point p (normally the centre of mass), the rotation q (normalised here), the linear velocity v and the
+ *   angular velocity w, all in the object space of the ocean's vertex outputs (the space of query xz).  Instance vertex x = p + R(q) h,
+ *   its velocity v + w x (x - p).
+ * Water at a vertex: eta = the world-mode query_surface height at (x.x, x.z), located exactly as that query locates it (same frame and
+ *   iterations, same walk), u = the water velocity at the same located point times velocity_scale (1 / t_division for FFTMesh gives
+ *   per-second units, 1 for OceanRenderer), depth d = eta - x.y.  The water velocity is the surface particle's at every depth (an
+ *   approximation: no attenuation of the orbital velocity with depth).
+ * Hydrostatics per triangle: the triangle clipped at d = 0 by linear interpolation along its edges (0, 1 or 2 submerged sub-triangles;
+ *   corners at d = 0 count as dry), per sub-triangle with corners x_i, depths d_i >= 0, D = sum d_i, S = (x1 - x0) x (x2 - x0) / 2,
+ *   r_i = x_i - p:  F = -rho g (D / 3) S,  tau = -(rho g / 12) (sum d_i r_i + D sum r_i) x S  -- the exact integrals of the linear
+ *   pressure rho g d over the sub-triangle.
+ * Drag per submerged sub-triangle, at its centroid c, area A, n = S / A: v_rel = v + w x (c - p) - u(c) (u at cut points interpolated
+ *   along the edge like d), F_lin = -linear_drag A v_rel, F_quad = -quadratic_drag A max(0, v_rel . n)^2 n (faces advancing into the
+ *   water only), tau = (c - p) x (F_lin + F_quad).
+ * coeffs [MW_HULL_NCOEFFS] (a host array in both forms) = density, gravity, linear_drag, quadratic_drag, velocity_scale.
+ * out [nbodies][8] = Fx Fy Fz wetted_area tx ty tz residual: total force, the summed area A of the submerged sub-triangles, torque
+ *   about p, and the largest world-mode residual over the body's vertices (NaN-propagating: it flags folds and hulls off the
+ *   footprint).  A body with a non-finite vertex, or a vertex whose query has no answer, gets a row of NaN; a body entirely above the
+ *   water gets exact zeros and its residual.  Every row is bitwise reproducible and independent of nbodies: body k alone gives the
+ *   bits body k gives in any batch.
+ * Frame and state: with linear_drag = quadratic_drag = 0 no velocity is computed and the rules are mw_ocean_query_surface's (frame -1,
+ *   or k of the latest OceanRenderer steps call); with drag on they are mw_ocean_query_velocity's, MW_ESTATE included once the spectrum
+ *   or phase moved past the latest frame.  The call changes nothing of the handle's state; its buffers (a vertex slab and per-chunk
+ *   partial sums) grow on demand and are freed by mw_ocean_destroy.
+ * MW_EINVAL for a batched handle, a NULL array with nbodies > 0 (coeffs always), nverts < 3 or ntris < 1, nbodies < 0,
+ *   nbodies * nverts or nbodies * ntris above 2^31 - 256, a negative or non-finite coefficient, a bad frame or iterations (as the
+ *   queries).  The host form also checks the triangle indices; in the device form an index outside [0, nverts) makes every row NaN
+ *   (the kernel checks each index and reads nothing out of range).  nbodies == 0 does nothing.                                  */
+#define MW_HULL_NCOEFFS 5
+/* host arrays, synchronous */
+mw_status mw_ocean_hull_forces(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles,
+                               int32_t ntris, const float* bodies, int32_t nbodies, const float* coeffs, int32_t iterations,
+                               float* out);
+/* device arrays (d_hull_xyz, d_triangles 4-byte, d_bodies, d_out 16-byte aligned), asynchronous on the handle's stream; coeffs host */
+mw_status mw_ocean_hull_forces_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
+                                      int32_t ntris, const void* d_bodies, int32_t nbodies, const float* coeffs,
+                                      int32_t iterations, void* d_out);
+
 /* ---- independent tiles on several devices (BASELINE configs[2]) ------------------------------------
  * Tiles are independent units in both semantics: tile k is the ocean of `params` with seed params->seed + k on its own
  * device, compute stream and output buffers; there is no data-path collective.  FFTMesh tiles advance up to max_steps

@@ -27,6 +27,7 @@
 #include "pond_kernels.h"
 #include "surface_query.h"
 #include "velocity_kernels.h"
+#include "hull_forces.h"
 static_assert(MW_SQ_REST == MW_QUERY_REST && MW_SQ_WORLD == MW_QUERY_WORLD, "surface_query.h and the ABI name the modes alike");
 
 #ifndef MW_WAVES_P1
@@ -564,6 +565,8 @@ struct mw_ocean {
     int or_steps_tail = -1;  // OceanRenderer: the last frame of the latest steps call while the phase is still that frame's, else -1
     bool frame_behind = false;  // the spectrum or the phase changed after the latest frame was made (mw_ocean_query_velocity refuses)
     VelState vel;            // mw_ocean_velocity: the weighted spectrum and the velocity buffers (velocity_kernels.h)
+    void* hull = nullptr;    // mw_ocean_hull_forces: vertex slab + chunk partials (hull_forces.h), grow-only
+    size_t hull_cap = 0;
     float* q_mesh = nullptr;  // OceanRenderer surface queries: the vertex stage of the queried frame, [res^2][3 + 3 + 1], allocated on first use
     void* scratch = nullptr;  // grow-only device staging of the host-pointer entry points (rest mesh, RGBA targets, ...):
     size_t scratch_cap = 0;   // allocated once at the largest size asked for, not per call
@@ -853,6 +856,7 @@ void mw_ocean_destroy(mw_ocean* o) {
     hipFree(o->h0); hipFree(o->h0c); hipFree(o->PQt); hipFree(o->Om); hipFree(o->dPQ_i0); hipFree(o->dPQ_j0);
     hipFree(o->TW); hipFree(o->TW2); hipFree(o->Wpre); hipFree(o->p1_jobs); hipFree(o->E); hipFree(o->Cj0); hipFree(o->s_vert); hipFree(o->s_norm); hipFree(o->s_white); hipFree(o->q_mesh); hipFree(o->scratch);
     vel_free(o->vel);
+    hipFree(o->hull);
     direct_free(o->direct);
     or_free(o->orr);
     if (o->own_stream) hipStreamDestroy(o->own_stream);
@@ -1671,6 +1675,116 @@ mw_status mw_ocean_query_velocity(mw_ocean* o, int32_t frame, int32_t mode, cons
     HIP_TRY(hipMemcpyAsync(base, xz, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, o->stream));
     if ((s = query_velocity_launch(o, m, mode, base, n, iterations, base + bin)) != MW_OK) return s;
     HIP_TRY(hipMemcpyAsync(out, base + bin, bout, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    return MW_OK;
+}
+
+// ---- hull forces (csrc/hull_forces.h) -----------------------------------------------------------------------------
+// Validates a hull-forces call and names the surface it reads: the surface query's rules and mesh (query_prepare) with drag off, the
+// velocity query's (query_velocity_prepare: frame rules of the velocity, MW_ESTATE once the spectrum or phase moved on) with drag on.
+static mw_status hull_prepare(mw_ocean* o, int32_t frame, const void* hull, int32_t nverts, const void* tris, int32_t ntris, const void* bodies,
+                              int32_t nbodies, const float* coeffs, int32_t iterations, const void* out, const char* who, SqMesh* m,
+                              HullCoeffs* cf, float* vscale) {
+    if (!o) return fail(MW_EINVAL, std::string(who) + ": NULL handle");
+    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
+        return fail(MW_EINVAL, std::string(who) + ": a batched handle (mw_ocean_create_batch) has no single surface");
+    if (nbodies < 0) return fail(MW_EINVAL, std::string(who) + ": nbodies < 0");
+    if (nverts < 3 || ntris < 1) return fail(MW_EINVAL, std::string(who) + ": a hull needs nverts >= 3 and ntris >= 1");
+    if (!coeffs) return fail(MW_EINVAL, std::string(who) + ": NULL coeffs");
+    if (nbodies > 0 && (!hull || !tris || !bodies || !out)) return fail(MW_EINVAL, std::string(who) + ": NULL array");
+    const int64_t lim = ((int64_t)1 << 31) - 256;
+    if ((int64_t)nbodies * nverts > lim || (int64_t)nbodies * ntris > lim)
+        return fail(MW_EINVAL, std::string(who) + ": nbodies * nverts and nbodies * ntris must not exceed 2^31 - 256");
+    for (int k = 0; k < MW_HULL_NCOEFFS; k++)
+        if (!(coeffs[k] >= 0.f && coeffs[k] <= 3.4e38f))
+            return fail(MW_EINVAL, std::string(who) + ": coefficients must be finite and >= 0");
+    cf->rho_g = coeffs[0] * coeffs[1];
+    cf->lin = coeffs[2];
+    cf->quad = coeffs[3];
+    cf->drag = (coeffs[2] > 0.f || coeffs[3] > 0.f) ? 1 : 0;
+    *vscale = coeffs[4];
+    // the surface (and, with drag on, the velocity) of the frame; the markers stand for the query's arrays, checked above
+    const void* mark = nbodies > 0 ? bodies : nullptr;
+    return cf->drag ? query_velocity_prepare(o, frame, MW_QUERY_WORLD, mark, nbodies, iterations, mark, who, m)
+                    : query_prepare(o, frame, MW_QUERY_WORLD, mark, nbodies, iterations, mark, who, m);
+}
+// the three launches on the handle's stream (nbodies > 0); the vertex slab and the chunk partials live in the handle's grow-only buffer
+static mw_status hull_launch(mw_ocean* o, const SqMesh& m, const HullCoeffs& cf, float vscale, int32_t iterations, const float* d_hull,
+                             int32_t nverts, const int32_t* d_tris, int32_t ntris, const void* d_bodies, int32_t nbodies, void* d_out) {
+    const int nchunks = (std::max(ntris, nverts) + MW_HULL_CHUNK - 1) / MW_HULL_CHUNK;
+    const size_t bslab = align256((size_t)nbodies * nverts * 8 * sizeof(float)), bpart = (size_t)nbodies * nchunks * 8 * sizeof(float);
+    if (o->hull_cap < bslab + bpart) {
+        if (o->hull) {
+            HIP_TRY(hipStreamSynchronize(o->stream));
+            HIP_TRY(hipFree(o->hull));
+            o->hull = nullptr;
+            o->hull_cap = 0;
+        }
+        if (hipMalloc(&o->hull, bslab + bpart) != hipSuccess) return fail(MW_ENOMEM, "hipMalloc of the hull-forces buffer failed");
+        o->hull_cap = bslab + bpart;
+    }
+    mw_status s;
+    if (cf.drag && ((s = velocity_stage(o)) != MW_OK || (s = velocity_run(o, o->vel.vert)) != MW_OK)) return s;
+    HullArgs a;
+    a.m = m;
+    a.vel = cf.drag ? o->vel.vert : nullptr;
+    a.vscale = vscale;
+    a.iters = iterations == 0 ? MW_SQ_DEFAULT_ITERS : iterations;
+    a.cf = cf;
+    a.hull = d_hull; a.tris = d_tris; a.bodies = static_cast<const float4*>(d_bodies);
+    a.nverts = nverts; a.ntris = ntris; a.nchunks = nchunks; a.nbodies = nbodies;
+    a.vslab = static_cast<float4*>(o->hull);
+    a.part = reinterpret_cast<float4*>(static_cast<char*>(o->hull) + bslab);
+    a.out = static_cast<float4*>(d_out);
+    const int64_t nv = (int64_t)nbodies * nverts, nblk = (int64_t)nbodies * nchunks;
+    k_hull_vertices<<<dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, o->stream>>>(a);
+    k_hull_triangles<<<dim3((unsigned)std::min<int64_t>(nblk, (int64_t)1 << 20)), dim3(MW_HULL_CHUNK), 0, o->stream>>>(a);
+    k_hull_reduce<<<dim3((unsigned)std::min<int64_t>(((int64_t)nbodies + 3) / 4, (int64_t)1 << 20)), dim3(256), 0, o->stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return MW_OK;
+}
+
+mw_status mw_ocean_hull_forces_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
+                                      int32_t ntris, const void* d_bodies, int32_t nbodies, const float* coeffs, int32_t iterations,
+                                      void* d_out) {
+    const char* who = "mw_ocean_hull_forces_device";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (nbodies > 0 && ((reinterpret_cast<uintptr_t>(d_hull_xyz) & 3) || (reinterpret_cast<uintptr_t>(d_triangles) & 3) ||
+                        (reinterpret_cast<uintptr_t>(d_bodies) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 15)))
+        return fail(MW_EINVAL, std::string(who) + ": d_hull_xyz and d_triangles must be 4-byte, d_bodies and d_out 16-byte aligned");
+    SqMesh m{};
+    HullCoeffs cf{};
+    float vscale = 0.f;
+    mw_status s = hull_prepare(o, frame, d_hull_xyz, nverts, d_triangles, ntris, d_bodies, nbodies, coeffs, iterations, d_out, who, &m, &cf,
+                               &vscale);
+    if (s != MW_OK || nbodies == 0) return s;
+    return hull_launch(o, m, cf, vscale, iterations, static_cast<const float*>(d_hull_xyz), nverts, static_cast<const int32_t*>(d_triangles),
+                       ntris, d_bodies, nbodies, d_out);
+}
+
+mw_status mw_ocean_hull_forces(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles, int32_t ntris,
+                               const float* bodies, int32_t nbodies, const float* coeffs, int32_t iterations, float* out) {
+    const char* who = "mw_ocean_hull_forces";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    SqMesh m{};
+    HullCoeffs cf{};
+    float vscale = 0.f;
+    mw_status s = hull_prepare(o, frame, hull_xyz, nverts, triangles, ntris, bodies, nbodies, coeffs, iterations, out, who, &m, &cf, &vscale);
+    if (s != MW_OK || nbodies == 0) return s;
+    for (int64_t k = 0; k < (int64_t)ntris * 3; k++)
+        if (triangles[k] < 0 || triangles[k] >= nverts) return fail(MW_EINVAL, std::string(who) + ": triangle index outside [0, nverts)");
+    const size_t bh = align256((size_t)nverts * 3 * sizeof(float)), bt = align256((size_t)ntris * 3 * sizeof(int32_t)),
+                 bb = align256((size_t)nbodies * 16 * sizeof(float)), bo = (size_t)nbodies * 8 * sizeof(float);
+    void* buf = nullptr;
+    if ((s = scratch_reserve(o, bh + bt + bb + bo, &buf)) != MW_OK) return s;
+    char* base = static_cast<char*>(buf);
+    HIP_TRY(hipMemcpyAsync(base, hull_xyz, (size_t)nverts * 3 * sizeof(float), hipMemcpyHostToDevice, o->stream));
+    HIP_TRY(hipMemcpyAsync(base + bh, triangles, (size_t)ntris * 3 * sizeof(int32_t), hipMemcpyHostToDevice, o->stream));
+    HIP_TRY(hipMemcpyAsync(base + bh + bt, bodies, (size_t)nbodies * 16 * sizeof(float), hipMemcpyHostToDevice, o->stream));
+    if ((s = hull_launch(o, m, cf, vscale, iterations, reinterpret_cast<const float*>(base), nverts, reinterpret_cast<const int32_t*>(base + bh),
+                         ntris, base + bh + bt, nbodies, base + bh + bt + bb)) != MW_OK)
+        return s;
+    HIP_TRY(hipMemcpyAsync(out, base + bh + bt + bb, bo, hipMemcpyDeviceToHost, o->stream));
     HIP_TRY(hipStreamSynchronize(o->stream));
     return MW_OK;
 }

@@ -52,6 +52,24 @@ inline void query_velocity(mw_ocean* o, int32_t frame, const std::vector<Vector2
                                   iterations, out.empty() ? nullptr : &out[0].velocity.x));
 }
 
+// mw_ocean_hull_forces: one body (64 B: reference point, rotation quaternion, velocity, angular velocity, in the ocean's object space)
+// and one answer (force, wetted area, torque about the reference point, residual)
+struct HullBody { Vector3 position; float pad0 = 0.f; float qx = 0.f, qy = 0.f, qz = 0.f, qw = 1.f; Vector3 velocity; float pad1 = 0.f;
+                  Vector3 angularVelocity; float pad2 = 0.f; };
+static_assert(sizeof(HullBody) == 64, "[nbodies][16] floats of mw_ocean_hull_forces");
+struct HullForce { Vector3 force; float wettedArea = 0.f; Vector3 torque; float residual = 0.f; };
+static_assert(sizeof(HullForce) == 32, "[nbodies][8] floats of mw_ocean_hull_forces");
+// hull: body-space vertices and triangles ((b - a) x (c - a) pointing out), shared by all bodies
+inline void hull_forces(mw_ocean* o, int32_t frame, const std::vector<Vector3>& hull, const std::vector<int32_t>& triangles,
+                        const std::vector<HullBody>& bodies, std::vector<HullForce>& out, float density, float gravity, float linearDrag,
+                        float quadraticDrag, float velocityScale) {
+    out.resize(bodies.size());
+    const float coeffs[MW_HULL_NCOEFFS] = {density, gravity, linearDrag, quadraticDrag, velocityScale};
+    check(mw_ocean_hull_forces(o, frame, hull.empty() ? nullptr : &hull[0].x, (int32_t)hull.size(), triangles.empty() ? nullptr : &triangles[0],
+                               (int32_t)(triangles.size() / 3), bodies.empty() ? nullptr : &bodies[0].position.x, (int32_t)bodies.size(),
+                               coeffs, 0, out.empty() ? nullptr : &out[0].force.x));
+}
+
 class FFTMesh {
 public:
     // ---- public Inspector fields, S/FFTMesh.cs:9-23 -------------------------------------------------
@@ -103,6 +121,13 @@ public:
     void QueryVelocity(const std::vector<Vector2>& xz, std::vector<VelocitySample>& out, bool world = true, int32_t iterations = 0) {
         query_velocity(ocean_, -1, xz, out, world, iterations);
         for (auto& s : out) { s.velocity.x /= tDivision; s.velocity.y /= tDivision; s.velocity.z /= tDivision; }
+    }
+    // Not in the reference: buoyancy and drag on bodies sharing one hull, from the latest EvaluateWaves() (drag uses the water's
+    // velocity per second of Update's deltaTime: the library's value over tDivision)
+    void HullForces(const std::vector<Vector3>& hull, const std::vector<int32_t>& triangles, const std::vector<HullBody>& bodies,
+                    std::vector<HullForce>& out, float density = 1000.f, float gravity = 9.81f, float linearDrag = 0.f,
+                    float quadraticDrag = 0.f) {
+        hull_forces(ocean_, -1, hull, triangles, bodies, out, density, gravity, linearDrag, quadraticDrag, 1.f / tDivision);
     }
     float timer() const { return timer_; }
     mw_ocean* handle() { return ocean_; }
@@ -199,6 +224,13 @@ public:
     }
     void QueryVelocity(const std::vector<Vector2>& xz, std::vector<VelocitySample>& out, bool world = true, int32_t iterations = 0) {
         query_velocity(ocean_, -1, xz, out, world, iterations);
+    }
+    // Not in the reference: buoyancy and drag on bodies sharing one hull, from the surface DisplaceMesh() describes (frame -1) or
+    // frame k of the latest steps call (drag on: frame -1 or the last one)
+    void HullForces(const std::vector<Vector3>& hull, const std::vector<int32_t>& triangles, const std::vector<HullBody>& bodies,
+                    std::vector<HullForce>& out, float density = 1000.f, float gravity = 9.81f, float linearDrag = 0.f,
+                    float quadraticDrag = 0.f, int32_t frame = -1) {
+        hull_forces(ocean_, frame, hull, triangles, bodies, out, density, gravity, linearDrag, quadraticDrag, 1.f);
     }
 
 private:

@@ -19,6 +19,16 @@ int main() {
         std::vector<VelocitySample> flow;
         m.QueryVelocity({{0.f, 0.f}}, flow);  // and how fast does it move there (per second)?
         std::printf("FFTMesh 256^2: water velocity at (0, 0) = (%.6g, %.6g, %.6g)\n", flow[0].velocity.x, flow[0].velocity.y, flow[0].velocity.z);
+        // and what does it do to a 2 x 1 x 4 crate floating at (0, 0, 0), moving at 1 m/s along x?
+        std::vector<Vector3> crate;
+        for (int k = 0; k < 8; k++) crate.push_back({k & 4 ? 1.f : -1.f, k & 2 ? 0.5f : -0.5f, k & 1 ? 2.f : -2.f});
+        const std::vector<int32_t> faces = {0, 1, 3, 0, 3, 2, 4, 6, 7, 4, 7, 5, 0, 4, 5, 0, 5, 1, 2, 3, 7, 2, 7, 6, 0, 2, 6, 0, 6, 4, 1, 5, 7, 1, 7, 3};
+        std::vector<HullBody> crates(1);
+        crates[0].velocity = {1.f, 0.f, 0.f};
+        std::vector<HullForce> push;
+        m.HullForces(crate, faces, crates, push, 1000.f, 9.81f, 10.f, 50.f);
+        std::printf("FFTMesh 256^2: force on the crate = (%.6g, %.6g, %.6g), wetted area %.4g\n", push[0].force.x, push[0].force.y,
+                    push[0].force.z, push[0].wettedArea);
         OceanRenderer r;
         r.resolution = 16; r.length = 60.f; r.amplitude = 0.41f; r.choppiness = 0.46f; r.mult = 1.5f; r.wind = {14.45f, 12.f};
         r.Awake();

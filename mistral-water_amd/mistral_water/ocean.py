@@ -333,6 +333,56 @@ class Ocean:
                                                             int(iterations), C.c_void_p(d_out)))
 
 
+    # -- hull forces (mw_ocean_hull_forces) ----------------------------------------------------
+    def _hull_coeffs(self, density, gravity, linear_drag, quadratic_drag, velocity_scale):
+        if velocity_scale is None:  # per second of delta_time: FFTMesh velocities are per unit of t = delta_time / t_division
+            velocity_scale = 1.0 / self.params.t_division if self.semantics == nat.MW_SEM_FFTMESH else 1.0
+        return np.asarray([density, gravity, linear_drag, quadratic_drag, velocity_scale], np.float32)
+
+    def hull_forces(self, hull_xyz, triangles, bodies, density=1000.0, gravity=9.81, linear_drag=0.0, quadratic_drag=0.0,
+                    velocity_scale=None, frame: int = -1, iterations: int = 0):
+        """Buoyancy and drag on nbodies instances of one hull -> [nbodies, 8] float32 rows (Fx, Fy, Fz, wetted_area, tx, ty, tz,
+        residual), torque about each body's reference point.  hull_xyz [nverts, 3] and triangles [ntris, 3] in body space,
+        (b - a) x (c - a) pointing out; bodies [nbodies, 16] (pack_bodies).  velocity_scale None: 1 / t_division (FFTMesh, per
+        second of delta_time) or 1 (OceanRenderer).  With both drag coefficients 0 no velocity is computed."""
+        hull = np.ascontiguousarray(hull_xyz, np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+        bodies = np.ascontiguousarray(bodies, np.float32).reshape(-1, 16)
+        cf = self._hull_coeffs(density, gravity, linear_drag, quadratic_drag, velocity_scale)
+        out = np.empty((bodies.shape[0], 8), np.float32)
+        nat.check(nat.lib().mw_ocean_hull_forces(self._h, int(frame), _p(hull), hull.shape[0], _p(tris), tris.shape[0], _p(bodies),
+                                                  bodies.shape[0], _p(cf), int(iterations), _p(out)))
+        return out
+
+    def hull_forces_device(self, d_hull_xyz: int, nverts: int, d_triangles: int, ntris: int, d_bodies: int, nbodies: int, d_out: int,
+                           density=1000.0, gravity=9.81, linear_drag=0.0, quadratic_drag=0.0, velocity_scale=None, frame: int = -1,
+                           iterations: int = 0):
+        """Device-pointer form: d_hull_xyz [nverts][3] float32, d_triangles [ntris][3] int32, d_bodies [nbodies][16] and d_out
+        [nbodies][8] float32 (16-byte aligned); asynchronous on the handle's stream.  Indices are not checked on the host: one
+        outside [0, nverts) makes every row NaN."""
+        cf = self._hull_coeffs(density, gravity, linear_drag, quadratic_drag, velocity_scale)
+        nat.check(nat.lib().mw_ocean_hull_forces_device(self._h, int(frame), C.c_void_p(d_hull_xyz), int(nverts), C.c_void_p(d_triangles),
+                                                         int(ntris), C.c_void_p(d_bodies), int(nbodies), _p(cf), int(iterations),
+                                                         C.c_void_p(d_out)))
+
+
+def pack_bodies(position, rotation=None, velocity=None, angular_velocity=None):
+    """bodies [n, 16] float32 for Ocean.hull_forces from position [n, 3], rotation quaternions [n, 4] (x, y, z, w; default identity),
+    velocity [n, 3] and angular_velocity [n, 3] (default 0), all in the ocean's object space."""
+    pos = np.asarray(position, np.float32).reshape(-1, 3)
+    n = pos.shape[0]
+    out = np.zeros((n, 16), np.float32)
+    out[:, 0:3] = pos
+    out[:, 7] = 1.0
+    if rotation is not None:
+        out[:, 4:8] = np.asarray(rotation, np.float32).reshape(n, 4)
+    if velocity is not None:
+        out[:, 8:11] = np.asarray(velocity, np.float32).reshape(n, 3)
+    if angular_velocity is not None:
+        out[:, 12:15] = np.asarray(angular_velocity, np.float32).reshape(n, 3)
+    return out
+
+
 class _Mesh:
     """The handful of UnityEngine.Mesh members the reference assigns (S/FFTMesh.cs:134-138,277-279)."""
     vertices = normals = colors = uv = indices = None
