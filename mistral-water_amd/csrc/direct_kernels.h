@@ -47,12 +47,16 @@ struct DirectState {
 };
 
 #if defined(__HIPCC__)
-// e^{i k_j pos_b}, S/FFTMesh.cs:201-208 (phase in f64), scattered into the four fixed GEMM operands
+// e^{i k_j pos_b}, S/FFTMesh.cs:201-208, scattered into the four fixed GEMM operands.  The wave number and the rest coordinate are formed
+// in f64 from the float32 length and unit width, as the chirp-z form's theta is: the float32 wave_k (PI = 3.1415926536f, three roundings)
+// is off by up to ~1e-7 relative, which at phases of thousands of radians (N > 2048, high wave numbers) moved outputs by 1e-4 of the
+// field scale and the normals of a Phillips sea at N = 4095 past the direct paths' 2e-5 (tests/test_direct_sizes_gpu.py)
 __global__ void k_direct_tables(int N, int Np, float length, float unit_width, float* B1re, float* B1im, float* A2re, float* A2im) {
     int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= N * N) return;
     const int j = idx / N, b = idx % N;
-    const double k = (double)wave_k(N, length, j), pos = (double)rest_coord(N, unit_width, b);
+    const double k = 2.0 * M_PI * ((double)j - N / 2.0) / (double)length;
+    const double pos = ((double)(b - N / 2) + (N % 2 == 0 ? 0.5 : 0.0)) * (double)unit_width;
     double s, c;
     sincos(k * pos, &s, &c);
     const float er = (float)c, ei = (float)s;

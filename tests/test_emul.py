@@ -326,13 +326,16 @@ def test_pipeline_random_inspector_settings(emul, oracle):
 
 
 @pytest.mark.parametrize("N,u,L", [(12, 1.0, 12.39), (33, 0.9, 33.0), (50, 1.0, 1.0), (64, 1.0, 64.0), (65, 0.5, 40.0), (100, 0.9, 100.0),
-                                   (200, 1.0, 212.5), (600, 1.0, 600.0)])
+                                   (200, 1.0, 212.5), (600, 1.0, 600.0), (256, 1.0, 248.5), (512, 1.0, 497.0), (1024, 1.0, 993.0),
+                                   (2048, 1.0, 1987.0)])
 def test_chirp_z_form_equals_the_separable_sum(emul, oracle, N, u, L):
     """czt_kernels.h: the reference's basis is bilinear in the two indices on ANY grid, k_i x_a = theta (i - N/2)(a - (N-1)/2), so one
     axis of S/FFTMesh.cs:199-217 is a chirp-modulated convolution: two Stockham transforms of size M >= 2N - 1 (the FFT path's own
     passes) instead of an O(N^2) sum.  The kernel's phase functions stepped on the host, both launches with their transposed
     stores, against the f64 matrix-product form of the oracle: the shipped scene, an odd grid, the Inspector defaults (phases up
-    to 3900 rad -- the chirps are reduced in f64), a commensurate grid, one past a power of two, M = 64 ... 2048."""
+    to 3900 rad -- the chirps are reduced in f64), a commensurate grid, one past a power of two, M = 64 ... 2048; and the powers of two
+    256 ... 2048 with a length that is not commensurate, where the packed planes' cyclic convolution is exactly full (N + 1 inputs and N
+    outputs: 2N lags in M = 2N slots, the largest negative lag in slot M / 2) -- M = 512 ... 4096."""
     p = oracle.Params(N=N, unit_width=u, length=L, wind_x=5.0, wind_y=3.0, amplitude=1.0 if L == 1.0 else 1e-3, choppiness=0.8)
     h0, h0c = oracle.generate_spectrum(p, 2)
     F = oracle.htilde_fields_f64(p, h0, h0c, 1.25)

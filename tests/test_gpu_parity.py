@@ -97,13 +97,15 @@ def test_fftmesh_survey_config2_literal_parameters(mw, oracle, N):
 
 @pytest.mark.parametrize("N,u,L,literal", [(64, 1.0, 64.0, False), (256, 0.5, 128.0, False), (512, 1.0, 512.0, False), (1024, 1.0, 1024.0, False),
                                            (2048, 1.0, 2048.0, False), (4096, 1.0, 4096.0, False), (12, 1.0, 12.39, False), (33, 0.9, 33.0, False),
-                                           (1024, 1.0, 1024.0, True), (4096, 1.0, 4096.0, True)])
+                                           (1024, 1.0, 1024.0, True), (4096, 1.0, 4096.0, True), (2048, 1.0, 1987.0, False),
+                                           (2049, 1.0, 2049.0, False)])
 def test_whitecap_stage_bit_exact_on_device(mw, oracle, N, u, L, literal):
     """The Jacobian / whitecap stage (S/FFTMesh.cs:251-276) is index and sign work once hds and the normals exist: forward
     differences, the i = N-1 and j = N-1 edge rules, strict-float32 J, noise, SmoothStep.  With hds taken from the device
     (mw_debug_evaluate_hds) the device's colours must equal the oracle's float32 whitecap of the SAME hds and normals bit
     for bit -- in every kernel family (8 and 4 rows + halo group, sequential halo with virtual threads, direct sum), which
-    also proves that a halo row handed to the previous workgroup is the very row its owner computed."""
+    also proves that a halo row handed to the previous workgroup is the very row its owner computed.  2048 with length 1987 runs the
+    chirp-z form at M = 4096, 2049 the GEMM form (k_direct_white)."""
     amp = 1.5e-8 * (1024.0 / N) ** 2 * u * u * 400.0          # steep enough that the mesh folds here and there
     p = oracle.Params(N=N, unit_width=u, length=L, wind_x=14.45, wind_y=12.0, amplitude=amp if N >= 64 else 0.01, choppiness=1.3)
     if literal:      # SURVEY 8d configs 2 / 4 literally (amplitude 0.41: what bench.py times) -- a saturated whitecap, so the
@@ -552,12 +554,15 @@ def test_direct_path_inspector_defaults(mw, oracle):
 
 @pytest.mark.parametrize("N,u,L", [(1000, 1.0, 1000.0), (200, 1.0, 212.5), (65, 0.5, 40.0)])
 def test_direct_path_large_and_odd_grids(mw, oracle, N, u, L):
-    """Grids the FFT cannot express, through the GEMM form of the separable sum (zero-padded to multiples of 64): N = 1000 (not
-    a power of two), a non-commensurate even grid, an odd grid one past a tile edge.  Checker: oracle.eval_matmul_f64."""
+    """Grids the FFT cannot express, through the chirp-z form of the separable sum (the product default for N <= 2048): N = 1000 (not
+    a power of two, M = 2048), a non-commensurate even grid (M = 512), an odd grid (M = 256, two launches).  Checker:
+    oracle.eval_matmul_f64.  The GEMM form is tested at its own sizes in tests/test_direct_sizes_gpu.py."""
     p = oracle.Params(N=N, unit_width=u, length=L, wind_x=14.45, wind_y=12.0, amplitude=1.5e-8 * (1024.0 / N) ** 2 * (L / N) ** 2, choppiness=0.46)
     h0, h0c = oracle.generate_spectrum(p, 4)
     rest = oracle.rest_mesh(p)[0]
     with make(mw, p) as o:
+        kinds = [k for k, _ in o.profile_kernels(nsteps=1, iters=2)]
+        assert kinds[0].startswith("k_czt") and ("rows_assemble" in kinds[1]) == (N <= 128), kinds
         o.set_spectrum(h0, h0c)
         for t in (0.5, 16.0):
             v, n, c = o.evaluate(t)

@@ -94,7 +94,8 @@ import mistral_water as mw, workloads
 from oracle import oracle as O
 mw.set_switch("MW_DIRECT_CZT", %(direct_czt)s)      # read when a handle is created
 for (N, u, L, amp, rel) in ((12, 1.0, 12.39, 0.01, 2e-5), (50, 1.0, 1.0, 1.0, %(inspector_rel)s), (65, 0.5, 40.0, 1e-5, 2e-5), (200, 1.0, 212.5, 4e-7, 2e-5),
-                            (1000, 1.0, 1000.0, 1.6e-8, 2e-5), (1500, 1.0, 1530.0, 7e-9, 2e-5)):      # 1500: M = 4096 = 16^3 (LastInRegs in k_czt)
+                            (1000, 1.0, 1000.0, 1.6e-8, 2e-5), (1500, 1.0, 1530.0, 7e-9, 2e-5),      # 1500: M = 4096 = 16^3 (LastInRegs in k_czt)
+                            (2048, 1.0, 2000.0, 3.6e-9, 2e-5)):      # 2048 with length 2000: the chirp-z convolution exactly full (2N = M = 4096)
     p = O.Params(N=N, unit_width=u, length=L, wind_x=5.0 if N < 100 else 14.45, wind_y=3.0 if N < 100 else 12.0, amplitude=amp, choppiness=0.8)
     h0, h0c = O.generate_spectrum(p, 4)
     rest = O.rest_mesh(p)[0]
@@ -112,7 +113,8 @@ print("CZT_OK")
 def test_both_forms_of_the_direct_sum(form):
     """The two forms of the separable sum through the C ABI, each in a child process with its selector set: the chirp-z form
     (csrc/czt_kernels.h, the default for N <= 2048) and the MFMA GEMM form (csrc/direct_kernels.h, MW_DIRECT_CZT=0: larger grids and
-    A/B) -- the shipped scene, the Inspector defaults, an odd grid, a non-commensurate grid and N = 1000 against the f64 oracle.
+    A/B) -- the shipped scene, the Inspector defaults, an odd grid, a non-commensurate grid, N = 1000 and N = 2048 with length 2000
+    (the largest chirp-z grid, where its cyclic convolution is exactly full) against the f64 oracle.
     Chirp-z: the FFT path's tolerance class everywhere (2e-5 stated; measured 2-5e-7), also on the Inspector-default grid, where a
     phase reaches 3900 rad and the float32 GEMM form needs 2e-4."""
     repo = REPO
