@@ -24,6 +24,7 @@ public static class MistralWaterNative
     public const uint OutWhiteScalar = 0u, OutColorRgba = 1u;
     public const int QueryRest = 0, QueryWorld = 1;
     public const int HullNCoeffs = 5;
+    public const int BodyNMass = 8;
 
     [StructLayout(LayoutKind.Sequential)]   // mw_params: 56 bytes
     public struct Params
@@ -125,6 +126,11 @@ public static class MistralWaterNative
     // linearDrag, quadraticDrag, velocityScale) -> result [nbodies][8] = (Fx, Fy, Fz, wettedArea, tx, ty, tz, residual)
     [DllImport(Lib)] public static extern Status mw_ocean_hull_forces(IntPtr ocean, int frame, float[] hullXyz, int nverts, int[] triangles, int ntris, float[] bodies, int nbodies, float[] coeffs, int iterations, [Out] float[] result);
     [DllImport(Lib)] public static extern Status mw_ocean_hull_forces_device(IntPtr ocean, int frame, IntPtr dHullXyz, int nverts, IntPtr dTriangles, int ntris, IntPtr dBodies, int nbodies, float[] coeffs, int iterations, IntPtr dResult);
+    // floating bodies: massProperties [10] = (mass, centroid xyz, Ixx Iyy Izz Ixy Ixz Iyz); bodies [nbodies][16] updated in place, mass
+    // [nbodies][BodyNMass] = (m, Ixx, Iyy, Izz, Ixy, Ixz, Iyz, 0) about the centre of mass, result [nbodies][8] or null (the last substep's row)
+    [DllImport(Lib)] public static extern Status mw_hull_mass_properties(float[] hullXyz, int nverts, int[] triangles, int ntris, float density, [Out] float[] massProperties);
+    [DllImport(Lib)] public static extern Status mw_ocean_step_bodies(IntPtr ocean, int frame, float[] hullXyz, int nverts, int[] triangles, int ntris, [In] [Out] float[] bodies, float[] mass, int nbodies, float[] coeffs, float dt, int substeps, int iterations, [Out] float[] result);
+    [DllImport(Lib)] public static extern Status mw_ocean_step_bodies_device(IntPtr ocean, int frame, IntPtr dHullXyz, int nverts, IntPtr dTriangles, int ntris, IntPtr dBodies, IntPtr dMass, int nbodies, float[] coeffs, float dt, int substeps, int iterations, IntPtr dResult);
 
     // ---- page-locked output arrays ------------------------------------------------------------------------------
     [DllImport(Lib)] public static extern Status mw_host_register(IntPtr ptr, UIntPtr bytes);

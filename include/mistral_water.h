@@ -314,7 +314,8 @@ mw_status mw_ocean_query_velocity_device(mw_ocean* o, int32_t frame, int32_t mod
 
 /* ---- hull forces: buoyancy and drag on floating bodies -----------------------------------------------------------
  * The force and torque the water exerts on nbodies instances of one hull, from the displaced surface mw_ocean_query_surface reads
- * and, with drag on, the velocity mw_ocean_query_velocity reads.  No rigid-body integration: the caller applies the result.
+ * and, with drag on, the velocity mw_ocean_query_velocity reads.  No rigid-body integration: the caller applies the result
+ *   (or mw_ocean_step_bodies integrates it on the device).
  * Hull: one triangle mesh in body space, hull_xyz [nverts][3], triangles [ntris][3] (int32), shared by all bodies.  (b - a) x (c - a)
  *   points OUT of the hull (the numeric convention of Unity's RecalculateNormals: a Unity mesh passes as it is).  The mesh need not
  *   be closed, but the buoyancy is exactly Archimedes (rho g V_submerged through the centre of buoyancy, on flat water) only for a
@@ -357,6 +358,48 @@ mw_status mw_ocean_hull_forces(mw_ocean* o, int32_t frame, const float* hull_xyz
 mw_status mw_ocean_hull_forces_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
                                       int32_t ntris, const void* d_bodies, int32_t nbodies, const float* coeffs,
                                       int32_t iterations, void* d_out);
+
+/* ---- floating bodies: step many rigid hulls on the ocean in one call ---------------------------------------------
+ * mw_ocean_step_bodies advances nbodies instances of one hull by dt under the forces mw_ocean_hull_forces computes, in `substeps`
+ * substeps, on the device: the state crosses the API once per call, not once per substep.
+ * Inputs: frame, hull_xyz / triangles, iterations and coeffs [MW_HULL_NCOEFFS] (density, gravity, linear_drag, quadratic_drag,
+ *   velocity_scale) mean exactly what they mean in mw_ocean_hull_forces; gravity also accelerates the bodies (along -y).  The hull must
+ *   be expressed about the centre of mass p (mw_hull_mass_properties gives the centroid to subtract).  bodies [nbodies][16] (p _ q v _
+ *   w _, as in mw_ocean_hull_forces) is updated in place; floats 3, 11 and 15 of a body pass through unchanged.  mass [nbodies]
+ *   [MW_BODY_NMASS] = m Ixx Iyy Izz Ixy Ixz Iyz 0: the mass and the inertia tensor's entries about p in body axes (Ixy = -int xy dm).
+ *   out [nbodies][8] is optional (NULL allowed): the hull-forces row of the LAST substep, evaluated at the state at its start.
+ * Integrator: semi-implicit Euler with h = dt / substeps (computed once in f32).  Each substep, in this order:
+ *   1. the row (F, A, tau) at the current state, exactly as mw_ocean_hull_forces computes it;
+ *   2. v <- v + h (F / m + (0, -g, 0)),  g = coeffs[1];
+ *   3. w <- w + h I_w^-1 (tau - w x (I_w w)),  I_w = R I_b R^T, I_w^-1 = R I_b^-1 R^T, R the rotation of q;
+ *   4. p <- p + h v;
+ *   5. q <- normalize(q + (h / 2) (w, 0) (x) q).
+ * Frozen surface: every substep reads the same frame's surface and, with drag on, the same velocity field, computed once per call;
+ *   the caller advances the ocean between calls.  The frame and state rules are mw_ocean_hull_forces', MW_ESTATE included.  The call
+ *   changes nothing of the handle's state; its buffers grow on demand and are freed by mw_ocean_destroy.
+ * Failures: a substep whose row is NaN (a vertex off the footprint, a non-finite pose, a bad device index) leaves the body with the bits
+ *   it had at the start of that substep for the rest of the call, and its out row is NaN.  A mass row is invalid when m <= 0 or not
+ *   finite, or when I_b is not positive definite in f32 (leading minors): the host form returns MW_EINVAL naming the body, the device
+ *   form gives that body a NaN row and leaves its state unchanged.
+ * MW_EINVAL for substeps outside [1, 64], a negative or non-finite dt, a NULL mass with nbodies > 0, the argument rules of
+ *   mw_ocean_hull_forces (out excepted) and misalignment (device form: d_hull_xyz and d_triangles 4-byte, d_bodies, d_mass and d_out
+ *   16-byte aligned).  nbodies == 0 does nothing.
+ * Reproducibility: a body's result depends only on its own inputs: it has the same bits alone as in a batch of any size.
+ * mw_hull_mass_properties (host arrays, no device needed): out[10] = mass, cx cy cz (the centroid, hull space), Ixx Iyy Izz Ixy Ixz
+ *   Iyz (the inertia tensor's entries about the centroid, hull axes; Ixy = -int xy dm) of the closed hull (outward winding) of uniform
+ *   density; sums in f64.  MW_EINVAL for a NULL array, nverts < 3 or ntris < 1, a bad index, a density not finite and > 0, or a
+ *   volume that is not positive (an open or inward-wound mesh).                                                                    */
+#define MW_BODY_NMASS 8   /* mass row: m Ixx Iyy Izz Ixy Ixz Iyz 0 -- about the centre of mass p, body axes */
+mw_status mw_hull_mass_properties(const float* hull_xyz, int32_t nverts, const int32_t* triangles, int32_t ntris, float density,
+                                  float* out);
+/* host arrays, synchronous */
+mw_status mw_ocean_step_bodies(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles,
+                               int32_t ntris, float* bodies, const float* mass, int32_t nbodies, const float* coeffs, float dt,
+                               int32_t substeps, int32_t iterations, float* out);
+/* device arrays, asynchronous on the handle's stream; coeffs host */
+mw_status mw_ocean_step_bodies_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
+                                      int32_t ntris, void* d_bodies, const void* d_mass, int32_t nbodies, const float* coeffs,
+                                      float dt, int32_t substeps, int32_t iterations, void* d_out);
 
 /* ---- independent tiles on several devices (BASELINE configs[2]) ------------------------------------
  * Tiles are independent units in both semantics: tile k is the ocean of `params` with seed params->seed + k on its own

@@ -28,6 +28,7 @@
 #include "surface_query.h"
 #include "velocity_kernels.h"
 #include "hull_forces.h"
+#include "rigid_bodies.h"
 static_assert(MW_SQ_REST == MW_QUERY_REST && MW_SQ_WORLD == MW_QUERY_WORLD, "surface_query.h and the ABI name the modes alike");
 
 #ifndef MW_WAVES_P1
@@ -567,6 +568,8 @@ struct mw_ocean {
     VelState vel;            // mw_ocean_velocity: the weighted spectrum and the velocity buffers (velocity_kernels.h)
     void* hull = nullptr;    // mw_ocean_hull_forces: vertex slab + chunk partials (hull_forces.h), grow-only
     size_t hull_cap = 0;
+    void* bodies = nullptr;  // mw_ocean_step_bodies, per-substep plan: the rows of a substep [nbodies][8], grow-only
+    size_t bodies_cap = 0;
     float* q_mesh = nullptr;  // OceanRenderer surface queries: the vertex stage of the queried frame, [res^2][3 + 3 + 1], allocated on first use
     void* scratch = nullptr;  // grow-only device staging of the host-pointer entry points (rest mesh, RGBA targets, ...):
     size_t scratch_cap = 0;   // allocated once at the largest size asked for, not per call
@@ -857,6 +860,7 @@ void mw_ocean_destroy(mw_ocean* o) {
     hipFree(o->TW); hipFree(o->TW2); hipFree(o->Wpre); hipFree(o->p1_jobs); hipFree(o->E); hipFree(o->Cj0); hipFree(o->s_vert); hipFree(o->s_norm); hipFree(o->s_white); hipFree(o->q_mesh); hipFree(o->scratch);
     vel_free(o->vel);
     hipFree(o->hull);
+    hipFree(o->bodies);
     direct_free(o->direct);
     or_free(o->orr);
     if (o->own_stream) hipStreamDestroy(o->own_stream);
@@ -1708,9 +1712,11 @@ static mw_status hull_prepare(mw_ocean* o, int32_t frame, const void* hull, int3
     return cf->drag ? query_velocity_prepare(o, frame, MW_QUERY_WORLD, mark, nbodies, iterations, mark, who, m)
                     : query_prepare(o, frame, MW_QUERY_WORLD, mark, nbodies, iterations, mark, who, m);
 }
-// the three launches on the handle's stream (nbodies > 0); the vertex slab and the chunk partials live in the handle's grow-only buffer
+// the three launches on the handle's stream (nbodies > 0); the vertex slab and the chunk partials live in the handle's grow-only buffer.
+// velocity = false: the velocity field of this frame is already in o->vel.vert (mw_ocean_step_bodies computes it once per call)
 static mw_status hull_launch(mw_ocean* o, const SqMesh& m, const HullCoeffs& cf, float vscale, int32_t iterations, const float* d_hull,
-                             int32_t nverts, const int32_t* d_tris, int32_t ntris, const void* d_bodies, int32_t nbodies, void* d_out) {
+                             int32_t nverts, const int32_t* d_tris, int32_t ntris, const void* d_bodies, int32_t nbodies, void* d_out,
+                             bool velocity = true) {
     const int nchunks = (std::max(ntris, nverts) + MW_HULL_CHUNK - 1) / MW_HULL_CHUNK;
     const size_t bslab = align256((size_t)nbodies * nverts * 8 * sizeof(float)), bpart = (size_t)nbodies * nchunks * 8 * sizeof(float);
     if (o->hull_cap < bslab + bpart) {
@@ -1724,7 +1730,7 @@ static mw_status hull_launch(mw_ocean* o, const SqMesh& m, const HullCoeffs& cf,
         o->hull_cap = bslab + bpart;
     }
     mw_status s;
-    if (cf.drag && ((s = velocity_stage(o)) != MW_OK || (s = velocity_run(o, o->vel.vert)) != MW_OK)) return s;
+    if (velocity && cf.drag && ((s = velocity_stage(o)) != MW_OK || (s = velocity_run(o, o->vel.vert)) != MW_OK)) return s;
     HullArgs a;
     a.m = m;
     a.vel = cf.drag ? o->vel.vert : nullptr;
@@ -1785,6 +1791,183 @@ mw_status mw_ocean_hull_forces(mw_ocean* o, int32_t frame, const float* hull_xyz
                          ntris, base + bh + bt, nbodies, base + bh + bt + bb)) != MW_OK)
         return s;
     HIP_TRY(hipMemcpyAsync(out, base + bh + bt + bb, bo, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    return MW_OK;
+}
+
+// ---- floating bodies (csrc/rigid_bodies.h) ------------------------------------------------------------------------
+static_assert(MW_BODY_NMASS == 8, "rigid_bodies.h reads 8 floats per mass row");
+// dynamic LDS k_bodies_step may take: one MI355X CU's 160 KiB less 1 KiB for its static arrays
+#define MW_BODIES_LDS_MAX (160 * 1024 - 1024)
+
+mw_status mw_hull_mass_properties(const float* hull_xyz, int32_t nverts, const int32_t* triangles, int32_t ntris, float density,
+                                  float* out) {
+    const char* who = "mw_hull_mass_properties";
+    if (!hull_xyz || !triangles || !out) return fail(MW_EINVAL, std::string(who) + ": NULL array");
+    if (nverts < 3 || ntris < 1) return fail(MW_EINVAL, std::string(who) + ": a hull needs nverts >= 3 and ntris >= 1");
+    if (!(density > 0.f && density <= 3.4e38f)) return fail(MW_EINVAL, std::string(who) + ": density must be finite and > 0");
+    for (int64_t k = 0; k < (int64_t)ntris * 3; k++)
+        if (triangles[k] < 0 || triangles[k] >= nverts) return fail(MW_EINVAL, std::string(who) + ": triangle index outside [0, nverts)");
+    // signed tetrahedra from the vertex mean o (conditioning): volume, first and second moments, all f64
+    double o3[3] = {0.0, 0.0, 0.0};
+    for (int v = 0; v < nverts; v++)
+        for (int c = 0; c < 3; c++) o3[c] += hull_xyz[3 * v + c];
+    for (int c = 0; c < 3; c++) o3[c] /= nverts;
+    double V = 0.0, M1[3] = {0.0, 0.0, 0.0}, M2[3][3] = {{0.0}};
+    for (int t = 0; t < ntris; t++) {
+        double p[3][3], s[3];
+        for (int i = 0; i < 3; i++)
+            for (int c = 0; c < 3; c++) p[i][c] = (double)hull_xyz[3 * triangles[3 * t + i] + c] - o3[c];
+        const double vt = (p[0][0] * (p[1][1] * p[2][2] - p[1][2] * p[2][1]) - p[0][1] * (p[1][0] * p[2][2] - p[1][2] * p[2][0]) +
+                           p[0][2] * (p[1][0] * p[2][1] - p[1][1] * p[2][0])) / 6.0;
+        for (int c = 0; c < 3; c++) s[c] = p[0][c] + p[1][c] + p[2][c];
+        V += vt;
+        for (int c = 0; c < 3; c++) M1[c] += vt * s[c] / 4.0;
+        // int x_i x_j over the tetrahedron (0, a, b, c) = V / 20 (sum_k a_i a_j + s_i s_j)
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++)
+                M2[i][j] += vt / 20.0 * (p[0][i] * p[0][j] + p[1][i] * p[1][j] + p[2][i] * p[2][j] + s[i] * s[j]);
+    }
+    if (!(V > 0.0) || !std::isfinite(V))
+        return fail(MW_EINVAL, std::string(who) + ": the hull's volume is not positive (an open or inward-wound mesh)");
+    double cen[3], C[3][3];
+    for (int c = 0; c < 3; c++) cen[c] = M1[c] / V;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) C[i][j] = density * (M2[i][j] - V * cen[i] * cen[j]);  // int x_i x_j dm about the centroid
+    out[0] = (float)(density * V);
+    for (int c = 0; c < 3; c++) out[1 + c] = (float)(cen[c] + o3[c]);
+    out[4] = (float)(C[1][1] + C[2][2]);
+    out[5] = (float)(C[0][0] + C[2][2]);
+    out[6] = (float)(C[0][0] + C[1][1]);
+    out[7] = (float)(-C[0][1]);
+    out[8] = (float)(-C[0][2]);
+    out[9] = (float)(-C[1][2]);
+    return MW_OK;
+}
+
+// Validates a step-bodies call: its own arguments, then the hull-forces rules (hull_prepare; out is optional here, so the bodies stand
+// in for it).  *g = coeffs[1].
+static mw_status bodies_prepare(mw_ocean* o, int32_t frame, const void* hull, int32_t nverts, const void* tris, int32_t ntris,
+                                const void* bodies, const void* mass, int32_t nbodies, const float* coeffs, float dt, int32_t substeps,
+                                int32_t iterations, const char* who, SqMesh* m, HullCoeffs* cf, float* vscale, float* g) {
+    if (!(substeps >= 1 && substeps <= 64)) return fail(MW_EINVAL, std::string(who) + ": substeps must be in [1, 64]");
+    if (!(dt >= 0.f && dt <= 3.4e38f)) return fail(MW_EINVAL, std::string(who) + ": dt must be finite and >= 0");
+    if (nbodies > 0 && !mass) return fail(MW_EINVAL, std::string(who) + ": NULL array");
+    mw_status s = hull_prepare(o, frame, hull, nverts, tris, ntris, bodies, nbodies, coeffs, iterations, bodies, who, m, cf, vscale);
+    if (s == MW_OK) *g = coeffs[1];
+    return s;
+}
+
+// The plan rule (MW_BODIES_PLAN = -1), DESIGN.md section 7e: one launch for hulls of at most 3 chunks (768 triangles and vertices),
+// per substep above.  Measured: 1024 icospheres (2 chunks) 0.49x the per-substep time; 64 barges (22 chunks) 1.8x.
+static bool bodies_one_launch_rule(int nchunks) { return nchunks < 4; }
+
+// every substep of the call on the handle's stream (nbodies > 0): the velocity field once (drag on), then one k_bodies_step launch, or
+// per substep hull_launch and k_bodies_integrate
+static mw_status bodies_launch(mw_ocean* o, const SqMesh& m, const HullCoeffs& cf, float vscale, float g, int32_t iterations,
+                               const float* d_hull, int32_t nverts, const int32_t* d_tris, int32_t ntris, void* d_bodies,
+                               const void* d_mass, int32_t nbodies, float dt, int32_t substeps, void* d_out) {
+    const int nchunks = (std::max(ntris, nverts) + MW_HULL_CHUNK - 1) / MW_HULL_CHUNK;
+    mw_status s;
+    if (cf.drag && ((s = velocity_stage(o)) != MW_OK || (s = velocity_run(o, o->vel.vert)) != MW_OK)) return s;
+    BodiesArgs a{};
+    a.h.m = m;
+    a.h.vel = cf.drag ? o->vel.vert : nullptr;
+    a.h.vscale = vscale;
+    a.h.iters = iterations == 0 ? MW_SQ_DEFAULT_ITERS : iterations;
+    a.h.cf = cf;
+    a.h.hull = d_hull; a.h.tris = d_tris; a.h.bodies = static_cast<const float4*>(d_bodies);
+    a.h.nverts = nverts; a.h.ntris = ntris; a.h.nchunks = nchunks; a.h.nbodies = nbodies;
+    a.bodies = static_cast<float4*>(d_bodies);
+    a.mass = static_cast<const float4*>(d_mass);
+    a.out = static_cast<float4*>(d_out);
+    a.g = g;
+    a.dt = dt / (float)substeps;
+    a.substeps = substeps;
+    const size_t lds = bodies_step_lds(nverts, nchunks);
+    const int plan = sw(SW_BODIES_PLAN);
+    if (lds <= MW_BODIES_LDS_MAX && (plan == 1 || (plan < 0 && bodies_one_launch_rule(nchunks)))) {
+        static AttrOnce attr;
+        HIP_TRY(attr.set(reinterpret_cast<const void*>(k_bodies_step), MW_BODIES_LDS_MAX));
+        k_bodies_step<<<dim3((unsigned)nbodies), dim3(MW_HULL_CHUNK), lds, o->stream>>>(a);
+        HIP_TRY(hipGetLastError());
+        return MW_OK;
+    }
+    const size_t brows = (size_t)nbodies * 8 * sizeof(float);
+    if (o->bodies_cap < brows) {
+        if (o->bodies) {
+            HIP_TRY(hipStreamSynchronize(o->stream));
+            HIP_TRY(hipFree(o->bodies));
+            o->bodies = nullptr;
+            o->bodies_cap = 0;
+        }
+        if (hipMalloc(&o->bodies, brows) != hipSuccess) return fail(MW_ENOMEM, "hipMalloc of the step-bodies row buffer failed");
+        o->bodies_cap = brows;
+    }
+    a.rows = static_cast<const float4*>(o->bodies);
+    for (int k = 0; k < substeps; k++) {
+        if ((s = hull_launch(o, m, cf, vscale, iterations, d_hull, nverts, d_tris, ntris, d_bodies, nbodies, o->bodies, false)) != MW_OK)
+            return s;
+        a.last = k == substeps - 1;
+        k_bodies_integrate<<<dim3((unsigned)(((int64_t)nbodies + 255) / 256)), dim3(256), 0, o->stream>>>(a);
+        HIP_TRY(hipGetLastError());
+    }
+    return MW_OK;
+}
+
+mw_status mw_ocean_step_bodies_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
+                                      int32_t ntris, void* d_bodies, const void* d_mass, int32_t nbodies, const float* coeffs,
+                                      float dt, int32_t substeps, int32_t iterations, void* d_out) {
+    const char* who = "mw_ocean_step_bodies_device";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (nbodies > 0 && ((reinterpret_cast<uintptr_t>(d_hull_xyz) & 3) || (reinterpret_cast<uintptr_t>(d_triangles) & 3) ||
+                        (reinterpret_cast<uintptr_t>(d_bodies) & 15) || (reinterpret_cast<uintptr_t>(d_mass) & 15) ||
+                        (reinterpret_cast<uintptr_t>(d_out) & 15)))
+        return fail(MW_EINVAL, std::string(who) + ": d_hull_xyz and d_triangles must be 4-byte, d_bodies, d_mass and d_out 16-byte aligned");
+    SqMesh m{};
+    HullCoeffs cf{};
+    float vscale = 0.f, g = 0.f;
+    mw_status s = bodies_prepare(o, frame, d_hull_xyz, nverts, d_triangles, ntris, d_bodies, d_mass, nbodies, coeffs, dt, substeps,
+                                 iterations, who, &m, &cf, &vscale, &g);
+    if (s != MW_OK || nbodies == 0) return s;
+    return bodies_launch(o, m, cf, vscale, g, iterations, static_cast<const float*>(d_hull_xyz), nverts,
+                         static_cast<const int32_t*>(d_triangles), ntris, d_bodies, d_mass, nbodies, dt, substeps, d_out);
+}
+
+mw_status mw_ocean_step_bodies(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles,
+                               int32_t ntris, float* bodies, const float* mass, int32_t nbodies, const float* coeffs, float dt,
+                               int32_t substeps, int32_t iterations, float* out) {
+    const char* who = "mw_ocean_step_bodies";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    SqMesh m{};
+    HullCoeffs cf{};
+    float vscale = 0.f, g = 0.f;
+    mw_status s = bodies_prepare(o, frame, hull_xyz, nverts, triangles, ntris, bodies, mass, nbodies, coeffs, dt, substeps, iterations,
+                                 who, &m, &cf, &vscale, &g);
+    if (s != MW_OK || nbodies == 0) return s;
+    for (int64_t k = 0; k < (int64_t)ntris * 3; k++)
+        if (triangles[k] < 0 || triangles[k] >= nverts) return fail(MW_EINVAL, std::string(who) + ": triangle index outside [0, nverts)");
+    for (int32_t b = 0; b < nbodies; b++)
+        if (!body_mass_valid(mass + 8 * (size_t)b))
+            return fail(MW_EINVAL, std::string(who) + ": the mass row of body " + std::to_string(b) +
+                                       " is invalid (m <= 0 or not finite, or I_b not positive definite)");
+    const size_t bh = align256((size_t)nverts * 3 * sizeof(float)), bt = align256((size_t)ntris * 3 * sizeof(int32_t)),
+                 bb = align256((size_t)nbodies * 16 * sizeof(float)), bm = align256((size_t)nbodies * 8 * sizeof(float)),
+                 bo = (size_t)nbodies * 8 * sizeof(float);
+    void* buf = nullptr;
+    if ((s = scratch_reserve(o, bh + bt + bb + bm + bo, &buf)) != MW_OK) return s;
+    char* base = static_cast<char*>(buf);
+    HIP_TRY(hipMemcpyAsync(base, hull_xyz, (size_t)nverts * 3 * sizeof(float), hipMemcpyHostToDevice, o->stream));
+    HIP_TRY(hipMemcpyAsync(base + bh, triangles, (size_t)ntris * 3 * sizeof(int32_t), hipMemcpyHostToDevice, o->stream));
+    HIP_TRY(hipMemcpyAsync(base + bh + bt, bodies, (size_t)nbodies * 16 * sizeof(float), hipMemcpyHostToDevice, o->stream));
+    HIP_TRY(hipMemcpyAsync(base + bh + bt + bb, mass, (size_t)nbodies * 8 * sizeof(float), hipMemcpyHostToDevice, o->stream));
+    char* d_out = out ? base + bh + bt + bb + bm : nullptr;
+    if ((s = bodies_launch(o, m, cf, vscale, g, iterations, reinterpret_cast<const float*>(base), nverts,
+                           reinterpret_cast<const int32_t*>(base + bh), ntris, base + bh + bt, base + bh + bt + bb, nbodies, dt, substeps,
+                           d_out)) != MW_OK)
+        return s;
+    HIP_TRY(hipMemcpyAsync(bodies, base + bh + bt, (size_t)nbodies * 16 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
+    if (out) HIP_TRY(hipMemcpyAsync(out, d_out, bo, hipMemcpyDeviceToHost, o->stream));
     HIP_TRY(hipStreamSynchronize(o->stream));
     return MW_OK;
 }

@@ -70,6 +70,39 @@ inline void hull_forces(mw_ocean* o, int32_t frame, const std::vector<Vector3>& 
                                coeffs, 0, out.empty() ? nullptr : &out[0].force.x));
 }
 
+// mw_hull_mass_properties: mass, centroid and inertia tensor entries (Ixx Iyy Izz Ixy Ixz Iyz, about the centroid) of a closed hull
+struct MassProperties { float mass = 0.f; Vector3 centroid; float inertia[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; };
+inline MassProperties hull_mass_properties(const std::vector<Vector3>& hull, const std::vector<int32_t>& triangles, float density) {
+    float o[10];
+    check(mw_hull_mass_properties(hull.empty() ? nullptr : &hull[0].x, (int32_t)hull.size(), triangles.empty() ? nullptr : &triangles[0],
+                                  (int32_t)(triangles.size() / 3), density, o));
+    MassProperties r;
+    r.mass = o[0];
+    r.centroid = {o[1], o[2], o[3]};
+    for (int k = 0; k < 6; k++) r.inertia[k] = o[4 + k];
+    return r;
+}
+// mw_ocean_step_bodies: one mass row (m, Ixx Iyy Izz Ixy Ixz Iyz about the centre of mass, body axes)
+struct BodyMass { float mass = 1.f; float inertia[6] = {1.f, 1.f, 1.f, 0.f, 0.f, 0.f}; float pad = 0.f; };
+static_assert(sizeof(BodyMass) == MW_BODY_NMASS * sizeof(float), "[nbodies][MW_BODY_NMASS] floats of mw_ocean_step_bodies");
+inline BodyMass body_mass(const MassProperties& p) {
+    BodyMass m;
+    m.mass = p.mass;
+    for (int k = 0; k < 6; k++) m.inertia[k] = p.inertia[k];
+    return m;
+}
+// bodies advanced in place by dt in `substeps` substeps on the frozen surface of `frame`; forces (optional) gets the last substep's rows
+inline void step_bodies(mw_ocean* o, int32_t frame, const std::vector<Vector3>& hull, const std::vector<int32_t>& triangles,
+                        std::vector<HullBody>& bodies, const std::vector<BodyMass>& mass, float dt, int32_t substeps, float density,
+                        float gravity, float linearDrag, float quadraticDrag, float velocityScale, std::vector<HullForce>* forces) {
+    if (forces) forces->resize(bodies.size());
+    const float coeffs[MW_HULL_NCOEFFS] = {density, gravity, linearDrag, quadraticDrag, velocityScale};
+    check(mw_ocean_step_bodies(o, frame, hull.empty() ? nullptr : &hull[0].x, (int32_t)hull.size(), triangles.empty() ? nullptr : &triangles[0],
+                               (int32_t)(triangles.size() / 3), bodies.empty() ? nullptr : &bodies[0].position.x,
+                               mass.empty() ? nullptr : &mass[0].mass, (int32_t)bodies.size(), coeffs, dt, substeps, 0,
+                               forces && !forces->empty() ? &(*forces)[0].force.x : nullptr));
+}
+
 class FFTMesh {
 public:
     // ---- public Inspector fields, S/FFTMesh.cs:9-23 -------------------------------------------------
@@ -128,6 +161,14 @@ public:
                     std::vector<HullForce>& out, float density = 1000.f, float gravity = 9.81f, float linearDrag = 0.f,
                     float quadraticDrag = 0.f) {
         hull_forces(ocean_, -1, hull, triangles, bodies, out, density, gravity, linearDrag, quadraticDrag, 1.f / tDivision);
+    }
+    // Not in the reference: advance bodies sharing one hull (about their centres of mass) by deltaTime seconds on the surface of the
+    // latest EvaluateWaves(), in `substeps` substeps on the device
+    void StepBodies(const std::vector<Vector3>& hull, const std::vector<int32_t>& triangles, std::vector<HullBody>& bodies,
+                    const std::vector<BodyMass>& mass, float deltaTime, int32_t substeps = 1, float density = 1000.f, float gravity = 9.81f,
+                    float linearDrag = 0.f, float quadraticDrag = 0.f, std::vector<HullForce>* forces = nullptr) {
+        step_bodies(ocean_, -1, hull, triangles, bodies, mass, deltaTime, substeps, density, gravity, linearDrag, quadraticDrag,
+                    1.f / tDivision, forces);
     }
     float timer() const { return timer_; }
     mw_ocean* handle() { return ocean_; }
@@ -231,6 +272,14 @@ public:
                     std::vector<HullForce>& out, float density = 1000.f, float gravity = 9.81f, float linearDrag = 0.f,
                     float quadraticDrag = 0.f, int32_t frame = -1) {
         hull_forces(ocean_, frame, hull, triangles, bodies, out, density, gravity, linearDrag, quadraticDrag, 1.f);
+    }
+    // Not in the reference: advance bodies sharing one hull (about their centres of mass) by deltaTime seconds on the surface
+    // DisplaceMesh() describes (frame -1) or frame k of the latest steps call, in `substeps` substeps on the device
+    void StepBodies(const std::vector<Vector3>& hull, const std::vector<int32_t>& triangles, std::vector<HullBody>& bodies,
+                    const std::vector<BodyMass>& mass, float deltaTime, int32_t substeps = 1, float density = 1000.f, float gravity = 9.81f,
+                    float linearDrag = 0.f, float quadraticDrag = 0.f, std::vector<HullForce>* forces = nullptr, int32_t frame = -1) {
+        step_bodies(ocean_, frame, hull, triangles, bodies, mass, deltaTime, substeps, density, gravity, linearDrag, quadraticDrag, 1.f,
+                    forces);
     }
 
 private:

@@ -22,6 +22,7 @@ MW_SEM_FFTMESH, MW_SEM_OCEANRENDERER = 0, 1
 MW_OUT_WHITE_SCALAR, MW_OUT_COLOR_RGBA = 0, 1
 MW_QUERY_REST, MW_QUERY_WORLD = 0, 1
 MW_HULL_NCOEFFS = 5
+MW_BODY_NMASS = 8
 STATUS_NAMES = {0: "MW_OK", 1: "MW_EINVAL", 2: "MW_ENOTPOW2", 3: "MW_ENOTCOMMENSURATE", 4: "MW_ENOMEM",
                 5: "MW_EDEVICE", 6: "MW_ESTATE"}
 
@@ -205,6 +206,11 @@ def lib():
         "mw_ocean_query_velocity_device": (C.c_int, [vp, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int32, vp]),
         "mw_ocean_hull_forces": (C.c_int, [vp, C.c_int32, f32p, C.c_int32, i32p, C.c_int32, f32p, C.c_int32, f32p, C.c_int32, f32p]),
         "mw_ocean_hull_forces_device": (C.c_int, [vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, f32p, C.c_int32, vp]),
+        "mw_hull_mass_properties": (C.c_int, [f32p, C.c_int32, i32p, C.c_int32, C.c_float, f32p]),
+        "mw_ocean_step_bodies": (C.c_int, [vp, C.c_int32, f32p, C.c_int32, i32p, C.c_int32, f32p, f32p, C.c_int32, f32p, C.c_float,
+                                           C.c_int32, C.c_int32, f32p]),
+        "mw_ocean_step_bodies_device": (C.c_int, [vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, f32p, C.c_float,
+                                                  C.c_int32, C.c_int32, vp]),
         "mw_ocean_profile_kernels": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
         "mw_ocean_profile_kernels_stats": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
         "mw_gerstner_displace": (C.c_int, [f32p, C.c_int64, f32p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
@@ -253,7 +259,7 @@ ABI_SYMBOLS = [
     "mw_ocean_generate_texture_steps", "mw_ocean_generate_texture_steps_rgba", "mw_ocean_max_frames", "mw_ocean_advance_phase", "mw_ocean_frame_textures", "mw_host_register", "mw_host_unregister", "mw_ocean_generate_texture_rgba", "mw_ocean_generate_texture_rgba_device",
     "mw_ocean_displace_mesh", "mw_ocean_displace_mesh_device", "mw_ocean_query_surface", "mw_ocean_query_surface_device",
     "mw_ocean_velocity", "mw_ocean_velocity_device", "mw_ocean_query_velocity", "mw_ocean_query_velocity_device",
-    "mw_ocean_hull_forces", "mw_ocean_hull_forces_device",
+    "mw_ocean_hull_forces", "mw_ocean_hull_forces_device", "mw_hull_mass_properties", "mw_ocean_step_bodies", "mw_ocean_step_bodies_device",
     "mw_gerstner_displace",
     "mw_gerstner_displace_device", "mw_gerstner_displace_steps_device", "mw_gerstner_max_steps", "mw_pond_displace", "mw_pond_displace_device",
 ]

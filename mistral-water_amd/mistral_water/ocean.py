@@ -366,6 +366,63 @@ class Ocean:
                                                          C.c_void_p(d_out)))
 
 
+    # -- floating bodies (mw_ocean_step_bodies) --------------------------------------------------
+    def step_bodies(self, hull_xyz, triangles, bodies, mass, dt, substeps: int = 1, density=1000.0, gravity=9.81, linear_drag=0.0,
+                    quadratic_drag=0.0, velocity_scale=None, frame: int = -1, iterations: int = 0, return_forces: bool = False):
+        """Advance nbodies instances of one hull by dt in `substeps` semi-implicit Euler substeps under buoyancy, drag and gravity, on
+        the frozen surface of `frame` -> bodies [nbodies, 16] float32 (p _ q v _ w _), and with return_forces the hull-forces rows
+        [nbodies, 8] of the last substep (at the state at its start).  bodies is updated in place when it is a C-contiguous float32
+        array (the same array is returned); mass [nbodies, 8] (pack_mass) about each body's centre of mass p, the hull about p too.
+        The other arguments mean what they mean in hull_forces; gravity also pulls the bodies along -y."""
+        hull = np.ascontiguousarray(hull_xyz, np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+        b = np.ascontiguousarray(bodies, np.float32).reshape(-1, 16)
+        m = np.ascontiguousarray(mass, np.float32).reshape(-1, nat.MW_BODY_NMASS)
+        if m.shape[0] != b.shape[0]:
+            raise ValueError(f"step_bodies: {b.shape[0]} bodies but {m.shape[0]} mass rows")
+        cf = self._hull_coeffs(density, gravity, linear_drag, quadratic_drag, velocity_scale)
+        out = np.empty((b.shape[0], 8), np.float32) if return_forces else None
+        nat.check(nat.lib().mw_ocean_step_bodies(self._h, int(frame), _p(hull), hull.shape[0], _p(tris), tris.shape[0], _p(b), _p(m),
+                                                  b.shape[0], _p(cf), float(dt), int(substeps), int(iterations),
+                                                  _p(out)))
+        return (b, out) if return_forces else b
+
+    def step_bodies_device(self, d_hull_xyz: int, nverts: int, d_triangles: int, ntris: int, d_bodies: int, d_mass: int, nbodies: int,
+                           dt, substeps: int = 1, d_out: int = 0, density=1000.0, gravity=9.81, linear_drag=0.0, quadratic_drag=0.0,
+                           velocity_scale=None, frame: int = -1, iterations: int = 0):
+        """Device-pointer form: d_bodies [nbodies][16] float32 updated in place, d_mass [nbodies][8], d_out [nbodies][8] or 0 (16-byte
+        aligned); asynchronous on the handle's stream.  An invalid mass row gives that body a NaN row and leaves it unchanged."""
+        cf = self._hull_coeffs(density, gravity, linear_drag, quadratic_drag, velocity_scale)
+        nat.check(nat.lib().mw_ocean_step_bodies_device(self._h, int(frame), C.c_void_p(d_hull_xyz), int(nverts), C.c_void_p(d_triangles),
+                                                         int(ntris), C.c_void_p(d_bodies), C.c_void_p(d_mass), int(nbodies), _p(cf),
+                                                         float(dt), int(substeps), int(iterations), C.c_void_p(d_out or None)))
+
+
+def hull_mass_properties(hull_xyz, triangles, density=1000.0):
+    """(mass, centroid [3], inertia [3, 3]) of the closed hull (outward winding) of uniform density: the inertia tensor about the
+    centroid in hull axes (off-diagonal entries -int x y dm), from mw_hull_mass_properties (f64 sums; no device needed)."""
+    hull = np.ascontiguousarray(hull_xyz, np.float32).reshape(-1, 3)
+    tris = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+    out = np.empty(10, np.float32)
+    nat.check(nat.lib().mw_hull_mass_properties(_p(hull), hull.shape[0], _p(tris), tris.shape[0], float(density), _p(out)))
+    xx, yy, zz, xy, xz, yz = (float(v) for v in out[4:10])
+    return float(out[0]), out[1:4].copy(), np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]], np.float32)
+
+
+def pack_mass(mass, inertia):
+    """mass rows [n, 8] float32 (m, Ixx, Iyy, Izz, Ixy, Ixz, Iyz, 0) for Ocean.step_bodies from mass [n] (or a scalar) and inertia
+    tensors [n, 3, 3] (or one [3, 3]) about the centre of mass in body axes; n is broadcast."""
+    m = np.atleast_1d(np.asarray(mass, np.float32))
+    I = np.asarray(inertia, np.float32).reshape(-1, 3, 3)
+    n = max(len(m), len(I))
+    m, I = np.broadcast_to(m, (n,)), np.broadcast_to(I, (n, 3, 3))
+    out = np.zeros((n, 8), np.float32)
+    out[:, 0] = m
+    out[:, 1], out[:, 2], out[:, 3] = I[:, 0, 0], I[:, 1, 1], I[:, 2, 2]
+    out[:, 4], out[:, 5], out[:, 6] = I[:, 0, 1], I[:, 0, 2], I[:, 1, 2]
+    return out
+
+
 def pack_bodies(position, rotation=None, velocity=None, angular_velocity=None):
     """bodies [n, 16] float32 for Ocean.hull_forces from position [n, 3], rotation quaternions [n, 4] (x, y, z, w; default identity),
     velocity [n, 3] and angular_velocity [n, 3] (default 0), all in the ocean's object space."""
