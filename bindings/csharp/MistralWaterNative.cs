@@ -131,6 +131,10 @@ public static class MistralWaterNative
     [DllImport(Lib)] public static extern Status mw_hull_mass_properties(float[] hullXyz, int nverts, int[] triangles, int ntris, float density, [Out] float[] massProperties);
     [DllImport(Lib)] public static extern Status mw_ocean_step_bodies(IntPtr ocean, int frame, float[] hullXyz, int nverts, int[] triangles, int ntris, [In] [Out] float[] bodies, float[] mass, int nbodies, float[] coeffs, float dt, int substeps, int iterations, [Out] float[] result);
     [DllImport(Lib)] public static extern Status mw_ocean_step_bodies_device(IntPtr ocean, int frame, IntPtr dHullXyz, int nverts, IntPtr dTriangles, int ntris, IntPtr dBodies, IntPtr dMass, int nbodies, float[] coeffs, float dt, int substeps, int iterations, IntPtr dResult);
+    // raycasts: rays [n][8] = (ox, oy, oz, tmin, dx, dy, dz, tmax) -> result [n][8] = (t, px, py, pz, nx, ny, nz, white), hit [n][2] =
+    // (triangle, facing) or null; a miss: t = +infinity, an invalid ray: NaN
+    [DllImport(Lib)] public static extern Status mw_ocean_raycast(IntPtr ocean, int frame, float[] rays, long n, [Out] float[] result, [Out] int[] hit);
+    [DllImport(Lib)] public static extern Status mw_ocean_raycast_device(IntPtr ocean, int frame, IntPtr dRays, long n, IntPtr dResult, IntPtr dHit);
 
     // ---- page-locked output arrays ------------------------------------------------------------------------------
     [DllImport(Lib)] public static extern Status mw_host_register(IntPtr ptr, UIntPtr bytes);

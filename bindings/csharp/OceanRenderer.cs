@@ -173,6 +173,18 @@ public class OceanRenderer : MonoBehaviour
         Native.Check(Native.mw_ocean_query_velocity(ocean, -1, world ? Native.QueryWorld : Native.QueryRest, xz, xz.Length / 2, 0, result));
     }
 
+    /// Not in the reference: the first hit of rays on the displaced surface of the latest GenerateTexture() (mw_ocean_raycast), in the
+    /// mesh's object space.  rays (8 floats per ray) = origin xyz, tmin, direction xyz, tmax: t is in units of the direction, a segment
+    /// p0 -> p1 is (p0, 0, p1 - p0, 1).  result (8 floats per ray) = t, point xyz, normal xyz, whitecap; t = +infinity on a miss, NaN
+    /// for an invalid ray.  hit (2 ints per ray, may be null) = triangle id, facing: +1 the ray met the water from above, -1 from below.
+    public void Raycast(float[] rays, float[] result, int[] hit = null)
+    {
+        if (rays.Length % 8 != 0) throw new ArgumentException("rays needs 8 floats per ray");
+        if (result.Length < rays.Length) throw new ArgumentException("result needs 8 floats per ray");
+        if (hit != null && hit.Length < rays.Length / 4) throw new ArgumentException("hit needs 2 ints per ray");
+        Native.Check(Native.mw_ocean_raycast(ocean, -1, rays, rays.Length / 8, result, hit));
+    }
+
     /// Not in the reference: buoyancy and drag on bodies sharing one hull mesh, from the surface of the latest GenerateTexture()
     /// (mw_ocean_hull_forces).  result (8 floats per body) = force xyz, wetted area, torque xyz about the centre of mass, residual, in
     /// the ocean's object space (unscaled ocean transform assumed: ocean.TransformDirection maps them to world space).  The water

@@ -401,6 +401,40 @@ mw_status mw_ocean_step_bodies_device(mw_ocean* o, int32_t frame, const void* d_
                                       int32_t ntris, void* d_bodies, const void* d_mass, int32_t nbodies, const float* coeffs,
                                       float dt, int32_t substeps, int32_t iterations, void* d_out);
 
+/* ---- raycasts: where does this ray hit the water? -----------------------------------------------------------------
+ * The first hit of each of n rays on the surface mw_ocean_query_surface reads, under its frame rules: FFTMesh frame -1 (the latest
+ *   frame); OceanRenderer -1 or frame k of the latest steps call.  Triangles: rest cell (i, j), i along x and j along z, holds the lower
+ *   triangle A B C = (i,j) (i+1,j) (i,j+1) and the upper triangle (i+1,j+1) (i+1,j) (i,j+1); triangle id = 2 * (i * (R-1) + j) + upper,
+ *   R the grid size (FFTMesh) or resolution (OceanRenderer), vertex (i, j) at i * R + j.
+ * rays [n][8] = ox oy oz tmin | dx dy dz tmax: the ray o + t d, t in units of d (d need not be unit length); a hit counts when
+ *   tmin <= t <= tmax, tmax = +inf allowed.  A segment p0 -> p1 is o = p0, d = p1 - p0, tmin = 0, tmax = 1.  A ray is invalid when o or
+ *   d is not finite, d = 0, tmin < 0, tmin > tmax, or tmin or tmax is NaN.
+ * Intersection: two-sided and watertight (Woop, Benthin and Wald 2013); every float32 operation is uncontracted and correctly rounded.
+ *   Per ray: kz = the axis of largest |d| (lowest index on ties), kx = (kz+1)%3, ky = (kx+1)%3, kx and ky swapped when d[kz] < 0;
+ *     Sx = d[kx]/d[kz], Sy = d[ky]/d[kz], Sz = 1/d[kz].
+ *   Per vertex P: P' = P - o; Px = P'[kx] - Sx*P'[kz], Py = P'[ky] - Sy*P'[kz], Pz = Sz*P'[kz].
+ *   Per triangle A B C: U = Cx*By - Cy*Bx, V = Ax*Cy - Ay*Cx, W = Bx*Ay - By*Ax, each recomputed in float64 from the same float32
+ *     values and rounded to float32 when it is exactly 0.  A hit when U, V and W are all >= 0 or all <= 0 and det = (U+V)+W != 0;
+ *     t = ((U*Az + V*Bz) + W*Cz) / det; the barycentric weights of A, B and C are U/det, V/det and W/det.
+ *   Each edge value is Qx*Py - Qy*Px of the edge's directed corners P -> Q.  A shared edge enters its two triangles in the same or in
+ *   opposite directions, so its two values are equal or exact negatives, and no ray slips between two triangles.
+ * First hit: the smallest accepted t over all triangles, ties to the smallest triangle id: a pure function of (mesh, ray), independent
+ *   of n, of the ray's place in the batch and of the acceleration structure.
+ * out [n][8] = t px py pz nx ny nz white: p = o + t d; the vertex normals interpolated with the hit's weights, then normalised (the
+ *   triangle's map is affine, so these are the rest-plane weights query_surface uses); white the whitecap channel, same weights.
+ * hit [n][2] int32 (optional, NULL allowed) = triangle id, facing: +1 when d . n_g < 0 in float64, n_g the displaced triangle's
+ *   geometric normal oriented as the rest triangle's +y (lower: (P(i,j+1) - P(i,j)) x (P(i+1,j) - P(i,j)); upper: (P(i+1,j) -
+ *   P(i+1,j+1)) x (P(i,j+1) - P(i+1,j+1))): the ray met the water from above; -1 otherwise: from below.
+ * A miss gives t = +inf, NaN in the other 7 floats and hit (-1, 0); an invalid ray NaN in all 8 and (-1, 0).  The status is MW_OK.
+ * MW_ESTATE before the first frame; MW_EINVAL for a batched handle, a bad frame, a NULL rays or out array with n > 0, n < 0 or
+ *   n > 2^32 - 256, and in the device form d_rays or d_out not 16-byte aligned or d_hit not 8-byte aligned.  n == 0 does nothing.
+ * Every call builds a bounds hierarchy of the surface on the handle's stream, in a buffer of the handle that
+ *   grows on demand and is freed by mw_ocean_destroy; the call changes nothing of the handle's state.                          */
+/* host arrays, synchronous */
+mw_status mw_ocean_raycast(mw_ocean* o, int32_t frame, const float* rays, int64_t n, float* out, int32_t* hit);
+/* device arrays, asynchronous on the handle's stream */
+mw_status mw_ocean_raycast_device(mw_ocean* o, int32_t frame, const void* d_rays, int64_t n, void* d_out, void* d_hit);
+
 /* ---- independent tiles on several devices (BASELINE configs[2]) ------------------------------------
  * Tiles are independent units in both semantics: tile k is the ocean of `params` with seed params->seed + k on its own
  * device, compute stream and output buffers; there is no data-path collective.  FFTMesh tiles advance up to max_steps

@@ -29,6 +29,7 @@
 #include "velocity_kernels.h"
 #include "hull_forces.h"
 #include "rigid_bodies.h"
+#include "raycast.h"
 static_assert(MW_SQ_REST == MW_QUERY_REST && MW_SQ_WORLD == MW_QUERY_WORLD, "surface_query.h and the ABI name the modes alike");
 
 #ifndef MW_WAVES_P1
@@ -570,6 +571,8 @@ struct mw_ocean {
     size_t hull_cap = 0;
     void* bodies = nullptr;  // mw_ocean_step_bodies, per-substep plan: the rows of a substep [nbodies][8], grow-only
     size_t bodies_cap = 0;
+    void* rc_tree = nullptr;  // mw_ocean_raycast: the bounds hierarchy of the queried surface (raycast.h), rebuilt every call, grow-only
+    size_t rc_cap = 0;
     float* q_mesh = nullptr;  // OceanRenderer surface queries: the vertex stage of the queried frame, [res^2][3 + 3 + 1], allocated on first use
     void* scratch = nullptr;  // grow-only device staging of the host-pointer entry points (rest mesh, RGBA targets, ...):
     size_t scratch_cap = 0;   // allocated once at the largest size asked for, not per call
@@ -861,6 +864,7 @@ void mw_ocean_destroy(mw_ocean* o) {
     vel_free(o->vel);
     hipFree(o->hull);
     hipFree(o->bodies);
+    hipFree(o->rc_tree);
     direct_free(o->direct);
     or_free(o->orr);
     if (o->own_stream) hipStreamDestroy(o->own_stream);
@@ -1968,6 +1972,66 @@ mw_status mw_ocean_step_bodies(mw_ocean* o, int32_t frame, const float* hull_xyz
         return s;
     HIP_TRY(hipMemcpyAsync(bodies, base + bh + bt, (size_t)nbodies * 16 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
     if (out) HIP_TRY(hipMemcpyAsync(out, d_out, bo, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    return MW_OK;
+}
+
+// ---- raycasts (csrc/raycast.h) -------------------------------------------------------------------------------------
+// The surface query's validation and mesh (query_prepare, world mode), then the hierarchy of that mesh into the handle's tree buffer
+// (k_rc_build_leaves, and k_rc_build_top for trees deeper than 4 levels) and one lane per ray (k_raycast), all on the handle's stream.
+static mw_status raycast_launch(mw_ocean* o, const SqMesh& m, const void* d_rays, int64_t n, void* d_out, void* d_hit) {
+    int B = sw(SW_RC_BLOCK);
+    if (B <= 0) B = MW_RC_DEFAULT_BLOCK;
+    const int minB = (m.R - 2) / (1 << MW_RC_MAX_LEVEL) + 1;  // at most 2^MW_RC_MAX_LEVEL leaves per side
+    RcTree tr = rc_tree(nullptr, m.R, B < minB ? minB : B);
+    const size_t bytes = (size_t)rc_nodes(tr.D) * 8 * sizeof(float);
+    if (o->rc_cap < bytes) {
+        if (o->rc_tree) {
+            HIP_TRY(hipStreamSynchronize(o->stream));
+            HIP_TRY(hipFree(o->rc_tree));
+            o->rc_tree = nullptr;
+            o->rc_cap = 0;
+        }
+        if (hipMalloc(&o->rc_tree, bytes) != hipSuccess) return fail(MW_ENOMEM, "hipMalloc of the raycast hierarchy failed");
+        o->rc_cap = bytes;
+    }
+    tr.box = static_cast<float*>(o->rc_tree);
+    const int T = tr.D >= 4 ? 16 : (1 << tr.D), tiles = (1 << tr.D) / T;
+    k_rc_build_leaves<<<dim3((unsigned)(tiles * tiles)), dim3(256), 0, o->stream>>>(m, tr);
+    if (tr.D > 4) k_rc_build_top<<<dim3(1), dim3(256), 0, o->stream>>>(tr);
+    k_raycast<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, tr, static_cast<const float4*>(d_rays), n,
+                                                                              static_cast<float4*>(d_out), static_cast<int2*>(d_hit));
+    HIP_TRY(hipGetLastError());
+    return MW_OK;
+}
+
+mw_status mw_ocean_raycast_device(mw_ocean* o, int32_t frame, const void* d_rays, int64_t n, void* d_out, void* d_hit) {
+    const char* who = "mw_ocean_raycast_device";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (n > 0 && ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 15) ||
+                  (reinterpret_cast<uintptr_t>(d_hit) & 7)))
+        return fail(MW_EINVAL, std::string(who) + ": d_rays and d_out must be 16-byte and d_hit 8-byte aligned");
+    SqMesh m{};
+    mw_status s = query_prepare(o, frame, MW_QUERY_WORLD, d_rays, n, 0, d_out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    return raycast_launch(o, m, d_rays, n, d_out, d_hit);
+}
+
+mw_status mw_ocean_raycast(mw_ocean* o, int32_t frame, const float* rays, int64_t n, float* out, int32_t* hit) {
+    const char* who = "mw_ocean_raycast";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    SqMesh m{};
+    mw_status s = query_prepare(o, frame, MW_QUERY_WORLD, rays, n, 0, out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    const size_t b8 = (size_t)n * 8 * sizeof(float), bh = (size_t)n * 2 * sizeof(int32_t);
+    void* buf = nullptr;
+    if ((s = scratch_reserve(o, 2 * align256(b8) + bh, &buf)) != MW_OK) return s;
+    char* base = static_cast<char*>(buf);
+    char* d_hit = hit ? base + 2 * align256(b8) : nullptr;
+    HIP_TRY(hipMemcpyAsync(base, rays, b8, hipMemcpyHostToDevice, o->stream));
+    if ((s = raycast_launch(o, m, base, n, base + align256(b8), d_hit)) != MW_OK) return s;
+    HIP_TRY(hipMemcpyAsync(out, base + align256(b8), b8, hipMemcpyDeviceToHost, o->stream));
+    if (hit) HIP_TRY(hipMemcpyAsync(hit, d_hit, bh, hipMemcpyDeviceToHost, o->stream));
     HIP_TRY(hipStreamSynchronize(o->stream));
     return MW_OK;
 }

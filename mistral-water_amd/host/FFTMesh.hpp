@@ -6,6 +6,7 @@
 // computes in private methods is delegated to libmistral_water.so (HIP, MI355X).  Header-only.
 #pragma once
 #include <cstdint>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -50,6 +51,20 @@ inline void query_velocity(mw_ocean* o, int32_t frame, const std::vector<Vector2
     out.resize(xz.size());
     check(mw_ocean_query_velocity(o, frame, world ? MW_QUERY_WORLD : MW_QUERY_REST, xz.empty() ? nullptr : &xz[0].x, (int64_t)xz.size(),
                                   iterations, out.empty() ? nullptr : &out[0].velocity.x));
+}
+
+// mw_ocean_raycast: one ray (t in units of direction; a segment p0 -> p1 is {p0, 0, p1 - p0, 1}) and its first hit on the surface
+// (t = +inf on a miss, NaN for an invalid ray); facing +1: the ray met the water from above, -1: from below; triangle -1: no hit
+struct Ray { Vector3 origin; float tmin = 0.f; Vector3 direction; float tmax = std::numeric_limits<float>::infinity(); };
+static_assert(sizeof(Ray) == 32, "[n][8] floats of mw_ocean_raycast");
+struct RayHit { float t = 0.f; Vector3 point, normal; float white = 0.f; };
+static_assert(sizeof(RayHit) == 32, "[n][8] floats of mw_ocean_raycast");
+struct RayHitId { int32_t triangle = -1, facing = 0; };
+inline void raycast(mw_ocean* o, int32_t frame, const std::vector<Ray>& rays, std::vector<RayHit>& out, std::vector<RayHitId>* ids) {
+    out.resize(rays.size());
+    if (ids) ids->resize(rays.size());
+    check(mw_ocean_raycast(o, frame, rays.empty() ? nullptr : &rays[0].origin.x, (int64_t)rays.size(), out.empty() ? nullptr : &out[0].t,
+                           ids && !ids->empty() ? &(*ids)[0].triangle : nullptr));
 }
 
 // mw_ocean_hull_forces: one body (64 B: reference point, rotation quaternion, velocity, angular velocity, in the ocean's object space)
@@ -154,6 +169,10 @@ public:
     void QueryVelocity(const std::vector<Vector2>& xz, std::vector<VelocitySample>& out, bool world = true, int32_t iterations = 0) {
         query_velocity(ocean_, -1, xz, out, world, iterations);
         for (auto& s : out) { s.velocity.x /= tDivision; s.velocity.y /= tDivision; s.velocity.z /= tDivision; }
+    }
+    // Not in the reference: the first hit of rays on the surface of the latest EvaluateWaves() (mouse picking, projectile segments, ...)
+    void Raycast(const std::vector<Ray>& rays, std::vector<RayHit>& out, std::vector<RayHitId>* ids = nullptr) {
+        raycast(ocean_, -1, rays, out, ids);
     }
     // Not in the reference: buoyancy and drag on bodies sharing one hull, from the latest EvaluateWaves() (drag uses the water's
     // velocity per second of Update's deltaTime: the library's value over tDivision)
@@ -265,6 +284,10 @@ public:
     }
     void QueryVelocity(const std::vector<Vector2>& xz, std::vector<VelocitySample>& out, bool world = true, int32_t iterations = 0) {
         query_velocity(ocean_, -1, xz, out, world, iterations);
+    }
+    // Not in the reference: the first hit of rays on the surface DisplaceMesh() describes (frame -1) or frame k of the latest steps call
+    void Raycast(const std::vector<Ray>& rays, std::vector<RayHit>& out, std::vector<RayHitId>* ids = nullptr, int32_t frame = -1) {
+        raycast(ocean_, frame, rays, out, ids);
     }
     // Not in the reference: buoyancy and drag on bodies sharing one hull, from the surface DisplaceMesh() describes (frame -1) or
     // frame k of the latest steps call (drag on: frame -1 or the last one)

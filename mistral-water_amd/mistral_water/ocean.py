@@ -366,6 +366,37 @@ class Ocean:
                                                          C.c_void_p(d_out)))
 
 
+    # -- raycasts (mw_ocean_raycast) -----------------------------------------------------------
+    @staticmethod
+    def pack_rays(origins, directions, tmin=0.0, tmax=np.inf):
+        """[n, 8] float32 rays (ox, oy, oz, tmin, dx, dy, dz, tmax) of mw_ocean_raycast; the four arguments broadcast against each
+        other (one origin for many directions, one tmax for all, ...)."""
+        o = np.asarray(origins, np.float32).reshape(-1, 3)
+        d = np.asarray(directions, np.float32).reshape(-1, 3)
+        t0 = np.asarray(tmin, np.float32).reshape(-1)
+        t1 = np.asarray(tmax, np.float32).reshape(-1)
+        (n,) = np.broadcast_shapes(o.shape[:1], d.shape[:1], t0.shape, t1.shape)   # empty origins with scalar tmin / tmax: n = 0
+        rays = np.empty((n, 8), np.float32)
+        rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7] = o, t0, d, t1
+        return rays
+
+    def raycast(self, origins, directions, tmin=0.0, tmax=np.inf, frame: int = -1):
+        """First hit of the rays o + t d, tmin <= t <= tmax (t in units of d), on the surface query_surface reads ->
+        (out [n, 8] float32 rows (t, px, py, pz, nx, ny, nz, white), hit [n, 2] int32 rows (triangle id, facing)).  A miss: t = +inf,
+        NaN, (-1, 0); an invalid ray: NaN, (-1, 0).  facing +1: the ray met the water from above, -1: from below.  A segment p0 -> p1 is
+        raycast(p0, p1 - p0, 0, 1).  frame -1 = the latest frame; k = frame k of the latest OceanRenderer steps call."""
+        rays = self.pack_rays(origins, directions, tmin, tmax)
+        out = np.empty((rays.shape[0], 8), np.float32)
+        hit = np.empty((rays.shape[0], 2), np.int32)
+        nat.check(nat.lib().mw_ocean_raycast(self._h, int(frame), _p(rays), rays.shape[0], _p(out), _p(hit)))
+        return out, hit
+
+    def raycast_device(self, d_rays: int, n: int, d_out: int, d_hit: int = 0, frame: int = -1):
+        """Device-pointer form: d_rays [n][8] and d_out [n][8] float32 (16-byte aligned), d_hit [n][2] int32 (8-byte aligned; 0 = none);
+        asynchronous on the handle's stream (synchronize() or the stream before reading d_out)."""
+        nat.check(nat.lib().mw_ocean_raycast_device(self._h, int(frame), C.c_void_p(d_rays), int(n), C.c_void_p(d_out),
+                                                     C.c_void_p(d_hit) if d_hit else None))
+
     # -- floating bodies (mw_ocean_step_bodies) --------------------------------------------------
     def step_bodies(self, hull_xyz, triangles, bodies, mass, dt, substeps: int = 1, density=1000.0, gravity=9.81, linear_drag=0.0,
                     quadratic_drag=0.0, velocity_scale=None, frame: int = -1, iterations: int = 0, return_forces: bool = False):
