@@ -49,6 +49,7 @@ static mw_status fail(mw_status s, const std::string& m) {
     g_err = m;
     return s;
 }
+static mw_status fail(mw_status s, const char* who, const std::string& m) { return fail(s, std::string(who) + ": " + m); }
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
@@ -540,6 +541,8 @@ __global__ __launch_bounds__((P2FrameGeom<N, P, R2>::NTHREADS)) void k_pass2_fra
 // ------------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------------
+// a grow-only device buffer of the handle: allocated at the largest size asked for so far, not per call (grow_reserve)
+struct GrowBuf { void* p = nullptr; size_t cap = 0; };
 struct mw_ocean {
     mw_params p;
     int N = 0;          // synthesis grid size
@@ -567,15 +570,12 @@ struct mw_ocean {
     int or_steps_tail = -1;  // OceanRenderer: the last frame of the latest steps call while the phase is still that frame's, else -1
     bool frame_behind = false;  // the spectrum or the phase changed after the latest frame was made (mw_ocean_query_velocity refuses)
     VelState vel;            // mw_ocean_velocity: the weighted spectrum and the velocity buffers (velocity_kernels.h)
-    void* hull = nullptr;    // mw_ocean_hull_forces: vertex slab + chunk partials (hull_forces.h), grow-only
-    size_t hull_cap = 0;
-    void* bodies = nullptr;  // mw_ocean_step_bodies, per-substep plan: the rows of a substep [nbodies][8], grow-only
-    size_t bodies_cap = 0;
-    void* rc_tree = nullptr;  // mw_ocean_raycast: the bounds hierarchy of the queried surface (raycast.h), rebuilt every call, grow-only
-    size_t rc_cap = 0;
+    // four separate buffers: the host forms keep their staged inputs in scratch while hull, bodies and rc_tree are in use
+    GrowBuf hull;     // mw_ocean_hull_forces: vertex slab + chunk partials (hull_forces.h)
+    GrowBuf bodies;   // mw_ocean_step_bodies, per-substep plan: the rows of a substep [nbodies][8]
+    GrowBuf rc_tree;  // mw_ocean_raycast: the bounds hierarchy of the queried surface (raycast.h), rebuilt every call
+    GrowBuf scratch;  // device staging of the host-pointer entry points (Stage)
     float* q_mesh = nullptr;  // OceanRenderer surface queries: the vertex stage of the queried frame, [res^2][3 + 3 + 1], allocated on first use
-    void* scratch = nullptr;  // grow-only device staging of the host-pointer entry points (rest mesh, RGBA targets, ...):
-    size_t scratch_cap = 0;   // allocated once at the largest size asked for, not per call
     DirectState direct;
     // OceanRenderer state
     OrState orr;
@@ -589,22 +589,110 @@ static mw_status dmalloc(T** p, size_t count) {
     return MW_OK;
 }
 
-// device staging for the host-pointer entry points: one grow-only buffer per handle
-static mw_status scratch_reserve(mw_ocean* o, size_t bytes, void** out) {
-    if (o->scratch_cap < bytes) {
-        if (o->scratch) {
-            HIP_TRY(hipStreamSynchronize(o->stream));
-            HIP_TRY(hipFree(o->scratch));
-            o->scratch = nullptr;
-            o->scratch_cap = 0;
-        }
-        if (hipMalloc(&o->scratch, bytes) != hipSuccess) return fail(MW_ENOMEM, "hipMalloc of the host-API staging buffer failed");
-        o->scratch_cap = bytes;
+// b holds at least `bytes` afterwards; growing waits for the work on the handle's stream that may still read the old buffer
+static mw_status grow_reserve(mw_ocean* o, GrowBuf& b, size_t bytes, const char* what) {
+    if (b.cap >= bytes) return MW_OK;
+    if (b.p) {
+        HIP_TRY(hipStreamSynchronize(o->stream));
+        HIP_TRY(hipFree(b.p));
+        b.p = nullptr;
+        b.cap = 0;
     }
-    *out = o->scratch;
+    if (hipMalloc(&b.p, bytes) != hipSuccess) return fail(MW_ENOMEM, std::string("hipMalloc of ") + what + " failed");
+    b.cap = bytes;
     return MW_OK;
 }
+static mw_status scratch_reserve(mw_ocean* o, size_t bytes) { return grow_reserve(o, o->scratch, bytes, "the host-API staging buffer"); }
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// Device staging of one host-pointer call in the handle's scratch buffer.  The call declares its arrays in order (in / out / inout:
+// copied to the device before the launches, back after them, or both); each region starts on a 256-byte boundary.  begin() reserves
+// the sum, sets every declared device pointer and issues the copies in; finish() issues the copies out and waits for the stream.  All
+// copies run on the handle's stream in declaration order.  An array the caller left out (NULL) gets no region and a NULL device pointer.
+namespace {  // internal linkage: at file scope Stage::begin / finish would join the library's exported symbols
+struct Stage {
+    struct Region { void** dev; const void* in; void* out; size_t bytes, off; };
+    static constexpr int MAX = 5;
+    mw_ocean* o;
+    Region r[MAX];
+    int n = 0;
+    size_t total = 0;
+    explicit Stage(mw_ocean* o_) : o(o_) {}
+    void add(void** dev, const void* in, void* out, size_t bytes) {
+        *dev = nullptr;
+        if (!in && !out) return;
+        if (n == MAX) std::abort();  // a sixth region is a mistake in this file, never a caller's: stop before writing past r[]
+        const size_t off = align256(total);
+        r[n++] = Region{dev, in, out, bytes, off};
+        total = off + bytes;
+    }
+    void in(void** dev, const void* host, size_t bytes) { add(dev, host, nullptr, bytes); }
+    void out(void** dev, void* host, size_t bytes) { add(dev, nullptr, host, bytes); }
+    void inout(void** dev, void* host, size_t bytes) { add(dev, host, host, bytes); }
+    mw_status begin() {
+        mw_status s = scratch_reserve(o, total);
+        if (s != MW_OK) return s;
+        for (int k = 0; k < n; k++) *r[k].dev = static_cast<char*>(o->scratch.p) + r[k].off;
+        for (int k = 0; k < n; k++)
+            if (r[k].in) HIP_TRY(hipMemcpyAsync(*r[k].dev, r[k].in, r[k].bytes, hipMemcpyHostToDevice, o->stream));
+        return MW_OK;
+    }
+    mw_status finish() {
+        for (int k = 0; k < n; k++)
+            if (r[k].out) HIP_TRY(hipMemcpyAsync(r[k].out, *r[k].dev, r[k].bytes, hipMemcpyDeviceToHost, o->stream));
+        HIP_TRY(hipStreamSynchronize(o->stream));
+        return MW_OK;
+    }
+};
+}  // namespace
+
+// ---- the frame record ----------------------------------------------------------------------------
+// What the surface services may read -- s_have, s_wstride, s_t, s_chop, or_steps_tail, frame_behind, vel.ready, orr.frames_last,
+// orr.fr_have -- is written by the functions below and nowhere else: every entry point that makes a frame, moves the phase or changes
+// the spectrum calls the one that states what it did.
+// velocity_spectrum_built below is the seventh writer: the only place vel.ready turns true (or_velocity sets its own for OceanRenderer).
+// an FFTMesh frame evaluated at time t now stands in s_vert / s_norm / s_white, its whitecap at stride wstride (4: RGBA colours, 1: scalar)
+static void frame_fftmesh_made(mw_ocean* o, float t, int wstride) {
+    o->s_have = true; o->s_wstride = wstride; o->s_t = t; o->s_chop = o->p.choppiness; o->frame_behind = false;
+}
+// the launches that follow overwrite s_vert / s_norm / s_white: they hold no frame until frame_fftmesh_made says so (profiling hook)
+static void frame_fftmesh_overwritten(mw_ocean* o) { o->s_have = false; }
+// an OceanRenderer lone frame is being made: the latest frame is the phase's, and no frame of a steps call is
+static void frame_or_lone(mw_ocean* o) { o->or_steps_tail = -1; o->frame_behind = false; }
+// an OceanRenderer steps call made n frames and kept[k] says whether kind k (height, displacement, normal, whitecap) stayed in the
+// handle; tail: the frame of that call the phase now belongs to (n - 1), or -1 when the caller cannot vouch for it
+static void frame_or_steps(mw_ocean* o, int n, const bool kept[4], int tail) {
+    for (int k = 0; k < 4; k++) o->orr.fr_have[k] = kept[k];
+    o->orr.frames_last = n; o->or_steps_tail = tail; o->frame_behind = false;
+}
+// the OceanRenderer phase moved without a frame: no frame is the phase's any more
+static void frame_phase_moved(mw_ocean* o) { o->or_steps_tail = -1; o->frame_behind = true; }
+// the spectrum changed: the velocity spectrum derived from it is stale and the latest frame is not this spectrum's;
+// phase_restarts: the OceanRenderer phase went back to 0 with it, so no frame of a steps call is the phase's either
+static void frame_spectrum_changed(mw_ocean* o, bool phase_restarts) {
+    o->vel.ready = false; o->frame_behind = true;
+    if (phase_restarts) o->or_steps_tail = -1;
+}
+// the velocity spectrum was rebuilt from the current spectrum (velocity_run; or_velocity does the same for OceanRenderer)
+static void velocity_spectrum_built(mw_ocean* o) { o->vel.ready = true; }
+
+// The four arrays that hold OceanRenderer frame k: the latest frame (k = -1), frame k of the latest steps call otherwise -- the handle's
+// latest-frame textures too when that call made one frame (it ran the lone-frame plan), else slot k of the frame buffers.  A kind the
+// steps call sent to caller buffers is NULL; complete: all four are here.
+struct OrFrame { float* height; cf* disp; float *normal, *white; bool complete; };
+static OrFrame or_frame(const OrState& r, int k) {
+    if (k < 0) return OrFrame{r.out_height, r.out_disp_cf, r.out_normal, r.out_white, true};
+    const bool lone = r.frames_last == 1;
+    const size_t off = (size_t)k * r.M * r.M;
+    const bool* have = r.fr_have;
+    OrFrame f;
+    f.height = !have[0] ? nullptr : (lone ? r.out_height : r.fr_height + off);
+    f.disp = !have[1] ? nullptr : (lone ? r.out_disp_cf : r.fr_disp + off);
+    f.normal = !have[2] ? nullptr : (lone ? r.out_normal : r.fr_normal + 3 * off);
+    f.white = !have[3] ? nullptr : (lone ? r.out_white : r.fr_white + off);
+    f.complete = have[0] && have[1] && have[2] && have[3];
+    return f;
+}
 
 // host-side geometry mirror of FftGeom<N,P> / Plan<N>
 static int plan_points(int N, int pass) {
@@ -860,11 +948,9 @@ void mw_ocean_destroy(mw_ocean* o) {
     hipSetDevice(o->device);
     if (hipStreamSynchronize(o->stream) != hipSuccess) (void)hipGetLastError();  // a dead caller stream has nothing pending
     hipFree(o->h0); hipFree(o->h0c); hipFree(o->PQt); hipFree(o->Om); hipFree(o->dPQ_i0); hipFree(o->dPQ_j0);
-    hipFree(o->TW); hipFree(o->TW2); hipFree(o->Wpre); hipFree(o->p1_jobs); hipFree(o->E); hipFree(o->Cj0); hipFree(o->s_vert); hipFree(o->s_norm); hipFree(o->s_white); hipFree(o->q_mesh); hipFree(o->scratch);
+    hipFree(o->TW); hipFree(o->TW2); hipFree(o->Wpre); hipFree(o->p1_jobs); hipFree(o->E); hipFree(o->Cj0); hipFree(o->s_vert); hipFree(o->s_norm); hipFree(o->s_white); hipFree(o->q_mesh);
+    for (GrowBuf* b : {&o->scratch, &o->hull, &o->bodies, &o->rc_tree}) hipFree(b->p);
     vel_free(o->vel);
-    hipFree(o->hull);
-    hipFree(o->bodies);
-    hipFree(o->rc_tree);
     direct_free(o->direct);
     or_free(o->orr);
     if (o->own_stream) hipStreamDestroy(o->own_stream);
@@ -1011,25 +1097,22 @@ mw_status mw_ocean_reset_timer(mw_ocean* o) {
 mw_status mw_ocean_set_spectrum(mw_ocean* o, const float* h0_xy, const float* h0conj_xy) {
     if (!o || !h0_xy || !h0conj_xy) return fail(MW_EINVAL, "mw_ocean_set_spectrum: NULL argument");
     HIP_TRY(hipSetDevice(o->device));
-    o->vel.ready = false;  // the velocity spectrum is derived from this one
-    o->or_steps_tail = -1;  // OceanRenderer: the phase restarts
-    o->frame_behind = true;
+    frame_spectrum_changed(o, true);  // OceanRenderer: the phase restarts
     const int tiles = (o->sem == MW_SEM_OCEANRENDERER) ? o->orr.tiles : 1;
     const size_t bytes = sizeof(cf) * (size_t)o->N * o->N * tiles;
     if (o->sem == MW_SEM_OCEANRENDERER) {  // initialTexture.rg / .ba, texel (px,py) at py*M + px, tile-major
-        void* buf = nullptr;
-        mw_status s = scratch_reserve(o, 2 * align256(bytes), &buf);
+        void *a, *b;
+        Stage st(o);
+        st.in(&a, h0_xy, bytes);
+        st.in(&b, h0conj_xy, bytes);
+        mw_status s = st.begin();
         if (s != MW_OK) return s;
-        cf *a = static_cast<cf*>(buf), *b = reinterpret_cast<cf*>(static_cast<char*>(buf) + align256(bytes));
-        HIP_TRY(hipMemcpyAsync(a, h0_xy, bytes, hipMemcpyHostToDevice, o->stream));
-        HIP_TRY(hipMemcpyAsync(b, h0conj_xy, bytes, hipMemcpyHostToDevice, o->stream));
-        k_or_set_init<<<dim3((unsigned)(((size_t)o->N * o->N + 255) / 256), tiles), dim3(256), 0, o->stream>>>(o->N, a, b, o->orr.initT,
-                                                                                                          o->orr.phaseT);
+        k_or_set_init<<<dim3((unsigned)(((size_t)o->N * o->N + 255) / 256), tiles), dim3(256), 0, o->stream>>>(
+            o->N, static_cast<const cf*>(a), static_cast<const cf*>(b), o->orr.initT, o->orr.phaseT);
         k_or_prep<<<dim3((unsigned)(((size_t)o->N * o->N + 255) / 256), tiles), dim3(256), 0, o->stream>>>(o->N, o->orr.initT, o->orr.PQT);
         HIP_TRY(hipGetLastError());
         o->orr.phase_sym = true;  // a fresh spectrum restarts the phase at 0
-        HIP_TRY(hipStreamSynchronize(o->stream));
-        return MW_OK;
+        return st.finish();
     }
     HIP_TRY(hipMemcpyAsync(o->h0, h0_xy, bytes, hipMemcpyHostToDevice, o->stream));
     HIP_TRY(hipMemcpyAsync(o->h0c, h0conj_xy, bytes, hipMemcpyHostToDevice, o->stream));
@@ -1044,16 +1127,16 @@ mw_status mw_ocean_get_spectrum(mw_ocean* o, float* h0_xy, float* h0conj_xy) {
     const int tiles = (o->sem == MW_SEM_OCEANRENDERER) ? o->orr.tiles : 1;
     const size_t bytes = sizeof(cf) * (size_t)o->N * o->N * tiles;
     if (o->sem == MW_SEM_OCEANRENDERER) {
-        void* buf = nullptr;
-        mw_status s = scratch_reserve(o, 2 * align256(bytes), &buf);
+        void *a, *b;
+        Stage st(o);
+        st.out(&a, h0_xy, bytes);
+        st.out(&b, h0conj_xy, bytes);
+        mw_status s = st.begin();
         if (s != MW_OK) return s;
-        cf *a = static_cast<cf*>(buf), *b = reinterpret_cast<cf*>(static_cast<char*>(buf) + align256(bytes));
-        k_or_get_init<<<dim3((unsigned)(((size_t)o->N * o->N + 255) / 256), tiles), dim3(256), 0, o->stream>>>(o->N, o->orr.initT, a, b);
+        k_or_get_init<<<dim3((unsigned)(((size_t)o->N * o->N + 255) / 256), tiles), dim3(256), 0, o->stream>>>(o->N, o->orr.initT, static_cast<cf*>(a),
+                                                                                                          static_cast<cf*>(b));
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h0_xy, a, bytes, hipMemcpyDeviceToHost, o->stream));
-        HIP_TRY(hipMemcpyAsync(h0conj_xy, b, bytes, hipMemcpyDeviceToHost, o->stream));
-        HIP_TRY(hipStreamSynchronize(o->stream));
-        return MW_OK;
+        return st.finish();
     }
     HIP_TRY(hipMemcpyAsync(h0_xy, o->h0, bytes, hipMemcpyDeviceToHost, o->stream));
     HIP_TRY(hipMemcpyAsync(h0conj_xy, o->h0c, bytes, hipMemcpyDeviceToHost, o->stream));
@@ -1065,8 +1148,7 @@ mw_status mw_ocean_reinit_spectrum(mw_ocean* o, float length, float wind_x, floa
     if (!o) return fail(MW_EINVAL, "NULL handle");
     if (!(length > 0.f)) return fail(MW_EINVAL, "mw_ocean_reinit_spectrum: length must be positive");
     HIP_TRY(hipSetDevice(o->device));
-    o->vel.ready = false;  // new spectrum and dispersion
-    o->frame_behind = true;
+    frame_spectrum_changed(o, false);  // new spectrum and dispersion; the phase textures stay
     if (o->sem == MW_SEM_OCEANRENDERER) {  // S/OceanRenderer.cs:98-109: RenderInitial() again, phase textures untouched
         mw_status s = or_reinit(o->orr, length, wind_x, wind_y, amplitude, seed, o->stream);
         if (s != MW_OK) return fail(s, or_last_error());
@@ -1127,22 +1209,20 @@ mw_status mw_ocean_set_normal_length(mw_ocean* o, float normal_length) {
 }
 
 static mw_status phase_copy(mw_ocean* o, float* host_out, const float* host_in, const char* who) {
-    if (!o || (!host_out && !host_in)) return fail(MW_EINVAL, std::string(who) + ": NULL argument");
-    if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, std::string(who) + ": OceanRenderer semantics only (FFTMesh state is the timer)");
+    if (!o || (!host_out && !host_in)) return fail(MW_EINVAL, who, "NULL argument");
+    if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, who, "OceanRenderer semantics only (FFTMesh state is the timer)");
     HIP_TRY(hipSetDevice(o->device));
     const size_t MM = (size_t)o->N * o->N, bytes = MM * sizeof(float) * o->orr.tiles;
-    void* buf = nullptr;
-    mw_status s = scratch_reserve(o, bytes, &buf);
+    mw_status s = scratch_reserve(o, bytes);
     if (s != MW_OK) return s;
-    float* tmp = static_cast<float*>(buf);
+    float* tmp = static_cast<float*>(o->scratch.p);
     const dim3 grid((unsigned)((MM + 255) / 256), o->orr.tiles), block(256);
     if (host_out) {  // device [px][py] -> host texel order py*M + px
         k_or_phase_transpose<<<grid, block, 0, o->stream>>>(o->N, o->orr.phaseT, tmp);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(host_out, tmp, bytes, hipMemcpyDeviceToHost, o->stream));
     } else {
-        o->or_steps_tail = -1;
-        o->frame_behind = true;
+        frame_phase_moved(o);
         HIP_TRY(hipMemcpyAsync(tmp, host_in, bytes, hipMemcpyHostToDevice, o->stream));
         k_or_phase_transpose<<<grid, block, 0, o->stream>>>(o->N, tmp, o->orr.phaseT);
         HIP_TRY(hipGetLastError());
@@ -1177,24 +1257,18 @@ mw_status mw_ocean_rest_mesh(mw_ocean* o, float* vertices_xyz, float* normals_xy
     HIP_TRY(hipSetDevice(o->device));
     const int N = o->p.resolution;  // mesh resolution (not the 8x texture size in OceanRenderer mode)
     const size_t NN = (size_t)N * N, nidx = (size_t)(N - 1) * (N - 1) * 6;
-    const size_t bv = align256(NN * 3 * sizeof(float)), bu = align256(NN * 2 * sizeof(float)), bi = align256(nidx * sizeof(int32_t));
-    void* buf = nullptr;
-    mw_status s = scratch_reserve(o, 2 * bv + bu + bi, &buf);
+    void *dv, *dn, *du, *di;
+    Stage st(o);
+    st.out(&dv, vertices_xyz, NN * 3 * sizeof(float));
+    st.out(&dn, normals_xyz, NN * 3 * sizeof(float));
+    st.out(&du, uvs_xy, NN * 2 * sizeof(float));
+    st.out(&di, indices, nidx * sizeof(int32_t));
+    mw_status s = st.begin();
     if (s != MW_OK) return s;
-    char* base = static_cast<char*>(buf);
-    float* dv = vertices_xyz ? reinterpret_cast<float*>(base) : nullptr;
-    float* dn = normals_xyz ? reinterpret_cast<float*>(base + bv) : nullptr;
-    float* du = uvs_xy ? reinterpret_cast<float*>(base + 2 * bv) : nullptr;
-    int32_t* di = indices ? reinterpret_cast<int32_t*>(base + 2 * bv + bu) : nullptr;
-    hipLaunchKernelGGL(k_rest_mesh, dim3((unsigned)((NN + 255) / 256)), dim3(256), 0, o->stream, N, o->p.unit_width, dv,
-                       dn, du, di);
+    hipLaunchKernelGGL(k_rest_mesh, dim3((unsigned)((NN + 255) / 256)), dim3(256), 0, o->stream, N, o->p.unit_width, static_cast<float*>(dv),
+                       static_cast<float*>(dn), static_cast<float*>(du), static_cast<int32_t*>(di));
     HIP_TRY(hipGetLastError());
-    if (dv) HIP_TRY(hipMemcpyAsync(vertices_xyz, dv, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    if (dn) HIP_TRY(hipMemcpyAsync(normals_xyz, dn, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    if (du) HIP_TRY(hipMemcpyAsync(uvs_xy, du, NN * 2 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    if (di) HIP_TRY(hipMemcpyAsync(indices, di, nidx * sizeof(int32_t), hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    return MW_OK;
+    return st.finish();
 }
 
 mw_status mw_ocean_evaluate_device(mw_ocean* o, const float* t, int32_t nsteps, void* d_vertices, void* d_normals,
@@ -1223,10 +1297,7 @@ mw_status mw_ocean_evaluate(mw_ocean* o, float t, float* vertices_xyz, float* no
     if (o->sem != MW_SEM_FFTMESH) return fail(MW_ESTATE, "mw_ocean_evaluate: FFTMesh semantics only");
     mw_status s = mw_ocean_evaluate_device(o, &t, 1, o->s_vert, o->s_norm, o->s_white, MW_OUT_COLOR_RGBA);
     if (s != MW_OK) return s;
-    o->s_have = true;
-    o->s_wstride = 4;
-    o->s_t = t;
-    o->s_chop = o->p.choppiness; o->frame_behind = false;
+    frame_fftmesh_made(o, t, 4);
     const size_t NN = (size_t)o->N * o->N;
     if (vertices_xyz) HIP_TRY(hipMemcpyAsync(vertices_xyz, o->s_vert, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
     if (normals_xyz) HIP_TRY(hipMemcpyAsync(normals_xyz, o->s_norm, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
@@ -1247,8 +1318,7 @@ mw_status mw_ocean_generate_texture_device(mw_ocean* o, float delta_time, void* 
     if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture: OceanRenderer semantics only");
     HIP_TRY(hipSetDevice(o->device));
     o->orr.choppiness = o->p.choppiness;
-    o->or_steps_tail = -1;
-    o->frame_behind = false;
+    frame_or_lone(o);
     mw_status s = or_generate(o->orr, delta_time, (float*)d_height, (float*)d_disp_xz, (float*)d_normal_xyz, (float*)d_white,
                               o->stream);
     if (s != MW_OK) return fail(s, or_last_error());
@@ -1284,16 +1354,14 @@ mw_status mw_ocean_generate_texture_steps_device(mw_ocean* o, const float* delta
                                : or_generate_steps(o->orr, delta_time, nframes, (float*)d_height, (float*)d_disp_xz, (float*)d_normal_xyz,
                                                    (float*)d_white, o->stream);
     if (s != MW_OK) return fail(s, or_last_error());
-    o->orr.fr_have[0] = !d_height; o->orr.fr_have[1] = !d_disp_xz; o->orr.fr_have[2] = !d_normal_xyz; o->orr.fr_have[3] = !d_white;
-    o->orr.frames_last = nframes;
-    o->or_steps_tail = nframes - 1;
-    o->frame_behind = false;
+    const bool kept[4] = {!d_height, !d_disp_xz, !d_normal_xyz, !d_white};  // what the caller did not take stays in the handle
+    frame_or_steps(o, nframes, kept, nframes - 1);
     return MW_OK;
 }
 // host forms of the steps calls: the frames stay in the handle's frame buffers, then leave over PCIe into the caller's [nframes][...] arrays
 static mw_status steps_to_host(mw_ocean* o, const float* delta_time, int32_t nframes, bool rgba, float* const host[4], const char* who) {
-    if (!o || !delta_time) return fail(MW_EINVAL, std::string(who) + ": NULL argument");
-    if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, std::string(who) + ": OceanRenderer semantics only");
+    if (!o || !delta_time) return fail(MW_EINVAL, who, "NULL argument");
+    if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, who, "OceanRenderer semantics only");
     HIP_TRY(hipSetDevice(o->device));
     const size_t MM = (size_t)o->N * o->N;
     if (!rgba) {
@@ -1307,20 +1375,13 @@ static mw_status steps_to_host(mw_ocean* o, const float* delta_time, int32_t nfr
         HIP_TRY(hipStreamSynchronize(o->stream));
         return MW_OK;
     }
-    const size_t bytes = MM * 4 * sizeof(float) * (size_t)nframes, stride = align256(bytes);
-    void* buf = nullptr;
-    int wanted = 0;
-    for (int k = 0; k < 4; k++) wanted += host[k] ? 1 : 0;
-    mw_status s = scratch_reserve(o, (size_t)(wanted ? wanted : 1) * stride, &buf);
+    void* dev[4];
+    Stage st(o);
+    for (int k = 0; k < 4; k++) st.out(&dev[k], host[k], MM * 4 * sizeof(float) * (size_t)nframes);
+    mw_status s = st.begin();
     if (s != MW_OK) return s;
-    float* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0, j = 0; k < 4; k++)
-        if (host[k]) dev[k] = reinterpret_cast<float*>(static_cast<char*>(buf) + (size_t)(j++) * stride);
     if ((s = mw_ocean_generate_texture_steps_rgba_device(o, delta_time, nframes, dev[0], dev[1], dev[2], dev[3])) != MW_OK) return s;
-    for (int k = 0; k < 4; k++)
-        if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], dev[k], bytes, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    return MW_OK;
+    return st.finish();
 }
 mw_status mw_ocean_generate_texture_steps(mw_ocean* o, const float* delta_time, int32_t nframes, float* height, float* disp_xz, float* normal_xyz,
                                           float* white) {
@@ -1338,8 +1399,7 @@ mw_status mw_ocean_advance_phase(mw_ocean* o, const float* delta_time, int32_t n
     if (nframes < 0) return fail(MW_EINVAL, "mw_ocean_advance_phase: nframes < 0");
     if (nframes == 0) return MW_OK;
     HIP_TRY(hipSetDevice(o->device));
-    o->or_steps_tail = -1;
-    o->frame_behind = true;
+    frame_phase_moved(o);
     mw_status s = or_advance_phase(o->orr, delta_time, nframes, o->stream);
     if (s != MW_OK) return fail(s, or_last_error());
     return MW_OK;
@@ -1351,18 +1411,11 @@ mw_status mw_ocean_frame_textures(mw_ocean* o, int32_t frame, void** d_height, v
     const OrState& s = o->orr;
     if (s.frames_last < 1) return fail(MW_ESTATE, "mw_ocean_frame_textures: no mw_ocean_generate_texture_steps_device call yet");
     if (frame < 0 || frame >= s.frames_last) return fail(MW_EINVAL, "mw_ocean_frame_textures: frame out of range");
-    const size_t off = (size_t)frame * s.M * s.M;
-    if (s.frames_last == 1) {  // a one-frame call ran the lone-frame plan: the frame is the handle's latest
-        if (d_height) *d_height = s.fr_have[0] ? s.out_height : nullptr;
-        if (d_disp_xz) *d_disp_xz = s.fr_have[1] ? s.out_disp : nullptr;
-        if (d_normal_xyz) *d_normal_xyz = s.fr_have[2] ? s.out_normal : nullptr;
-        if (d_white) *d_white = s.fr_have[3] ? s.out_white : nullptr;
-        return MW_OK;
-    }
-    if (d_height) *d_height = s.fr_have[0] ? s.fr_height + off : nullptr;
-    if (d_disp_xz) *d_disp_xz = s.fr_have[1] ? s.fr_disp + off : nullptr;
-    if (d_normal_xyz) *d_normal_xyz = s.fr_have[2] ? s.fr_normal + 3 * off : nullptr;
-    if (d_white) *d_white = s.fr_have[3] ? s.fr_white + off : nullptr;
+    const OrFrame f = or_frame(s, frame);
+    if (d_height) *d_height = f.height;
+    if (d_disp_xz) *d_disp_xz = f.disp;  // out_disp / fr_disp as the caller sees them: (x, z) float pairs
+    if (d_normal_xyz) *d_normal_xyz = f.normal;
+    if (d_white) *d_white = f.white;
     return MW_OK;
 }
 mw_status mw_ocean_generate_texture_steps_rgba_device(mw_ocean* o, const float* delta_time, int32_t nframes, void* d_height_rgba,
@@ -1377,10 +1430,8 @@ mw_status mw_ocean_generate_texture_steps_rgba_device(mw_ocean* o, const float* 
                                : or_generate_steps_rgba(o->orr, delta_time, nframes, (f4*)d_height_rgba, (f4*)d_disp_rgba, (f4*)d_normal_rgba,
                                                         (f4*)d_white_rgba, o->stream);
     if (s != MW_OK) return fail(s, or_last_error());
-    for (int k = 0; k < 4; k++) o->orr.fr_have[k] = true;
-    o->orr.frames_last = nframes;
-    o->or_steps_tail = nframes - 1;
-    o->frame_behind = false;
+    const bool kept[4] = {true, true, true, true};
+    frame_or_steps(o, nframes, kept, nframes - 1);
     return MW_OK;
 }
 
@@ -1401,8 +1452,7 @@ mw_status mw_ocean_generate_texture_rgba_device(mw_ocean* o, float delta_time, v
     if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture_rgba: OceanRenderer semantics only");
     HIP_TRY(hipSetDevice(o->device));
     o->orr.choppiness = o->p.choppiness;
-    o->or_steps_tail = -1;
-    o->frame_behind = false;
+    frame_or_lone(o);
     mw_status s = or_generate_rgba(o->orr, delta_time, (f4*)d_height_rgba, (f4*)d_disp_rgba, (f4*)d_normal_rgba,
                                    (f4*)d_white_rgba, o->stream);
     if (s != MW_OK) return fail(s, or_last_error());
@@ -1414,19 +1464,14 @@ mw_status mw_ocean_generate_texture_rgba(mw_ocean* o, float delta_time, float* h
     if (!o) return fail(MW_EINVAL, "NULL handle");
     if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture_rgba: OceanRenderer semantics only");
     HIP_TRY(hipSetDevice(o->device));
-    const size_t bytes = (size_t)o->N * o->N * 4 * sizeof(float) * o->orr.tiles, stride = align256(bytes);
     float* host[4] = {height_rgba, disp_rgba, normal_rgba, white_rgba};
-    float* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    void* buf = nullptr;
-    mw_status s = scratch_reserve(o, 4 * stride, &buf);
+    void* dev[4];
+    Stage st(o);
+    for (int k = 0; k < 4; k++) st.out(&dev[k], host[k], (size_t)o->N * o->N * 4 * sizeof(float) * o->orr.tiles);
+    mw_status s = st.begin();
     if (s != MW_OK) return s;
-    for (int k = 0; k < 4; k++)
-        if (host[k]) dev[k] = reinterpret_cast<float*>(static_cast<char*>(buf) + k * stride);
     if ((s = mw_ocean_generate_texture_rgba_device(o, delta_time, dev[0], dev[1], dev[2], dev[3])) != MW_OK) return s;
-    for (int k = 0; k < 4; k++)
-        if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], dev[k], bytes, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    return MW_OK;
+    return st.finish();
 }
 
 mw_status mw_ocean_displace_mesh_device(mw_ocean* o, void* d_vertices_xyz, void* d_normals_xyz, void* d_colors) {
@@ -1443,598 +1488,20 @@ mw_status mw_ocean_displace_mesh(mw_ocean* o, float* vertices_xyz, float* normal
     if (!o || !vertices_xyz) return fail(MW_EINVAL, "mw_ocean_displace_mesh: NULL argument");
     if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_displace_mesh: OceanRenderer semantics only");
     HIP_TRY(hipSetDevice(o->device));
-    const size_t nv = (size_t)o->p.resolution * o->p.resolution * o->orr.tiles, b3 = align256(nv * 3 * sizeof(float));
-    void* buf = nullptr;
-    mw_status s = scratch_reserve(o, 2 * b3 + align256(nv * sizeof(float)), &buf);
+    const size_t nv = (size_t)o->p.resolution * o->p.resolution * o->orr.tiles;
+    void *dv, *dn, *dc;
+    Stage st(o);
+    st.out(&dv, vertices_xyz, nv * 3 * sizeof(float));
+    st.out(&dn, normals_xyz, nv * 3 * sizeof(float));
+    st.out(&dc, colors, nv * sizeof(float));
+    mw_status s = st.begin();
     if (s != MW_OK) return s;
-    char* base = static_cast<char*>(buf);
-    float* dv = reinterpret_cast<float*>(base);
-    float* dn = normals_xyz ? reinterpret_cast<float*>(base + b3) : nullptr;
-    float* dc = colors ? reinterpret_cast<float*>(base + 2 * b3) : nullptr;
     if ((s = mw_ocean_displace_mesh_device(o, dv, dn, dc)) != MW_OK) return s;
-    HIP_TRY(hipMemcpyAsync(vertices_xyz, dv, nv * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    if (dn) HIP_TRY(hipMemcpyAsync(normals_xyz, dn, nv * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    if (dc) HIP_TRY(hipMemcpyAsync(colors, dc, nv * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    return MW_OK;
+    return st.finish();
 }
 
-// ---- surface queries (csrc/surface_query.h) -------------------------------------------------------------------
-// Validates the call and names the vertex arrays of the queried frame.  OceanRenderer: the material's vertex stage of that frame
-// (k_or_displace_mesh, so the vertices are those of mw_ocean_displace_mesh bit for bit) runs into the handle's q_mesh first.
-static mw_status query_prepare(mw_ocean* o, int32_t frame, int32_t mode, const void* xz, int64_t n, int32_t iterations, const void* out,
-                               const char* who, SqMesh* m) {
-    if (!o) return fail(MW_EINVAL, std::string(who) + ": NULL handle");
-    if (n < 0) return fail(MW_EINVAL, std::string(who) + ": n < 0");
-    if (n > 0 && (!xz || !out)) return fail(MW_EINVAL, std::string(who) + ": NULL array");
-    if (mode != MW_QUERY_REST && mode != MW_QUERY_WORLD) return fail(MW_EINVAL, std::string(who) + ": mode must be MW_QUERY_REST or MW_QUERY_WORLD");
-    if (iterations < 0 || iterations > MW_SQ_MAX_ITERS) return fail(MW_EINVAL, std::string(who) + ": iterations must be in [0,64]");
-    // one launch: gridDim.x * blockDim.x must fit in 32 bits
-    if (n > (int64_t)UINT32_MAX - 255) return fail(MW_EINVAL, std::string(who) + ": n > 2^32 - 256 (one launch)");
-    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
-        return fail(MW_EINVAL, std::string(who) + ": a batched handle (mw_ocean_create_batch) has no single surface");
-    if (o->sem == MW_SEM_FFTMESH && frame != -1) return fail(MW_EINVAL, std::string(who) + ": FFTMesh handles keep one frame (frame = -1)");
-    if (o->sem == MW_SEM_OCEANRENDERER && (frame < -1 || (frame >= 0 && frame >= o->orr.frames_last)))
-        return fail(MW_EINVAL, std::string(who) + ": frame out of range (-1, or a frame of the latest steps call)");
-    if (!(o->p.unit_width > 0.f)) return fail(MW_EINVAL, std::string(who) + ": the mesh needs unit_width > 0");
-    m->unit_width = o->p.unit_width;
-    if (o->sem == MW_SEM_FFTMESH) {
-        if (!o->s_have) return fail(MW_ESTATE, std::string(who) + ": no frame yet (mw_ocean_evaluate / mw_ocean_update first)");
-        m->vert = o->s_vert; m->norm = o->s_norm; m->white = o->s_white; m->R = o->N; m->wstride = o->s_wstride;
-        return MW_OK;
-    }
-    OrState& r = o->orr;
-    const float *h, *nrm, *wh;
-    const cf* d;
-    if (frame == -1) {
-        if (!r.have_frame) return fail(MW_ESTATE, std::string(who) + ": no GenerateTexture() yet");
-        h = r.out_height; d = r.out_disp_cf; nrm = r.out_normal; wh = r.out_white;
-    } else if (r.frames_last == 1) {  // a one-frame steps call ran the lone-frame plan: its frame is the handle's latest (mw_ocean_frame_textures)
-        if (!(r.fr_have[0] && r.fr_have[1] && r.fr_have[2] && r.fr_have[3]))
-            return fail(MW_ESTATE, std::string(who) + ": the steps call sent this frame's textures to caller buffers");
-        h = r.out_height; d = r.out_disp_cf; nrm = r.out_normal; wh = r.out_white;
-    } else {
-        if (!(r.fr_have[0] && r.fr_have[1] && r.fr_have[2] && r.fr_have[3]))
-            return fail(MW_ESTATE, std::string(who) + ": the steps call sent this frame's textures to caller buffers");
-        const size_t off = (size_t)frame * r.M * r.M;
-        h = r.fr_height + off; d = r.fr_disp + off; nrm = r.fr_normal + 3 * off; wh = r.fr_white + off;
-    }
-    const int res = o->p.resolution, nv = res * res;
-    if (n == 0) return MW_OK;
-    if (!o->q_mesh) {
-        mw_status s = dmalloc(&o->q_mesh, (size_t)nv * 7);
-        if (s != MW_OK) return s;
-    }
-    float *qv = o->q_mesh, *qn = qv + (size_t)nv * 3, *qw = qn + (size_t)nv * 3;
-    k_or_displace_mesh<<<dim3((unsigned)((nv + 255) / 256), 1), dim3(256), 0, o->stream>>>(r.M, res, o->p.unit_width, h, d, nrm, wh, qv, qn, qw);
-    HIP_TRY(hipGetLastError());
-    m->vert = qv; m->norm = qn; m->white = qw; m->R = res; m->wstride = 1;
-    return MW_OK;
-}
-static mw_status query_launch(mw_ocean* o, const SqMesh& m, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
-    const int iters = iterations == 0 ? MW_SQ_DEFAULT_ITERS : iterations;
-    k_query_surface<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, mode, iters, static_cast<const float2*>(d_xz), n,
-                                                                                   static_cast<float4*>(d_out));
-    HIP_TRY(hipGetLastError());
-    return MW_OK;
-}
-
-mw_status mw_ocean_query_surface_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xz, int64_t n, int32_t iterations,
-                                        void* d_out) {
-    const char* who = "mw_ocean_query_surface_device";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (n > 0 && ((reinterpret_cast<uintptr_t>(d_xz) & 7) || (reinterpret_cast<uintptr_t>(d_out) & 15)))
-        return fail(MW_EINVAL, std::string(who) + ": d_xz must be 8-byte and d_out 16-byte aligned");
-    SqMesh m{};
-    mw_status s = query_prepare(o, frame, mode, d_xz, n, iterations, d_out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    return query_launch(o, m, mode, d_xz, n, iterations, d_out);
-}
-
-mw_status mw_ocean_query_surface(mw_ocean* o, int32_t frame, int32_t mode, const float* xz, int64_t n, int32_t iterations, float* out) {
-    const char* who = "mw_ocean_query_surface";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    SqMesh m{};
-    mw_status s = query_prepare(o, frame, mode, xz, n, iterations, out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    const size_t bin = align256((size_t)n * 2 * sizeof(float)), bout = (size_t)n * 8 * sizeof(float);
-    void* buf = nullptr;
-    if ((s = scratch_reserve(o, bin + bout, &buf)) != MW_OK) return s;
-    char* base = static_cast<char*>(buf);
-    HIP_TRY(hipMemcpyAsync(base, xz, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, o->stream));
-    if ((s = query_launch(o, m, mode, base, n, iterations, base + bin)) != MW_OK) return s;
-    HIP_TRY(hipMemcpyAsync(out, base + bin, bout, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    return MW_OK;
-}
-
-// ---- surface velocity (csrc/velocity_kernels.h) --------------------------------------------------------------------
-// The frame a velocity call differentiates: FFTMesh the latest frame (frame -1); OceanRenderer the current phase, which is the latest
-// frame's (-1) or the last frame of the latest steps call while no other call has moved the phase since.  Argument errors first, as
-// query_prepare orders them.
-static mw_status velocity_check(mw_ocean* o, int32_t frame, const char* who) {
-    if (!o) return fail(MW_EINVAL, std::string(who) + ": NULL handle");
-    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
-        return fail(MW_EINVAL, std::string(who) + ": a batched handle (mw_ocean_create_batch) has no single surface");
-    if (o->sem == MW_SEM_FFTMESH && frame != -1) return fail(MW_EINVAL, std::string(who) + ": FFTMesh handles keep one frame (frame = -1)");
-    if (o->sem == MW_SEM_OCEANRENDERER && frame != -1 && !(frame >= 0 && frame == o->or_steps_tail))
-        return fail(MW_EINVAL, std::string(who) + ": the handle keeps only the latest phase: frame must be -1 or the last frame of the latest "
-                                                  "steps call");
-    if (o->sem == MW_SEM_FFTMESH && !o->s_have) return fail(MW_ESTATE, std::string(who) + ": no frame yet (mw_ocean_evaluate / mw_ocean_update first)");
-    if (o->sem == MW_SEM_OCEANRENDERER && !o->orr.have_frame) return fail(MW_ESTATE, std::string(who) + ": no GenerateTexture() yet");
-    return MW_OK;
-}
-// the velocity of every vertex into d_vel [R*R][3], on the handle's stream; writes only the handle's velocity buffers
-static mw_status velocity_run(mw_ocean* o, float* d_vel) {
-    VelState& v = o->vel;
-    if (o->sem == MW_SEM_OCEANRENDERER) {
-        mw_status s = or_velocity(o->orr, v, o->p.resolution, d_vel, o->stream);
-        return s == MW_OK ? MW_OK : fail(s, or_last_error());
-    }
-    const int N = o->N;
-    const size_t NN = (size_t)N * N;
-    mw_status s = MW_OK;
-    if (!v.white) {  // the last buffer allocated: a failure half-way frees them all, and the next call starts again
-        if ((s = dmalloc(&v.h0, NN)) != MW_OK || (s = dmalloc(&v.h0c, NN)) != MW_OK || (s = dmalloc(&v.norm, 3 * NN)) != MW_OK ||
-            (o->use_fft && ((s = dmalloc(&v.PQt, NN)) != MW_OK || (s = dmalloc(&v.Om, NN)) != MW_OK ||
-                            (s = dmalloc(&v.dPQ_i0, (size_t)N)) != MW_OK || (s = dmalloc(&v.dPQ_j0, (size_t)N)) != MW_OK)) ||
-            (s = dmalloc(&v.white, NN)) != MW_OK) {
-            vel_free(v);
-            return s;
-        }
-    }
-    const unsigned nb = (unsigned)((NN + 255) / 256);
-    if (!v.ready) {  // (i w h0, -i w h0c) and, on the FFT path, its prep tables: once per spectrum
-        hipLaunchKernelGGL(k_velocity_spectrum, dim3(nb), dim3(256), 0, o->stream, N, o->p.length, o->p.gravity, o->h0, o->h0c, v.h0, v.h0c);
-        if (o->use_fft)
-            hipLaunchKernelGGL(k_prep, dim3(nb), dim3(256), 0, o->stream, N, o->p.length, o->p.gravity, v.h0, v.h0c, o->Wpre, v.PQt,
-                               v.dPQ_i0, v.dPQ_j0, v.Om);
-        HIP_TRY(hipGetLastError());
-        v.ready = true;
-    }
-    OceanConsts C = consts_of(o);
-    C.choppiness = o->s_chop;  // the frame's choppiness (mw_ocean_set_choppiness may have changed it since)
-    if (!o->use_fft) {
-        if (direct_evaluate(o->direct, C, v.h0, v.h0c, o->s_t, d_vel, v.norm, v.white, 1, o->stream) != hipSuccess)
-            return fail(MW_EDEVICE, "velocity: direct-sum kernels failed to launch");
-        hipLaunchKernelGGL(k_velocity_from_hds, dim3(nb), dim3(256), 0, o->stream, N, C.choppiness, o->direct.hds, d_vel);
-        HIP_TRY(hipGetLastError());
-        return MW_OK;
-    }
-    if ((s = ensure_exchange(o, 1)) != MW_OK) return s;
-    StepTimes tm;
-    tm.t[0] = o->s_t;
-    if ((s = launch_pass1(o, tm, 1, o->stream, &v, &C)) != MW_OK) return s;
-    C.unit_width = 0.f;  // rest coordinate +-0: the vertex the epilogue writes is (-chop Dx, h, -chop Dz) of the weighted spectrum
-    return launch_pass2(o, 1, d_vel, v.norm, v.white, 1, nullptr, &C);
-}
-static mw_status velocity_stage(mw_ocean* o) {
-    const int R = o->sem == MW_SEM_OCEANRENDERER ? o->p.resolution : o->N;
-    return o->vel.vert ? MW_OK : dmalloc(&o->vel.vert, (size_t)R * R * 3);
-}
-
-mw_status mw_ocean_velocity_device(mw_ocean* o, int32_t frame, void* d_velocity_xyz) {
-    const char* who = "mw_ocean_velocity_device";
-    mw_status s = velocity_check(o, frame, who);
-    if (s != MW_OK) return s;
-    if (!d_velocity_xyz) return fail(MW_EINVAL, std::string(who) + ": NULL array");
-    HIP_TRY(hipSetDevice(o->device));
-    return velocity_run(o, static_cast<float*>(d_velocity_xyz));
-}
-
-mw_status mw_ocean_velocity(mw_ocean* o, int32_t frame, float* velocity_xyz) {
-    const char* who = "mw_ocean_velocity";
-    mw_status s = velocity_check(o, frame, who);
-    if (s != MW_OK) return s;
-    if (!velocity_xyz) return fail(MW_EINVAL, std::string(who) + ": NULL array");
-    HIP_TRY(hipSetDevice(o->device));
-    if ((s = velocity_stage(o)) != MW_OK || (s = velocity_run(o, o->vel.vert)) != MW_OK) return s;
-    const int R = o->sem == MW_SEM_OCEANRENDERER ? o->p.resolution : o->N;
-    HIP_TRY(hipMemcpyAsync(velocity_xyz, o->vel.vert, (size_t)R * R * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    return MW_OK;
-}
-
-// velocity queries: the surface query's validation and mesh (query_prepare), the per-vertex velocity into the handle's buffer, one lane
-// per point locating exactly as k_query_surface does (sq_locate)
-// The located surface is the latest frame's; the velocity is that of the handle's current spectrum and phase.  Once either moved on
-// without a new frame (mw_ocean_set_spectrum / reinit_spectrum / set_phase / advance_phase) the two would belong to different
-// instants: MW_ESTATE until the next frame.
-static mw_status query_velocity_prepare(mw_ocean* o, int32_t frame, int32_t mode, const void* xz, int64_t n, int32_t iterations, const void* out,
-                                        const char* who, SqMesh* m) {
-    mw_status s = query_prepare(o, frame, mode, xz, n, iterations, out, who, m);
-    if (s == MW_OK) s = velocity_check(o, frame, who);
-    if (s == MW_OK && o->frame_behind)
-        return fail(MW_ESTATE, std::string(who) + ": the spectrum or phase changed after the latest frame: the surface and the velocity would "
-                                                  "belong to different instants (make a frame first)");
-    return s;
-}
-static mw_status query_velocity_launch(mw_ocean* o, const SqMesh& m, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
-    mw_status s;
-    if ((s = velocity_stage(o)) != MW_OK || (s = velocity_run(o, o->vel.vert)) != MW_OK) return s;
-    const int iters = iterations == 0 ? MW_SQ_DEFAULT_ITERS : iterations;
-    k_query_velocity<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, o->vel.vert, mode, iters, static_cast<const float2*>(d_xz), n,
-                                                                                    static_cast<float4*>(d_out));
-    HIP_TRY(hipGetLastError());
-    return MW_OK;
-}
-
-mw_status mw_ocean_query_velocity_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
-    const char* who = "mw_ocean_query_velocity_device";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (n > 0 && ((reinterpret_cast<uintptr_t>(d_xz) & 7) || (reinterpret_cast<uintptr_t>(d_out) & 15)))
-        return fail(MW_EINVAL, std::string(who) + ": d_xz must be 8-byte and d_out 16-byte aligned");
-    SqMesh m{};
-    mw_status s = query_velocity_prepare(o, frame, mode, d_xz, n, iterations, d_out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    return query_velocity_launch(o, m, mode, d_xz, n, iterations, d_out);
-}
-
-mw_status mw_ocean_query_velocity(mw_ocean* o, int32_t frame, int32_t mode, const float* xz, int64_t n, int32_t iterations, float* out) {
-    const char* who = "mw_ocean_query_velocity";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    SqMesh m{};
-    mw_status s = query_velocity_prepare(o, frame, mode, xz, n, iterations, out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    const size_t bin = align256((size_t)n * 2 * sizeof(float)), bout = (size_t)n * 4 * sizeof(float);
-    void* buf = nullptr;
-    if ((s = scratch_reserve(o, bin + bout, &buf)) != MW_OK) return s;
-    char* base = static_cast<char*>(buf);
-    HIP_TRY(hipMemcpyAsync(base, xz, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, o->stream));
-    if ((s = query_velocity_launch(o, m, mode, base, n, iterations, base + bin)) != MW_OK) return s;
-    HIP_TRY(hipMemcpyAsync(out, base + bin, bout, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    return MW_OK;
-}
-
-// ---- hull forces (csrc/hull_forces.h) -----------------------------------------------------------------------------
-// Validates a hull-forces call and names the surface it reads: the surface query's rules and mesh (query_prepare) with drag off, the
-// velocity query's (query_velocity_prepare: frame rules of the velocity, MW_ESTATE once the spectrum or phase moved on) with drag on.
-static mw_status hull_prepare(mw_ocean* o, int32_t frame, const void* hull, int32_t nverts, const void* tris, int32_t ntris, const void* bodies,
-                              int32_t nbodies, const float* coeffs, int32_t iterations, const void* out, const char* who, SqMesh* m,
-                              HullCoeffs* cf, float* vscale) {
-    if (!o) return fail(MW_EINVAL, std::string(who) + ": NULL handle");
-    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
-        return fail(MW_EINVAL, std::string(who) + ": a batched handle (mw_ocean_create_batch) has no single surface");
-    if (nbodies < 0) return fail(MW_EINVAL, std::string(who) + ": nbodies < 0");
-    if (nverts < 3 || ntris < 1) return fail(MW_EINVAL, std::string(who) + ": a hull needs nverts >= 3 and ntris >= 1");
-    if (!coeffs) return fail(MW_EINVAL, std::string(who) + ": NULL coeffs");
-    if (nbodies > 0 && (!hull || !tris || !bodies || !out)) return fail(MW_EINVAL, std::string(who) + ": NULL array");
-    const int64_t lim = ((int64_t)1 << 31) - 256;
-    if ((int64_t)nbodies * nverts > lim || (int64_t)nbodies * ntris > lim)
-        return fail(MW_EINVAL, std::string(who) + ": nbodies * nverts and nbodies * ntris must not exceed 2^31 - 256");
-    for (int k = 0; k < MW_HULL_NCOEFFS; k++)
-        if (!(coeffs[k] >= 0.f && coeffs[k] <= 3.4e38f))
-            return fail(MW_EINVAL, std::string(who) + ": coefficients must be finite and >= 0");
-    cf->rho_g = coeffs[0] * coeffs[1];
-    cf->lin = coeffs[2];
-    cf->quad = coeffs[3];
-    cf->drag = (coeffs[2] > 0.f || coeffs[3] > 0.f) ? 1 : 0;
-    *vscale = coeffs[4];
-    // the surface (and, with drag on, the velocity) of the frame; the markers stand for the query's arrays, checked above
-    const void* mark = nbodies > 0 ? bodies : nullptr;
-    return cf->drag ? query_velocity_prepare(o, frame, MW_QUERY_WORLD, mark, nbodies, iterations, mark, who, m)
-                    : query_prepare(o, frame, MW_QUERY_WORLD, mark, nbodies, iterations, mark, who, m);
-}
-// the three launches on the handle's stream (nbodies > 0); the vertex slab and the chunk partials live in the handle's grow-only buffer.
-// velocity = false: the velocity field of this frame is already in o->vel.vert (mw_ocean_step_bodies computes it once per call)
-static mw_status hull_launch(mw_ocean* o, const SqMesh& m, const HullCoeffs& cf, float vscale, int32_t iterations, const float* d_hull,
-                             int32_t nverts, const int32_t* d_tris, int32_t ntris, const void* d_bodies, int32_t nbodies, void* d_out,
-                             bool velocity = true) {
-    const int nchunks = (std::max(ntris, nverts) + MW_HULL_CHUNK - 1) / MW_HULL_CHUNK;
-    const size_t bslab = align256((size_t)nbodies * nverts * 8 * sizeof(float)), bpart = (size_t)nbodies * nchunks * 8 * sizeof(float);
-    if (o->hull_cap < bslab + bpart) {
-        if (o->hull) {
-            HIP_TRY(hipStreamSynchronize(o->stream));
-            HIP_TRY(hipFree(o->hull));
-            o->hull = nullptr;
-            o->hull_cap = 0;
-        }
-        if (hipMalloc(&o->hull, bslab + bpart) != hipSuccess) return fail(MW_ENOMEM, "hipMalloc of the hull-forces buffer failed");
-        o->hull_cap = bslab + bpart;
-    }
-    mw_status s;
-    if (velocity && cf.drag && ((s = velocity_stage(o)) != MW_OK || (s = velocity_run(o, o->vel.vert)) != MW_OK)) return s;
-    HullArgs a;
-    a.m = m;
-    a.vel = cf.drag ? o->vel.vert : nullptr;
-    a.vscale = vscale;
-    a.iters = iterations == 0 ? MW_SQ_DEFAULT_ITERS : iterations;
-    a.cf = cf;
-    a.hull = d_hull; a.tris = d_tris; a.bodies = static_cast<const float4*>(d_bodies);
-    a.nverts = nverts; a.ntris = ntris; a.nchunks = nchunks; a.nbodies = nbodies;
-    a.vslab = static_cast<float4*>(o->hull);
-    a.part = reinterpret_cast<float4*>(static_cast<char*>(o->hull) + bslab);
-    a.out = static_cast<float4*>(d_out);
-    const int64_t nv = (int64_t)nbodies * nverts, nblk = (int64_t)nbodies * nchunks;
-    k_hull_vertices<<<dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, o->stream>>>(a);
-    k_hull_triangles<<<dim3((unsigned)std::min<int64_t>(nblk, (int64_t)1 << 20)), dim3(MW_HULL_CHUNK), 0, o->stream>>>(a);
-    k_hull_reduce<<<dim3((unsigned)std::min<int64_t>(((int64_t)nbodies + 3) / 4, (int64_t)1 << 20)), dim3(256), 0, o->stream>>>(a);
-    HIP_TRY(hipGetLastError());
-    return MW_OK;
-}
-
-mw_status mw_ocean_hull_forces_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
-                                      int32_t ntris, const void* d_bodies, int32_t nbodies, const float* coeffs, int32_t iterations,
-                                      void* d_out) {
-    const char* who = "mw_ocean_hull_forces_device";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (nbodies > 0 && ((reinterpret_cast<uintptr_t>(d_hull_xyz) & 3) || (reinterpret_cast<uintptr_t>(d_triangles) & 3) ||
-                        (reinterpret_cast<uintptr_t>(d_bodies) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 15)))
-        return fail(MW_EINVAL, std::string(who) + ": d_hull_xyz and d_triangles must be 4-byte, d_bodies and d_out 16-byte aligned");
-    SqMesh m{};
-    HullCoeffs cf{};
-    float vscale = 0.f;
-    mw_status s = hull_prepare(o, frame, d_hull_xyz, nverts, d_triangles, ntris, d_bodies, nbodies, coeffs, iterations, d_out, who, &m, &cf,
-                               &vscale);
-    if (s != MW_OK || nbodies == 0) return s;
-    return hull_launch(o, m, cf, vscale, iterations, static_cast<const float*>(d_hull_xyz), nverts, static_cast<const int32_t*>(d_triangles),
-                       ntris, d_bodies, nbodies, d_out);
-}
-
-mw_status mw_ocean_hull_forces(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles, int32_t ntris,
-                               const float* bodies, int32_t nbodies, const float* coeffs, int32_t iterations, float* out) {
-    const char* who = "mw_ocean_hull_forces";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    SqMesh m{};
-    HullCoeffs cf{};
-    float vscale = 0.f;
-    mw_status s = hull_prepare(o, frame, hull_xyz, nverts, triangles, ntris, bodies, nbodies, coeffs, iterations, out, who, &m, &cf, &vscale);
-    if (s != MW_OK || nbodies == 0) return s;
-    for (int64_t k = 0; k < (int64_t)ntris * 3; k++)
-        if (triangles[k] < 0 || triangles[k] >= nverts) return fail(MW_EINVAL, std::string(who) + ": triangle index outside [0, nverts)");
-    const size_t bh = align256((size_t)nverts * 3 * sizeof(float)), bt = align256((size_t)ntris * 3 * sizeof(int32_t)),
-                 bb = align256((size_t)nbodies * 16 * sizeof(float)), bo = (size_t)nbodies * 8 * sizeof(float);
-    void* buf = nullptr;
-    if ((s = scratch_reserve(o, bh + bt + bb + bo, &buf)) != MW_OK) return s;
-    char* base = static_cast<char*>(buf);
-    HIP_TRY(hipMemcpyAsync(base, hull_xyz, (size_t)nverts * 3 * sizeof(float), hipMemcpyHostToDevice, o->stream));
-    HIP_TRY(hipMemcpyAsync(base + bh, triangles, (size_t)ntris * 3 * sizeof(int32_t), hipMemcpyHostToDevice, o->stream));
-    HIP_TRY(hipMemcpyAsync(base + bh + bt, bodies, (size_t)nbodies * 16 * sizeof(float), hipMemcpyHostToDevice, o->stream));
-    if ((s = hull_launch(o, m, cf, vscale, iterations, reinterpret_cast<const float*>(base), nverts, reinterpret_cast<const int32_t*>(base + bh),
-                         ntris, base + bh + bt, nbodies, base + bh + bt + bb)) != MW_OK)
-        return s;
-    HIP_TRY(hipMemcpyAsync(out, base + bh + bt + bb, bo, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    return MW_OK;
-}
-
-// ---- floating bodies (csrc/rigid_bodies.h) ------------------------------------------------------------------------
-static_assert(MW_BODY_NMASS == 8, "rigid_bodies.h reads 8 floats per mass row");
-// dynamic LDS k_bodies_step may take: one MI355X CU's 160 KiB less 1 KiB for its static arrays
-#define MW_BODIES_LDS_MAX (160 * 1024 - 1024)
-
-mw_status mw_hull_mass_properties(const float* hull_xyz, int32_t nverts, const int32_t* triangles, int32_t ntris, float density,
-                                  float* out) {
-    const char* who = "mw_hull_mass_properties";
-    if (!hull_xyz || !triangles || !out) return fail(MW_EINVAL, std::string(who) + ": NULL array");
-    if (nverts < 3 || ntris < 1) return fail(MW_EINVAL, std::string(who) + ": a hull needs nverts >= 3 and ntris >= 1");
-    if (!(density > 0.f && density <= 3.4e38f)) return fail(MW_EINVAL, std::string(who) + ": density must be finite and > 0");
-    for (int64_t k = 0; k < (int64_t)ntris * 3; k++)
-        if (triangles[k] < 0 || triangles[k] >= nverts) return fail(MW_EINVAL, std::string(who) + ": triangle index outside [0, nverts)");
-    // signed tetrahedra from the vertex mean o (conditioning): volume, first and second moments, all f64
-    double o3[3] = {0.0, 0.0, 0.0};
-    for (int v = 0; v < nverts; v++)
-        for (int c = 0; c < 3; c++) o3[c] += hull_xyz[3 * v + c];
-    for (int c = 0; c < 3; c++) o3[c] /= nverts;
-    double V = 0.0, M1[3] = {0.0, 0.0, 0.0}, M2[3][3] = {{0.0}};
-    for (int t = 0; t < ntris; t++) {
-        double p[3][3], s[3];
-        for (int i = 0; i < 3; i++)
-            for (int c = 0; c < 3; c++) p[i][c] = (double)hull_xyz[3 * triangles[3 * t + i] + c] - o3[c];
-        const double vt = (p[0][0] * (p[1][1] * p[2][2] - p[1][2] * p[2][1]) - p[0][1] * (p[1][0] * p[2][2] - p[1][2] * p[2][0]) +
-                           p[0][2] * (p[1][0] * p[2][1] - p[1][1] * p[2][0])) / 6.0;
-        for (int c = 0; c < 3; c++) s[c] = p[0][c] + p[1][c] + p[2][c];
-        V += vt;
-        for (int c = 0; c < 3; c++) M1[c] += vt * s[c] / 4.0;
-        // int x_i x_j over the tetrahedron (0, a, b, c) = V / 20 (sum_k a_i a_j + s_i s_j)
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++)
-                M2[i][j] += vt / 20.0 * (p[0][i] * p[0][j] + p[1][i] * p[1][j] + p[2][i] * p[2][j] + s[i] * s[j]);
-    }
-    if (!(V > 0.0) || !std::isfinite(V))
-        return fail(MW_EINVAL, std::string(who) + ": the hull's volume is not positive (an open or inward-wound mesh)");
-    double cen[3], C[3][3];
-    for (int c = 0; c < 3; c++) cen[c] = M1[c] / V;
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) C[i][j] = density * (M2[i][j] - V * cen[i] * cen[j]);  // int x_i x_j dm about the centroid
-    out[0] = (float)(density * V);
-    for (int c = 0; c < 3; c++) out[1 + c] = (float)(cen[c] + o3[c]);
-    out[4] = (float)(C[1][1] + C[2][2]);
-    out[5] = (float)(C[0][0] + C[2][2]);
-    out[6] = (float)(C[0][0] + C[1][1]);
-    out[7] = (float)(-C[0][1]);
-    out[8] = (float)(-C[0][2]);
-    out[9] = (float)(-C[1][2]);
-    return MW_OK;
-}
-
-// Validates a step-bodies call: its own arguments, then the hull-forces rules (hull_prepare; out is optional here, so the bodies stand
-// in for it).  *g = coeffs[1].
-static mw_status bodies_prepare(mw_ocean* o, int32_t frame, const void* hull, int32_t nverts, const void* tris, int32_t ntris,
-                                const void* bodies, const void* mass, int32_t nbodies, const float* coeffs, float dt, int32_t substeps,
-                                int32_t iterations, const char* who, SqMesh* m, HullCoeffs* cf, float* vscale, float* g) {
-    if (!(substeps >= 1 && substeps <= 64)) return fail(MW_EINVAL, std::string(who) + ": substeps must be in [1, 64]");
-    if (!(dt >= 0.f && dt <= 3.4e38f)) return fail(MW_EINVAL, std::string(who) + ": dt must be finite and >= 0");
-    if (nbodies > 0 && !mass) return fail(MW_EINVAL, std::string(who) + ": NULL array");
-    mw_status s = hull_prepare(o, frame, hull, nverts, tris, ntris, bodies, nbodies, coeffs, iterations, bodies, who, m, cf, vscale);
-    if (s == MW_OK) *g = coeffs[1];
-    return s;
-}
-
-// The plan rule (MW_BODIES_PLAN = -1), DESIGN.md section 7e: one launch for hulls of at most 3 chunks (768 triangles and vertices),
-// per substep above.  Measured: 1024 icospheres (2 chunks) 0.49x the per-substep time; 64 barges (22 chunks) 1.8x.
-static bool bodies_one_launch_rule(int nchunks) { return nchunks < 4; }
-
-// every substep of the call on the handle's stream (nbodies > 0): the velocity field once (drag on), then one k_bodies_step launch, or
-// per substep hull_launch and k_bodies_integrate
-static mw_status bodies_launch(mw_ocean* o, const SqMesh& m, const HullCoeffs& cf, float vscale, float g, int32_t iterations,
-                               const float* d_hull, int32_t nverts, const int32_t* d_tris, int32_t ntris, void* d_bodies,
-                               const void* d_mass, int32_t nbodies, float dt, int32_t substeps, void* d_out) {
-    const int nchunks = (std::max(ntris, nverts) + MW_HULL_CHUNK - 1) / MW_HULL_CHUNK;
-    mw_status s;
-    if (cf.drag && ((s = velocity_stage(o)) != MW_OK || (s = velocity_run(o, o->vel.vert)) != MW_OK)) return s;
-    BodiesArgs a{};
-    a.h.m = m;
-    a.h.vel = cf.drag ? o->vel.vert : nullptr;
-    a.h.vscale = vscale;
-    a.h.iters = iterations == 0 ? MW_SQ_DEFAULT_ITERS : iterations;
-    a.h.cf = cf;
-    a.h.hull = d_hull; a.h.tris = d_tris; a.h.bodies = static_cast<const float4*>(d_bodies);
-    a.h.nverts = nverts; a.h.ntris = ntris; a.h.nchunks = nchunks; a.h.nbodies = nbodies;
-    a.bodies = static_cast<float4*>(d_bodies);
-    a.mass = static_cast<const float4*>(d_mass);
-    a.out = static_cast<float4*>(d_out);
-    a.g = g;
-    a.dt = dt / (float)substeps;
-    a.substeps = substeps;
-    const size_t lds = bodies_step_lds(nverts, nchunks);
-    const int plan = sw(SW_BODIES_PLAN);
-    if (lds <= MW_BODIES_LDS_MAX && (plan == 1 || (plan < 0 && bodies_one_launch_rule(nchunks)))) {
-        static AttrOnce attr;
-        HIP_TRY(attr.set(reinterpret_cast<const void*>(k_bodies_step), MW_BODIES_LDS_MAX));
-        k_bodies_step<<<dim3((unsigned)nbodies), dim3(MW_HULL_CHUNK), lds, o->stream>>>(a);
-        HIP_TRY(hipGetLastError());
-        return MW_OK;
-    }
-    const size_t brows = (size_t)nbodies * 8 * sizeof(float);
-    if (o->bodies_cap < brows) {
-        if (o->bodies) {
-            HIP_TRY(hipStreamSynchronize(o->stream));
-            HIP_TRY(hipFree(o->bodies));
-            o->bodies = nullptr;
-            o->bodies_cap = 0;
-        }
-        if (hipMalloc(&o->bodies, brows) != hipSuccess) return fail(MW_ENOMEM, "hipMalloc of the step-bodies row buffer failed");
-        o->bodies_cap = brows;
-    }
-    a.rows = static_cast<const float4*>(o->bodies);
-    for (int k = 0; k < substeps; k++) {
-        if ((s = hull_launch(o, m, cf, vscale, iterations, d_hull, nverts, d_tris, ntris, d_bodies, nbodies, o->bodies, false)) != MW_OK)
-            return s;
-        a.last = k == substeps - 1;
-        k_bodies_integrate<<<dim3((unsigned)(((int64_t)nbodies + 255) / 256)), dim3(256), 0, o->stream>>>(a);
-        HIP_TRY(hipGetLastError());
-    }
-    return MW_OK;
-}
-
-mw_status mw_ocean_step_bodies_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
-                                      int32_t ntris, void* d_bodies, const void* d_mass, int32_t nbodies, const float* coeffs,
-                                      float dt, int32_t substeps, int32_t iterations, void* d_out) {
-    const char* who = "mw_ocean_step_bodies_device";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (nbodies > 0 && ((reinterpret_cast<uintptr_t>(d_hull_xyz) & 3) || (reinterpret_cast<uintptr_t>(d_triangles) & 3) ||
-                        (reinterpret_cast<uintptr_t>(d_bodies) & 15) || (reinterpret_cast<uintptr_t>(d_mass) & 15) ||
-                        (reinterpret_cast<uintptr_t>(d_out) & 15)))
-        return fail(MW_EINVAL, std::string(who) + ": d_hull_xyz and d_triangles must be 4-byte, d_bodies, d_mass and d_out 16-byte aligned");
-    SqMesh m{};
-    HullCoeffs cf{};
-    float vscale = 0.f, g = 0.f;
-    mw_status s = bodies_prepare(o, frame, d_hull_xyz, nverts, d_triangles, ntris, d_bodies, d_mass, nbodies, coeffs, dt, substeps,
-                                 iterations, who, &m, &cf, &vscale, &g);
-    if (s != MW_OK || nbodies == 0) return s;
-    return bodies_launch(o, m, cf, vscale, g, iterations, static_cast<const float*>(d_hull_xyz), nverts,
-                         static_cast<const int32_t*>(d_triangles), ntris, d_bodies, d_mass, nbodies, dt, substeps, d_out);
-}
-
-mw_status mw_ocean_step_bodies(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles,
-                               int32_t ntris, float* bodies, const float* mass, int32_t nbodies, const float* coeffs, float dt,
-                               int32_t substeps, int32_t iterations, float* out) {
-    const char* who = "mw_ocean_step_bodies";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    SqMesh m{};
-    HullCoeffs cf{};
-    float vscale = 0.f, g = 0.f;
-    mw_status s = bodies_prepare(o, frame, hull_xyz, nverts, triangles, ntris, bodies, mass, nbodies, coeffs, dt, substeps, iterations,
-                                 who, &m, &cf, &vscale, &g);
-    if (s != MW_OK || nbodies == 0) return s;
-    for (int64_t k = 0; k < (int64_t)ntris * 3; k++)
-        if (triangles[k] < 0 || triangles[k] >= nverts) return fail(MW_EINVAL, std::string(who) + ": triangle index outside [0, nverts)");
-    for (int32_t b = 0; b < nbodies; b++)
-        if (!body_mass_valid(mass + 8 * (size_t)b))
-            return fail(MW_EINVAL, std::string(who) + ": the mass row of body " + std::to_string(b) +
-                                       " is invalid (m <= 0 or not finite, or I_b not positive definite)");
-    const size_t bh = align256((size_t)nverts * 3 * sizeof(float)), bt = align256((size_t)ntris * 3 * sizeof(int32_t)),
-                 bb = align256((size_t)nbodies * 16 * sizeof(float)), bm = align256((size_t)nbodies * 8 * sizeof(float)),
-                 bo = (size_t)nbodies * 8 * sizeof(float);
-    void* buf = nullptr;
-    if ((s = scratch_reserve(o, bh + bt + bb + bm + bo, &buf)) != MW_OK) return s;
-    char* base = static_cast<char*>(buf);
-    HIP_TRY(hipMemcpyAsync(base, hull_xyz, (size_t)nverts * 3 * sizeof(float), hipMemcpyHostToDevice, o->stream));
-    HIP_TRY(hipMemcpyAsync(base + bh, triangles, (size_t)ntris * 3 * sizeof(int32_t), hipMemcpyHostToDevice, o->stream));
-    HIP_TRY(hipMemcpyAsync(base + bh + bt, bodies, (size_t)nbodies * 16 * sizeof(float), hipMemcpyHostToDevice, o->stream));
-    HIP_TRY(hipMemcpyAsync(base + bh + bt + bb, mass, (size_t)nbodies * 8 * sizeof(float), hipMemcpyHostToDevice, o->stream));
-    char* d_out = out ? base + bh + bt + bb + bm : nullptr;
-    if ((s = bodies_launch(o, m, cf, vscale, g, iterations, reinterpret_cast<const float*>(base), nverts,
-                           reinterpret_cast<const int32_t*>(base + bh), ntris, base + bh + bt, base + bh + bt + bb, nbodies, dt, substeps,
-                           d_out)) != MW_OK)
-        return s;
-    HIP_TRY(hipMemcpyAsync(bodies, base + bh + bt, (size_t)nbodies * 16 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    if (out) HIP_TRY(hipMemcpyAsync(out, d_out, bo, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    return MW_OK;
-}
-
-// ---- raycasts (csrc/raycast.h) -------------------------------------------------------------------------------------
-// The surface query's validation and mesh (query_prepare, world mode), then the hierarchy of that mesh into the handle's tree buffer
-// (k_rc_build_leaves, and k_rc_build_top for trees deeper than 4 levels) and one lane per ray (k_raycast), all on the handle's stream.
-static mw_status raycast_launch(mw_ocean* o, const SqMesh& m, const void* d_rays, int64_t n, void* d_out, void* d_hit) {
-    int B = sw(SW_RC_BLOCK);
-    if (B <= 0) B = MW_RC_DEFAULT_BLOCK;
-    const int minB = (m.R - 2) / (1 << MW_RC_MAX_LEVEL) + 1;  // at most 2^MW_RC_MAX_LEVEL leaves per side
-    RcTree tr = rc_tree(nullptr, m.R, B < minB ? minB : B);
-    const size_t bytes = (size_t)rc_nodes(tr.D) * 8 * sizeof(float);
-    if (o->rc_cap < bytes) {
-        if (o->rc_tree) {
-            HIP_TRY(hipStreamSynchronize(o->stream));
-            HIP_TRY(hipFree(o->rc_tree));
-            o->rc_tree = nullptr;
-            o->rc_cap = 0;
-        }
-        if (hipMalloc(&o->rc_tree, bytes) != hipSuccess) return fail(MW_ENOMEM, "hipMalloc of the raycast hierarchy failed");
-        o->rc_cap = bytes;
-    }
-    tr.box = static_cast<float*>(o->rc_tree);
-    const int T = tr.D >= 4 ? 16 : (1 << tr.D), tiles = (1 << tr.D) / T;
-    k_rc_build_leaves<<<dim3((unsigned)(tiles * tiles)), dim3(256), 0, o->stream>>>(m, tr);
-    if (tr.D > 4) k_rc_build_top<<<dim3(1), dim3(256), 0, o->stream>>>(tr);
-    k_raycast<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, tr, static_cast<const float4*>(d_rays), n,
-                                                                              static_cast<float4*>(d_out), static_cast<int2*>(d_hit));
-    HIP_TRY(hipGetLastError());
-    return MW_OK;
-}
-
-mw_status mw_ocean_raycast_device(mw_ocean* o, int32_t frame, const void* d_rays, int64_t n, void* d_out, void* d_hit) {
-    const char* who = "mw_ocean_raycast_device";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (n > 0 && ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 15) ||
-                  (reinterpret_cast<uintptr_t>(d_hit) & 7)))
-        return fail(MW_EINVAL, std::string(who) + ": d_rays and d_out must be 16-byte and d_hit 8-byte aligned");
-    SqMesh m{};
-    mw_status s = query_prepare(o, frame, MW_QUERY_WORLD, d_rays, n, 0, d_out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    return raycast_launch(o, m, d_rays, n, d_out, d_hit);
-}
-
-mw_status mw_ocean_raycast(mw_ocean* o, int32_t frame, const float* rays, int64_t n, float* out, int32_t* hit) {
-    const char* who = "mw_ocean_raycast";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    SqMesh m{};
-    mw_status s = query_prepare(o, frame, MW_QUERY_WORLD, rays, n, 0, out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    const size_t b8 = (size_t)n * 8 * sizeof(float), bh = (size_t)n * 2 * sizeof(int32_t);
-    void* buf = nullptr;
-    if ((s = scratch_reserve(o, 2 * align256(b8) + bh, &buf)) != MW_OK) return s;
-    char* base = static_cast<char*>(buf);
-    char* d_hit = hit ? base + 2 * align256(b8) : nullptr;
-    HIP_TRY(hipMemcpyAsync(base, rays, b8, hipMemcpyHostToDevice, o->stream));
-    if ((s = raycast_launch(o, m, base, n, base + align256(b8), d_hit)) != MW_OK) return s;
-    HIP_TRY(hipMemcpyAsync(out, base + align256(b8), b8, hipMemcpyDeviceToHost, o->stream));
-    if (hit) HIP_TRY(hipMemcpyAsync(hit, d_hit, bh, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    return MW_OK;
-}
+// ---- surface services: queries, velocity, hull forces, floating bodies, raycasts ----------------------------------
+#include "surface_services.inc"
 
 // per-launch durations -> (mean, median, p10, p90, min, max), milliseconds
 static void launch_stats(std::vector<float>& v, float* out6) {
@@ -2074,8 +1541,7 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
         float dts[MW_OR_MAX_FRAMES];
         for (int k = 0; k < MW_OR_MAX_FRAMES; k++) dts[k] = 1.0f / 60.0f;
         o->orr.choppiness = o->p.choppiness;
-        o->or_steps_tail = -1;
-        o->frame_behind = false;
+        frame_or_lone(o);
         auto call = [&](hipEvent_t* ev) {
             return nsteps == 1 ? or_generate(o->orr, dts[0], nullptr, nullptr, nullptr, nullptr, o->stream, ev)
                                : or_generate_steps(o->orr, dts, nsteps, nullptr, nullptr, nullptr, nullptr, o->stream, ev);
@@ -2115,8 +1581,8 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
             if (stats_out) launch_stats(per[k], stats_out + 6 * k);
         }
         *nkernels = 4;
-        o->orr.frames_last = nsteps;
-        for (int k = 0; k < 4; k++) o->orr.fr_have[k] = true;
+        const bool kept[4] = {true, true, true, true};
+        frame_or_steps(o, nsteps, kept, -1);  // the hook has always left the steps tail unset: mw_ocean_velocity takes frame -1 only after it
         return MW_OK;
     }
     if (!o->use_fft) {  // direct-sum path: kernel 0 = the four GEMM launches of one step, kernel 1 = spectrum + assembly + whitecap
@@ -2132,7 +1598,7 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
         }
         hipEvent_t ev[4];
         for (auto& e : ev) hipEventCreate(&e);
-        o->s_have = false;  // the launches below overwrite the host-API frame (whitecap scalar, stride 1)
+        frame_fftmesh_overwritten(o);  // by the launches below (whitecap scalar, stride 1)
         hipError_t he = hipSuccess;
         for (int w = 0; w < 5 && he == hipSuccess; w++)
             he = direct_evaluate(o->direct, consts_of(o), o->h0, o->h0c, 1.0f, o->s_vert, o->s_norm, o->s_white, 1, o->stream);
@@ -2153,10 +1619,7 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
         }
         for (auto& e : ev) hipEventDestroy(e);
         if (he != hipSuccess) return fail(MW_EDEVICE, std::string("direct-sum profile: ") + hipGetErrorString(he));
-        o->s_have = true;  // the chirp-z / direct kernels above wrote the host-API frame: it is the latest frame now
-        o->s_wstride = 1;
-        o->s_t = 1.0f + (float)(iters - 1) / 60.f;
-        o->s_chop = o->p.choppiness; o->frame_behind = false;
+        frame_fftmesh_made(o, 1.0f + (float)(iters - 1) / 60.f, 1);  // the chirp-z / direct kernels above wrote the host-API frame
         for (int k = 0; k < 2; k++) {
             ms_out[k] = (float)(acc[k] / iters);
             if (names_out) names_out[k] = dnames[k];
@@ -2169,7 +1632,7 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
     if (s != MW_OK) return s;
     const size_t NN = (size_t)o->N * o->N;
     float *dv = nullptr, *dn = nullptr, *dw = nullptr;
-    if (nsteps == 1) { dv = o->s_vert; dn = o->s_norm; dw = o->s_white; o->s_have = false; }  // overwritten below, whitecap stride 1
+    if (nsteps == 1) { dv = o->s_vert; dn = o->s_norm; dw = o->s_white; frame_fftmesh_overwritten(o); }  // by the launches below, whitecap stride 1
     else {
         if ((s = dmalloc(&dv, NN * 3 * nsteps)) != MW_OK || (s = dmalloc(&dn, NN * 3 * nsteps)) != MW_OK ||
             (s = dmalloc(&dw, NN * nsteps)) != MW_OK) { hipFree(dv); hipFree(dn); hipFree(dw); return s; }
@@ -2221,7 +1684,7 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
     }
     for (auto& e : ev) hipEventDestroy(e);
     if (nsteps != 1) { hipFree(dv); hipFree(dn); hipFree(dw); }
-    else if (s == MW_OK) { o->s_have = true; o->s_wstride = 1; o->s_t = 1.0f; o->s_chop = o->p.choppiness; o->frame_behind = false; }  // the host-API frame is the profiled step (t = 1) now
+    else if (s == MW_OK) frame_fftmesh_made(o, 1.0f, 1);  // the host-API frame is the profiled step (t = 1) now
     *nkernels = 2;
     return s;
 }
@@ -2252,10 +1715,9 @@ mw_status mw_debug_evaluate_hds(mw_ocean* o, float t, float* vertices_xyz, float
     const size_t NN = (size_t)o->N * o->N;
     cf* dh = nullptr;
     if (o->use_fft) {
-        void* buf = nullptr;
-        mw_status s = scratch_reserve(o, NN * sizeof(cf), &buf);
+        mw_status s = scratch_reserve(o, NN * sizeof(cf));
         if (s != MW_OK) return s;
-        dh = static_cast<cf*>(buf);
+        dh = static_cast<cf*>(o->scratch.p);
         if ((s = ensure_exchange(o, 1)) != MW_OK) return s;
         StepTimes tm;
         tm.t[0] = t;
@@ -2266,10 +1728,7 @@ mw_status mw_debug_evaluate_hds(mw_ocean* o, float t, float* vertices_xyz, float
         if (s != MW_OK) return s;
         dh = o->direct.hds;
     }
-    o->s_have = true;
-    o->s_wstride = 4;
-    o->s_t = t;
-    o->s_chop = o->p.choppiness; o->frame_behind = false;
+    frame_fftmesh_made(o, t, 4);
     if (vertices_xyz) HIP_TRY(hipMemcpyAsync(vertices_xyz, o->s_vert, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
     if (normals_xyz) HIP_TRY(hipMemcpyAsync(normals_xyz, o->s_norm, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
     if (colors_rgba) HIP_TRY(hipMemcpyAsync(colors_rgba, o->s_white, NN * 4 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
@@ -2461,9 +1920,9 @@ mw_status mw_gerstner_displace(const float* pos_xyz, int64_t nverts, const float
 }
 
 static mw_status pond_params_of(const mw_pond_params* p, PondParams* P, const char* who) {
-    if (!p) return fail(MW_EINVAL, std::string(who) + ": NULL params");
+    if (!p) return fail(MW_EINVAL, who, "NULL params");
     if (p->mode != MW_POND_WAVE && p->mode != MW_POND_GERSTNER && p->mode != MW_POND_GERSTNER_LEVEL_ONE)
-        return fail(MW_EINVAL, std::string(who) + ": unknown displacement mode");
+        return fail(MW_EINVAL, who, "unknown displacement mode");
     P->mode = p->mode; P->amplitude = p->amplitude; P->frequency = p->frequency; P->speed = p->speed;
     P->steepness = p->steepness; P->smoothing = p->smoothing;
     for (int i = 0; i < 4; i++) { P->wspeed[i] = p->wspeed[i]; P->dir_ab[i] = p->dir_ab[i]; P->dir_cd[i] = p->dir_cd[i]; }

@@ -13,7 +13,7 @@
 // computes the same NaN row); an invalid mass row (m <= 0 or not finite, I_b not positive definite by its leading minors in f32)
 // leaves the body unchanged with a NaN row.
 //
-// Two plans with the same bits (mistral_water.hip: bodies_launch, switch MW_BODIES_PLAN):
+// Two plans with the same bits (surface_services.inc: bodies_launch, switch MW_BODIES_PLAN):
 //   per substep   hull_launch's three kernels, then k_bodies_integrate (one lane per body), once per substep
 //   one launch    k_bodies_step: one workgroup per body runs every substep; the vertex slab (32 B per vertex), the per-chunk partial
 //                 rows and the pose stay in LDS.  Each phase repeats k_hull_vertices, k_hull_triangles and k_hull_reduce's arithmetic

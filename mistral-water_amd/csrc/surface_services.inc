@@ -1,0 +1,519 @@
+// surface_services.inc -- the host code of the services that read the displaced surface: surface queries, surface velocity, hull
+// forces, floating bodies, raycasts.  Included by mistral_water.hip inside its extern "C" block (one translation unit: the handle, fail,
+// HIP_TRY, dmalloc, grow_reserve, Stage and the frame record are file-static there).  Every service is a pair of entry points over a
+// shared prepare (validate, name the mesh of the queried frame) and launch (the kernels, on the handle's stream): the device form
+// checks alignment and launches on the caller's arrays, the host form stages its arrays in the handle's scratch buffer (Stage).
+
+static int sq_iters(int32_t iterations) { return iterations == 0 ? MW_SQ_DEFAULT_ITERS : iterations; }
+// device entry points: p is not a multiple of `bytes` (a power of two)
+static bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
+static bool triangles_in_range(const int32_t* triangles, int32_t ntris, int32_t nverts) {
+    for (int64_t k = 0; k < (int64_t)ntris * 3; k++)
+        if (triangles[k] < 0 || triangles[k] >= nverts) return false;
+    return true;
+}
+
+// ---- surface queries (csrc/surface_query.h) -------------------------------------------------------------------
+// Validates the call and names the vertex arrays of the queried frame.  OceanRenderer: the material's vertex stage of that frame
+// (k_or_displace_mesh, so the vertices are those of mw_ocean_displace_mesh bit for bit) runs into the handle's q_mesh first.
+static mw_status query_prepare(mw_ocean* o, int32_t frame, int32_t mode, const void* xz, int64_t n, int32_t iterations, const void* out,
+                               const char* who, SqMesh* m) {
+    if (!o) return fail(MW_EINVAL, who, "NULL handle");
+    if (n < 0) return fail(MW_EINVAL, who, "n < 0");
+    if (n > 0 && (!xz || !out)) return fail(MW_EINVAL, who, "NULL array");
+    if (mode != MW_QUERY_REST && mode != MW_QUERY_WORLD) return fail(MW_EINVAL, who, "mode must be MW_QUERY_REST or MW_QUERY_WORLD");
+    if (iterations < 0 || iterations > MW_SQ_MAX_ITERS) return fail(MW_EINVAL, who, "iterations must be in [0,64]");
+    // one launch: gridDim.x * blockDim.x must fit in 32 bits
+    if (n > (int64_t)UINT32_MAX - 255) return fail(MW_EINVAL, who, "n > 2^32 - 256 (one launch)");
+    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
+        return fail(MW_EINVAL, who, "a batched handle (mw_ocean_create_batch) has no single surface");
+    if (o->sem == MW_SEM_FFTMESH && frame != -1) return fail(MW_EINVAL, who, "FFTMesh handles keep one frame (frame = -1)");
+    if (o->sem == MW_SEM_OCEANRENDERER && (frame < -1 || (frame >= 0 && frame >= o->orr.frames_last)))
+        return fail(MW_EINVAL, who, "frame out of range (-1, or a frame of the latest steps call)");
+    if (!(o->p.unit_width > 0.f)) return fail(MW_EINVAL, who, "the mesh needs unit_width > 0");
+    m->unit_width = o->p.unit_width;
+    if (o->sem == MW_SEM_FFTMESH) {
+        if (!o->s_have) return fail(MW_ESTATE, who, "no frame yet (mw_ocean_evaluate / mw_ocean_update first)");
+        m->vert = o->s_vert; m->norm = o->s_norm; m->white = o->s_white; m->R = o->N; m->wstride = o->s_wstride;
+        return MW_OK;
+    }
+    OrState& r = o->orr;
+    if (frame == -1 && !r.have_frame) return fail(MW_ESTATE, who, "no GenerateTexture() yet");
+    const OrFrame f = or_frame(r, frame);
+    if (!f.complete) return fail(MW_ESTATE, who, "the steps call sent this frame's textures to caller buffers");
+    const int res = o->p.resolution, nv = res * res;
+    if (n == 0) return MW_OK;
+    if (!o->q_mesh) {
+        mw_status s = dmalloc(&o->q_mesh, (size_t)nv * 7);
+        if (s != MW_OK) return s;
+    }
+    float *qv = o->q_mesh, *qn = qv + (size_t)nv * 3, *qw = qn + (size_t)nv * 3;
+    k_or_displace_mesh<<<dim3((unsigned)((nv + 255) / 256), 1), dim3(256), 0, o->stream>>>(r.M, res, o->p.unit_width, f.height, f.disp, f.normal,
+                                                                                          f.white, qv, qn, qw);
+    HIP_TRY(hipGetLastError());
+    m->vert = qv; m->norm = qn; m->white = qw; m->R = res; m->wstride = 1;
+    return MW_OK;
+}
+static mw_status query_launch(mw_ocean* o, const SqMesh& m, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
+    k_query_surface<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, mode, sq_iters(iterations), static_cast<const float2*>(d_xz),
+                                                                                   n, static_cast<float4*>(d_out));
+    HIP_TRY(hipGetLastError());
+    return MW_OK;
+}
+
+mw_status mw_ocean_query_surface_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xz, int64_t n, int32_t iterations,
+                                        void* d_out) {
+    const char* who = "mw_ocean_query_surface_device";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (n > 0 && (misaligned(d_xz, 8) || misaligned(d_out, 16))) return fail(MW_EINVAL, who, "d_xz must be 8-byte and d_out 16-byte aligned");
+    SqMesh m{};
+    mw_status s = query_prepare(o, frame, mode, d_xz, n, iterations, d_out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    return query_launch(o, m, mode, d_xz, n, iterations, d_out);
+}
+
+mw_status mw_ocean_query_surface(mw_ocean* o, int32_t frame, int32_t mode, const float* xz, int64_t n, int32_t iterations, float* out) {
+    const char* who = "mw_ocean_query_surface";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    SqMesh m{};
+    mw_status s = query_prepare(o, frame, mode, xz, n, iterations, out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    void *d_xz, *d_out;
+    Stage st(o);
+    st.in(&d_xz, xz, (size_t)n * 2 * sizeof(float));
+    st.out(&d_out, out, (size_t)n * 8 * sizeof(float));
+    if ((s = st.begin()) != MW_OK || (s = query_launch(o, m, mode, d_xz, n, iterations, d_out)) != MW_OK) return s;
+    return st.finish();
+}
+
+// ---- surface velocity (csrc/velocity_kernels.h) --------------------------------------------------------------------
+// The frame a velocity call differentiates: FFTMesh the latest frame (frame -1); OceanRenderer the current phase, which is the latest
+// frame's (-1) or the last frame of the latest steps call while no other call has moved the phase since.  Argument errors first, as
+// query_prepare orders them.
+static mw_status velocity_check(mw_ocean* o, int32_t frame, const char* who) {
+    if (!o) return fail(MW_EINVAL, who, "NULL handle");
+    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
+        return fail(MW_EINVAL, who, "a batched handle (mw_ocean_create_batch) has no single surface");
+    if (o->sem == MW_SEM_FFTMESH && frame != -1) return fail(MW_EINVAL, who, "FFTMesh handles keep one frame (frame = -1)");
+    if (o->sem == MW_SEM_OCEANRENDERER && frame != -1 && !(frame >= 0 && frame == o->or_steps_tail))
+        return fail(MW_EINVAL, who, "the handle keeps only the latest phase: frame must be -1 or the last frame of the latest "
+                                    "steps call");
+    if (o->sem == MW_SEM_FFTMESH && !o->s_have) return fail(MW_ESTATE, who, "no frame yet (mw_ocean_evaluate / mw_ocean_update first)");
+    if (o->sem == MW_SEM_OCEANRENDERER && !o->orr.have_frame) return fail(MW_ESTATE, who, "no GenerateTexture() yet");
+    return MW_OK;
+}
+// the velocity of every vertex into d_vel [R*R][3], on the handle's stream; writes only the handle's velocity buffers
+static mw_status velocity_run(mw_ocean* o, float* d_vel) {
+    VelState& v = o->vel;
+    if (o->sem == MW_SEM_OCEANRENDERER) {
+        mw_status s = or_velocity(o->orr, v, o->p.resolution, d_vel, o->stream);
+        return s == MW_OK ? MW_OK : fail(s, or_last_error());
+    }
+    const int N = o->N;
+    const size_t NN = (size_t)N * N;
+    mw_status s = MW_OK;
+    if (!v.white) {  // the last buffer allocated: a failure half-way frees them all, and the next call starts again
+        if ((s = dmalloc(&v.h0, NN)) != MW_OK || (s = dmalloc(&v.h0c, NN)) != MW_OK || (s = dmalloc(&v.norm, 3 * NN)) != MW_OK ||
+            (o->use_fft && ((s = dmalloc(&v.PQt, NN)) != MW_OK || (s = dmalloc(&v.Om, NN)) != MW_OK ||
+                            (s = dmalloc(&v.dPQ_i0, (size_t)N)) != MW_OK || (s = dmalloc(&v.dPQ_j0, (size_t)N)) != MW_OK)) ||
+            (s = dmalloc(&v.white, NN)) != MW_OK) {
+            vel_free(v);
+            return s;
+        }
+    }
+    const unsigned nb = (unsigned)((NN + 255) / 256);
+    if (!v.ready) {  // (i w h0, -i w h0c) and, on the FFT path, its prep tables: once per spectrum
+        hipLaunchKernelGGL(k_velocity_spectrum, dim3(nb), dim3(256), 0, o->stream, N, o->p.length, o->p.gravity, o->h0, o->h0c, v.h0, v.h0c);
+        if (o->use_fft)
+            hipLaunchKernelGGL(k_prep, dim3(nb), dim3(256), 0, o->stream, N, o->p.length, o->p.gravity, v.h0, v.h0c, o->Wpre, v.PQt,
+                               v.dPQ_i0, v.dPQ_j0, v.Om);
+        HIP_TRY(hipGetLastError());
+        velocity_spectrum_built(o);
+    }
+    OceanConsts C = consts_of(o);
+    C.choppiness = o->s_chop;  // the frame's choppiness (mw_ocean_set_choppiness may have changed it since)
+    if (!o->use_fft) {
+        if (direct_evaluate(o->direct, C, v.h0, v.h0c, o->s_t, d_vel, v.norm, v.white, 1, o->stream) != hipSuccess)
+            return fail(MW_EDEVICE, "velocity: direct-sum kernels failed to launch");
+        hipLaunchKernelGGL(k_velocity_from_hds, dim3(nb), dim3(256), 0, o->stream, N, C.choppiness, o->direct.hds, d_vel);
+        HIP_TRY(hipGetLastError());
+        return MW_OK;
+    }
+    if ((s = ensure_exchange(o, 1)) != MW_OK) return s;
+    StepTimes tm;
+    tm.t[0] = o->s_t;
+    if ((s = launch_pass1(o, tm, 1, o->stream, &v, &C)) != MW_OK) return s;
+    C.unit_width = 0.f;  // rest coordinate +-0: the vertex the epilogue writes is (-chop Dx, h, -chop Dz) of the weighted spectrum
+    return launch_pass2(o, 1, d_vel, v.norm, v.white, 1, nullptr, &C);
+}
+static size_t velocity_count(const mw_ocean* o) {  // floats of the per-vertex velocity [R*R][3]
+    const int R = o->sem == MW_SEM_OCEANRENDERER ? o->p.resolution : o->N;
+    return (size_t)R * R * 3;
+}
+// the velocity of every vertex into the handle's own buffer o->vel.vert (allocated on first use)
+static mw_status velocity_to_handle(mw_ocean* o) {
+    mw_status s = o->vel.vert ? MW_OK : dmalloc(&o->vel.vert, velocity_count(o));
+    return s != MW_OK ? s : velocity_run(o, o->vel.vert);
+}
+
+mw_status mw_ocean_velocity_device(mw_ocean* o, int32_t frame, void* d_velocity_xyz) {
+    const char* who = "mw_ocean_velocity_device";
+    mw_status s = velocity_check(o, frame, who);
+    if (s != MW_OK) return s;
+    if (!d_velocity_xyz) return fail(MW_EINVAL, who, "NULL array");
+    HIP_TRY(hipSetDevice(o->device));
+    return velocity_run(o, static_cast<float*>(d_velocity_xyz));
+}
+
+mw_status mw_ocean_velocity(mw_ocean* o, int32_t frame, float* velocity_xyz) {
+    const char* who = "mw_ocean_velocity";
+    mw_status s = velocity_check(o, frame, who);
+    if (s != MW_OK) return s;
+    if (!velocity_xyz) return fail(MW_EINVAL, who, "NULL array");
+    HIP_TRY(hipSetDevice(o->device));
+    if ((s = velocity_to_handle(o)) != MW_OK) return s;
+    HIP_TRY(hipMemcpyAsync(velocity_xyz, o->vel.vert, velocity_count(o) * sizeof(float), hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    return MW_OK;
+}
+
+// velocity queries: the surface query's validation and mesh (query_prepare), the per-vertex velocity into the handle's buffer, one lane
+// per point locating exactly as k_query_surface does (sq_locate)
+// The located surface is the latest frame's; the velocity is that of the handle's current spectrum and phase.  Once either moved on
+// without a new frame (mw_ocean_set_spectrum / reinit_spectrum / set_phase / advance_phase) the two would belong to different
+// instants: MW_ESTATE until the next frame.
+static mw_status query_velocity_prepare(mw_ocean* o, int32_t frame, int32_t mode, const void* xz, int64_t n, int32_t iterations, const void* out,
+                                        const char* who, SqMesh* m) {
+    mw_status s = query_prepare(o, frame, mode, xz, n, iterations, out, who, m);
+    if (s == MW_OK) s = velocity_check(o, frame, who);
+    if (s == MW_OK && o->frame_behind)
+        return fail(MW_ESTATE, who, "the spectrum or phase changed after the latest frame: the surface and the velocity would "
+                                    "belong to different instants (make a frame first)");
+    return s;
+}
+static mw_status query_velocity_launch(mw_ocean* o, const SqMesh& m, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
+    mw_status s = velocity_to_handle(o);
+    if (s != MW_OK) return s;
+    k_query_velocity<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, o->vel.vert, mode, sq_iters(iterations),
+                                                                                    static_cast<const float2*>(d_xz), n, static_cast<float4*>(d_out));
+    HIP_TRY(hipGetLastError());
+    return MW_OK;
+}
+
+mw_status mw_ocean_query_velocity_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
+    const char* who = "mw_ocean_query_velocity_device";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (n > 0 && (misaligned(d_xz, 8) || misaligned(d_out, 16))) return fail(MW_EINVAL, who, "d_xz must be 8-byte and d_out 16-byte aligned");
+    SqMesh m{};
+    mw_status s = query_velocity_prepare(o, frame, mode, d_xz, n, iterations, d_out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    return query_velocity_launch(o, m, mode, d_xz, n, iterations, d_out);
+}
+
+mw_status mw_ocean_query_velocity(mw_ocean* o, int32_t frame, int32_t mode, const float* xz, int64_t n, int32_t iterations, float* out) {
+    const char* who = "mw_ocean_query_velocity";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    SqMesh m{};
+    mw_status s = query_velocity_prepare(o, frame, mode, xz, n, iterations, out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    void *d_xz, *d_out;
+    Stage st(o);
+    st.in(&d_xz, xz, (size_t)n * 2 * sizeof(float));
+    st.out(&d_out, out, (size_t)n * 4 * sizeof(float));
+    if ((s = st.begin()) != MW_OK || (s = query_velocity_launch(o, m, mode, d_xz, n, iterations, d_out)) != MW_OK) return s;
+    return st.finish();
+}
+
+// ---- hull forces (csrc/hull_forces.h) -----------------------------------------------------------------------------
+// The arguments of a hull-forces or step-bodies call.  The host and the device form of an entry point differ only in which pointers
+// it holds: the caller's own (prepare reads none of them but the host-side coeffs), or their staged copies (launch).
+struct HullCall {
+    const void *hull, *tris; void* bodies; const void* mass; void* out;  // bodies: updated in place by step bodies
+    int32_t nverts, ntris, nbodies, iterations; const float* coeffs; float dt; int32_t substeps;
+};
+// what prepare derives from the call and the handle: the mesh of the queried frame and the coefficients as the kernels take them
+struct HullPlan { SqMesh m; HullCoeffs cf; float vscale, g; };  // vscale = coeffs[4]; g = coeffs[1], gravity (step bodies)
+
+// Validates a hull-forces call and names the surface it reads: the surface query's rules and mesh (query_prepare) with drag off, the
+// velocity query's (query_velocity_prepare: frame rules of the velocity, MW_ESTATE once the spectrum or phase moved on) with drag on.
+static mw_status hull_prepare(mw_ocean* o, int32_t frame, const HullCall& c, const char* who, HullPlan* p) {
+    if (!o) return fail(MW_EINVAL, who, "NULL handle");
+    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
+        return fail(MW_EINVAL, who, "a batched handle (mw_ocean_create_batch) has no single surface");
+    if (c.nbodies < 0) return fail(MW_EINVAL, who, "nbodies < 0");
+    if (c.nverts < 3 || c.ntris < 1) return fail(MW_EINVAL, who, "a hull needs nverts >= 3 and ntris >= 1");
+    if (!c.coeffs) return fail(MW_EINVAL, who, "NULL coeffs");
+    if (c.nbodies > 0 && (!c.hull || !c.tris || !c.bodies || !c.out)) return fail(MW_EINVAL, who, "NULL array");
+    const int64_t lim = ((int64_t)1 << 31) - 256;
+    if ((int64_t)c.nbodies * c.nverts > lim || (int64_t)c.nbodies * c.ntris > lim)
+        return fail(MW_EINVAL, who, "nbodies * nverts and nbodies * ntris must not exceed 2^31 - 256");
+    for (int k = 0; k < MW_HULL_NCOEFFS; k++)
+        if (!(c.coeffs[k] >= 0.f && c.coeffs[k] <= 3.4e38f)) return fail(MW_EINVAL, who, "coefficients must be finite and >= 0");
+    p->cf.rho_g = c.coeffs[0] * c.coeffs[1];
+    p->cf.lin = c.coeffs[2];
+    p->cf.quad = c.coeffs[3];
+    p->cf.drag = (c.coeffs[2] > 0.f || c.coeffs[3] > 0.f) ? 1 : 0;
+    p->g = c.coeffs[1];
+    p->vscale = c.coeffs[4];
+    // the surface (and, with drag on, the velocity) of the frame; the markers stand for the query's arrays, checked above
+    const void* mark = c.nbodies > 0 ? c.bodies : nullptr;
+    return p->cf.drag ? query_velocity_prepare(o, frame, MW_QUERY_WORLD, mark, c.nbodies, c.iterations, mark, who, &p->m)
+                      : query_prepare(o, frame, MW_QUERY_WORLD, mark, c.nbodies, c.iterations, mark, who, &p->m);
+}
+static int hull_chunks(const HullCall& c) { return (std::max(c.ntris, c.nverts) + MW_HULL_CHUNK - 1) / MW_HULL_CHUNK; }
+// the kernels' view of a call on device pointers; vslab, part and out are the launch's own (hull_launch)
+static HullArgs hull_args(const mw_ocean* o, const HullPlan& p, const HullCall& c) {
+    HullArgs a{};
+    a.m = p.m;
+    a.vel = p.cf.drag ? o->vel.vert : nullptr;
+    a.vscale = p.vscale;
+    a.iters = sq_iters(c.iterations);
+    a.cf = p.cf;
+    a.hull = static_cast<const float*>(c.hull); a.tris = static_cast<const int32_t*>(c.tris); a.bodies = static_cast<const float4*>(c.bodies);
+    a.nverts = c.nverts; a.ntris = c.ntris; a.nchunks = hull_chunks(c); a.nbodies = c.nbodies;
+    return a;
+}
+// the three launches on the handle's stream (nbodies > 0), the rows into c.out; the vertex slab and the chunk partials live in the
+// handle's grow-only buffer.
+// velocity = false: the velocity field of this frame is already in o->vel.vert (mw_ocean_step_bodies computes it once per call)
+static mw_status hull_launch(mw_ocean* o, const HullPlan& p, const HullCall& c, bool velocity = true) {
+    const int nchunks = hull_chunks(c);
+    const size_t bslab = align256((size_t)c.nbodies * c.nverts * 8 * sizeof(float)), bpart = (size_t)c.nbodies * nchunks * 8 * sizeof(float);
+    mw_status s = grow_reserve(o, o->hull, bslab + bpart, "the hull-forces buffer");
+    if (s != MW_OK) return s;
+    if (velocity && p.cf.drag && (s = velocity_to_handle(o)) != MW_OK) return s;
+    HullArgs a = hull_args(o, p, c);
+    a.vslab = static_cast<float4*>(o->hull.p);
+    a.part = reinterpret_cast<float4*>(static_cast<char*>(o->hull.p) + bslab);
+    a.out = static_cast<float4*>(c.out);
+    const int64_t nv = (int64_t)c.nbodies * c.nverts, nblk = (int64_t)c.nbodies * nchunks;
+    k_hull_vertices<<<dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, o->stream>>>(a);
+    k_hull_triangles<<<dim3((unsigned)std::min<int64_t>(nblk, (int64_t)1 << 20)), dim3(MW_HULL_CHUNK), 0, o->stream>>>(a);
+    k_hull_reduce<<<dim3((unsigned)std::min<int64_t>(((int64_t)c.nbodies + 3) / 4, (int64_t)1 << 20)), dim3(256), 0, o->stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return MW_OK;
+}
+
+mw_status mw_ocean_hull_forces_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
+                                      int32_t ntris, const void* d_bodies, int32_t nbodies, const float* coeffs, int32_t iterations,
+                                      void* d_out) {
+    const char* who = "mw_ocean_hull_forces_device";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (nbodies > 0 && (misaligned(d_hull_xyz, 4) || misaligned(d_triangles, 4) || misaligned(d_bodies, 16) || misaligned(d_out, 16)))
+        return fail(MW_EINVAL, who, "d_hull_xyz and d_triangles must be 4-byte, d_bodies and d_out 16-byte aligned");
+    const HullCall c{d_hull_xyz, d_triangles, const_cast<void*>(d_bodies), nullptr, d_out, nverts, ntris, nbodies, iterations, coeffs, 0.f, 1};
+    HullPlan p{};
+    mw_status s = hull_prepare(o, frame, c, who, &p);
+    if (s != MW_OK || nbodies == 0) return s;
+    return hull_launch(o, p, c);
+}
+
+mw_status mw_ocean_hull_forces(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles, int32_t ntris,
+                               const float* bodies, int32_t nbodies, const float* coeffs, int32_t iterations, float* out) {
+    const char* who = "mw_ocean_hull_forces";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    const HullCall c{hull_xyz, triangles, const_cast<float*>(bodies), nullptr, out, nverts, ntris, nbodies, iterations, coeffs, 0.f, 1};
+    HullPlan p{};
+    mw_status s = hull_prepare(o, frame, c, who, &p);
+    if (s != MW_OK || nbodies == 0) return s;
+    if (!triangles_in_range(triangles, ntris, nverts)) return fail(MW_EINVAL, who, "triangle index outside [0, nverts)");
+    void *d_hull, *d_tris, *d_bodies, *d_out;
+    Stage st(o);
+    st.in(&d_hull, hull_xyz, (size_t)nverts * 3 * sizeof(float));
+    st.in(&d_tris, triangles, (size_t)ntris * 3 * sizeof(int32_t));
+    st.in(&d_bodies, bodies, (size_t)nbodies * 16 * sizeof(float));
+    st.out(&d_out, out, (size_t)nbodies * 8 * sizeof(float));
+    if ((s = st.begin()) != MW_OK) return s;
+    HullCall d = c;
+    d.hull = d_hull; d.tris = d_tris; d.bodies = d_bodies; d.out = d_out;
+    if ((s = hull_launch(o, p, d)) != MW_OK) return s;
+    return st.finish();
+}
+
+// ---- floating bodies (csrc/rigid_bodies.h) ------------------------------------------------------------------------
+static_assert(MW_BODY_NMASS == 8, "rigid_bodies.h reads 8 floats per mass row");
+// dynamic LDS k_bodies_step may take: one MI355X CU's 160 KiB less 1 KiB for its static arrays
+#define MW_BODIES_LDS_MAX (160 * 1024 - 1024)
+
+mw_status mw_hull_mass_properties(const float* hull_xyz, int32_t nverts, const int32_t* triangles, int32_t ntris, float density,
+                                  float* out) {
+    const char* who = "mw_hull_mass_properties";
+    if (!hull_xyz || !triangles || !out) return fail(MW_EINVAL, who, "NULL array");
+    if (nverts < 3 || ntris < 1) return fail(MW_EINVAL, who, "a hull needs nverts >= 3 and ntris >= 1");
+    if (!(density > 0.f && density <= 3.4e38f)) return fail(MW_EINVAL, who, "density must be finite and > 0");
+    if (!triangles_in_range(triangles, ntris, nverts)) return fail(MW_EINVAL, who, "triangle index outside [0, nverts)");
+    // signed tetrahedra from the vertex mean o (conditioning): volume, first and second moments, all f64
+    double o3[3] = {0.0, 0.0, 0.0};
+    for (int v = 0; v < nverts; v++)
+        for (int c = 0; c < 3; c++) o3[c] += hull_xyz[3 * v + c];
+    for (int c = 0; c < 3; c++) o3[c] /= nverts;
+    double V = 0.0, M1[3] = {0.0, 0.0, 0.0}, M2[3][3] = {{0.0}};
+    for (int t = 0; t < ntris; t++) {
+        double p[3][3], s[3];
+        for (int i = 0; i < 3; i++)
+            for (int c = 0; c < 3; c++) p[i][c] = (double)hull_xyz[3 * triangles[3 * t + i] + c] - o3[c];
+        const double vt = (p[0][0] * (p[1][1] * p[2][2] - p[1][2] * p[2][1]) - p[0][1] * (p[1][0] * p[2][2] - p[1][2] * p[2][0]) +
+                           p[0][2] * (p[1][0] * p[2][1] - p[1][1] * p[2][0])) / 6.0;
+        for (int c = 0; c < 3; c++) s[c] = p[0][c] + p[1][c] + p[2][c];
+        V += vt;
+        for (int c = 0; c < 3; c++) M1[c] += vt * s[c] / 4.0;
+        // int x_i x_j over the tetrahedron (0, a, b, c) = V / 20 (sum_k a_i a_j + s_i s_j)
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++)
+                M2[i][j] += vt / 20.0 * (p[0][i] * p[0][j] + p[1][i] * p[1][j] + p[2][i] * p[2][j] + s[i] * s[j]);
+    }
+    if (!(V > 0.0) || !std::isfinite(V)) return fail(MW_EINVAL, who, "the hull's volume is not positive (an open or inward-wound mesh)");
+    double cen[3], C[3][3];
+    for (int c = 0; c < 3; c++) cen[c] = M1[c] / V;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) C[i][j] = density * (M2[i][j] - V * cen[i] * cen[j]);  // int x_i x_j dm about the centroid
+    out[0] = (float)(density * V);
+    for (int c = 0; c < 3; c++) out[1 + c] = (float)(cen[c] + o3[c]);
+    out[4] = (float)(C[1][1] + C[2][2]);
+    out[5] = (float)(C[0][0] + C[2][2]);
+    out[6] = (float)(C[0][0] + C[1][1]);
+    out[7] = (float)(-C[0][1]);
+    out[8] = (float)(-C[0][2]);
+    out[9] = (float)(-C[1][2]);
+    return MW_OK;
+}
+
+// Validates a step-bodies call: its own arguments, then the hull-forces rules (hull_prepare; out is optional here, so the bodies stand
+// in for it).
+static mw_status bodies_prepare(mw_ocean* o, int32_t frame, const HullCall& c, const char* who, HullPlan* p) {
+    if (!(c.substeps >= 1 && c.substeps <= 64)) return fail(MW_EINVAL, who, "substeps must be in [1, 64]");
+    if (!(c.dt >= 0.f && c.dt <= 3.4e38f)) return fail(MW_EINVAL, who, "dt must be finite and >= 0");
+    if (c.nbodies > 0 && !c.mass) return fail(MW_EINVAL, who, "NULL array");
+    HullCall h = c;
+    h.out = c.bodies;
+    return hull_prepare(o, frame, h, who, p);
+}
+
+// The plan rule (MW_BODIES_PLAN = -1), DESIGN.md section 7e: one launch for hulls of at most 3 chunks (768 triangles and vertices),
+// per substep above.  Measured: 1024 icospheres (2 chunks) 0.49x the per-substep time; 64 barges (22 chunks) 1.8x.
+static bool bodies_one_launch_rule(int nchunks) { return nchunks < 4; }
+
+// every substep of the call on the handle's stream (nbodies > 0): the velocity field once (drag on), then one k_bodies_step launch, or
+// per substep hull_launch and k_bodies_integrate
+static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c) {
+    const int nchunks = hull_chunks(c);
+    mw_status s;
+    if (p.cf.drag && (s = velocity_to_handle(o)) != MW_OK) return s;
+    BodiesArgs a{};
+    a.h = hull_args(o, p, c);
+    a.bodies = static_cast<float4*>(c.bodies);
+    a.mass = static_cast<const float4*>(c.mass);
+    a.out = static_cast<float4*>(c.out);
+    a.g = p.g;
+    a.dt = c.dt / (float)c.substeps;
+    a.substeps = c.substeps;
+    const size_t lds = bodies_step_lds(c.nverts, nchunks);
+    const int plan = sw(SW_BODIES_PLAN);
+    if (lds <= MW_BODIES_LDS_MAX && (plan == 1 || (plan < 0 && bodies_one_launch_rule(nchunks)))) {
+        static AttrOnce attr;
+        HIP_TRY(attr.set(reinterpret_cast<const void*>(k_bodies_step), MW_BODIES_LDS_MAX));
+        k_bodies_step<<<dim3((unsigned)c.nbodies), dim3(MW_HULL_CHUNK), lds, o->stream>>>(a);
+        HIP_TRY(hipGetLastError());
+        return MW_OK;
+    }
+    if ((s = grow_reserve(o, o->bodies, (size_t)c.nbodies * 8 * sizeof(float), "the step-bodies row buffer")) != MW_OK) return s;
+    a.rows = static_cast<const float4*>(o->bodies.p);
+    HullCall rows = c;  // the hull forces of a substep: the same call, its rows into the handle's buffer
+    rows.out = o->bodies.p;
+    for (int k = 0; k < c.substeps; k++) {
+        if ((s = hull_launch(o, p, rows, false)) != MW_OK) return s;
+        a.last = k == c.substeps - 1;
+        k_bodies_integrate<<<dim3((unsigned)(((int64_t)c.nbodies + 255) / 256)), dim3(256), 0, o->stream>>>(a);
+        HIP_TRY(hipGetLastError());
+    }
+    return MW_OK;
+}
+
+mw_status mw_ocean_step_bodies_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
+                                      int32_t ntris, void* d_bodies, const void* d_mass, int32_t nbodies, const float* coeffs,
+                                      float dt, int32_t substeps, int32_t iterations, void* d_out) {
+    const char* who = "mw_ocean_step_bodies_device";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (nbodies > 0 && (misaligned(d_hull_xyz, 4) || misaligned(d_triangles, 4) || misaligned(d_bodies, 16) || misaligned(d_mass, 16) ||
+                        misaligned(d_out, 16)))
+        return fail(MW_EINVAL, who, "d_hull_xyz and d_triangles must be 4-byte, d_bodies, d_mass and d_out 16-byte aligned");
+    const HullCall c{d_hull_xyz, d_triangles, d_bodies, d_mass, d_out, nverts, ntris, nbodies, iterations, coeffs, dt, substeps};
+    HullPlan p{};
+    mw_status s = bodies_prepare(o, frame, c, who, &p);
+    if (s != MW_OK || nbodies == 0) return s;
+    return bodies_launch(o, p, c);
+}
+
+mw_status mw_ocean_step_bodies(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles,
+                               int32_t ntris, float* bodies, const float* mass, int32_t nbodies, const float* coeffs, float dt,
+                               int32_t substeps, int32_t iterations, float* out) {
+    const char* who = "mw_ocean_step_bodies";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    const HullCall c{hull_xyz, triangles, bodies, mass, out, nverts, ntris, nbodies, iterations, coeffs, dt, substeps};
+    HullPlan p{};
+    mw_status s = bodies_prepare(o, frame, c, who, &p);
+    if (s != MW_OK || nbodies == 0) return s;
+    if (!triangles_in_range(triangles, ntris, nverts)) return fail(MW_EINVAL, who, "triangle index outside [0, nverts)");
+    for (int32_t b = 0; b < nbodies; b++)
+        if (!body_mass_valid(mass + 8 * (size_t)b))
+            return fail(MW_EINVAL, who, "the mass row of body " + std::to_string(b) +
+                                            " is invalid (m <= 0 or not finite, or I_b not positive definite)");
+    void *d_hull, *d_tris, *d_bodies, *d_mass, *d_out;
+    Stage st(o);
+    st.in(&d_hull, hull_xyz, (size_t)nverts * 3 * sizeof(float));
+    st.in(&d_tris, triangles, (size_t)ntris * 3 * sizeof(int32_t));
+    st.inout(&d_bodies, bodies, (size_t)nbodies * 16 * sizeof(float));
+    st.in(&d_mass, mass, (size_t)nbodies * 8 * sizeof(float));
+    st.out(&d_out, out, (size_t)nbodies * 8 * sizeof(float));  // optional
+    if ((s = st.begin()) != MW_OK) return s;
+    HullCall d = c;
+    d.hull = d_hull; d.tris = d_tris; d.bodies = d_bodies; d.mass = d_mass; d.out = d_out;
+    if ((s = bodies_launch(o, p, d)) != MW_OK) return s;
+    return st.finish();
+}
+
+// ---- raycasts (csrc/raycast.h) -------------------------------------------------------------------------------------
+// The surface query's validation and mesh (query_prepare, world mode), then the hierarchy of that mesh into the handle's tree buffer
+// (k_rc_build_leaves, and k_rc_build_top for trees deeper than 4 levels) and one lane per ray (k_raycast), all on the handle's stream.
+static mw_status raycast_launch(mw_ocean* o, const SqMesh& m, const void* d_rays, int64_t n, void* d_out, void* d_hit) {
+    int B = sw(SW_RC_BLOCK);
+    if (B <= 0) B = MW_RC_DEFAULT_BLOCK;
+    const int minB = (m.R - 2) / (1 << MW_RC_MAX_LEVEL) + 1;  // at most 2^MW_RC_MAX_LEVEL leaves per side
+    RcTree tr = rc_tree(nullptr, m.R, B < minB ? minB : B);
+    mw_status s = grow_reserve(o, o->rc_tree, (size_t)rc_nodes(tr.D) * 8 * sizeof(float), "the raycast hierarchy");
+    if (s != MW_OK) return s;
+    tr.box = static_cast<float*>(o->rc_tree.p);
+    const int T = tr.D >= 4 ? 16 : (1 << tr.D), tiles = (1 << tr.D) / T;
+    k_rc_build_leaves<<<dim3((unsigned)(tiles * tiles)), dim3(256), 0, o->stream>>>(m, tr);
+    if (tr.D > 4) k_rc_build_top<<<dim3(1), dim3(256), 0, o->stream>>>(tr);
+    k_raycast<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, tr, static_cast<const float4*>(d_rays), n,
+                                                                              static_cast<float4*>(d_out), static_cast<int2*>(d_hit));
+    HIP_TRY(hipGetLastError());
+    return MW_OK;
+}
+
+mw_status mw_ocean_raycast_device(mw_ocean* o, int32_t frame, const void* d_rays, int64_t n, void* d_out, void* d_hit) {
+    const char* who = "mw_ocean_raycast_device";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (n > 0 && (misaligned(d_rays, 16) || misaligned(d_out, 16) || misaligned(d_hit, 8)))
+        return fail(MW_EINVAL, who, "d_rays and d_out must be 16-byte and d_hit 8-byte aligned");
+    SqMesh m{};
+    mw_status s = query_prepare(o, frame, MW_QUERY_WORLD, d_rays, n, 0, d_out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    return raycast_launch(o, m, d_rays, n, d_out, d_hit);
+}
+
+mw_status mw_ocean_raycast(mw_ocean* o, int32_t frame, const float* rays, int64_t n, float* out, int32_t* hit) {
+    const char* who = "mw_ocean_raycast";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    SqMesh m{};
+    mw_status s = query_prepare(o, frame, MW_QUERY_WORLD, rays, n, 0, out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    void *d_rays, *d_out, *d_hit;
+    Stage st(o);
+    st.in(&d_rays, rays, (size_t)n * 8 * sizeof(float));
+    st.out(&d_out, out, (size_t)n * 8 * sizeof(float));
+    st.out(&d_hit, hit, (size_t)n * 2 * sizeof(int32_t));  // optional
+    if ((s = st.begin()) != MW_OK || (s = raycast_launch(o, m, d_rays, n, d_out, d_hit)) != MW_OK) return s;
+    return st.finish();
+}
