@@ -20,6 +20,7 @@
 
 #include "../../include/mistral_water.h"
 #include "../../include/mistral_water_hooks.h"
+#include "mw_host.h"  // fail(), HIP_TRY, MW_FOR_SIZE
 #include "fftmesh_kernels.h"
 #include "ocean_renderer_device.h"
 #include "direct_kernels.h"
@@ -40,22 +41,6 @@ static_assert(MW_SQ_REST == MW_QUERY_REST && MW_SQ_WORLD == MW_QUERY_WORLD, "sur
 #endif
 
 using namespace mw;
-
-// ------------------------------------------------------------------------------------------------
-// error plumbing
-// ------------------------------------------------------------------------------------------------
-static thread_local std::string g_err;
-static mw_status fail(mw_status s, const std::string& m) {
-    g_err = m;
-    return s;
-}
-static mw_status fail(mw_status s, const char* who, const std::string& m) { return fail(s, std::string(who) + ": " + m); }
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return fail(MW_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
-    } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // __global__ wrappers: FFTMesh semantics
@@ -681,27 +666,21 @@ static void velocity_spectrum_built(mw_ocean* o) { o->vel.ready = true; }
 // steps call sent to caller buffers is NULL; complete: all four are here.
 struct OrFrame { float* height; cf* disp; float *normal, *white; bool complete; };
 static OrFrame or_frame(const OrState& r, int k) {
-    if (k < 0) return OrFrame{r.out_height, r.out_disp_cf, r.out_normal, r.out_white, true};
-    const bool lone = r.frames_last == 1;
-    const size_t off = (size_t)k * r.M * r.M;
+    if (k < 0) return OrFrame{r.out.height, r.out.disp, r.out.normal, r.out.white, true};
+    const OrTex t = r.frames_last == 1 ? r.out : r.fr.at((size_t)k * r.M * r.M);
     const bool* have = r.fr_have;
     OrFrame f;
-    f.height = !have[0] ? nullptr : (lone ? r.out_height : r.fr_height + off);
-    f.disp = !have[1] ? nullptr : (lone ? r.out_disp_cf : r.fr_disp + off);
-    f.normal = !have[2] ? nullptr : (lone ? r.out_normal : r.fr_normal + 3 * off);
-    f.white = !have[3] ? nullptr : (lone ? r.out_white : r.fr_white + off);
+    f.height = have[0] ? t.height : nullptr;
+    f.disp = have[1] ? t.disp : nullptr;
+    f.normal = have[2] ? t.normal : nullptr;
+    f.white = have[3] ? t.white : nullptr;
     f.complete = have[0] && have[1] && have[2] && have[3];
     return f;
 }
 
 // host-side geometry mirror of FftGeom<N,P> / Plan<N>
 static int plan_points(int N, int pass) {
-    switch (N) {
-#define MW_PLAN_CASE(NN) case NN: return pass == 1 ? Plan<NN>::P1 : Plan<NN>::P2;
-        MW_PLAN_CASE(64) MW_PLAN_CASE(128) MW_PLAN_CASE(256) MW_PLAN_CASE(512) MW_PLAN_CASE(1024) MW_PLAN_CASE(2048) MW_PLAN_CASE(4096)
-#undef MW_PLAN_CASE
-        default: return 16;
-    }
+    MW_FOR_SIZE(N, return 16, return pass == 1 ? Plan<NN>::P1 : Plan<NN>::P2);
 }
 
 // concatenated twiddle table [TS1 | TS2 | TS3 | TF] in the layout of TwGeom<N,P>
@@ -807,18 +786,6 @@ static hipError_t launch_pass2_n(const P2Args& A, int nsteps, hipStream_t st) {
     return hipGetLastError();
 }
 
-#define MW_DISPATCH_N(N_, CALL)                  \
-    switch (N_) {                                \
-        case 64: { constexpr int NN = 64; CALL; } break;     \
-        case 128: { constexpr int NN = 128; CALL; } break;   \
-        case 256: { constexpr int NN = 256; CALL; } break;   \
-        case 512: { constexpr int NN = 512; CALL; } break;   \
-        case 1024: { constexpr int NN = 1024; CALL; } break; \
-        case 2048: { constexpr int NN = 2048; CALL; } break; \
-        case 4096: { constexpr int NN = 4096; CALL; } break; \
-        default: return fail(MW_EINVAL, "unsupported FFT size"); \
-    }
-
 // time-steps of one pass-1 column job issued back to back on one XCD (p1_block_map): the largest divisor of nsteps up to
 // the handle's p1_tgroup (8), any divisor -- a 20-step enqueue groups by 5 --, 0 = plain 2-D grid
 static int p1_time_group(const mw_ocean* o, int nsteps) {
@@ -839,7 +806,7 @@ static mw_status launch_pass1(mw_ocean* o, const StepTimes& tm, int nsteps, hipS
     A.field_split = nsteps == 1 && mw_frame_plan_n(o->N);
     if (A.field_split) { A.jobs = o->p1_jobs; A.njobs = o->p1_njobs; }
     hipError_t e = hipSuccess;
-    MW_DISPATCH_N(o->N, e = launch_pass1_n<NN>(A, tm, nsteps, st));
+    MW_FOR_SIZE(o->N, return fail(MW_EINVAL, "unsupported FFT size"), e = launch_pass1_n<NN>(A, tm, nsteps, st));
     if (e != hipSuccess) return fail(MW_EDEVICE, std::string("pass1 launch: ") + hipGetErrorString(e));
     return MW_OK;
 }
@@ -850,8 +817,8 @@ static mw_status launch_pass2(mw_ocean* o, int nsteps, float* dv, float* dn, flo
     A.hds_dump = hds_dump;
     A.c = c ? *c : consts_of(o);
     hipError_t e = hipSuccess;
-    if (hds_dump) { MW_DISPATCH_N(o->N, (e = launch_pass2_n<NN, true>(A, nsteps, o->stream))); }
-    else { MW_DISPATCH_N(o->N, (e = launch_pass2_n<NN, false>(A, nsteps, o->stream))); }
+    if (hds_dump) { MW_FOR_SIZE(o->N, return fail(MW_EINVAL, "unsupported FFT size"), e = launch_pass2_n<NN, true>(A, nsteps, o->stream)); }
+    else { MW_FOR_SIZE(o->N, return fail(MW_EINVAL, "unsupported FFT size"), e = launch_pass2_n<NN, false>(A, nsteps, o->stream)); }
     if (e != hipSuccess) return fail(MW_EDEVICE, std::string("pass2 launch: ") + hipGetErrorString(e));
     return MW_OK;
 }
@@ -1023,9 +990,8 @@ static mw_status ocean_create_impl(const mw_params* params, int tiles, mw_ocean*
         if (M < 64 || M > 4096) { mw_ocean_destroy(o); return fail(MW_EINVAL, "OceanRenderer: texture size must be in [64,4096]"); }
         o->N = M;
         if ((s = or_create(o->orr, *params, M, o->stream, tiles)) != MW_OK) {
-            std::string m = or_last_error();
-            mw_ocean_destroy(o);
-            return fail(s, m);
+            mw_ocean_destroy(o);  // (the message or_create left stands: nothing on the way out calls fail())
+            return s;
         }
     }
     he = hipStreamSynchronize(o->stream);
@@ -1151,7 +1117,7 @@ mw_status mw_ocean_reinit_spectrum(mw_ocean* o, float length, float wind_x, floa
     frame_spectrum_changed(o, false);  // new spectrum and dispersion; the phase textures stay
     if (o->sem == MW_SEM_OCEANRENDERER) {  // S/OceanRenderer.cs:98-109: RenderInitial() again, phase textures untouched
         mw_status s = or_reinit(o->orr, length, wind_x, wind_y, amplitude, seed, o->stream);
-        if (s != MW_OK) return fail(s, or_last_error());
+        if (s != MW_OK) return s;
     } else {
         const int N = o->N;
         const bool fft = is_pow2(N) && N >= 64 && (o->p.unit_width * (float)N == length);
@@ -1312,34 +1278,30 @@ mw_status mw_ocean_update(mw_ocean* o, float delta_time, float* vertices_xyz, fl
     return mw_ocean_evaluate(o, o->timer, vertices_xyz, normals_xyz, colors_rgba);
 }
 
+// ---- OceanRenderer frames: planar / RGBA x one frame / steps x device / host --------------------------------------------------
+// What the four device forms do once their arguments stand: n frames through or_frames, and the frame record.  A lone call's latest frame
+// is the phase's; a steps call (n == 1 included: the lone-frame plan, its textures the handle's own) records what it kept.
+static mw_status make_frames(mw_ocean* o, const float* delta_time, int n, bool steps, bool rgba, void* const (&d)[4]) {
+    HIP_TRY(hipSetDevice(o->device));
+    if (!steps) frame_or_lone(o);
+    mw_status s = or_frames(o->orr, o->p.choppiness, delta_time, n, rgba, d, o->stream);
+    if (s != MW_OK || !steps) return s;
+    const bool kept[4] = {rgba || !d[0], rgba || !d[1], rgba || !d[2], rgba || !d[3]};  // what the caller did not take stays in the handle
+    frame_or_steps(o, n, kept, n - 1);
+    return MW_OK;
+}
 mw_status mw_ocean_generate_texture_device(mw_ocean* o, float delta_time, void* d_height, void* d_disp_xz,
                                            void* d_normal_xyz, void* d_white) {
     if (!o) return fail(MW_EINVAL, "NULL handle");
     if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture: OceanRenderer semantics only");
-    HIP_TRY(hipSetDevice(o->device));
-    o->orr.choppiness = o->p.choppiness;
-    frame_or_lone(o);
-    mw_status s = or_generate(o->orr, delta_time, (float*)d_height, (float*)d_disp_xz, (float*)d_normal_xyz, (float*)d_white,
-                              o->stream);
-    if (s != MW_OK) return fail(s, or_last_error());
-    return MW_OK;
+    return make_frames(o, &delta_time, 1, false, false, {d_height, d_disp_xz, d_normal_xyz, d_white});
 }
-
-mw_status mw_ocean_generate_texture(mw_ocean* o, float delta_time, float* height, float* disp_xz, float* normal_xyz,
-                                    float* white) {
+mw_status mw_ocean_generate_texture_rgba_device(mw_ocean* o, float delta_time, void* d_height_rgba, void* d_disp_rgba,
+                                                void* d_normal_rgba, void* d_white_rgba) {
     if (!o) return fail(MW_EINVAL, "NULL handle");
-    if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture: OceanRenderer semantics only");
-    mw_status s = mw_ocean_generate_texture_device(o, delta_time, nullptr, nullptr, nullptr, nullptr);
-    if (s != MW_OK) return s;
-    const size_t MM = (size_t)o->N * o->N * o->orr.tiles;
-    if (height) HIP_TRY(hipMemcpyAsync(height, o->orr.out_height, MM * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    if (disp_xz) HIP_TRY(hipMemcpyAsync(disp_xz, o->orr.out_disp, MM * 2 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    if (normal_xyz) HIP_TRY(hipMemcpyAsync(normal_xyz, o->orr.out_normal, MM * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    if (white) HIP_TRY(hipMemcpyAsync(white, o->orr.out_white, MM * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    return MW_OK;
+    if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture_rgba: OceanRenderer semantics only");
+    return make_frames(o, &delta_time, 1, false, true, {d_height_rgba, d_disp_rgba, d_normal_rgba, d_white_rgba});
 }
-
 mw_status mw_ocean_generate_texture_steps_device(mw_ocean* o, const float* delta_time, int32_t nframes, void* d_height,
                                                  void* d_disp_xz, void* d_normal_xyz, void* d_white) {
     if (!o || !delta_time) return fail(MW_EINVAL, "mw_ocean_generate_texture_steps: NULL argument");
@@ -1347,51 +1309,66 @@ mw_status mw_ocean_generate_texture_steps_device(mw_ocean* o, const float* delta
     if (nframes < 1 || nframes > mw_ocean_max_frames(o))
         return fail(o->orr.tiles != 1 ? MW_ESTATE : MW_EINVAL, o->orr.tiles != 1 ? "mw_ocean_generate_texture_steps: a batched handle (mw_ocean_create_batch) advances one frame per call"
                                                                                  : "mw_ocean_generate_texture_steps: nframes out of range (mw_ocean_max_frames)");
+    return make_frames(o, delta_time, nframes, true, false, {d_height, d_disp_xz, d_normal_xyz, d_white});
+}
+mw_status mw_ocean_generate_texture_steps_rgba_device(mw_ocean* o, const float* delta_time, int32_t nframes, void* d_height_rgba,
+                                                      void* d_disp_rgba, void* d_normal_rgba, void* d_white_rgba) {
+    if (!o || !delta_time) return fail(MW_EINVAL, "mw_ocean_generate_texture_steps_rgba: NULL argument");
+    if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture_steps_rgba: OceanRenderer semantics only");
+    if (nframes < 1 || nframes > mw_ocean_max_frames(o))
+        return fail(o->orr.tiles != 1 ? MW_ESTATE : MW_EINVAL, "mw_ocean_generate_texture_steps_rgba: nframes out of range, or a batched handle");
+    return make_frames(o, delta_time, nframes, true, true, {d_height_rgba, d_disp_rgba, d_normal_rgba, d_white_rgba});
+}
+// The host forms, once their arguments stand, around the device form of the same name.  Planar textures stay in the handle (the latest
+// frame, or the frame buffers of a steps call) and leave from there over PCIe; the RGBA targets are staged.  host: [n][...] arrays.
+static mw_status frames_to_host(mw_ocean* o, const float* delta_time, int n, bool steps, bool rgba, float* const (&host)[4]) {
     HIP_TRY(hipSetDevice(o->device));
-    o->orr.choppiness = o->p.choppiness;
-    // one frame: the lone-frame plan of mw_ocean_generate_texture_device (latency-bound launch forms); its textures are the handle's own
-    mw_status s = nframes == 1 ? or_generate(o->orr, delta_time[0], (float*)d_height, (float*)d_disp_xz, (float*)d_normal_xyz, (float*)d_white, o->stream)
-                               : or_generate_steps(o->orr, delta_time, nframes, (float*)d_height, (float*)d_disp_xz, (float*)d_normal_xyz,
-                                                   (float*)d_white, o->stream);
-    if (s != MW_OK) return fail(s, or_last_error());
-    const bool kept[4] = {!d_height, !d_disp_xz, !d_normal_xyz, !d_white};  // what the caller did not take stays in the handle
-    frame_or_steps(o, nframes, kept, nframes - 1);
+    const size_t texels = (size_t)o->N * o->N * (size_t)(steps ? n : o->orr.tiles);
+    void* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Stage st(o);
+    if (rgba) {
+        for (int k = 0; k < 4; k++) st.out(&dev[k], host[k], texels * 4 * sizeof(float));
+        mw_status s = st.begin();
+        if (s != MW_OK) return s;
+    }
+    mw_status s = steps ? (rgba ? mw_ocean_generate_texture_steps_rgba_device(o, delta_time, n, dev[0], dev[1], dev[2], dev[3])
+                                : mw_ocean_generate_texture_steps_device(o, delta_time, n, nullptr, nullptr, nullptr, nullptr))
+                        : (rgba ? mw_ocean_generate_texture_rgba_device(o, delta_time[0], dev[0], dev[1], dev[2], dev[3])
+                                : mw_ocean_generate_texture_device(o, delta_time[0], nullptr, nullptr, nullptr, nullptr));
+    if (s != MW_OK) return s;
+    if (rgba) return st.finish();
+    const OrFrame f = or_frame(o->orr, steps ? 0 : -1);
+    const void* const src[4] = {f.height, f.disp, f.normal, f.white};
+    const size_t per[4] = {1, 2, 3, 1};
+    for (int k = 0; k < 4; k++)
+        if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], src[k], texels * per[k] * sizeof(float), hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipStreamSynchronize(o->stream));
     return MW_OK;
 }
-// host forms of the steps calls: the frames stay in the handle's frame buffers, then leave over PCIe into the caller's [nframes][...] arrays
-static mw_status steps_to_host(mw_ocean* o, const float* delta_time, int32_t nframes, bool rgba, float* const host[4], const char* who) {
+mw_status mw_ocean_generate_texture(mw_ocean* o, float delta_time, float* height, float* disp_xz, float* normal_xyz,
+                                    float* white) {
+    if (!o) return fail(MW_EINVAL, "NULL handle");
+    if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture: OceanRenderer semantics only");
+    return frames_to_host(o, &delta_time, 1, false, false, {height, disp_xz, normal_xyz, white});
+}
+mw_status mw_ocean_generate_texture_rgba(mw_ocean* o, float delta_time, float* height_rgba, float* disp_rgba,
+                                         float* normal_rgba, float* white_rgba) {
+    if (!o) return fail(MW_EINVAL, "NULL handle");
+    if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture_rgba: OceanRenderer semantics only");
+    return frames_to_host(o, &delta_time, 1, false, true, {height_rgba, disp_rgba, normal_rgba, white_rgba});
+}
+static mw_status steps_to_host(mw_ocean* o, const float* delta_time, int32_t nframes, bool rgba, float* const (&host)[4], const char* who) {
     if (!o || !delta_time) return fail(MW_EINVAL, who, "NULL argument");
     if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, who, "OceanRenderer semantics only");
-    HIP_TRY(hipSetDevice(o->device));
-    const size_t MM = (size_t)o->N * o->N;
-    if (!rgba) {
-        mw_status s = mw_ocean_generate_texture_steps_device(o, delta_time, nframes, nullptr, nullptr, nullptr, nullptr);
-        if (s != MW_OK) return s;
-        void* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-        if ((s = mw_ocean_frame_textures(o, 0, &dev[0], &dev[1], &dev[2], &dev[3])) != MW_OK) return s;
-        const size_t per[4] = {MM, 2 * MM, 3 * MM, MM};
-        for (int k = 0; k < 4; k++)
-            if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], dev[k], per[k] * (size_t)nframes * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-        HIP_TRY(hipStreamSynchronize(o->stream));
-        return MW_OK;
-    }
-    void* dev[4];
-    Stage st(o);
-    for (int k = 0; k < 4; k++) st.out(&dev[k], host[k], MM * 4 * sizeof(float) * (size_t)nframes);
-    mw_status s = st.begin();
-    if (s != MW_OK) return s;
-    if ((s = mw_ocean_generate_texture_steps_rgba_device(o, delta_time, nframes, dev[0], dev[1], dev[2], dev[3])) != MW_OK) return s;
-    return st.finish();
+    return frames_to_host(o, delta_time, nframes, true, rgba, host);
 }
 mw_status mw_ocean_generate_texture_steps(mw_ocean* o, const float* delta_time, int32_t nframes, float* height, float* disp_xz, float* normal_xyz,
                                           float* white) {
-    float* const host[4] = {height, disp_xz, normal_xyz, white};
-    return steps_to_host(o, delta_time, nframes, false, host, "mw_ocean_generate_texture_steps");
+    return steps_to_host(o, delta_time, nframes, false, {height, disp_xz, normal_xyz, white}, "mw_ocean_generate_texture_steps");
 }
 mw_status mw_ocean_generate_texture_steps_rgba(mw_ocean* o, const float* delta_time, int32_t nframes, float* height_rgba, float* disp_rgba,
                                                float* normal_rgba, float* white_rgba) {
-    float* const host[4] = {height_rgba, disp_rgba, normal_rgba, white_rgba};
-    return steps_to_host(o, delta_time, nframes, true, host, "mw_ocean_generate_texture_steps_rgba");
+    return steps_to_host(o, delta_time, nframes, true, {height_rgba, disp_rgba, normal_rgba, white_rgba}, "mw_ocean_generate_texture_steps_rgba");
 }
 mw_status mw_ocean_advance_phase(mw_ocean* o, const float* delta_time, int32_t nframes) {
     if (!o || (!delta_time && nframes > 0)) return fail(MW_EINVAL, "mw_ocean_advance_phase: NULL argument");
@@ -1400,9 +1377,7 @@ mw_status mw_ocean_advance_phase(mw_ocean* o, const float* delta_time, int32_t n
     if (nframes == 0) return MW_OK;
     HIP_TRY(hipSetDevice(o->device));
     frame_phase_moved(o);
-    mw_status s = or_advance_phase(o->orr, delta_time, nframes, o->stream);
-    if (s != MW_OK) return fail(s, or_last_error());
-    return MW_OK;
+    return or_advance_phase(o->orr, delta_time, nframes, o->stream);
 }
 int32_t mw_ocean_max_frames(const mw_ocean* o) { return (o && o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles == 1) ? MW_OR_MAX_FRAMES : 0; }
 mw_status mw_ocean_frame_textures(mw_ocean* o, int32_t frame, void** d_height, void** d_disp_xz, void** d_normal_xyz, void** d_white) {
@@ -1413,25 +1388,9 @@ mw_status mw_ocean_frame_textures(mw_ocean* o, int32_t frame, void** d_height, v
     if (frame < 0 || frame >= s.frames_last) return fail(MW_EINVAL, "mw_ocean_frame_textures: frame out of range");
     const OrFrame f = or_frame(s, frame);
     if (d_height) *d_height = f.height;
-    if (d_disp_xz) *d_disp_xz = f.disp;  // out_disp / fr_disp as the caller sees them: (x, z) float pairs
+    if (d_disp_xz) *d_disp_xz = f.disp;  // (x, z) float pairs
     if (d_normal_xyz) *d_normal_xyz = f.normal;
     if (d_white) *d_white = f.white;
-    return MW_OK;
-}
-mw_status mw_ocean_generate_texture_steps_rgba_device(mw_ocean* o, const float* delta_time, int32_t nframes, void* d_height_rgba,
-                                                      void* d_disp_rgba, void* d_normal_rgba, void* d_white_rgba) {
-    if (!o || !delta_time) return fail(MW_EINVAL, "mw_ocean_generate_texture_steps_rgba: NULL argument");
-    if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture_steps_rgba: OceanRenderer semantics only");
-    if (nframes < 1 || nframes > mw_ocean_max_frames(o))
-        return fail(o->orr.tiles != 1 ? MW_ESTATE : MW_EINVAL, "mw_ocean_generate_texture_steps_rgba: nframes out of range, or a batched handle");
-    HIP_TRY(hipSetDevice(o->device));
-    o->orr.choppiness = o->p.choppiness;
-    mw_status s = nframes == 1 ? or_generate_rgba(o->orr, delta_time[0], (f4*)d_height_rgba, (f4*)d_disp_rgba, (f4*)d_normal_rgba, (f4*)d_white_rgba, o->stream)
-                               : or_generate_steps_rgba(o->orr, delta_time, nframes, (f4*)d_height_rgba, (f4*)d_disp_rgba, (f4*)d_normal_rgba,
-                                                        (f4*)d_white_rgba, o->stream);
-    if (s != MW_OK) return fail(s, or_last_error());
-    const bool kept[4] = {true, true, true, true};
-    frame_or_steps(o, nframes, kept, nframes - 1);
     return MW_OK;
 }
 
@@ -1446,42 +1405,11 @@ mw_status mw_host_unregister(void* ptr) {
     return MW_OK;
 }
 
-mw_status mw_ocean_generate_texture_rgba_device(mw_ocean* o, float delta_time, void* d_height_rgba, void* d_disp_rgba,
-                                                void* d_normal_rgba, void* d_white_rgba) {
-    if (!o) return fail(MW_EINVAL, "NULL handle");
-    if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture_rgba: OceanRenderer semantics only");
-    HIP_TRY(hipSetDevice(o->device));
-    o->orr.choppiness = o->p.choppiness;
-    frame_or_lone(o);
-    mw_status s = or_generate_rgba(o->orr, delta_time, (f4*)d_height_rgba, (f4*)d_disp_rgba, (f4*)d_normal_rgba,
-                                   (f4*)d_white_rgba, o->stream);
-    if (s != MW_OK) return fail(s, or_last_error());
-    return MW_OK;
-}
-
-mw_status mw_ocean_generate_texture_rgba(mw_ocean* o, float delta_time, float* height_rgba, float* disp_rgba,
-                                         float* normal_rgba, float* white_rgba) {
-    if (!o) return fail(MW_EINVAL, "NULL handle");
-    if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_generate_texture_rgba: OceanRenderer semantics only");
-    HIP_TRY(hipSetDevice(o->device));
-    float* host[4] = {height_rgba, disp_rgba, normal_rgba, white_rgba};
-    void* dev[4];
-    Stage st(o);
-    for (int k = 0; k < 4; k++) st.out(&dev[k], host[k], (size_t)o->N * o->N * 4 * sizeof(float) * o->orr.tiles);
-    mw_status s = st.begin();
-    if (s != MW_OK) return s;
-    if ((s = mw_ocean_generate_texture_rgba_device(o, delta_time, dev[0], dev[1], dev[2], dev[3])) != MW_OK) return s;
-    return st.finish();
-}
-
 mw_status mw_ocean_displace_mesh_device(mw_ocean* o, void* d_vertices_xyz, void* d_normals_xyz, void* d_colors) {
     if (!o || !d_vertices_xyz) return fail(MW_EINVAL, "mw_ocean_displace_mesh: NULL argument");
     if (o->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_ocean_displace_mesh: OceanRenderer semantics only");
     HIP_TRY(hipSetDevice(o->device));
-    mw_status s = or_displace_mesh(o->orr, o->p.resolution, o->p.unit_width, (float*)d_vertices_xyz, (float*)d_normals_xyz,
-                                   (float*)d_colors, o->stream);
-    if (s != MW_OK) return fail(s, or_last_error());
-    return MW_OK;
+    return or_displace_mesh(o->orr, o->p.resolution, o->p.unit_width, (float*)d_vertices_xyz, (float*)d_normals_xyz, (float*)d_colors, o->stream);
 }
 
 mw_status mw_ocean_displace_mesh(mw_ocean* o, float* vertices_xyz, float* normals_xyz, float* colors) {
@@ -1540,12 +1468,8 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
         static const char* snames[4] = {"k_or_pass1_steps (phase chain + spectra + transform along py, all frames)", rnames[1], rnames[2], rnames[3]};
         float dts[MW_OR_MAX_FRAMES];
         for (int k = 0; k < MW_OR_MAX_FRAMES; k++) dts[k] = 1.0f / 60.0f;
-        o->orr.choppiness = o->p.choppiness;
         frame_or_lone(o);
-        auto call = [&](hipEvent_t* ev) {
-            return nsteps == 1 ? or_generate(o->orr, dts[0], nullptr, nullptr, nullptr, nullptr, o->stream, ev)
-                               : or_generate_steps(o->orr, dts, nsteps, nullptr, nullptr, nullptr, nullptr, o->stream, ev);
-        };
+        auto call = [&](hipEvent_t* ev) { return or_frames(o->orr, o->p.choppiness, dts, nsteps, false, {nullptr, nullptr, nullptr, nullptr}, o->stream, ev); };
         mw_status s = MW_OK;
         {
             const auto t0 = std::chrono::steady_clock::now();
@@ -1554,7 +1478,7 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
                 hipStreamSynchronize(o->stream);
             } while (s == MW_OK && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < 0.12);
         }
-        if (s != MW_OK) return fail(s, or_last_error());
+        if (s != MW_OK) return s;
         // events of one call, per chunk j of frames (one chunk in the lone-frame plan): [3j] before its spectrum launch, [3j + 1] after it,
         // [3j + 2] after its pass 2, [3j + 3] after its normal / whitecap pass; [3 nch + 1] after the copies
         const int nch = nsteps == 1 ? 1 : or_steps_chunks(o->orr.M, nsteps);
@@ -1574,7 +1498,7 @@ static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters
             for (int k = 0; k < 4; k++) { acc[k] += m[k]; per[k].push_back(m[k]); }
         }
         for (auto& e : ev) hipEventDestroy(e);
-        if (s != MW_OK) return fail(s, or_last_error());
+        if (s != MW_OK) return s;
         for (int k = 0; k < 4; k++) {
             ms_out[k] = (float)(acc[k] / iters);
             if (names_out) names_out[k] = (nsteps == 1 ? rnames : snames)[k];

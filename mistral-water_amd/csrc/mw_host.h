@@ -1,0 +1,38 @@
+// mw_host.h -- host-side helpers every part of the library shares (device build only): the error channel behind mw_last_error() and the
+// one list of transform sizes.  Everything here has internal linkage: nothing joins the library's exported symbols.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/mistral_water.h"
+
+// ------------------------------------------------------------------------------------------------
+// error plumbing
+// ------------------------------------------------------------------------------------------------
+static thread_local std::string g_err;
+static mw_status fail(mw_status s, const std::string& m) {
+    g_err = m;
+    return s;
+}
+static mw_status fail(mw_status s, const char* who, const std::string& m) { return fail(s, std::string(who) + ": " + m); }
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess)                                                                           \
+            return fail(MW_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
+    } while (0)
+
+// The transform sizes the library has kernels for, named once.  The statement(s) after DEFAULT run with NN a constant expression equal
+// to N_; any other N_ runs DEFAULT (the caller's own message and status).
+#define MW_FOR_SIZE(N_, DEFAULT, ...)                                 \
+    switch (N_) {                                                     \
+        case 64: { constexpr int NN = 64; __VA_ARGS__; } break;       \
+        case 128: { constexpr int NN = 128; __VA_ARGS__; } break;     \
+        case 256: { constexpr int NN = 256; __VA_ARGS__; } break;     \
+        case 512: { constexpr int NN = 512; __VA_ARGS__; } break;     \
+        case 1024: { constexpr int NN = 1024; __VA_ARGS__; } break;   \
+        case 2048: { constexpr int NN = 2048; __VA_ARGS__; } break;   \
+        case 4096: { constexpr int NN = 4096; __VA_ARGS__; } break;   \
+        default: DEFAULT;                                             \
+    }

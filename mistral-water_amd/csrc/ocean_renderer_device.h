@@ -3,11 +3,11 @@
 #include <hip/hip_runtime.h>
 
 #include <mutex>
-#include <string>
 #include <utility>
 #include <vector>
 
 #include "../../include/mistral_water.h"
+#include "mw_host.h"
 #include "ocean_renderer_kernels.h"
 #include "mw_switches.h"
 
@@ -27,6 +27,20 @@ struct AttrOnce {
     }
 };
 
+// One set of the seven arrays a frame is made of.  The handle holds two: `out`, the latest frame (tile-major on a batched handle), and
+// `fr`, the frame buffers of a steps call ([frames_cap] frames each).  A set whose height_g / disp_a are NULL is a planar frame.
+struct OrTex {
+    float* height = nullptr;  // heightTexture.r
+    cf* disp = nullptr;       // displacementTexture.rb: (x, z) pairs
+    float *disp_g = nullptr, *normal = nullptr, *white = nullptr;
+    float *height_g = nullptr, *disp_a = nullptr;  // Im h, Im Dz: written only by the calls that deliver the RGBA layout
+    // the set `texels` further on: frame k of the frame buffers is at(k * M * M)
+    OrTex at(size_t texels) const {
+        auto mv = [texels](auto* p, size_t per) { return p ? p + per * texels : p; };
+        return OrTex{mv(height, 1), mv(disp, 1), mv(disp_g, 1), mv(normal, 3), mv(white, 1), mv(height_g, 1), mv(disp_a, 1)};
+    }
+    OrTex real_only() const { OrTex t = *this; t.height_g = t.disp_a = nullptr; return t; }
+};
 // `tiles` independent oceans (seed, seed + 1, ...) share one handle: every buffer below carries a leading tile axis and
 // every kernel one more grid dimension, so a GenerateTexture() of all tiles is still three launches (mw_ocean_create_batch).
 // A frame of ONE 1024^2 texture is latency-bound (three launches of 256-768 workgroups); the phase recurrence forbids
@@ -34,29 +48,23 @@ struct AttrOnce {
 struct OrState {
     int M = 0;
     int tiles = 1;
-    OrConsts c{};
-    float mult = 1.f, choppiness = 0.f;
+    OrConsts c{};  // c.choppiness: that of the latest frame (or_frames sets it; or_velocity differentiates that frame)
+    float mult = 1.f;
     f4* initT = nullptr;
     f4* PQT = nullptr;     // [px][py] Hermitian parts (P, Q) of the initial spectrum: the packed plan (or_prep_element), rebuilt with initT
     bool phase_sym = true; // the phase texture equals its mirror image (true from creation on; mw_ocean_set_phase checks what it is given)
     float* omT = nullptr;  // [px][py] angular frequency (or_omega), fixed per handle
     float *phaseT = nullptr, *phaseT2 = nullptr;  // current phase / next phase (swapped after every frame)
     cf *TW = nullptr, *E = nullptr;
-    float *out_height = nullptr, *out_disp_g = nullptr, *out_normal = nullptr, *out_white = nullptr;
-    cf* out_disp_cf = nullptr;
-    float* out_disp = nullptr;  // alias of out_disp_cf as floats (r, b)
-    float *out_height_g = nullptr, *out_disp_a = nullptr;  // Im h, Im Dz: written only once the RGBA layout was asked for
-    bool want_imag = false, have_imag = false, have_frame = false;
+    OrTex out;  // the latest frame; height_g / disp_a allocated by the first call that asks for the RGBA layout (or_imag_planes)
+    bool have_frame = false;
     // mw_ocean_generate_texture_steps_device: [frames_cap] frames of the exchange buffer and of the textures the caller did not ask for
     // (disp.g always: OceanNormal reads it, no entry point hands it out alone); grown on demand, never shrunk
     int frames_cap = 0, frames_last = 0;  // capacity / frames of the latest steps call
     cf* fr_E = nullptr;
-    float *fr_height = nullptr, *fr_disp_g = nullptr, *fr_normal = nullptr, *fr_white = nullptr, *fr_height_g = nullptr, *fr_disp_a = nullptr;
-    cf* fr_disp = nullptr;
+    OrTex fr;
     bool fr_have[4] = {false, false, false, false};  // which textures the latest steps call kept here
 };
-static thread_local std::string g_or_err;
-static inline const char* or_last_error() { return g_or_err.c_str(); }
 
 __global__ void k_or_omega(OrConsts c, float* omT) {
     int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -407,54 +415,85 @@ __global__ void k_or_displace_mesh(int M, int res, float unit_width, const float
 std::vector<cf> build_twiddle_table(int N, int P, int sgn);  // mistral_water.hip
 int plan_points_host(int N);
 
+// Every device buffer of an OrState, named once: the rows or_alloc allocates (in this order) and or_release frees.  `when` says which call
+// brings a row: creation; the first call that wants Im h / Im Dz; a steps call -- always, for a texture kind the caller gave no
+// destination for, or for the RGBA layout.
+enum : unsigned {
+    OR_B_HANDLE = 1u, OR_B_IMAG = 2u, OR_B_FR = 4u, OR_B_FR_HEIGHT = 8u, OR_B_FR_DISP = 16u, OR_B_FR_NORMAL = 32u, OR_B_FR_WHITE = 64u,
+    OR_B_FR_IMAG = 128u, OR_B_FRAMES = 252u, OR_B_ALL = 255u
+};
+struct OrBuf { void** p; size_t bytes; unsigned when; };
+constexpr int OR_NBUF = 22;
+// tw_count: entries of the twiddle table; frames: capacity of the frame buffers (either may be 0 for a caller that only frees)
+static inline void or_buffers(OrState& s, size_t tw_count, size_t frames, OrBuf (&b)[OR_NBUF]) {
+    const size_t MM = (size_t)s.M * s.M, TM = MM * (size_t)s.tiles, FM = MM * frames;
+    int n = 0;
+    auto row = [&](auto*& p, size_t count, unsigned when) { b[n++] = OrBuf{(void**)&p, sizeof(*p) * count, when}; };
+    row(s.initT, TM, OR_B_HANDLE); row(s.PQT, TM, OR_B_HANDLE); row(s.phaseT, TM, OR_B_HANDLE); row(s.phaseT2, TM, OR_B_HANDLE);
+    row(s.omT, MM, OR_B_HANDLE); row(s.TW, tw_count, OR_B_HANDLE); row(s.E, 3 * TM, OR_B_HANDLE);
+    row(s.out.height, TM, OR_B_HANDLE); row(s.out.disp, TM, OR_B_HANDLE); row(s.out.disp_g, TM, OR_B_HANDLE);
+    row(s.out.normal, 3 * TM, OR_B_HANDLE); row(s.out.white, TM, OR_B_HANDLE);
+    row(s.out.height_g, TM, OR_B_IMAG); row(s.out.disp_a, TM, OR_B_IMAG);
+    row(s.fr_E, 3 * FM, OR_B_FR); row(s.fr.disp_g, FM, OR_B_FR);
+    row(s.fr.height, FM, OR_B_FR_HEIGHT); row(s.fr.disp, FM, OR_B_FR_DISP); row(s.fr.normal, 3 * FM, OR_B_FR_NORMAL);
+    row(s.fr.white, FM, OR_B_FR_WHITE); row(s.fr.height_g, FM, OR_B_FR_IMAG); row(s.fr.disp_a, FM, OR_B_FR_IMAG);
+}
+// the rows of `when` that are not there yet; false: a hipMalloc failed (what it did allocate stays, for or_free)
+static inline bool or_alloc(OrState& s, unsigned when, size_t tw_count, size_t frames) {
+    OrBuf b[OR_NBUF];
+    or_buffers(s, tw_count, frames, b);
+    for (const OrBuf& r : b)
+        if ((r.when & when) && !*r.p && hipMalloc(r.p, r.bytes) != hipSuccess) return false;
+    return true;
+}
+static inline void or_release(OrState& s, unsigned when) {  // (hipFree waits for the device)
+    OrBuf b[OR_NBUF];
+    or_buffers(s, 0, 0, b);
+    for (const OrBuf& r : b)
+        if (r.when & when) { hipFree(*r.p); *r.p = nullptr; }
+}
 static inline void or_free(OrState& s) {
-    hipFree(s.initT); hipFree(s.PQT); hipFree(s.phaseT); hipFree(s.phaseT2); hipFree(s.omT); hipFree(s.TW); hipFree(s.E); hipFree(s.out_height); hipFree(s.out_disp_cf);
-    hipFree(s.out_disp_g); hipFree(s.out_normal); hipFree(s.out_white); hipFree(s.out_height_g); hipFree(s.out_disp_a);
-    hipFree(s.fr_E); hipFree(s.fr_height); hipFree(s.fr_disp_g); hipFree(s.fr_normal); hipFree(s.fr_white); hipFree(s.fr_height_g);
-    hipFree(s.fr_disp_a); hipFree(s.fr_disp);
+    or_release(s, OR_B_ALL);
     s = OrState();
 }
 
+// RenderInitial() (S/OceanRenderer.cs:94-109): initialTexture from length / wind / amplitude, then the dispersion and spectrum tables on that
+// length.  At creation the phase starts at 0 with it; after a parameter change (mw_ocean_reinit_spectrum) the phase textures and the normal
+// pass's length stay.
+static inline mw_status or_reinit(OrState& s, float length, float wind_x, float wind_y, float amplitude, uint64_t seed, hipStream_t st,
+                                  bool restart_phase = false) {
+    const size_t MM = (size_t)s.M * s.M;
+    s.c.length = length;
+    k_or_init<<<dim3((unsigned)((MM + 255) / 256), s.tiles), dim3(256), 0, st>>>(s.M, length, wind_x, wind_y, amplitude / 10000.f,
+                                                                                s.c.gravity, seed, s.initT, restart_phase ? s.phaseT : nullptr);
+    k_or_omega<<<dim3((unsigned)((MM + 255) / 256)), dim3(256), 0, st>>>(s.c, s.omT);
+    k_or_prep<<<dim3((unsigned)((MM + 255) / 256), s.tiles), dim3(256), 0, st>>>(s.M, s.initT, s.PQT);
+    if (hipGetLastError() != hipSuccess) return fail(MW_EDEVICE, "k_or_init launch failed");
+    return MW_OK;
+}
 static inline mw_status or_create(OrState& s, const mw_params& p, int M, hipStream_t st, int tiles = 1) {
     s.M = M;
     s.tiles = tiles;
     s.c.M = M; s.c.length = p.length; s.c.gravity = p.gravity; s.c.choppiness = p.choppiness; s.c.normal_length = p.length;
-    s.mult = p.mult; s.choppiness = p.choppiness;
-    const size_t MM = (size_t)M * M, TM = MM * (size_t)tiles;
+    s.mult = p.mult;
     std::vector<cf> tab = build_twiddle_table(M, plan_points_host(M), -1);
-#define OR_ALLOC(ptr, bytes) if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) { g_or_err = "OceanRenderer: hipMalloc failed"; return MW_ENOMEM; }
-    OR_ALLOC(s.initT, sizeof(f4) * TM) OR_ALLOC(s.PQT, sizeof(f4) * TM) OR_ALLOC(s.phaseT, sizeof(float) * TM) OR_ALLOC(s.phaseT2, sizeof(float) * TM) OR_ALLOC(s.omT, sizeof(float) * MM) OR_ALLOC(s.TW, sizeof(cf) * tab.size())
-    OR_ALLOC(s.E, sizeof(cf) * 3 * TM) OR_ALLOC(s.out_height, sizeof(float) * TM) OR_ALLOC(s.out_disp_cf, sizeof(cf) * TM)
-    OR_ALLOC(s.out_disp_g, sizeof(float) * TM) OR_ALLOC(s.out_normal, sizeof(float) * 3 * TM) OR_ALLOC(s.out_white, sizeof(float) * TM)
-#undef OR_ALLOC
-    s.out_disp = reinterpret_cast<float*>(s.out_disp_cf);
-    if (hipMemcpy(s.TW, tab.data(), sizeof(cf) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) { g_or_err = "twiddle upload failed"; return MW_EDEVICE; }
-    k_or_init<<<dim3((unsigned)((MM + 255) / 256), tiles), dim3(256), 0, st>>>(M, p.length, p.wind_x, p.wind_y, p.amplitude / 10000.f,
-                                                                              p.gravity, p.seed, s.initT, s.phaseT);
-    k_or_omega<<<dim3((unsigned)((MM + 255) / 256)), dim3(256), 0, st>>>(s.c, s.omT);
-    k_or_prep<<<dim3((unsigned)((MM + 255) / 256), tiles), dim3(256), 0, st>>>(M, s.initT, s.PQT);
-    if (hipGetLastError() != hipSuccess) { g_or_err = "k_or_init launch failed"; return MW_EDEVICE; }
-    return MW_OK;
+    if (!or_alloc(s, OR_B_HANDLE, tab.size(), 0)) return fail(MW_ENOMEM, "OceanRenderer: hipMalloc failed");
+    if (hipMemcpy(s.TW, tab.data(), sizeof(cf) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(MW_EDEVICE, "twiddle upload failed");
+    return or_reinit(s, p.length, p.wind_x, p.wind_y, p.amplitude, p.seed, st, true);
+}
+// Im h and Im Dz of the latest frame: allocated by the first call that delivers the RGBA layout
+static inline mw_status or_imag_planes(OrState& s) {
+    if (s.out.height_g) return MW_OK;
+    return or_alloc(s, OR_B_IMAG, 0, 0) ? MW_OK : fail(MW_ENOMEM, "OceanRenderer: hipMalloc failed");
 }
 // the planar-texture plan of a call: two transforms per frame where the identity holds (or_prep_element), else the shaders' three
 // (4096^2 textures keep three: their 1024-thread P = 16 workgroups have 128 registers per lane, and two animated spectra at once spill --
 // one GenerateTexture() 545 -> 637 us; 2048^2: 127 -> 110 us, 4 / 8 tiles per call 24.0 / 25.1 -> 24.3 / 23.3 us per tile-frame)
-static inline bool or_use_packed(const OrState& s) {
-    return MW_OR_PACKED != 0 && sw(SW_OR_PACKED) != 0 && !s.want_imag && s.phase_sym && s.M < MW_OR_PACKED_MAX_M;
+// imag: the call delivers Im h and Im Dz (the RGBA layout): they are channels of the targets, so it runs the three-transform plan
+static inline bool or_use_packed(const OrState& s, bool imag) {
+    return MW_OR_PACKED != 0 && sw(SW_OR_PACKED) != 0 && !imag && s.phase_sym && s.M < MW_OR_PACKED_MAX_M;
 }
 
-// RenderInitial() after a parameter change (S/OceanRenderer.cs:98-109): initialTexture again from the new length / wind /
-// amplitude, dispersion and spectrum passes on the new length (:94-97); the phase textures and the normal pass's length stay
-static inline mw_status or_reinit(OrState& s, float length, float wind_x, float wind_y, float amplitude, uint64_t seed, hipStream_t st) {
-    const size_t MM = (size_t)s.M * s.M;
-    s.c.length = length;
-    k_or_init<<<dim3((unsigned)((MM + 255) / 256), s.tiles), dim3(256), 0, st>>>(s.M, length, wind_x, wind_y, amplitude / 10000.f,
-                                                                                s.c.gravity, seed, s.initT, nullptr);
-    k_or_omega<<<dim3((unsigned)((MM + 255) / 256)), dim3(256), 0, st>>>(s.c, s.omT);
-    k_or_prep<<<dim3((unsigned)((MM + 255) / 256), s.tiles), dim3(256), 0, st>>>(s.M, s.initT, s.PQT);
-    if (hipGetLastError() != hipSuccess) { g_or_err = "k_or_init launch failed"; return MW_EDEVICE; }
-    return MW_OK;
-}
 // phase texture <-> host order (texel (px,py) at py*M + px); the device keeps it transposed
 __global__ void k_or_phase_transpose(int M, const float* src, float* dst) {
     int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -474,33 +513,40 @@ __global__ void k_or_phase_transpose(int M, const float* src, float* dst) {
 #ifndef MW_OR_STREAM_BIG_N
 #define MW_OR_STREAM_BIG_N MW_OR_BIG_N
 #endif
+static inline bool or_call_is_big(const OrState& s) { return s.tiles >= MW_OR_STREAM_E_TILES || s.M >= MW_OR_STREAM_BIG_N; }
+// all fields of a column job in one pass-1 workgroup (else one field per workgroup: the lone frame)
+static inline bool or_all_fields(const OrState& s) { return s.tiles > 1 || s.M >= MW_OR_BIG_N; }
+// The arguments of a spectrum launch at the handle's current phase: (initT, PQT) the spectrum it animates (the handle's, or the velocity's
+// weighted one), phase_out where the advanced phase goes, E the exchange buffer it fills.
+static inline OrP1Args or_p1_args(const OrState& s, const f4* initT, const f4* PQT, float* phase_out, cf* E, float dt, bool stream_E) {
+    OrP1Args A;
+    A.initT = initT; A.PQT = PQT; A.omT = s.omT; A.phase_in = s.phaseT; A.phase_out = phase_out; A.TW = s.TW; A.E = E; A.c = s.c; A.dt = dt;
+    A.stream_E = stream_E ? 1 : 0;
+    return A;
+}
+// ... and of the second pass from E into the set t (a planar set: no Im h / Im Dz written)
+static inline OrP2Args or_p2_args(const OrState& s, const cf* E, const OrTex& t) {
+    OrP2Args A;
+    A.E = E; A.TW = s.TW; A.height = t.height; A.disp = t.disp; A.disp_g = t.disp_g; A.c = s.c;
+    A.height_g = t.height_g; A.disp_a = t.disp_a;
+    return A;
+}
 template <int N>
-static inline bool or_call_is_big(const OrState& s) { return s.tiles >= MW_OR_STREAM_E_TILES || N >= MW_OR_STREAM_BIG_N; }
-template <int N>
-static hipError_t or_launch_passes(OrState& s, float dt, hipStream_t st, hipEvent_t* ev = nullptr) {
+static hipError_t or_launch_passes(OrState& s, float dt, bool imag, hipStream_t st, hipEvent_t* ev = nullptr) {
     constexpr int P = Plan<N>::P;
     static AttrOnce attr1, attr2;
-    {
-        hipError_t e = attr1.set(reinterpret_cast<const void*>(&k_or_pass1<N, P>), OrP1Geom<N, P>::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        e = attr2.set(reinterpret_cast<const void*>(&k_or_pass2<N, P>), OrP2Geom<N, P>::LDS_BYTES);
-        if (e != hipSuccess) return e;
-    }
-    OrP1Args A1;
-    A1.initT = s.initT; A1.PQT = s.PQT; A1.omT = s.omT; A1.phase_in = s.phaseT; A1.phase_out = s.phaseT2; A1.TW = s.TW; A1.E = s.E; A1.c = s.c; A1.dt = dt;
-    A1.stream_E = or_call_is_big<N>(s) ? 1 : 0;
+    hipError_t e = attr1.set(reinterpret_cast<const void*>(&k_or_pass1<N, P>), OrP1Geom<N, P>::LDS_BYTES);
+    if (e == hipSuccess) e = attr2.set(reinterpret_cast<const void*>(&k_or_pass2<N, P>), OrP2Geom<N, P>::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    const OrP1Args A1 = or_p1_args(s, s.initT, s.PQT, s.phaseT2, s.E, dt, or_call_is_big(s));
+    const OrP2Args A2 = or_p2_args(s, s.E, imag ? s.out : s.out.real_only());
     constexpr int NT1 = OrP1Geom<N, P>::NTHREADS, LB1 = OrP1Geom<N, P>::LDS_BYTES;
     constexpr int NT2 = OrP2Geom<N, P>::NTHREADS, LB2 = OrP2Geom<N, P>::LDS_BYTES;
-    const bool packed = or_use_packed(s), all_fields = (s.tiles > 1 || N >= MW_OR_BIG_N);
-    OrP2Args A2;
-    A2.E = s.E; A2.TW = s.TW; A2.height = s.out_height; A2.disp = s.out_disp_cf; A2.disp_g = s.out_disp_g; A2.c = s.c;
-    A2.height_g = s.want_imag ? s.out_height_g : nullptr;
-    A2.disp_a = s.want_imag ? s.out_disp_a : nullptr;
+    const bool packed = or_use_packed(s, imag), all_fields = or_all_fields(s);
     if constexpr (N < MW_OR_PACKED_MAX_M) if (packed) {
         static AttrOnce attr1p, attr2p;
-        hipError_t e = attr1p.set(reinterpret_cast<const void*>(&k_or_pass1_packed<N, P>), LB1);
-        if (e != hipSuccess) return e;
-        e = attr2p.set(reinterpret_cast<const void*>(&k_or_pass2_packed<N, P>), LB2);
+        e = attr1p.set(reinterpret_cast<const void*>(&k_or_pass1_packed<N, P>), LB1);
+        if (e == hipSuccess) e = attr2p.set(reinterpret_cast<const void*>(&k_or_pass2_packed<N, P>), LB2);
         if (e != hipSuccess) return e;
         if (ev) hipEventRecord(ev[0], st);
         k_or_pass1_packed<N, P><<<dim3(N / 4, all_fields ? 1 : 2, s.tiles), dim3(NT1), LB1, st>>>(A1);
@@ -519,84 +565,48 @@ static hipError_t or_launch_passes(OrState& s, float dt, hipStream_t st, hipEven
     return hipGetLastError();
 }
 
-// one GenerateTexture(): results land in s.out_*; optional device destinations receive copies
+// one GenerateTexture(): results land in s.out (imag: Im h and Im Dz too); optional device destinations receive copies
 // ev (measurement hook, 5 events): recorded before pass 1 and after pass 1, pass 2, the normal / whitecap pass and the copies
-static inline mw_status or_generate(OrState& s, float delta_time, float* d_height, float* d_disp, float* d_normal, float* d_white,
+static inline mw_status or_generate(OrState& s, float delta_time, bool imag, float* d_height, float* d_disp, float* d_normal, float* d_white,
                                     hipStream_t st, hipEvent_t* ev = nullptr) {
-    s.c.choppiness = s.choppiness;
     const float dt = delta_time * s.mult;  // S/OceanRenderer.cs:223
-    if (s.want_imag && !s.out_height_g) {
-        const size_t bytes = sizeof(float) * (size_t)s.M * s.M * s.tiles;
-        if (hipMalloc((void**)&s.out_height_g, bytes) != hipSuccess || hipMalloc((void**)&s.out_disp_a, bytes) != hipSuccess) {
-            g_or_err = "OceanRenderer: hipMalloc failed";
-            return MW_ENOMEM;
-        }
-    }
+    const mw_status r = imag ? or_imag_planes(s) : MW_OK;
+    if (r != MW_OK) return r;
     hipError_t e = hipSuccess;
-    switch (s.M) {
-        case 64: e = or_launch_passes<64>(s, dt, st, ev); break;
-        case 128: e = or_launch_passes<128>(s, dt, st, ev); break;
-        case 256: e = or_launch_passes<256>(s, dt, st, ev); break;
-        case 512: e = or_launch_passes<512>(s, dt, st, ev); break;
-        case 1024: e = or_launch_passes<1024>(s, dt, st, ev); break;
-        case 2048: e = or_launch_passes<2048>(s, dt, st, ev); break;
-        case 4096: e = or_launch_passes<4096>(s, dt, st, ev); break;
-        default: g_or_err = "OceanRenderer: unsupported texture size"; return MW_EINVAL;
-    }
-    if (e != hipSuccess) { g_or_err = std::string("OceanRenderer pass launch: ") + hipGetErrorString(e); return MW_EDEVICE; }
+    MW_FOR_SIZE(s.M, return fail(MW_EINVAL, "OceanRenderer: unsupported texture size"), e = or_launch_passes<NN>(s, dt, imag, st, ev));
+    if (e != hipSuccess) return fail(MW_EDEVICE, std::string("OceanRenderer pass launch: ") + hipGetErrorString(e));
     const size_t MM = (size_t)s.M * s.M, TM = MM * (size_t)s.tiles;
     const unsigned nb = or_nw_blocks(MM);
-    if (s.tiles >= MW_OR_STREAM_E_TILES || s.M >= MW_OR_STREAM_BIG_N)
-        k_or_normal_white<true><<<dim3(nb, s.tiles), dim3(256), 0, st>>>(s.c, s.out_height, s.out_disp_cf, s.out_disp_g, s.out_normal, s.out_white);
-    else
-        k_or_normal_white<false><<<dim3(nb, s.tiles), dim3(256), 0, st>>>(s.c, s.out_height, s.out_disp_cf, s.out_disp_g, s.out_normal, s.out_white);
-    if (hipGetLastError() != hipSuccess) { g_or_err = "OceanRenderer normal/white launch failed"; return MW_EDEVICE; }
+    const OrTex& o = s.out;
+    if (or_call_is_big(s)) k_or_normal_white<true><<<dim3(nb, s.tiles), dim3(256), 0, st>>>(s.c, o.height, o.disp, o.disp_g, o.normal, o.white);
+    else k_or_normal_white<false><<<dim3(nb, s.tiles), dim3(256), 0, st>>>(s.c, o.height, o.disp, o.disp_g, o.normal, o.white);
+    if (hipGetLastError() != hipSuccess) return fail(MW_EDEVICE, "OceanRenderer normal/white launch failed");
     if (ev) hipEventRecord(ev[3], st);
     s.have_frame = true;
-    s.have_imag = s.want_imag;
     hipError_t ce = hipSuccess;
-    if (d_height && ce == hipSuccess) ce = hipMemcpyAsync(d_height, s.out_height, TM * 4, hipMemcpyDeviceToDevice, st);
-    if (d_disp && ce == hipSuccess) ce = hipMemcpyAsync(d_disp, s.out_disp_cf, TM * 8, hipMemcpyDeviceToDevice, st);
-    if (d_normal && ce == hipSuccess) ce = hipMemcpyAsync(d_normal, s.out_normal, TM * 12, hipMemcpyDeviceToDevice, st);
-    if (d_white && ce == hipSuccess) ce = hipMemcpyAsync(d_white, s.out_white, TM * 4, hipMemcpyDeviceToDevice, st);
-    if (ce != hipSuccess) { g_or_err = std::string("OceanRenderer result copy: ") + hipGetErrorString(ce); return MW_EDEVICE; }
+    if (d_height && ce == hipSuccess) ce = hipMemcpyAsync(d_height, o.height, TM * 4, hipMemcpyDeviceToDevice, st);
+    if (d_disp && ce == hipSuccess) ce = hipMemcpyAsync(d_disp, o.disp, TM * 8, hipMemcpyDeviceToDevice, st);
+    if (d_normal && ce == hipSuccess) ce = hipMemcpyAsync(d_normal, o.normal, TM * 12, hipMemcpyDeviceToDevice, st);
+    if (d_white && ce == hipSuccess) ce = hipMemcpyAsync(d_white, o.white, TM * 4, hipMemcpyDeviceToDevice, st);
+    if (ce != hipSuccess) return fail(MW_EDEVICE, std::string("OceanRenderer result copy: ") + hipGetErrorString(ce));
     if (ev) hipEventRecord(ev[4], st);
-    return MW_OK;
-}
-
-// one GenerateTexture() delivered as the reference's four ARGBFloat render targets (any destination may be NULL)
-static inline mw_status or_generate_rgba(OrState& s, float delta_time, f4* d_height, f4* d_disp, f4* d_normal, f4* d_white,
-                                         hipStream_t st) {
-    s.want_imag = true;  // for this call: Im h and Im Dz are channels of the targets, so it runs the three-transform plan (or_use_packed)
-    mw_status r = or_generate(s, delta_time, nullptr, nullptr, nullptr, nullptr, st);
-    s.want_imag = false;
-    if (r != MW_OK) return r;
-    const size_t MM = (size_t)s.M * s.M;
-    k_or_pack_rgba<<<dim3((unsigned)((MM + 255) / 256), s.tiles), dim3(256), 0, st>>>(s.M, s.out_height, s.out_height_g, s.out_disp_cf,
-                                                                              s.out_disp_g, s.out_disp_a, s.out_normal,
-                                                                              s.out_white, d_height, d_disp, d_normal, d_white);
-    if (hipGetLastError() != hipSuccess) { g_or_err = "k_or_pack_rgba launch failed"; return MW_EDEVICE; }
     return MW_OK;
 }
 
 // ---- nframes consecutive GenerateTexture() calls in one enqueue ------------------------------------------------------------------
 // frame buffers of the handle: the exchange buffer and disp.g for `n` frames, plus every texture the caller gave no destination for
 static inline mw_status or_frames_reserve(OrState& s, int n, const bool (&need)[4], bool imag) {
-    const size_t MM = (size_t)s.M * s.M;
-    if (n > s.frames_cap) {  // grow: drop everything (hipFree waits for the device), the arrays come back below at the new size
-        hipFree(s.fr_E); hipFree(s.fr_height); hipFree(s.fr_disp_g); hipFree(s.fr_normal); hipFree(s.fr_white); hipFree(s.fr_height_g);
-        hipFree(s.fr_disp_a); hipFree(s.fr_disp);
-        s.fr_E = nullptr; s.fr_disp = nullptr;
-        s.fr_height = s.fr_disp_g = s.fr_normal = s.fr_white = s.fr_height_g = s.fr_disp_a = nullptr;
+    if (n > s.frames_cap) {  // grow: drop everything, the arrays come back below at the new size
+        or_release(s, OR_B_FRAMES);
         s.frames_cap = 0; s.frames_last = 0;
     }
     const size_t cap = (size_t)(s.frames_cap ? s.frames_cap : n);
-#define OR_FR(ptr, cond, bytes) if ((cond) && !(ptr) && hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) { (void)hipGetLastError(); g_or_err = "OceanRenderer: hipMalloc of the frame buffers failed"; return MW_ENOMEM; }
-    OR_FR(s.fr_E, true, sizeof(cf) * 3 * MM * cap) OR_FR(s.fr_disp_g, true, sizeof(float) * MM * cap)
-    OR_FR(s.fr_height, need[0], sizeof(float) * MM * cap) OR_FR(s.fr_disp, need[1], sizeof(cf) * MM * cap)
-    OR_FR(s.fr_normal, need[2], sizeof(float) * 3 * MM * cap) OR_FR(s.fr_white, need[3], sizeof(float) * MM * cap)
-    OR_FR(s.fr_height_g, imag, sizeof(float) * MM * cap) OR_FR(s.fr_disp_a, imag, sizeof(float) * MM * cap)
-#undef OR_FR
+    const unsigned when = OR_B_FR | (need[0] ? OR_B_FR_HEIGHT : 0u) | (need[1] ? OR_B_FR_DISP : 0u) | (need[2] ? OR_B_FR_NORMAL : 0u) |
+                          (need[3] ? OR_B_FR_WHITE : 0u) | (imag ? OR_B_FR_IMAG : 0u);
+    if (!or_alloc(s, when, 0, cap)) {
+        (void)hipGetLastError();
+        return fail(MW_ENOMEM, "OceanRenderer: hipMalloc of the frame buffers failed");
+    }
     s.frames_cap = (int)cap;
     return MW_OK;
 }
@@ -617,8 +627,9 @@ static inline int or_steps_chunks(int M, int n) { const int c = or_steps_chunk(M
 #ifndef MW_OR_STEPS_MAX_N
 #define MW_OR_STEPS_MAX_N 2048  // above: the 1024-thread P = 16 workgroup has 128 VGPRs per lane, no room for a chain in registers
 #endif
+// f: where the n frames go (the frame buffers, or the caller's arrays for the kinds it gave)
 template <int N, bool PACKED>
-static hipError_t or_launch_steps(OrState& s, const float* dt, int n, const OrP2Args& A2, float* f_n, float* f_w, hipStream_t st, hipEvent_t* ev = nullptr) {
+static hipError_t or_launch_steps(OrState& s, const float* dt, int n, const OrTex& f, hipStream_t st, hipEvent_t* ev = nullptr) {
     constexpr int P = Plan<N>::P, NF = PACKED ? 2 : 3;
     // KEEP: (h0, h0c) -- and in the packed plan (P, Q) -- of a workgroup's points stay in registers over its frames (P = 16: no registers to spare)
     constexpr bool KEEP = P <= 8;
@@ -636,15 +647,12 @@ static hipError_t or_launch_steps(OrState& s, const float* dt, int n, const OrP2
     const int chunk = or_steps_chunk(N);
     // pass 2 and the normal / whitecap pass of the frames [c0, c0 + cn)
     auto rest = [&](int c0, int cn, int j) {
-        OrP2Args B2 = A2;
-        const size_t off = MM * (size_t)c0;
-        B2.E += NF * off; B2.height += off; B2.disp += off; B2.disp_g += off;
-        if (B2.height_g) B2.height_g += off;
-        if (B2.disp_a) B2.disp_a += off;
+        const OrTex c = f.at(MM * (size_t)c0);
+        const OrP2Args B2 = or_p2_args(s, s.fr_E + NF * MM * (size_t)c0, c);
         if constexpr (PACKED) k_or_pass2_packed<N, P><<<dim3(N / 4, 1, cn), dim3(NT2), LB2, st>>>(B2);
         else k_or_pass2<N, P><<<dim3(N / 4, 2, cn), dim3(NT2), LB2, st>>>(B2);
         if (ev) hipEventRecord(ev[2 + 3 * j], st);
-        k_or_normal_white<true><<<dim3(or_nw_blocks(MM), cn), dim3(256), 0, st>>>(s.c, B2.height, B2.disp, B2.disp_g, f_n + 3 * off, f_w + off);
+        k_or_normal_white<true><<<dim3(or_nw_blocks(MM), cn), dim3(256), 0, st>>>(s.c, c.height, c.disp, c.disp_g, c.normal, c.white);
         if (ev) hipEventRecord(ev[3 + 3 * j], st);
     };
     // Pass 2 and the normal / whitecap pass alternate over chunks of frames: the height / displacement textures a chunk writes (16 B per texel
@@ -655,8 +663,7 @@ static hipError_t or_launch_steps(OrState& s, const float* dt, int n, const OrP2
         hipError_t e = attr1.set(reinterpret_cast<const void*>(&k_or_pass1_steps<N, P, KEEP, PACKED>), LB1);
         if (e != hipSuccess) return e;
         OrP1StepsArgs S;
-        S.a.initT = s.initT; S.a.PQT = s.PQT; S.a.omT = s.omT; S.a.phase_in = s.phaseT; S.a.phase_out = s.phaseT2; S.a.TW = s.TW; S.a.E = s.fr_E; S.a.c = s.c;
-        S.a.dt = 0.f; S.a.stream_E = 1;
+        S.a = or_p1_args(s, s.initT, s.PQT, s.phaseT2, s.fr_E, 0.f, true);
         for (int k = 0; k < MW_OR_MAX_FRAMES; k++) S.dt[k] = k < n ? dt[k] : 0.f;
         S.nframes = n;
         // ONE spectrum launch over all frames: per chunk (so that pass 2 would find the exchange buffer in the cache) it ran 195 -> 283 us per 32
@@ -679,10 +686,7 @@ static hipError_t or_launch_steps(OrState& s, const float* dt, int n, const OrP2
         for (int c0 = 0, j = 0; c0 < n; c0 += chunk, j++) {
             const int cn = (n - c0 < chunk) ? n - c0 : chunk;
             for (int k = c0; k < c0 + cn; k++) {
-                OrP1Args A1;
-                A1.initT = s.initT; A1.PQT = s.PQT; A1.omT = s.omT; A1.phase_in = s.phaseT; A1.phase_out = s.phaseT2; A1.TW = s.TW; A1.c = s.c; A1.dt = dt[k];
-                A1.E = s.fr_E + (size_t)NF * N * N * k;
-                A1.stream_E = 1;
+                const OrP1Args A1 = or_p1_args(s, s.initT, s.PQT, s.phaseT2, s.fr_E + (size_t)NF * N * N * k, dt[k], true);
                 if constexpr (PACKED) k_or_pass1_packed<N, P><<<dim3(N / 4, 1, 1), dim3(NT1), LB1, st>>>(A1);
                 else k_or_pass1<N, P><<<dim3(N / 4, 1, 1), dim3(NT1), LB1, st>>>(A1);
                 std::swap(s.phaseT, s.phaseT2);
@@ -693,73 +697,54 @@ static hipError_t or_launch_steps(OrState& s, const float* dt, int n, const OrP2
     }
     return hipGetLastError();
 }
-template <int N>
-static hipError_t or_launch_steps_plan(bool packed, OrState& s, const float* dt, int n, const OrP2Args& A2, float* f_n, float* f_w, hipStream_t st, hipEvent_t* ev) {
-    if constexpr (N < MW_OR_PACKED_MAX_M) { if (packed) return or_launch_steps<N, true>(s, dt, n, A2, f_n, f_w, st, ev); }
-    return or_launch_steps<N, false>(s, dt, n, A2, f_n, f_w, st, ev);
-}
 // frames k = 0 .. n-1 advance the phase by delta_time[k] * mult one after the other, exactly as n calls of or_generate would; device
 // destinations are [n][M*M*...] (NULL: the frame stays in the handle's own frame buffers).  The handle's latest-frame textures
-// (out_*) receive frame n-1.
-static inline mw_status or_generate_steps(OrState& s, const float* delta_time, int n, float* d_height, float* d_disp, float* d_normal,
+// (s.out) receive frame n-1.
+static inline mw_status or_generate_steps(OrState& s, const float* delta_time, int n, bool imag, float* d_height, float* d_disp, float* d_normal,
                                           float* d_white, hipStream_t st, hipEvent_t* ev = nullptr) {
-    if (s.tiles != 1) { g_or_err = "generate_texture_steps: a batched handle (mw_ocean_create_batch) advances one frame per call"; return MW_ESTATE; }
-    if (n < 1 || n > MW_OR_MAX_FRAMES) { g_or_err = "generate_texture_steps: nframes out of range"; return MW_EINVAL; }
-    s.c.choppiness = s.choppiness;
+    if (s.tiles != 1) return fail(MW_ESTATE, "generate_texture_steps: a batched handle (mw_ocean_create_batch) advances one frame per call");
+    if (n < 1 || n > MW_OR_MAX_FRAMES) return fail(MW_EINVAL, "generate_texture_steps: nframes out of range");
     const size_t MM = (size_t)s.M * s.M;
-    if (s.want_imag && !s.out_height_g) {
-        if (hipMalloc((void**)&s.out_height_g, sizeof(float) * MM) != hipSuccess || hipMalloc((void**)&s.out_disp_a, sizeof(float) * MM) != hipSuccess) {
-            g_or_err = "OceanRenderer: hipMalloc failed";
-            return MW_ENOMEM;
-        }
-    }
-    const bool need[4] = {!d_height, !d_disp, !d_normal, !d_white};
-    mw_status r = or_frames_reserve(s, n, need, s.want_imag);
+    mw_status r = imag ? or_imag_planes(s) : MW_OK;
     if (r != MW_OK) return r;
+    const bool need[4] = {!d_height, !d_disp, !d_normal, !d_white};
+    if ((r = or_frames_reserve(s, n, need, imag)) != MW_OK) return r;
     float dt[MW_OR_MAX_FRAMES];
     for (int k = 0; k < n; k++) dt[k] = delta_time[k] * s.mult;  // S/OceanRenderer.cs:223
-    float* const f_h = d_height ? d_height : s.fr_height;
-    cf* const f_d = d_disp ? reinterpret_cast<cf*>(d_disp) : s.fr_disp;
-    float* const f_n = d_normal ? d_normal : s.fr_normal;
-    float* const f_w = d_white ? d_white : s.fr_white;
-    OrP2Args A2;
-    A2.E = s.fr_E; A2.TW = s.TW; A2.height = f_h; A2.disp = f_d; A2.disp_g = s.fr_disp_g; A2.c = s.c;
-    A2.height_g = s.want_imag ? s.fr_height_g : nullptr;
-    A2.disp_a = s.want_imag ? s.fr_disp_a : nullptr;
+    OrTex f = imag ? s.fr : s.fr.real_only();
+    if (d_height) f.height = d_height;
+    if (d_disp) f.disp = reinterpret_cast<cf*>(d_disp);
+    if (d_normal) f.normal = d_normal;
+    if (d_white) f.white = d_white;
     hipError_t e = hipSuccess;
-    const bool packed = or_use_packed(s);
-    switch (s.M) {
-        case 64: e = or_launch_steps_plan<64>(packed, s, dt, n, A2, f_n, f_w, st, ev); break;
-        case 128: e = or_launch_steps_plan<128>(packed, s, dt, n, A2, f_n, f_w, st, ev); break;
-        case 256: e = or_launch_steps_plan<256>(packed, s, dt, n, A2, f_n, f_w, st, ev); break;
-        case 512: e = or_launch_steps_plan<512>(packed, s, dt, n, A2, f_n, f_w, st, ev); break;
-        case 1024: e = or_launch_steps_plan<1024>(packed, s, dt, n, A2, f_n, f_w, st, ev); break;
-        case 2048: e = or_launch_steps_plan<2048>(packed, s, dt, n, A2, f_n, f_w, st, ev); break;
-        case 4096: e = or_launch_steps_plan<4096>(packed, s, dt, n, A2, f_n, f_w, st, ev); break;
-        default: g_or_err = "OceanRenderer: unsupported texture size"; return MW_EINVAL;
-    }
-    if (e != hipSuccess) { g_or_err = std::string("OceanRenderer steps launch: ") + hipGetErrorString(e); return MW_EDEVICE; }
-    const size_t last = (size_t)(n - 1) * MM;
-    k_or_copy_frame<<<dim3((unsigned)((3 * MM / 4 + 255) / 256)), dim3(256), 0, st>>>(MM, f_h + last, f_d + last, s.fr_disp_g + last, f_n + 3 * last, f_w + last,
-                                                    s.want_imag ? s.fr_height_g + last : nullptr, s.want_imag ? s.fr_disp_a + last : nullptr,
-                                                    s.out_height, s.out_disp_cf, s.out_disp_g, s.out_normal, s.out_white, s.out_height_g, s.out_disp_a);
-    if (hipGetLastError() != hipSuccess) { g_or_err = "OceanRenderer normal/white launch failed"; return MW_EDEVICE; }
+    const bool packed = or_use_packed(s, imag);  // (false from MW_OR_PACKED_MAX_M up: no packed instantiation there)
+    MW_FOR_SIZE(s.M, return fail(MW_EINVAL, "OceanRenderer: unsupported texture size"),
+                e = packed ? or_launch_steps<NN, (NN < MW_OR_PACKED_MAX_M)>(s, dt, n, f, st, ev) : or_launch_steps<NN, false>(s, dt, n, f, st, ev));
+    if (e != hipSuccess) return fail(MW_EDEVICE, std::string("OceanRenderer steps launch: ") + hipGetErrorString(e));
+    const OrTex l = f.at((size_t)(n - 1) * MM), &o = s.out;
+    k_or_copy_frame<<<dim3((unsigned)((3 * MM / 4 + 255) / 256)), dim3(256), 0, st>>>(MM, l.height, l.disp, l.disp_g, l.normal, l.white, l.height_g, l.disp_a,
+                                                                                     o.height, o.disp, o.disp_g, o.normal, o.white, o.height_g, o.disp_a);
+    if (hipGetLastError() != hipSuccess) return fail(MW_EDEVICE, "OceanRenderer normal/white launch failed");
     if (ev) hipEventRecord(ev[1 + 3 * or_steps_chunks(s.M, n)], st);
     s.have_frame = true;
-    s.have_imag = s.want_imag;
     return MW_OK;
 }
-// the same n frames delivered as the four ARGBFloat render targets, [n][M*M*4] each (any destination may be NULL)
-static inline mw_status or_generate_steps_rgba(OrState& s, const float* delta_time, int n, f4* d_height, f4* d_disp, f4* d_normal, f4* d_white,
-                                               hipStream_t st) {
-    s.want_imag = true;
-    mw_status r = or_generate_steps(s, delta_time, n, nullptr, nullptr, nullptr, nullptr, st);
-    s.want_imag = false;
-    if (r != MW_OK) return r;
+
+// n consecutive frames at the handle's choppiness: the lone-frame plan at n == 1 (latency-bound launch forms; its textures are the handle's own
+// s.out), else the steps plan (s.fr).  Planar (d: height, displacement, normal, whitecap as floats; a NULL kind stays in the handle) or, rgba,
+// delivered as the reference's four ARGBFloat render targets ([n][M*M*4] each, any may be NULL).  ev: the measurement hook's events.
+static inline mw_status or_frames(OrState& s, float choppiness, const float* delta_time, int n, bool rgba, void* const (&d)[4], hipStream_t st,
+                                  hipEvent_t* ev = nullptr) {
+    s.c.choppiness = choppiness;
+    float* const p[4] = {rgba ? nullptr : (float*)d[0], rgba ? nullptr : (float*)d[1], rgba ? nullptr : (float*)d[2], rgba ? nullptr : (float*)d[3]};
+    const mw_status r = n == 1 ? or_generate(s, delta_time[0], rgba, p[0], p[1], p[2], p[3], st, ev)
+                               : or_generate_steps(s, delta_time, n, rgba, p[0], p[1], p[2], p[3], st, ev);
+    if (r != MW_OK || !rgba) return r;
     const size_t MM = (size_t)s.M * s.M;
-    k_or_pack_rgba<<<dim3((unsigned)((MM + 255) / 256), n), dim3(256), 0, st>>>(s.M, s.fr_height, s.fr_height_g, s.fr_disp, s.fr_disp_g, s.fr_disp_a,
-                                                                           s.fr_normal, s.fr_white, d_height, d_disp, d_normal, d_white);
-    if (hipGetLastError() != hipSuccess) { g_or_err = "k_or_pack_rgba launch failed"; return MW_EDEVICE; }
+    const OrTex& t = n == 1 ? s.out : s.fr;
+    k_or_pack_rgba<<<dim3((unsigned)((MM + 255) / 256), n == 1 ? s.tiles : n), dim3(256), 0, st>>>(s.M, t.height, t.height_g, t.disp, t.disp_g, t.disp_a, t.normal,
+                                                                                              t.white, (f4*)d[0], (f4*)d[1], (f4*)d[2], (f4*)d[3]);
+    if (hipGetLastError() != hipSuccess) return fail(MW_EDEVICE, "k_or_pack_rgba launch failed");
     return MW_OK;
 }
 
@@ -787,19 +772,19 @@ static inline mw_status or_advance_phase(OrState& s, const float* delta_time, in
         for (int k = 0; k < MW_OR_MAX_FRAMES; k++) A.dt[k] = k < A.n ? delta_time[k0 + k] * s.mult : 0.f;  // S/OceanRenderer.cs:223
         k_or_advance<<<dim3((unsigned)((MM + 255) / 256), s.tiles), dim3(256), 0, st>>>(MM, s.omT, s.phaseT, A);
     }
-    if (hipGetLastError() != hipSuccess) { g_or_err = "k_or_advance launch failed"; return MW_EDEVICE; }
+    if (hipGetLastError() != hipSuccess) return fail(MW_EDEVICE, "k_or_advance launch failed");
     return MW_OK;
 }
 
 // the ocean material's vertex stage on the res x res mesh, from the textures of the latest GenerateTexture()
 static inline mw_status or_displace_mesh(OrState& s, int res, float unit_width, float* d_vert, float* d_nrm, float* d_col,
                                          hipStream_t st) {
-    if (!s.have_frame) { g_or_err = "displace_mesh: no GenerateTexture() yet"; return MW_ESTATE; }
+    if (!s.have_frame) return fail(MW_ESTATE, "displace_mesh: no GenerateTexture() yet");
     const int nv = res * res;
-    k_or_displace_mesh<<<dim3((unsigned)((nv + 255) / 256), s.tiles), dim3(256), 0, st>>>(s.M, res, unit_width, s.out_height,
-                                                                                 s.out_disp_cf, s.out_normal, s.out_white,
+    k_or_displace_mesh<<<dim3((unsigned)((nv + 255) / 256), s.tiles), dim3(256), 0, st>>>(s.M, res, unit_width, s.out.height,
+                                                                                 s.out.disp, s.out.normal, s.out.white,
                                                                                  d_vert, d_nrm, d_col);
-    if (hipGetLastError() != hipSuccess) { g_or_err = "k_or_displace_mesh launch failed"; return MW_EDEVICE; }
+    if (hipGetLastError() != hipSuccess) return fail(MW_EDEVICE, "k_or_displace_mesh launch failed");
     return MW_OK;
 }
 

@@ -106,8 +106,7 @@ static mw_status velocity_check(mw_ocean* o, int32_t frame, const char* who) {
 static mw_status velocity_run(mw_ocean* o, float* d_vel) {
     VelState& v = o->vel;
     if (o->sem == MW_SEM_OCEANRENDERER) {
-        mw_status s = or_velocity(o->orr, v, o->p.resolution, d_vel, o->stream);
-        return s == MW_OK ? MW_OK : fail(s, or_last_error());
+        return or_velocity(o->orr, v, o->p.resolution, d_vel, o->stream);
     }
     const int N = o->N;
     const size_t NN = (size_t)N * N;

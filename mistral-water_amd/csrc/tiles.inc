@@ -116,8 +116,8 @@ struct mw_tiles {
             const size_t off = (size_t)step * N * N;
             return a == 0 ? L.fh + off : (a == 1 ? L.fd + 2 * off : (a == 2 ? L.fn + 3 * off : L.fw + off));
         }
-        const OrState& s = L.ocean->orr;
-        return a == 0 ? s.out_height : (a == 1 ? s.out_disp : (a == 2 ? s.out_normal : s.out_white));
+        const OrTex& s = L.ocean->orr.out;
+        return a == 0 ? s.height : (a == 1 ? reinterpret_cast<const float*>(s.disp) : (a == 2 ? s.normal : s.white));
     }
     Dev* dev_of(int device) { for (auto& d : devs) if (d.device == device) return &d; return nullptr; }
 };
@@ -318,11 +318,11 @@ mw_status mw_tiles_frames(mw_tiles* t, int32_t k, void** d_height, void** d_disp
 mw_status mw_tiles_textures(mw_tiles* t, int32_t k, void** d_height, void** d_disp_xz, void** d_normal_xyz, void** d_white) {
     if (!t || k < 0 || k >= (int)t->tiles.size()) return fail(MW_EINVAL, "mw_tiles_textures: bad tile index");
     if (t->sem != MW_SEM_OCEANRENDERER) return fail(MW_ESTATE, "mw_tiles_textures: OceanRenderer tiles only (FFTMesh tiles: mw_tiles_outputs)");
-    const OrState& s = t->tiles[k].ocean->orr;
-    if (d_height) *d_height = s.out_height;
-    if (d_disp_xz) *d_disp_xz = s.out_disp;
-    if (d_normal_xyz) *d_normal_xyz = s.out_normal;
-    if (d_white) *d_white = s.out_white;
+    const OrTex& s = t->tiles[k].ocean->orr.out;
+    if (d_height) *d_height = s.height;
+    if (d_disp_xz) *d_disp_xz = s.disp;
+    if (d_normal_xyz) *d_normal_xyz = s.normal;
+    if (d_white) *d_white = s.white;
     return MW_OK;
 }
 

@@ -91,17 +91,13 @@ static hipError_t or_velocity_passes(const OrState& s, VelState& v, hipStream_t 
     constexpr int P = Plan<N>::P;
     constexpr int NT1 = OrP1Geom<N, P>::NTHREADS, LB1 = OrP1Geom<N, P>::LDS_BYTES;
     constexpr int NT2 = OrP2Geom<N, P>::NTHREADS, LB2 = OrP2Geom<N, P>::LDS_BYTES;
-    OrP1Args A1;
-    A1.initT = v.initT; A1.PQT = v.PQT; A1.omT = s.omT; A1.phase_in = s.phaseT; A1.phase_out = v.phase; A1.TW = s.TW; A1.E = v.E; A1.c = s.c;
-    A1.dt = 0.f;
-    A1.stream_E = or_call_is_big<N>(s) ? 1 : 0;
-    OrP2Args A2;
-    A2.E = v.E; A2.TW = s.TW; A2.height = v.height; A2.disp = v.disp; A2.disp_g = v.disp_g; A2.c = s.c;
-    A2.height_g = nullptr;
-    A2.disp_a = nullptr;
-    const bool all_fields = (s.tiles > 1 || N >= MW_OR_BIG_N);
+    const OrP1Args A1 = or_p1_args(s, v.initT, v.PQT, v.phase, v.E, 0.f, or_call_is_big(s));
+    OrTex rate;
+    rate.height = v.height; rate.disp = v.disp; rate.disp_g = v.disp_g;
+    const OrP2Args A2 = or_p2_args(s, v.E, rate);
+    const bool all_fields = or_all_fields(s);
     static AttrOnce attr1, attr2;
-    if constexpr (N < MW_OR_PACKED_MAX_M) if (or_use_packed(s)) {
+    if constexpr (N < MW_OR_PACKED_MAX_M) if (or_use_packed(s, false)) {
         hipError_t e = attr1.set(reinterpret_cast<const void*>(&k_or_pass1_packed<N, P>), LB1);
         if (e == hipSuccess) e = attr2.set(reinterpret_cast<const void*>(&k_or_pass2_packed<N, P>), LB2);
         if (e != hipSuccess) return e;
@@ -124,7 +120,7 @@ static hipError_t or_velocity_passes(const OrState& s, VelState& v, hipStream_t 
 static inline mw_status or_velocity(const OrState& s, VelState& v, int res, float* d_vel, hipStream_t st) {
     const size_t MM = (size_t)s.M * s.M;
     if (!v.disp) {  // the last buffer allocated: a failure half-way frees them all, and the next call starts again
-#define VEL_ALLOC(ptr, bytes) if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) { vel_free(v); g_or_err = "velocity: hipMalloc failed"; return MW_ENOMEM; }
+#define VEL_ALLOC(ptr, bytes) if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) { vel_free(v); return fail(MW_ENOMEM, "velocity: hipMalloc failed"); }
         VEL_ALLOC(v.initT, sizeof(f4) * MM) VEL_ALLOC(v.PQT, sizeof(f4) * MM) VEL_ALLOC(v.phase, sizeof(float) * MM)
         VEL_ALLOC(v.E, sizeof(cf) * 3 * MM) VEL_ALLOC(v.height, sizeof(float) * MM) VEL_ALLOC(v.disp_g, sizeof(float) * MM)
         VEL_ALLOC(v.disp, sizeof(cf) * MM)
@@ -134,26 +130,17 @@ static inline mw_status or_velocity(const OrState& s, VelState& v, int res, floa
     if (!v.ready) {
         k_or_velocity_init<<<dim3(nb), dim3(256), 0, st>>>(s.M, s.omT, s.mult, s.initT, v.initT);
         k_or_prep<<<dim3(nb, 1), dim3(256), 0, st>>>(s.M, v.initT, v.PQT);
-        if (hipGetLastError() != hipSuccess) { g_or_err = "velocity spectrum launch failed"; return MW_EDEVICE; }
+        if (hipGetLastError() != hipSuccess) return fail(MW_EDEVICE, "velocity spectrum launch failed");
         v.ready = true;
     }
     hipError_t e = hipSuccess;
-    switch (s.M) {
-        case 64: e = or_velocity_passes<64>(s, v, st); break;
-        case 128: e = or_velocity_passes<128>(s, v, st); break;
-        case 256: e = or_velocity_passes<256>(s, v, st); break;
-        case 512: e = or_velocity_passes<512>(s, v, st); break;
-        case 1024: e = or_velocity_passes<1024>(s, v, st); break;
-        case 2048: e = or_velocity_passes<2048>(s, v, st); break;
-        case 4096: e = or_velocity_passes<4096>(s, v, st); break;
-        default: g_or_err = "OceanRenderer: unsupported texture size"; return MW_EINVAL;
-    }
-    if (e != hipSuccess) { g_or_err = std::string("velocity pass launch: ") + hipGetErrorString(e); return MW_EDEVICE; }
+    MW_FOR_SIZE(s.M, return fail(MW_EINVAL, "OceanRenderer: unsupported texture size"), e = or_velocity_passes<NN>(s, v, st));
+    if (e != hipSuccess) return fail(MW_EDEVICE, std::string("velocity pass launch: ") + hipGetErrorString(e));
     const unsigned nv = (unsigned)res * (unsigned)res;
     // normals / whitecap are not sampled (NULL outputs): the texture arguments are never read
     k_or_displace_mesh<<<dim3((nv + 255) / 256, 1), dim3(256), 0, st>>>(s.M, res, 0.f, v.height, v.disp, v.height, v.height, d_vel, nullptr,
                                                                        nullptr);
-    if (hipGetLastError() != hipSuccess) { g_or_err = "velocity vertex stage launch failed"; return MW_EDEVICE; }
+    if (hipGetLastError() != hipSuccess) return fail(MW_EDEVICE, "velocity vertex stage launch failed");
     return MW_OK;
 }
 #endif
