@@ -1081,4 +1081,28 @@ template <int N> struct Plan {
     static constexpr int VT1 = (N >= 4096) ? MW_VT1_4096 : (N == 2048 ? MW_VT1_2048 : 1);  // the same for pass 1
 };
 
+#if defined(__HIPCC__)
+}  // namespace mw
+#include "mw_host.h"
+namespace mw {
+// The spectrum a frame is evaluated from: (h0, h0c) and, on the FFT path, the tables k_prep derives from them.  A handle holds two: its own
+// (FmState, fftmesh_device.h) and the weighted one of the velocity (VelState, velocity_kernels.h).
+struct FmSpectrum {
+    cf *h0 = nullptr, *h0c = nullptr;
+    f4 *PQt = nullptr, *dPQ_i0 = nullptr, *dPQ_j0 = nullptr;
+    float* Om = nullptr;
+};
+// a failure half-way leaves what it did allocate, for fm_spectrum_free
+static inline mw_status fm_spectrum_alloc(FmSpectrum& sp, int N, bool use_fft) {
+    const size_t NN = (size_t)N * N;
+    mw_status s;
+    if ((s = dmalloc(&sp.h0, NN)) != MW_OK || (s = dmalloc(&sp.h0c, NN)) != MW_OK || !use_fft) return s;
+    if ((s = dmalloc(&sp.PQt, NN)) != MW_OK || (s = dmalloc(&sp.Om, NN)) != MW_OK || (s = dmalloc(&sp.dPQ_i0, (size_t)N)) != MW_OK) return s;
+    return dmalloc(&sp.dPQ_j0, (size_t)N);
+}
+static inline void fm_spectrum_free(FmSpectrum& sp) {
+    hipFree(sp.h0); hipFree(sp.h0c); hipFree(sp.PQt); hipFree(sp.Om); hipFree(sp.dPQ_i0); hipFree(sp.dPQ_j0); sp = FmSpectrum();
+}
+#endif
+
 }  // namespace mw

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <string>
@@ -20,7 +21,7 @@
 
 #include "../../include/mistral_water.h"
 #include "../../include/mistral_water_hooks.h"
-#include "mw_host.h"  // fail(), HIP_TRY, MW_FOR_SIZE
+#include "mw_host.h"  // fail(), HIP_TRY, dmalloc, MW_FOR_SIZE
 #include "fftmesh_kernels.h"
 #include "ocean_renderer_device.h"
 #include "direct_kernels.h"
@@ -42,486 +43,7 @@ static_assert(MW_SQ_REST == MW_QUERY_REST && MW_SQ_WORLD == MW_QUERY_WORLD, "sur
 
 using namespace mw;
 
-// ------------------------------------------------------------------------------------------------
-// __global__ wrappers: FFTMesh semantics
-// ------------------------------------------------------------------------------------------------
-__global__ void k_spectrum(int N, float length, float wind_x, float wind_y, float amplitude, float gravity,
-                           uint64_t seed, cf* h0, cf* h0c) {
-    int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= N * N) return;
-    spectrum_element(N, length, wind_x, wind_y, amplitude, gravity, seed, idx / N, idx % N, h0, h0c);
-}
-
-__global__ void k_rest_mesh(int N, float unit_width, float* vertices, float* normals, float* uvs, int32_t* indices) {
-    int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= N * N) return;
-    rest_mesh_element(N, unit_width, idx / N, idx % N, vertices, normals, uvs, indices);
-}
-
-__global__ void k_prep(int N, float length, float gravity, const cf* h0, const cf* h0c, const cf* Wpre, f4* PQt,
-                       f4* dPQ_i0, f4* dPQ_j0, float* Om) {
-    int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= N * N) return;
-    // idx enumerates the TRANSPOSED array so that the writes are the coalesced side
-    prep_element(N, length, gravity, idx % N, idx / N, h0, h0c, Wpre, PQt, dPQ_i0, dPQ_j0, Om);
-}
-
-__global__ void k_omega_t(int N, float length, float gravity, float t, float* out) {
-    int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= N * N) return;
-    out[idx] = omega_t_f32(N, length, gravity, idx / N, idx % N, t);
-}
-
-#if defined(MW_TIMING) && !defined(MW_LAB)
-#error "MW_TIMING (cycle stamps inside the pass kernels) is a lab build option: add -DMW_LAB (tools/build_variant.sh does)"
-#endif
-#ifdef MW_TIMING
-#ifndef MW_STAMP_STEP
-#define MW_STAMP_STEP 3
-#endif
-__device__ long long g_stamps[2][64][16][32];  // [kernel][block slot][wave][stamp]
-#define MW_STAMP(K, id)                                                                               \
-    do {                                                                                              \
-        if ((blockIdx.x % 37) == 5 && blockIdx.x / 37 < 64 && step == MW_STAMP_STEP && (threadIdx.x & 63) == 0 && threadIdx.x < 1024) \
-            g_stamps[K][blockIdx.x / 37][threadIdx.x >> 6][id] = __builtin_readcyclecounter();        \
-    } while (0)
-// the constant 100-MHz clock beside the cycle counter (slots 30 / 31: start / end of a kernel): calibrates cycles against kernel time
-#define MW_STAMP_RT(K, id)                                                                            \
-    do {                                                                                              \
-        if ((blockIdx.x % 37) == 5 && blockIdx.x / 37 < 64 && step == MW_STAMP_STEP && (threadIdx.x & 63) == 0 && threadIdx.x < 1024) \
-            g_stamps[K][blockIdx.x / 37][threadIdx.x >> 6][id] = __builtin_amdgcn_s_memrealtime();    \
-    } while (0)
-// where the 4-wave workgroups of a pass-1 launch ran: HW_ID / XCC_ID of EVERY workgroup b < 768, parked in the unused wave slots 4..15
-#define MW_STAMP_HWID(K)                                                                              \
-    do {                                                                                              \
-        if (threadIdx.x == 0 && blockIdx.x < 768 && step == MW_STAMP_STEP) {                          \
-            g_stamps[K][blockIdx.x % 64][4 + blockIdx.x / 64][0] = __builtin_amdgcn_s_getreg(63492);   \
-            g_stamps[K][blockIdx.x % 64][4 + blockIdx.x / 64][1] = __builtin_amdgcn_s_getreg(63508);   \
-            g_stamps[K][blockIdx.x % 64][4 + blockIdx.x / 64][2] = __builtin_amdgcn_s_memrealtime();    \
-        }                                                                                             \
-    } while (0)
-#define MW_STAMP_HWID_END(K)                                                                          \
-    do {                                                                                              \
-        if (threadIdx.x == 0 && blockIdx.x < 768 && step == MW_STAMP_STEP)                            \
-            g_stamps[K][blockIdx.x % 64][4 + blockIdx.x / 64][3] = __builtin_amdgcn_s_memrealtime();    \
-    } while (0)
-#elif defined(MW_SCHED_FENCE)
-#define MW_STAMP(K, id) __builtin_amdgcn_sched_barrier(0)
-#define MW_STAMP_RT(K, id) do { } while (0)
-#define MW_STAMP_HWID(K) do { } while (0)
-#define MW_STAMP_HWID_END(K) do { } while (0)
-#else
-#define MW_STAMP(K, id) do { } while (0)
-#define MW_STAMP_RT(K, id) do { } while (0)
-#define MW_STAMP_HWID(K) do { } while (0)
-#define MW_STAMP_HWID_END(K) do { } while (0)
-#endif
-
-// LDS layout of both pass kernels: [twiddle tables, if small] [one set of exchange buffers]; a second (WAR) barrier follows
-// every load.
-// VT = virtual threads per lane (see k_pass2_hs): the phase functions are written for 4*T virtual threads (4 spectrum
-// columns x T); a workgroup of 4*T/VT lanes runs virtual threads tid, tid + NT, ... of every phase back to back.
-// issue priority (s_setprio, 0..3) of the row groups by field once the loads are out: the slope groups -- the longest fetch, then the
-// normals to store -- ahead of displacement and halo row, the height groups (which only wait for hds after their transform) last.
-// Measured on top of the wave-level exchanges: pass 2 of a lone step 17.1 -> 15.6 us (the reverse order 16.6; profiles/r04_ab_notes.md).
-#ifndef MW_FRAME_PRIO_S
-#define MW_FRAME_PRIO_S 3
-#endif
-#ifndef MW_FRAME_PRIO_D
-#define MW_FRAME_PRIO_D 2
-#endif
-#ifndef MW_FRAME_PRIO_X
-#define MW_FRAME_PRIO_X 2
-#endif
-#ifndef MW_FRAME_PRIO_H
-#define MW_FRAME_PRIO_H 1
-#endif
-__device__ __forceinline__ void mw_setprio(int p) {  // the builtin wants a literal
-    switch (p) {
-        case 0: __builtin_amdgcn_s_setprio(0); break;
-        case 1: __builtin_amdgcn_s_setprio(1); break;
-        case 2: __builtin_amdgcn_s_setprio(2); break;
-        default: __builtin_amdgcn_s_setprio(3); break;
-    }
-}
-// FS = the single-step (frame-at-a-time) instantiation: one FIELD per workgroup, a 1-D grid over A.jobs
-template <int N, int P, int VT, bool FS = false>
-__global__ __launch_bounds__((P1Geom<N, P>::NTHREADS / VT))
-__attribute__((amdgpu_waves_per_eu(VT > 1 ? P1Geom<N, P>::NTHREADS / VT / 256 : (P == 8 ? MW_WAVES_P1 : 4)))) void k_pass1(P1Args A, StepTimes times) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    using G = P1Geom<N, P>;
-    cf* lds = reinterpret_cast<cf*>(smem);
-    constexpr int T = FftGeom<N, P>::T, NT = G::NTHREADS / VT;
-    static_assert(G::NTHREADS % VT == 0 && (VT == 1 || NT % T == 0), "a lane's virtual threads must belong to whole columns");
-    const int tid = threadIdx.x;
-    int jb = blockIdx.x, step = blockIdx.y;
-    // Frame-at-a-time plan (A.field_split, single-step enqueues): one FIELD per workgroup instead of the three one after the
-    // other, each workgroup re-forming the (cheap) animated spectrum.  A step is 257 workgroups at
-    // 1024^2 where the device has 1024 slots, so its latency is that of ONE workgroup: a third of the work each cuts it
-    // accordingly.  The arithmetic of a field does not depend on which workgroup runs it: same bits as the batched plan.
-    int f_lo = 0, f_hi = 3;
-    if constexpr (FS) {
-        const int job = A.jobs[blockIdx.x];  // 1-D grid over the list of active (column job, field) pairs (p1_frame_jobs)
-        if (job < 0) return;
-        jb = job & 0xffff;
-        f_lo = job >> 16;
-        f_hi = f_lo + 1;
-        step = 0;
-        if (!p1_field_active(N, jb, f_lo, G::CW)) return;  // block-uniform, before any barrier
-    } else if (A.tgroup > 0 && !p1_block_map((int)blockIdx.x, G::GRID_X, A.nsteps, A.tgroup, &jb, &step)) return;
-    // Up to its last exchange a column's buffer is written and read by the column's own T threads: where those are one wave (the
-    // single-step plan at T == 64) the exchanges need that wave's LDS operations in order and no workgroup barrier -- the four columns
-    // drift apart; the last exchange feeds the column-interleaved final pass and keeps the barrier.
-    constexpr bool WS = FS && VT == 1 && T == 64;
-    auto col_sync = [&](bool whole_group) {
-        if (WS && !whole_group) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-        else __syncthreads();
-    };
-    (void)col_sync;
-    const float t = times.t[step];
-    TwStage<N, P, NT> tws;
-    if (TwGeom<N, P>::LDS_ALL) tws.load(A.TW, tid);  // in LDS behind the spectrum requests, visible after the first barrier
-    const Twiddles tw = TwGeom<N, P>::view(A.TW, lds);
-    cf* set0 = lds + G::TW_LDS;
-    P1State<P> st[VT];
-    cf x[VT][P];
-#define MW_VT(h) for (int h = 0; h < VT; h++)
-#define MW_BUF(h) (set0 + ((tid + (h) * NT) / T) * G::BUFSTRIDE)
-#define MW_U(h) ((tid + (h) * NT) % T)
-    MW_STAMP(0, 0);
-    MW_STAMP_RT(0, 30);
-    if constexpr (FS) MW_STAMP_HWID(0);
-#pragma unroll
-    MW_VT(h) p1_animate<N, P>(A, jb, tid + h * NT, t, st[h]);
-    if (TwGeom<N, P>::LDS_ALL) tws.store(lds, tid);
-    MW_STAMP(0, 1);
-#pragma unroll
-    for (int f = 0; f < 3; f++) {
-        if (f < f_lo || f >= f_hi) continue;              // block-uniform: the frame-at-a-time plan runs one field per workgroup
-        if (!p1_field_active(N, jb, f, G::CW)) continue;  // block-uniform: height needs columns j <= N/2 only
-#pragma unroll
-        MW_VT(h) p1_build<N, P>(A, jb, tid + h * NT, f, st[h], x[h]);
-        if (f) __syncthreads();
-        MW_STAMP(0, 2 + 8 * f);
-#pragma unroll
-        MW_VT(h) stage0_store<N, P, +1>(x[h], MW_U(h), MW_BUF(h));
-        MW_STAMP(0, 3 + 8 * f);
-        __syncthreads();  // the first barrier of the kernel also publishes the staged twiddle tables: always the whole group
-#pragma unroll
-        for (int s = 1; s < p1_mid_passes<N, P>(); s++) {
-#pragma unroll
-            MW_VT(h) load_slots<N, P>(x[h], MW_U(h), MW_BUF(h), s - 1);
-            if (s == 1) MW_STAMP(0, 4 + 8 * f);
-            col_sync(false);
-            if (s == 1) MW_STAMP(0, 5 + 8 * f);
-#pragma unroll
-            MW_VT(h) stage_store<N, P, +1>(x[h], MW_U(h), MW_BUF(h), tw, s);
-            if (s == 1) MW_STAMP(0, 6 + 8 * f);
-            col_sync(s == p1_mid_passes<N, P>() - 1);
-        }
-        MW_STAMP(0, 7 + 8 * f);
-#pragma unroll
-        MW_VT(h) p1_finish<N, P>(A, tw, jb, step, tid + h * NT, f, x[h], set0);
-        MW_STAMP(0, 8 + 8 * f);
-    }
-    MW_STAMP(0, 26);
-    MW_STAMP_RT(0, 31);
-    if constexpr (FS) MW_STAMP_HWID_END(0);
-#undef MW_VT
-#undef MW_BUF
-#undef MW_U
-}
-
-#ifndef MW_XCD_GROUP
-#define MW_XCD_GROUP 8  // adjacent row blocks kept on one XCD (1 = plain round-robin); 8-32: pass 2 -3 % at steady clocks
-#endif
-template <int NBLK>
-__device__ __forceinline__ int p2_row_block(int b) {
-    constexpr int XG = MW_XCD_GROUP;
-    const int xcd = b % 8, cidx = b / 8;
-    return (XG > 1 && NBLK % (8 * XG) == 0) ? (cidx / XG) * (8 * XG) + xcd * XG + (cidx % XG) : b;
-}
-
-template <int N, int P, int R2, bool DUMP = false>
-__global__ __launch_bounds__((P2Geom<N, P, R2>::NTHREADS)) __attribute__((amdgpu_waves_per_eu(P == 8 ? MW_WAVES_P2 : 3))) void k_pass2(
-    P2Args A) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    using G = P2Geom<N, P, R2>;
-    cf* lds = reinterpret_cast<cf*>(smem);
-    constexpr int T = FftGeom<N, P>::T;
-    const int tid = threadIdx.x, step = blockIdx.y;
-    // XCD-aware row-block mapping: the dispatcher places block b on XCD b % 8 (speed only, never correctness); giving
-    // each XCD a contiguous range of row blocks makes a block's halo row (the first row of the NEXT block) a hit in
-    // the same XCD's L2 instead of a second 128-B line fill across the fabric.
-    const int ab = p2_row_block<N / R2>((int)blockIdx.x);
-    const int g = tid / T;
-    TwStage<N, P, G::NTHREADS> tws;
-    if (TwGeom<N, P>::LDS_ALL) tws.load(A.TW, tid);
-    const Twiddles tw = TwGeom<N, P>::view(A.TW, lds);
-    cf* set0 = lds + G::TW_LDS;
-    float* noise_lds = reinterpret_cast<float*>(lds + G::NOISE_OFF);
-    P2State<P> st;
-    cf x[P];
-    MW_STAMP(1, 0);
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const int f = p2_field(k);
-        const bool active = p2_active<N, P, R2>(ab, tid, f);
-        if (k) __syncthreads();
-        MW_STAMP(1, 1 + 8 * k);
-        if (active) p2_load<N, P, R2>(A, ab, step, tid, f, x, set0);
-        if (k == 0 && TwGeom<N, P>::LDS_ALL) tws.store(lds, tid);  // published by the barrier below
-        MW_STAMP(1, 2 + 8 * k);
-        __syncthreads();
-#pragma unroll
-        for (int s = 1; s < FftGeom<N, P>::S; s++) {
-            const bool in_regs = LastStays<N, P>::value && s == FftGeom<N, P>::S - 1;  // the last pass writes nothing to LDS: no barrier on either side of it
-            if (active) p2_mid_load<N, P, R2>(tid, s, x, set0);
-            if (!in_regs) __syncthreads();
-            if (active) p2_mid_store<N, P, R2>(tw, tid, s, x, set0);
-            if (!in_regs) __syncthreads();
-        }
-        MW_STAMP(1, 6 + 8 * k);
-        if (active) p2_finish<N, P, R2>(A, tw, ab, step, tid, f, x, st, set0, noise_lds);
-        MW_STAMP(1, 7 + 8 * k);
-    }
-    __syncthreads();
-    MW_STAMP(1, 25);
-    if (p2_active<N, P, R2>(ab, tid, 1)) p2_publish_hds<N, P, R2>(tid, st, set0);
-    __syncthreads();
-    if constexpr (DUMP) p2_dump_hds<N, P, R2>(A, ab, step, tid, G::NTHREADS, set0);  // test hook
-    MW_STAMP(1, 26);
-    if (g < R2) p2_epilogue<N, P, R2>(A, ab, step, tid, st, set0, noise_lds);
-    MW_STAMP(1, 27);
-}
-
-// Pass 2, sequential-halo variant (large N): R2 row groups, no halo group.  Height and displacement fields first; then
-// the vertices leave, every row publishes hds, rows 0..R2-2 form 1 - J, group 0 transforms the halo row in buffer 0, row R2-1 follows;
-// the slope field comes last and its final pass writes normals and whitecap together.
-//
-// VT = "virtual threads" per lane: the phase functions are written for R2*T virtual threads; a workgroup of R2*T/VT
-// lanes runs virtual threads tid, tid + NT, ... of every phase back to back.  With VT = 2 a 4096-point, 4-row block is 8
-// waves instead of 16: each lane owns 2 x 16 points, the register budget doubles to 256 (the 16-wave form spilled 29
-// dwords = 14 B of scratch traffic per grid point at its 128), the two independent rows of a lane give the scheduler two
-// instruction streams to interleave, and every barrier joins half as many waves.
-// minimum waves per SIMD the register allocator must leave room for: as many workgroups per CU as the LDS admits (at most 2)
-constexpr int hs_min_waves(int nthreads, int lds_bytes) {
-    const int wgs = (2 * lds_bytes <= 160 * 1024) ? 2 : 1;
-    const int w = nthreads / 64 * wgs / 4;
-    return w < 1 ? 1 : (w > 8 ? 8 : w);
-}
-template <int N, int P, int R2, int VT, bool DUMP = false>
-__global__ __launch_bounds__((P2Geom<N, P, R2, true>::NTHREADS / VT))
-__attribute__((amdgpu_waves_per_eu(hs_min_waves(P2Geom<N, P, R2, true>::NTHREADS / VT, P2Geom<N, P, R2, true>::LDS_BYTES)))) void k_pass2_hs(P2Args A) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    using G = P2Geom<N, P, R2, true>;
-    cf* lds = reinterpret_cast<cf*>(smem);
-    constexpr int T = FftGeom<N, P>::T, NT = G::NTHREADS / VT;  // NT lanes, each running VT virtual threads
-    static_assert(G::NTHREADS % VT == 0 && NT % T == 0, "a lane's virtual threads must belong to distinct whole row groups");
-    static_assert(T % 64 == 0, "row groups must be whole waves: the row group of a lane is treated as wave-uniform (512^2 at 16 points fails parity)");
-    const int tid0 = threadIdx.x, step = blockIdx.y;
-    const int ab = p2_row_block<N / R2>((int)blockIdx.x);  // neighbouring row blocks (halo rows, shared 128-B lines) on one XCD
-    const int g0 = wave_uniform<true>(tid0 / T);  // row group of virtual thread 0; virtual thread h is in group g0 + h * NT / T
-    TwStage<N, P, NT> tws;
-    if (TwGeom<N, P>::LDS_ALL) tws.load(A.TW, tid0);
-    const Twiddles tw = TwGeom<N, P>::view(A.TW, lds);
-    cf* set0 = lds + G::TW_LDS;
-    P2StateHS<P> st[VT];
-    cf x[VT][P];
-    // The halo row's lines are the next row block's own lines: fetched while that block (same XCD, same phase) loads
-    // them too, they are L2 hits; fetched two phases later they have left the L2 and cost a second 128-B fill per
-    // 32-B piece (measured +6 B per grid point).  Needs 2P spare VGPRs across the displacement transform: VT >= 2.
-    // Not at 4096^2, where it measured slower (profiles/r03_ab_notes.md).
-    constexpr bool HALO_EARLY = N <= 2048 && VT >= 2;
-    cf xh[HALO_EARLY ? P : 1];  // halo row data parked in registers across the displacement transform
-    const int tid = tid0;  // MW_STAMP
-    MW_STAMP(1, 0);
-#define MW_VT(h) for (int h = 0; h < VT; h++)
-#define MW_VTID(h) (tid0 + (h) * NT)
-    constexpr bool SPARTS = P2SlopeParts<N, P>::value;
-    constexpr bool KEEP = KeepT1<N, P>::value && P2SlopeParts<N, P>::value;
-    cf t1m[KEEP ? VT : 1][KEEP ? P / 2 : 1];   // raw mirrored height-row values, from the height fetch to the slope assembly (KeepT1)
-    (void)t1m;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const int f = p2_hs_field(k);
-        if (k != 0) __syncthreads();  // the previous phase's LDS reads are done (k = 0: nothing to wait for -- the twiddle tables
-                                      // go to LDS behind the first requests below and are published by the barrier after stage 0)
-        MW_STAMP(1, 1 + 8 * k);
-        if (f == 2 && SPARTS) {  // the slope half of every virtual thread in flight, then height rows + stage 0 one at a time
-#pragma unroll
-            MW_VT(h) p2_fetch<N, P, R2, 1>(A, ab, step, MW_VTID(h), f, x[h]);
-        } else {
-#pragma unroll
-            MW_VT(h) p2_fetch<N, P, R2>(A, ab, step, MW_VTID(h), f, x[h], (KEEP && f == 0) ? t1m[h] : nullptr);
-        }
-        if constexpr (HALO_EARLY)
-            if (k == 1 && g0 == 0 && ab * R2 + R2 < N) p2_hs_halo_fetch<N, P, R2>(A, ab, step, tid0 % T, xh);
-        if (k == 0 && TwGeom<N, P>::LDS_ALL) tws.store(lds, tid0);
-        if (f == 2 && SPARTS) {
-#pragma unroll
-            MW_VT(h) {
-                p2_fetch<N, P, R2, 2>(A, ab, step, MW_VTID(h), f, x[h], KEEP ? t1m[h] : nullptr);
-                p2_stage0<N, P, R2>(MW_VTID(h), x[h], set0);
-                mw_sched_fence();
-            }
-        } else {
-#pragma unroll
-            MW_VT(h) p2_stage0<N, P, R2>(MW_VTID(h), x[h], set0);
-        }
-        MW_STAMP(1, 2 + 8 * k);
-        __syncthreads();
-#pragma unroll
-        for (int s = 1; s < FftGeom<N, P>::S; s++) {
-            const bool in_regs = mw_pass_in_regs<N, P>(s);  // the last pass writes nothing to LDS (LastInRegs / LastInWave)
-#pragma unroll
-            MW_VT(h) p2_mid_load<N, P, R2>(MW_VTID(h), s, x[h], set0);
-            if (!in_regs) __syncthreads();
-#pragma unroll
-            MW_VT(h) p2_mid_store<N, P, R2>(tw, MW_VTID(h), s, x[h], set0);
-            if (!in_regs) __syncthreads();
-        }
-        MW_STAMP(1, 6 + 8 * k);
-        if (f == 2) {
-#pragma unroll
-            MW_VT(h) p2_hs_finish_slopes<N, P, R2>(A, tw, ab, step, MW_VTID(h), x[h], st[h], set0);
-            MW_STAMP(1, 7 + 8 * k);
-            break;
-        }
-#pragma unroll
-        MW_VT(h) p2_hs_finish<N, P, R2>(tw, ab, MW_VTID(h), f, x[h], st[h], set0);
-        MW_STAMP(1, 7 + 8 * k);
-        if (f != 1) continue;
-        // ---- displacement done: vertices, halo row, Jacobian ----
-#pragma unroll
-        MW_VT(h) p2_vertices<N, P, R2>(A, ab, step, MW_VTID(h), st[h]);
-        MW_STAMP(1, 24);
-        __syncthreads();  // every final-pass read of the displacement buffers is done
-#pragma unroll
-        MW_VT(h) p2_publish_hds<N, P, R2>(MW_VTID(h), st[h], set0);  // every row into its own buffer, plain index b
-        __syncthreads();
-        if constexpr (DUMP) p2_dump_hds<N, P, R2>(A, ab, step, tid0, NT, set0);  // test hook
-        const bool has_halo = (ab * R2 + R2 < N);  // block-uniform
-        // Rows 0..R2-2 have their (a+1) neighbour published already: they form 1 - J now.  Buffer 0 (row 0's copy) is
-        // then free for the halo row's transform; row R2-1 waits for it and works from its own published copy, so that
-        // nobody's d is live across the halo transform (P = 16: the transform alone takes ~100 VGPRs).
-#pragma unroll
-        MW_VT(h) {
-            const int g = g0 + h * (NT / T);
-            if (g != R2 - 1) p2_hs_jacobian<N, P, R2>(ab, MW_VTID(h), st[h], set0 + g * G::BUFSTRIDE, set0 + (g + 1) * G::BUFSTRIDE);
-        }
-        __syncthreads();  // group 0 no longer reads its own row
-        MW_STAMP(1, 25);
-        if (has_halo) {  // group 0 = virtual thread 0 of the lanes below T
-            const int u = tid0 % T;
-            cf xq[P];  // the halo row in registers of its own: the allocator no longer ties it to x[0] (248 -> 219 VGPRs at 1024^2)
-            if (g0 == 0) {
-                if constexpr (HALO_EARLY) {
-#pragma unroll
-                    for (int q = 0; q < P; q++) xq[q] = xh[q];
-                } else {
-                    p2_hs_halo_fetch<N, P, R2>(A, ab, step, u, xq);
-                }
-                stage0_store<N, P, +1>(xq, u, set0);
-            }
-            __syncthreads();
-#pragma unroll
-            for (int s = 1; s < FftGeom<N, P>::S; s++) {
-                const bool in_regs = mw_pass_in_regs<N, P>(s);
-                if (g0 == 0) load_slots<N, P>(xq, u, set0, s - 1);
-                if (!in_regs) __syncthreads();
-                if (g0 == 0) { if (in_regs) stage_last_regs<N, P, +1>(xq, u, tw, s); else stage_store<N, P, +1>(xq, u, set0, tw, s); }  // g0 is wave-uniform: whole waves
-                if (!in_regs) __syncthreads();
-            }
-            if (g0 == 0) {
-                p2_last_load<N, P>(xq, u, set0);
-                final_stage<N, P, +1>(xq, u, tw.TF);
-            }
-            __syncthreads();
-            if (g0 == 0) p2_hs_halo_publish<N, P, R2>(ab, u, xq, set0);
-            __syncthreads();
-        }
-        MW_STAMP(1, 26);
-        if (g0 + (VT - 1) * (NT / T) == R2 - 1)  // the lane whose LAST virtual thread owns the block's last row
-            p2_hs_jacobian_lds<N, P, R2>(ab, MW_VTID(VT - 1), st[VT - 1], set0 + (R2 - 1) * G::BUFSTRIDE, set0);
-        MW_STAMP(1, 27);
-    }
-#undef MW_VT
-#undef MW_VTID
-}
-
-// Pass 2 of a single-step enqueue (the frame-at-a-time plan, P2FrameGeom in fftmesh_kernels.h): 3 R2 + 1 row groups transform the
-// three fields of the block's rows and the halo row at the same time; the latency of the workgroup -- which IS the latency of the
-// step, 256 workgroups on 256 CUs -- is one transform instead of four.
-template <int N, int P, int R2>
-__global__ __launch_bounds__((P2FrameGeom<N, P, R2>::NTHREADS)) void k_pass2_frame(P2Args A) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    using G = P2FrameGeom<N, P, R2>;
-    static_assert(G::OK, "frame variant: geometry");
-    cf* lds = reinterpret_cast<cf*>(smem);
-    constexpr int T = G::T;
-    const int tid = threadIdx.x, step = blockIdx.y;
-    const int ab = p2_row_block<N / R2>((int)blockIdx.x);
-    const int fg = wave_uniform<true>(tid / G::FT);  // 0 height, 1 displacement, 2 slopes, 3 the halo row (displacement of row a0 + R2)
-    const int tl = tid - fg * G::FT;
-    const bool has_halo = (ab * R2 + R2 < N);        // block-uniform
-    const bool row = fg < 3, halo = (fg == 3) && has_halo;
-    cf* set0 = lds + G::TW_LDS;
-    cf* set_d = set0 + G::SETSTRIDE;
-    cf* hbuf = set0 + 3 * G::SETSTRIDE;
-    cf* mine = set0 + fg * G::SETSTRIDE;  // fg == 3: the halo row's buffer
-    cf x[P];
-    MW_STAMP(1, 0);
-    MW_STAMP_RT(1, 30);
-    TwStage<N, P, G::NTHREADS> tws;
-    if (TwGeom<N, P>::LDS_ALL) tws.load(A.TW, tid);  // requested first (vmcnt is in order), written to LDS behind the row requests
-    if (row) p2_fetch<N, P, R2>(A, ab, step, tl, fg, x);
-    else if (halo) p2_hs_halo_fetch<N, P, R2>(A, ab, step, tl, x);
-    if (TwGeom<N, P>::LDS_ALL) tws.store(lds, tid);
-    const Twiddles tw = TwGeom<N, P>::view(A.TW, lds);
-    if (row) p2_stage0<N, P, R2>(tl, x, mine);
-    else if (halo) stage0_store<N, P, +1>(x, tl, mine);
-    MW_STAMP(1, 1);
-    __syncthreads();  // stage 0 was written in the row-interleaved mapping of the loads: every wave of a field into all of its rows
-    // From here to the final pass a row buffer belongs to ONE wave (exact layouts: row-major mapping, T == 64): its exchanges need the
-    // wave's own LDS operations in order, nothing else -- the row groups drift apart, and the first to finish starts its stores while
-    // the others still transform.
-    static_assert((T == 64 || T == 32) && G::FT % 64 == 0, "a wave holds whole row groups of one field");
-    constexpr bool WSYNC = XLay<N, P>::EXACT;  // the middle passes of a row stay inside its own wave (the padded layouts' run row-interleaved: barriers)
-    auto row_sync = [&]() {
-        if constexpr (WSYNC) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-        else __syncthreads();
-    };
-    mw_setprio(fg == 0 ? MW_FRAME_PRIO_H : (fg == 1 ? MW_FRAME_PRIO_D : (fg == 2 ? MW_FRAME_PRIO_S : MW_FRAME_PRIO_X)));
-#pragma unroll
-    for (int s = 1; s < FftGeom<N, P>::S; s++) {
-        const bool in_regs = mw_pass_in_regs<N, P>(s);
-        if (row) p2_mid_load<N, P, R2>(tl, s, x, mine);
-        else if (halo) load_slots<N, P>(x, tl, mine, s - 1);
-        if (!in_regs) row_sync();
-        if (row) p2_mid_store<N, P, R2>(tw, tl, s, x, mine);  // (fg is wave-uniform: the in-wave exchange of LastInWave runs in whole waves)
-        else if (halo) { if (in_regs) stage_last_regs<N, P, +1>(x, tl, tw, s); else stage_store<N, P, +1>(x, tl, mine, tw, s); }
-        if (!in_regs) row_sync();
-    }
-    MW_STAMP(1, 2);
-    // the final pass reads a row buffer by its own row group alone, too: that group may write it again without a barrier
-    cf* set_s = set0 + 2 * G::SETSTRIDE;
-    if (row || halo) {
-        p2_last_load<N, P>(x, tl % T, mine + (row ? tl / T : 0) * G::BUFSTRIDE);
-        final_stage<N, P, +1>(x, tl % T, tw.TF);
-    }
-    MW_STAMP(1, 3);
-    if (fg == 1) p2_frame_hds<N, P, R2>(ab, tl, x, set_d);
-    else if (fg == 2) p2_frame_normals<N, P, R2>(A, ab, step, tl, x, set_s);
-    else if (halo) p2_hs_halo_publish<N, P, R2>(ab, tl, x, hbuf);
-    MW_STAMP(1, 4);
-    __syncthreads();
-    MW_STAMP(1, 5);
-    if (fg == 0) p2_frame_vertices<N, P, R2>(A, ab, step, tl, x, set_d);
-    else if (fg == 1) p2_frame_white<N, P, R2>(A, ab, step, tl, set_d, hbuf, set_s);
-    MW_STAMP(1, 6);
-    MW_STAMP_RT(1, 31);
-}
+#include "fftmesh_device.h"  // the FFTMesh kernels and FmState: here, where the kernels stand in the code object
 
 // ------------------------------------------------------------------------------------------------
 // handle
@@ -536,22 +58,8 @@ struct mw_ocean {
     bool use_fft = false;
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
-    int p1_tgroup = 8;  // time-steps of one pass-1 column job grouped on one XCD (p1_block_map): -25 % pass-1 time;
-                        // switch MW_P1_TGROUP overrides (0 = plain 2-D grid)
     float timer = 0.f;
-    // FFTMesh state
-    cf *h0 = nullptr, *h0c = nullptr;
-    f4 *PQt = nullptr, *dPQ_i0 = nullptr, *dPQ_j0 = nullptr;
-    float* Om = nullptr;
-    cf *TW = nullptr, *TW2 = nullptr, *Wpre = nullptr;  // twiddle tables of pass 1 / pass 2
-    int* p1_jobs = nullptr;  // single-step plan: pass-1 job list (p1_frame_jobs)
-    int p1_njobs = 0;
-    cf *E = nullptr, *Cj0 = nullptr;
-    int e_cap = 0;  // steps the exchange buffer holds
-    float *s_vert = nullptr, *s_norm = nullptr, *s_white = nullptr;  // 1-step scratch for the host API
-    bool s_have = false;  // s_vert / s_norm / s_white hold a frame: the "latest frame" of mw_ocean_query_surface
-    int s_wstride = 4;    // ... and the whitecap stride its writer used: 4 (RGBA colours, the host API) or 1 (the profiling hook)
-    float s_t = 0.f, s_chop = 0.f;  // ... and the time and choppiness it was evaluated with (mw_ocean_velocity differentiates there)
+    FmState fm;  // FFTMesh state: spectrum, tables, exchange buffers and the host-API frame (fftmesh_device.h)
     int or_steps_tail = -1;  // OceanRenderer: the last frame of the latest steps call while the phase is still that frame's, else -1
     bool frame_behind = false;  // the spectrum or the phase changed after the latest frame was made (mw_ocean_query_velocity refuses)
     VelState vel;            // mw_ocean_velocity: the weighted spectrum and the velocity buffers (velocity_kernels.h)
@@ -567,12 +75,6 @@ struct mw_ocean {
 };
 
 static bool is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
-
-template <typename T>
-static mw_status dmalloc(T** p, size_t count) {
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
-    return MW_OK;
-}
 
 // b holds at least `bytes` afterwards; growing waits for the work on the handle's stream that may still read the old buffer
 static mw_status grow_reserve(mw_ocean* o, GrowBuf& b, size_t bytes, const char* what) {
@@ -638,10 +140,10 @@ struct Stage {
 // velocity_spectrum_built below is the seventh writer: the only place vel.ready turns true (or_velocity sets its own for OceanRenderer).
 // an FFTMesh frame evaluated at time t now stands in s_vert / s_norm / s_white, its whitecap at stride wstride (4: RGBA colours, 1: scalar)
 static void frame_fftmesh_made(mw_ocean* o, float t, int wstride) {
-    o->s_have = true; o->s_wstride = wstride; o->s_t = t; o->s_chop = o->p.choppiness; o->frame_behind = false;
+    o->fm.s_have = true; o->fm.s_wstride = wstride; o->fm.s_t = t; o->fm.s_chop = o->p.choppiness; o->frame_behind = false;
 }
 // the launches that follow overwrite s_vert / s_norm / s_white: they hold no frame until frame_fftmesh_made says so (profiling hook)
-static void frame_fftmesh_overwritten(mw_ocean* o) { o->s_have = false; }
+static void frame_fftmesh_overwritten(mw_ocean* o) { o->fm.s_have = false; }
 // an OceanRenderer lone frame is being made: the latest frame is the phase's, and no frame of a steps call is
 static void frame_or_lone(mw_ocean* o) { o->or_steps_tail = -1; o->frame_behind = false; }
 // an OceanRenderer steps call made n frames and kept[k] says whether kind k (height, displacement, normal, whitecap) stayed in the
@@ -678,176 +180,16 @@ static OrFrame or_frame(const OrState& r, int k) {
     return f;
 }
 
-// host-side geometry mirror of FftGeom<N,P> / Plan<N>
-static int plan_points(int N, int pass) {
-    MW_FOR_SIZE(N, return 16, return pass == 1 ? Plan<NN>::P1 : Plan<NN>::P2);
-}
-
 // concatenated twiddle table [TS1 | TS2 | TS3 | TF] in the layout of TwGeom<N,P>
 namespace mw {
 int plan_points_host(int N) { return N >= 2048 ? 16 : MW_PT; }
 std::vector<cf> build_twiddle_table(int N, int P, int sgn) { return build_twiddle_table_host(N, P, sgn); }
 }  // namespace mw
 
-static mw_status upload_twiddles(mw_ocean* o) {
-    const int N = o->N;
-    std::vector<cf> tab = build_twiddle_table(N, plan_points(N, 1), +1), tab2 = build_twiddle_table(N, plan_points(N, 2), +1);
-    std::vector<cf> Wpre(2 * N);
-    for (int m = 0; m < 2 * N; m++) {
-        double a = M_PI * (double)m / (double)N;  // (-1)^m e^{i pi m/N}
-        double sg = (m & 1) ? -1.0 : 1.0;
-        Wpre[m] = mk((float)(sg * cos(a)), (float)(sg * sin(a)));
-    }
-    mw_status st;
-    if ((st = dmalloc(&o->TW, tab.size())) != MW_OK) return st;
-    if ((st = dmalloc(&o->TW2, tab2.size())) != MW_OK) return st;
-    if ((st = dmalloc(&o->Wpre, 2 * N)) != MW_OK) return st;
-    HIP_TRY(hipMemcpy(o->TW, tab.data(), sizeof(cf) * tab.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(o->TW2, tab2.data(), sizeof(cf) * tab2.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(o->Wpre, Wpre.data(), sizeof(cf) * 2 * N, hipMemcpyHostToDevice));
-    if (mw_frame_plan_n(N)) {
-        const std::vector<int> jobs = p1_frame_jobs(N, N >= MW_CW2_MIN_N ? 2 : 4);
-        if ((st = dmalloc(&o->p1_jobs, jobs.size())) != MW_OK) return st;
-        HIP_TRY(hipMemcpy(o->p1_jobs, jobs.data(), sizeof(int) * jobs.size(), hipMemcpyHostToDevice));
-        o->p1_njobs = (int)jobs.size();
-    }
-    return MW_OK;
-}
+static OceanConsts consts_of(const mw_ocean* o) { return OceanConsts{o->N, o->p.length, o->p.gravity, o->p.unit_width, o->p.choppiness}; }
 
-static OceanConsts consts_of(const mw_ocean* o) {
-    OceanConsts c;
-    c.N = o->N;
-    c.length = o->p.length;
-    c.gravity = o->p.gravity;
-    c.unit_width = o->p.unit_width;
-    c.choppiness = o->p.choppiness;
-    return c;
-}
-
-// ---- kernel dispatch over N ----------------------------------------------------------------------
-template <int N>
-static hipError_t launch_pass1_n(const P1Args& A, const StepTimes& tm, int nsteps, hipStream_t st) {
-    constexpr int P = Plan<N>::P1, VT = Plan<N>::VT1;
-    static AttrOnce attr;  // per device: the attribute belongs to the function on the current device
-    {
-        hipError_t e = attr.set(reinterpret_cast<const void*>(&k_pass1<N, P, VT>), P1Geom<N, P>::LDS_BYTES);
-        if (e != hipSuccess) return e;
-    }
-    constexpr int NT = P1Geom<N, P>::NTHREADS / VT, LB = P1Geom<N, P>::LDS_BYTES, GX = P1Geom<N, P>::GRID_X;
-    if constexpr (mw_frame_plan_n(N)) {
-        if (A.field_split) {
-            static AttrOnce attrf;
-            hipError_t e = attrf.set(reinterpret_cast<const void*>(&k_pass1<N, P, VT, true>), LB);
-            if (e != hipSuccess) return e;
-            k_pass1<N, P, VT, true><<<dim3(A.njobs), dim3(NT), LB, st>>>(A, tm);
-            return hipGetLastError();
-        }
-    }
-    if (A.tgroup > 0)
-        k_pass1<N, P, VT><<<dim3(p1_grid_blocks(GX, nsteps, A.tgroup)), dim3(NT), LB, st>>>(A, tm);
-    else
-        k_pass1<N, P, VT><<<dim3(GX, nsteps), dim3(NT), LB, st>>>(A, tm);
-    return hipGetLastError();
-}
-template <int N, bool DUMP>
-static hipError_t launch_pass2_n(const P2Args& A, int nsteps, hipStream_t st) {
-    constexpr int P = Plan<N>::P2, R2 = Plan<N>::R2;
-    constexpr bool HS = Plan<N>::HS;
-    constexpr int VT = HS ? Plan<N>::VT : 1;
-    constexpr int NT = P2Geom<N, P, R2, HS>::NTHREADS / VT, LB = P2Geom<N, P, R2, HS>::LDS_BYTES;
-    static AttrOnce attr;
-    {
-        const void* fn;
-        if constexpr (HS) fn = reinterpret_cast<const void*>(&k_pass2_hs<N, P, R2, VT, DUMP>);
-        else fn = reinterpret_cast<const void*>(&k_pass2<N, P, R2, DUMP>);
-        hipError_t e = attr.set(fn, LB);
-        if (e != hipSuccess) return e;
-    }
-    // Frame-at-a-time plan (FFTMesh.Update, S/FFTMesh.cs:60-73: ONE step per call; 256^2 to 1024^2): a step cannot fill the device,
-    // its latency is that of one workgroup.  k_pass2_frame transforms the three fields of a row block side by side.  The arithmetic
-    // of a row does not depend on which kernel runs it: same bits as the batched plan.
-    if constexpr (mw_frame_plan_n(N) && !DUMP) {
-        constexpr int RF = mw_frame_r2(N);
-        if constexpr (P2FrameGeom<N, P, RF>::OK) {
-            if (nsteps == 1) {
-                static AttrOnce attrf;
-                constexpr int LBF = P2FrameGeom<N, P, RF>::LDS_BYTES;
-                hipError_t e = attrf.set(reinterpret_cast<const void*>(&k_pass2_frame<N, P, RF>), LBF);
-                if (e != hipSuccess) return e;
-                k_pass2_frame<N, P, RF><<<dim3(N / RF, 1), dim3(P2FrameGeom<N, P, RF>::NTHREADS), LBF, st>>>(A);
-                return hipGetLastError();
-            }
-        }
-    }
-    if constexpr (HS)
-        k_pass2_hs<N, P, R2, VT, DUMP><<<dim3(N / R2, nsteps), dim3(NT), LB, st>>>(A);
-    else
-        k_pass2<N, P, R2, DUMP><<<dim3(N / R2, nsteps), dim3(NT), LB, st>>>(A);
-    return hipGetLastError();
-}
-
-// time-steps of one pass-1 column job issued back to back on one XCD (p1_block_map): the largest divisor of nsteps up to
-// the handle's p1_tgroup (8), any divisor -- a 20-step enqueue groups by 5 --, 0 = plain 2-D grid
-static int p1_time_group(const mw_ocean* o, int nsteps) {
-    for (int g = o->p1_tgroup; g > 1; g--)
-        if (nsteps % g == 0) return g;
-    return 0;
-}
-// vel: pass 1 of the velocity (mw_ocean_velocity) -- the prep tables of the weighted spectrum and the consts the frame was made with
-static mw_status launch_pass1(mw_ocean* o, const StepTimes& tm, int nsteps, hipStream_t st, const VelState* vel = nullptr,
-                              const OceanConsts* c = nullptr) {
-    P1Args A;
-    A.PQt = o->PQt; A.dPQ_i0 = o->dPQ_i0; A.dPQ_j0 = o->dPQ_j0; A.Om = o->Om; A.TW = o->TW;
-    if (vel) { A.PQt = vel->PQt; A.dPQ_i0 = vel->dPQ_i0; A.dPQ_j0 = vel->dPQ_j0; A.Om = vel->Om; }
-    A.E = o->E; A.Cj0 = o->Cj0;
-    A.c = c ? *c : consts_of(o);
-    A.nsteps = nsteps;
-    A.tgroup = p1_time_group(o, nsteps);
-    A.field_split = nsteps == 1 && mw_frame_plan_n(o->N);
-    if (A.field_split) { A.jobs = o->p1_jobs; A.njobs = o->p1_njobs; }
-    hipError_t e = hipSuccess;
-    MW_FOR_SIZE(o->N, return fail(MW_EINVAL, "unsupported FFT size"), e = launch_pass1_n<NN>(A, tm, nsteps, st));
-    if (e != hipSuccess) return fail(MW_EDEVICE, std::string("pass1 launch: ") + hipGetErrorString(e));
-    return MW_OK;
-}
-static mw_status launch_pass2(mw_ocean* o, int nsteps, float* dv, float* dn, float* dw, int white_stride, cf* hds_dump = nullptr,
-                              const OceanConsts* c = nullptr) {
-    P2Args A;
-    A.E = o->E; A.Cj0 = o->Cj0; A.TW = o->TW2; A.vertices = dv; A.normals = dn; A.white = dw; A.white_stride = white_stride;
-    A.hds_dump = hds_dump;
-    A.c = c ? *c : consts_of(o);
-    hipError_t e = hipSuccess;
-    if (hds_dump) { MW_FOR_SIZE(o->N, return fail(MW_EINVAL, "unsupported FFT size"), e = launch_pass2_n<NN, true>(A, nsteps, o->stream)); }
-    else { MW_FOR_SIZE(o->N, return fail(MW_EINVAL, "unsupported FFT size"), e = launch_pass2_n<NN, false>(A, nsteps, o->stream)); }
-    if (e != hipSuccess) return fail(MW_EDEVICE, std::string("pass2 launch: ") + hipGetErrorString(e));
-    return MW_OK;
-}
-
-static mw_status ensure_exchange(mw_ocean* o, int nsteps) {
-    if (o->e_cap >= nsteps) return MW_OK;
-    if (o->E) {
-        HIP_TRY(hipStreamSynchronize(o->stream));
-        HIP_TRY(hipFree(o->E));
-        HIP_TRY(hipFree(o->Cj0));
-        o->E = o->Cj0 = nullptr;
-        o->e_cap = 0;
-    }
-    mw_status s = dmalloc(&o->E, (size_t)nsteps * 3 * o->N * o->N);
-    if (s != MW_OK) return s;
-    if ((s = dmalloc(&o->Cj0, (size_t)nsteps * 3 * o->N)) != MW_OK) return s;
-    o->e_cap = nsteps;
-    return MW_OK;
-}
-
-static mw_status run_prep(mw_ocean* o) {
-    const int N = o->N;
-    if (o->use_fft) {
-        hipLaunchKernelGGL(k_prep, dim3((N * N + 255) / 256), dim3(256), 0, o->stream, N, o->p.length, o->p.gravity,
-                           o->h0, o->h0c, o->Wpre, o->PQt, o->dPQ_i0, o->dPQ_j0, o->Om);
-        HIP_TRY(hipGetLastError());
-    }
-    return MW_OK;
-}
+// the prep tables of the handle's spectrum at the handle's length (FFT path; the direct-sum path has none)
+static mw_status run_prep(mw_ocean* o) { return o->use_fft ? fm_prep(o->fm.sp, o->N, o->p.length, o->p.gravity, o->fm.Wpre, o->stream) : MW_OK; }
 
 // FETCH_SIZE calibration streams (MI355X_MICROARCH.md "HBM": calibrate the counter on a known byte count in your own
 // access width): every lane reads `width` bytes, lanes contiguous, `bytes` in total; one float per block is written.
@@ -914,11 +256,11 @@ void mw_ocean_destroy(mw_ocean* o) {
     if (!o) return;
     hipSetDevice(o->device);
     if (hipStreamSynchronize(o->stream) != hipSuccess) (void)hipGetLastError();  // a dead caller stream has nothing pending
-    hipFree(o->h0); hipFree(o->h0c); hipFree(o->PQt); hipFree(o->Om); hipFree(o->dPQ_i0); hipFree(o->dPQ_j0);
-    hipFree(o->TW); hipFree(o->TW2); hipFree(o->Wpre); hipFree(o->p1_jobs); hipFree(o->E); hipFree(o->Cj0); hipFree(o->s_vert); hipFree(o->s_norm); hipFree(o->s_white); hipFree(o->q_mesh);
+    hipFree(o->q_mesh);
     for (GrowBuf* b : {&o->scratch, &o->hull, &o->bodies, &o->rc_tree}) hipFree(b->p);
     vel_free(o->vel);
     direct_free(o->direct);
+    fm_free(o->fm);
     or_free(o->orr);
     if (o->own_stream) hipStreamDestroy(o->own_stream);
     delete o;
@@ -955,47 +297,27 @@ static mw_status ocean_create_impl(const mw_params* params, int tiles, mw_ocean*
     hipError_t he = hipStreamCreateWithFlags(&o->own_stream, hipStreamNonBlocking);
     if (he != hipSuccess) { delete o; return fail(MW_EDEVICE, "hipStreamCreate failed"); }
     o->stream = o->own_stream;
-    if (sw(SW_P1_TGROUP) >= 0) o->p1_tgroup = sw(SW_P1_TGROUP);
+    if (sw(SW_P1_TGROUP) >= 0) o->fm.p1_tgroup = sw(SW_P1_TGROUP);
 
     if (o->sem == MW_SEM_FFTMESH) {
         const int N = params->resolution;
-        if (N > 4096) { mw_ocean_destroy(o); return fail(MW_EINVAL, "FFTMesh: resolution > 4096 unsupported"); }
         o->N = N;
         // FFT path precondition: power of two and unit_width == length / N exactly.
         o->use_fft = is_pow2(N) && N >= 64 && (params->unit_width * (float)N == params->length);
-        const size_t NN = (size_t)N * N;
-        if ((s = dmalloc(&o->h0, NN)) != MW_OK || (s = dmalloc(&o->h0c, NN)) != MW_OK ||
-            (s = dmalloc(&o->s_vert, NN * 3)) != MW_OK || (s = dmalloc(&o->s_norm, NN * 3)) != MW_OK ||
-            (s = dmalloc(&o->s_white, NN * 4)) != MW_OK) { mw_ocean_destroy(o); return s; }
-        if (o->use_fft) {
-            if ((s = dmalloc(&o->PQt, NN)) != MW_OK || (s = dmalloc(&o->Om, NN)) != MW_OK ||
-                (s = dmalloc(&o->dPQ_i0, (size_t)N)) != MW_OK ||
-                (s = dmalloc(&o->dPQ_j0, (size_t)N)) != MW_OK || (s = upload_twiddles(o)) != MW_OK) {
-                mw_ocean_destroy(o); return s;
-            }
-        } else {
-            if (direct_alloc(o->direct, N, o->stream) != 0) { mw_ocean_destroy(o); return fail(MW_ENOMEM, "direct path alloc failed"); }
-            if (direct_prepare_tables(o->direct, N, params->unit_width, params->length, params->gravity, o->stream) != hipSuccess) {
-                mw_ocean_destroy(o);
-                return fail(MW_EDEVICE, "direct path: chirp tables could not be uploaded");
-            }
-        }
-        hipLaunchKernelGGL(k_spectrum, dim3((unsigned)((NN + 255) / 256)), dim3(256), 0, o->stream, N, params->length,
-                           params->wind_x, params->wind_y, params->amplitude, params->gravity, params->seed, o->h0, o->h0c);
-        if (hipGetLastError() != hipSuccess) { mw_ocean_destroy(o); return fail(MW_EDEVICE, "k_spectrum launch failed"); }
-        if ((s = run_prep(o)) != MW_OK) { mw_ocean_destroy(o); return s; }
+        if (N > 4096) s = fail(MW_EINVAL, "FFTMesh: resolution > 4096 unsupported");
+        else if (!o->use_fft && direct_alloc(o->direct, N, o->stream) != 0) s = fail(MW_ENOMEM, "direct path alloc failed");
+        else if (!o->use_fft && direct_prepare_tables(o->direct, N, params->unit_width, params->length, params->gravity, o->stream) != hipSuccess)
+            s = fail(MW_EDEVICE, "direct path: chirp tables could not be uploaded");
+        else s = fm_create(o->fm, *params, N, o->use_fft, o->stream);
     } else {
         const int M = params->resolution * 8;  // S/OceanRenderer.cs:136
-        if (!is_pow2(M)) { mw_ocean_destroy(o); return fail(MW_ENOTPOW2, "OceanRenderer: 8*resolution must be a power of two"); }
-        if (M < 64 || M > 4096) { mw_ocean_destroy(o); return fail(MW_EINVAL, "OceanRenderer: texture size must be in [64,4096]"); }
         o->N = M;
-        if ((s = or_create(o->orr, *params, M, o->stream, tiles)) != MW_OK) {
-            mw_ocean_destroy(o);  // (the message or_create left stands: nothing on the way out calls fail())
-            return s;
-        }
+        if (!is_pow2(M)) s = fail(MW_ENOTPOW2, "OceanRenderer: 8*resolution must be a power of two");
+        else if (M < 64 || M > 4096) s = fail(MW_EINVAL, "OceanRenderer: texture size must be in [64,4096]");
+        else s = or_create(o->orr, *params, M, o->stream, tiles);
     }
-    he = hipStreamSynchronize(o->stream);
-    if (he != hipSuccess) { mw_ocean_destroy(o); return fail(MW_EDEVICE, std::string("create sync: ") + hipGetErrorString(he)); }
+    if (s == MW_OK && (he = hipStreamSynchronize(o->stream)) != hipSuccess) s = fail(MW_EDEVICE, std::string("create sync: ") + hipGetErrorString(he));
+    if (s != MW_OK) { mw_ocean_destroy(o); return s; }  // (the message the failing step left stands: nothing on the way out calls fail())
     *out = o;
     return MW_OK;
 }
@@ -1080,8 +402,8 @@ mw_status mw_ocean_set_spectrum(mw_ocean* o, const float* h0_xy, const float* h0
         o->orr.phase_sym = true;  // a fresh spectrum restarts the phase at 0
         return st.finish();
     }
-    HIP_TRY(hipMemcpyAsync(o->h0, h0_xy, bytes, hipMemcpyHostToDevice, o->stream));
-    HIP_TRY(hipMemcpyAsync(o->h0c, h0conj_xy, bytes, hipMemcpyHostToDevice, o->stream));
+    HIP_TRY(hipMemcpyAsync(o->fm.sp.h0, h0_xy, bytes, hipMemcpyHostToDevice, o->stream));
+    HIP_TRY(hipMemcpyAsync(o->fm.sp.h0c, h0conj_xy, bytes, hipMemcpyHostToDevice, o->stream));
     mw_status s = run_prep(o);
     if (s != MW_OK) return s;
     HIP_TRY(hipStreamSynchronize(o->stream));
@@ -1104,8 +426,8 @@ mw_status mw_ocean_get_spectrum(mw_ocean* o, float* h0_xy, float* h0conj_xy) {
         HIP_TRY(hipGetLastError());
         return st.finish();
     }
-    HIP_TRY(hipMemcpyAsync(h0_xy, o->h0, bytes, hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipMemcpyAsync(h0conj_xy, o->h0c, bytes, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipMemcpyAsync(h0_xy, o->fm.sp.h0, bytes, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipMemcpyAsync(h0conj_xy, o->fm.sp.h0c, bytes, hipMemcpyDeviceToHost, o->stream));
     HIP_TRY(hipStreamSynchronize(o->stream));
     return MW_OK;
 }
@@ -1137,15 +459,15 @@ mw_status mw_ocean_reinit_spectrum(mw_ocean* o, float length, float wind_x, floa
                            amplitude, o->p.gravity, seed, n0, n0c);
         hipError_t e = hipGetLastError();
         const float old_length = o->p.length;
-        cf *old0 = o->h0, *old0c = o->h0c;
+        cf *old0 = o->fm.sp.h0, *old0c = o->fm.sp.h0c;
         o->p.length = length;  // run_prep reads it (omega table, S/FFTMesh.cs:141-147)
-        o->h0 = n0; o->h0c = n0c;
+        o->fm.sp.h0 = n0; o->fm.sp.h0c = n0c;
         if (e == hipSuccess) s = run_prep(o);
         if (s == MW_OK && e == hipSuccess) e = hipStreamSynchronize(o->stream);
         if (s == MW_OK && e == hipSuccess && !o->use_fft && length != old_length)  // chirp tables of the new length, here and not inside the next enqueue
             e = direct_prepare_tables(o->direct, N, o->p.unit_width, length, o->p.gravity, o->stream);
         if (s != MW_OK || e != hipSuccess) {
-            o->h0 = old0; o->h0c = old0c;
+            o->fm.sp.h0 = old0; o->fm.sp.h0c = old0c;
             o->p.length = old_length;
             (void)run_prep(o);  // tables back to (old spectrum, old length); if the device is gone, the handle is too (MW_EDEVICE)
             (void)hipStreamSynchronize(o->stream);
@@ -1244,32 +566,19 @@ mw_status mw_ocean_evaluate_device(mw_ocean* o, const float* t, int32_t nsteps, 
     if (nsteps < 1 || nsteps > mw_ocean_max_batch(o)) return fail(MW_EINVAL, "mw_ocean_evaluate_device: nsteps out of range");
     HIP_TRY(hipSetDevice(o->device));
     const int white_stride = (flags & MW_OUT_COLOR_RGBA) ? 4 : 1;
-    if (!o->use_fft) {
-        return direct_evaluate(o->direct, consts_of(o), o->h0, o->h0c, t[0], (float*)d_vertices, (float*)d_normals,
-                               (float*)d_white, white_stride, o->stream) == hipSuccess
-                   ? MW_OK
-                   : fail(MW_EDEVICE, "direct-sum kernels failed to launch");
-    }
-    mw_status s = ensure_exchange(o, nsteps);
-    if (s != MW_OK) return s;
-    StepTimes tm;
-    for (int k = 0; k < nsteps; k++) tm.t[k] = t[k];
-    if ((s = launch_pass1(o, tm, nsteps, o->stream)) != MW_OK) return s;
-    return launch_pass2(o, nsteps, (float*)d_vertices, (float*)d_normals, (float*)d_white, white_stride);
+    if (!o->use_fft)
+        return direct_evaluate(o->direct, consts_of(o), o->fm.sp.h0, o->fm.sp.h0c, t[0], (float*)d_vertices, (float*)d_normals, (float*)d_white,
+                               white_stride, o->stream) == hipSuccess ? MW_OK : fail(MW_EDEVICE, "direct-sum kernels failed to launch");
+    return fm_evaluate(o->fm, o->fm.sp, consts_of(o), t, nsteps, (float*)d_vertices, (float*)d_normals, (float*)d_white, white_stride, o->stream);
 }
 
 mw_status mw_ocean_evaluate(mw_ocean* o, float t, float* vertices_xyz, float* normals_xyz, float* colors_rgba) {
     if (!o) return fail(MW_EINVAL, "NULL handle");
     if (o->sem != MW_SEM_FFTMESH) return fail(MW_ESTATE, "mw_ocean_evaluate: FFTMesh semantics only");
-    mw_status s = mw_ocean_evaluate_device(o, &t, 1, o->s_vert, o->s_norm, o->s_white, MW_OUT_COLOR_RGBA);
+    mw_status s = mw_ocean_evaluate_device(o, &t, 1, o->fm.s_vert, o->fm.s_norm, o->fm.s_white, MW_OUT_COLOR_RGBA);
     if (s != MW_OK) return s;
     frame_fftmesh_made(o, t, 4);
-    const size_t NN = (size_t)o->N * o->N;
-    if (vertices_xyz) HIP_TRY(hipMemcpyAsync(vertices_xyz, o->s_vert, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    if (normals_xyz) HIP_TRY(hipMemcpyAsync(normals_xyz, o->s_norm, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    if (colors_rgba) HIP_TRY(hipMemcpyAsync(colors_rgba, o->s_white, NN * 4 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    return MW_OK;
+    return fm_frame_to_host(o->fm, (size_t)o->N * o->N, vertices_xyz, normals_xyz, colors_rgba, nullptr, nullptr, o->stream);
 }
 
 mw_status mw_ocean_update(mw_ocean* o, float delta_time, float* vertices_xyz, float* normals_xyz, float* colors_rgba) {
@@ -1440,8 +749,158 @@ static void launch_stats(std::vector<float>& v, float* out6) {
     auto pct = [&](double q) { return v[(size_t)std::min<double>((double)n - 1.0, std::floor(q * (double)(n - 1) + 0.5))]; };
     out6[0] = (float)(acc / (double)n); out6[1] = pct(0.5); out6[2] = pct(0.1); out6[3] = pct(0.9); out6[4] = v.front(); out6[5] = v.back();
 }
+// ---- the profiling hook: the launches of one call of the handle's path, timed in situ with a HIP event between every two.  profile_or /
+// profile_direct / profile_fft say what one timed call of their path is; KernelTimes owns the samples and everything reported from them.
+namespace {  // internal linkage, like Stage
+struct KernelTimes {
+    int n = 0;  // kernels of the profiled path, and their names
+    const char* const* names = nullptr;
+    bool report_failed = false;  // the FFT path reports its names (and zero means) even when a launch failed
+    std::vector<float> per[4];   // per kernel: one duration per timed call, in call order
+    void add(const float* ms) { for (int k = 0; k < n; k++) per[k].push_back(ms[k]); }
+    // the mean is the sum in call order (taken before launch_stats sorts); stats only for a run whose launches all succeeded
+    void report(int iters, bool ok, float* ms_out, float* stats_out, const char** names_out, int32_t* nkernels) {
+        for (int k = 0; k < n; k++) {
+            double acc = 0.0;
+            for (float x : per[k]) acc += x;
+            ms_out[k] = (float)(acc / iters);
+            if (names_out) names_out[k] = names[k];
+            if (stats_out && ok) launch_stats(per[k], stats_out + 6 * k);
+        }
+        *nkernels = n;
+    }
+};
+struct Events : std::vector<hipEvent_t> {  // n HIP events, created here and destroyed with the scope
+    explicit Events(size_t n) : std::vector<hipEvent_t>(n) { for (auto& e : *this) hipEventCreate(&e); }
+    ~Events() { for (auto& e : *this) hipEventDestroy(e); }
+};
+}  // namespace
+// warm-up: the first ~10 ms after idle run at reduced clocks (bench.py preheats its timed region for the same reason): 120 ms of `call`
+static mw_status warm_up(hipStream_t st, const std::function<mw_status()>& call) {
+    mw_status s = MW_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    do {
+        for (int w = 0; w < 2 && s == MW_OK; w++) s = call();
+        hipStreamSynchronize(st);
+    } while (s == MW_OK && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < 0.12);
+    return s;
+}
+// OceanRenderer: nsteps frames per enqueue (1: the lone-frame plan); the launches of a call follow one another as in
+// mw_ocean_generate_texture[_steps]_device; the frames stay in the handle.  The phase ADVANCES.
+static mw_status profile_or(mw_ocean* o, int nsteps, int iters, KernelTimes& kt) {
+    if (nsteps > 1 && o->orr.tiles != 1) return fail(MW_ESTATE, "mw_ocean_profile_kernels: a batched handle advances one frame per call");
+    static const char* rnames[4] = {"k_or_pass1 (dispersion + spectrum + transform along py)", "k_or_pass2 (transform along px, height / displacement)",
+                                    "k_or_normal_white", "copies (k_or_copy_frame: the last frame becomes the handle's latest)"};
+    static const char* snames[4] = {"k_or_pass1_steps (phase chain + spectra + transform along py, all frames)", rnames[1], rnames[2], rnames[3]};
+    kt.n = 4; kt.names = nsteps == 1 ? rnames : snames;
+    float dts[MW_OR_MAX_FRAMES];
+    for (int k = 0; k < MW_OR_MAX_FRAMES; k++) dts[k] = 1.0f / 60.0f;
+    frame_or_lone(o);
+    auto call = [&](hipEvent_t* ev) { return or_frames(o->orr, o->p.choppiness, dts, nsteps, false, {nullptr, nullptr, nullptr, nullptr}, o->stream, ev); };
+    mw_status s = warm_up(o->stream, [&] { return call(nullptr); });
+    if (s != MW_OK) return s;
+    // events of one call, per chunk j of frames (one chunk in the lone-frame plan): [3j] before its spectrum launch, [3j + 1] after it,
+    // [3j + 2] after its pass 2, [3j + 3] after its normal / whitecap pass; [3 nch + 1] after the copies.  All calls first, one wait.
+    const int nch = nsteps == 1 ? 1 : or_steps_chunks(o->orr.M, nsteps);
+    const size_t per_it = 2 + 3 * (size_t)nch;
+    Events ev(per_it * (size_t)iters);
+    for (int it = 0; it < iters && s == MW_OK; it++) s = call(&ev[per_it * (size_t)it]);
+    hipStreamSynchronize(o->stream);
+    for (int it = 0; it < iters && s == MW_OK; it++) {
+        hipEvent_t* e = &ev[per_it * (size_t)it];
+        float m[4] = {0.f, 0.f, 0.f, 0.f}, x = 0.f;
+        for (int j = 0; j < nch; j++)
+            for (int k = 0; k < 3; k++) { hipEventElapsedTime(&x, e[3 * j + k], e[3 * j + k + 1]); m[k] += x; }
+        hipEventElapsedTime(&m[3], e[3 * nch], e[3 * nch + 1]);
+        kt.add(m);
+    }
+    if (s != MW_OK) return s;
+    const bool kept[4] = {true, true, true, true};
+    frame_or_steps(o, nsteps, kept, -1);  // the hook has always left the steps tail unset: mw_ocean_velocity takes frame -1 only after it
+    return MW_OK;
+}
+// FFTMesh direct-sum path: kernel 0 = the four GEMM launches of one step, kernel 1 = spectrum + assembly + whitecap.  Five calls warm up;
+// every timed call is waited for on its own.
+static mw_status profile_direct(mw_ocean* o, int nsteps, int iters, KernelTimes& kt) {
+    if (nsteps != 1) return fail(MW_EINVAL, "mw_ocean_profile_kernels: the direct-sum path evaluates one step per enqueue");
+    static const char* gnames[2] = {"k_gemm_f32_mfma (4 launches: z sum, x sum)", "k_direct_spec + k_direct_assemble + k_direct_white"};
+    static const char* znames[2] = {"k_czt (2 launches: spectrum + chirp-z along j, chirp-z along i)", "k_czt_assemble_white"};
+    static const char* fnames[2] = {"k_czt (spectrum + chirp-z along j)", "k_czt_rows_assemble (chirp-z along i + vertices, normals, whitecap: one launch)"};
+    static const char* onames[2] = {"(no separate launch)", "k_czt_one (both axes + vertices, normals, whitecap: one workgroup, one launch)"};
+    kt.n = 2; kt.names = gnames;
+    if (o->direct.use_czt) {  // the names follow the plan czt_evaluate runs (czt_plan: the one place that decides)
+        const CztPlan plan = czt_plan(o->direct.czt, o->N);
+        kt.names = plan == CZT_PLAN_ONE ? onames : (plan == CZT_PLAN_TWO ? fnames : znames);
+    }
+    FmState& f = o->fm;
+    auto call = [&](float t, hipEvent_t* ev) {
+        return direct_evaluate(o->direct, consts_of(o), f.sp.h0, f.sp.h0c, t, f.s_vert, f.s_norm, f.s_white, 1, o->stream, ev);
+    };
+    Events ev(4);
+    frame_fftmesh_overwritten(o);  // by the launches below (whitecap scalar, stride 1)
+    hipError_t he = hipSuccess;
+    for (int w = 0; w < 5 && he == hipSuccess; w++) he = call(1.0f, nullptr);
+    for (int it = 0; it < iters && he == hipSuccess; it++) {
+        he = call(1.0f + (float)it / 60.f, &ev[0]);
+        hipEventRecord(ev[3], o->stream);
+        hipEventSynchronize(ev[3]);
+        float d[3] = {0.f, 0.f, 0.f};
+        for (int k = 0; k < 3; k++) hipEventElapsedTime(&d[k], ev[k], ev[k + 1]);
+        const float m[2] = {d[1], d[0] + d[2]};
+        kt.add(m);
+    }
+    if (he != hipSuccess) return fail(MW_EDEVICE, std::string("direct-sum profile: ") + hipGetErrorString(he));
+    frame_fftmesh_made(o, 1.0f + (float)(iters - 1) / 60.f, 1);  // the chirp-z / direct kernels above wrote the host-API frame
+    return MW_OK;
+}
+// FFTMesh FFT path: the two kernels alternate exactly as in mw_ocean_evaluate_device (pass 2 of a batch follows its pass 1), through
+// fm_evaluate with its event between the passes.  All calls first, one wait.
+static mw_status profile_fft(mw_ocean* o, int nsteps, int iters, KernelTimes& kt) {
+    FmState& f = o->fm;
+    const size_t NN = (size_t)o->N * o->N;
+    mw_status s = MW_OK;
+    float *dv = nullptr, *dn = nullptr, *dw = nullptr;
+    if (nsteps == 1) { dv = f.s_vert; dn = f.s_norm; dw = f.s_white; frame_fftmesh_overwritten(o); }  // by the launches below, whitecap stride 1
+    else if ((s = dmalloc(&dv, NN * 3 * nsteps)) != MW_OK || (s = dmalloc(&dn, NN * 3 * nsteps)) != MW_OK || (s = dmalloc(&dw, NN * nsteps)) != MW_OK) {
+        hipFree(dv); hipFree(dn); hipFree(dw);
+        return s;
+    }
+    static const char* names[2] = {"k_pass1 (h~ + transform along i)", "k_pass2 (transform along j + epilogue)"};
+    kt.n = 2; kt.names = names; kt.report_failed = true;
+    float t[MW_MAX_BATCH];
+    for (int k = 0; k < nsteps; k++) t[k] = 1.0f + (float)k / 60.f;
+    auto call = [&](hipEvent_t* between) { return fm_evaluate(f, f.sp, consts_of(o), t, nsteps, dv, dn, dw, 1, o->stream, false, nullptr, between); };
+    Events ev(2 * iters + 1);
+    s = warm_up(o->stream, [&] { return call(nullptr); });
+    hipEventRecord(ev[0], o->stream);
+    for (int it = 0; it < iters && s == MW_OK; it++) {
+        s = call(&ev[2 * it + 1]);
+        hipEventRecord(ev[2 * it + 2], o->stream);
+    }
+    hipEventSynchronize(ev[2 * iters]);
+    for (int it = 0; it < iters && s == MW_OK; it++) {
+        float m[2] = {0.f, 0.f};
+        hipEventElapsedTime(&m[0], ev[2 * it], ev[2 * it + 1]);
+        hipEventElapsedTime(&m[1], ev[2 * it + 1], ev[2 * it + 2]);
+        kt.add(m);
+    }
+    if (nsteps != 1) { hipFree(dv); hipFree(dn); hipFree(dw); }
+    else if (s == MW_OK) frame_fftmesh_made(o, 1.0f, 1);  // the host-API frame is the profiled step (t = 1) now
+    return s;
+}
 static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters, float* ms_out, float* stats_out, const char** names_out,
-                                      int32_t* nkernels);
+                                      int32_t* nkernels) {
+    if (!o || !ms_out || !nkernels || iters < 1) return fail(MW_EINVAL, "mw_ocean_profile_kernels: bad argument");
+    if (nsteps < 1 || nsteps > MW_MAX_BATCH) return fail(MW_EINVAL, "nsteps out of range");
+    HIP_TRY(hipSetDevice(o->device));
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    KernelTimes kt;
+    const mw_status s = o->sem == MW_SEM_OCEANRENDERER ? profile_or(o, nsteps, iters, kt)
+                        : !o->use_fft                  ? profile_direct(o, nsteps, iters, kt)
+                                                       : profile_fft(o, nsteps, iters, kt);
+    if (s == MW_OK || kt.report_failed) kt.report(iters, s == MW_OK, ms_out, stats_out, names_out, nkernels);
+    return s;
+}
 mw_status mw_ocean_profile_kernels(mw_ocean* o, int32_t nsteps, int32_t iters, float* ms_out, const char** names_out,
                                    int32_t* nkernels) {
     if (!ms_out) return fail(MW_EINVAL, "mw_ocean_profile_kernels: bad argument");
@@ -1452,165 +911,6 @@ mw_status mw_ocean_profile_kernels_stats(mw_ocean* o, int32_t nsteps, int32_t it
     if (!stats_out) return fail(MW_EINVAL, "mw_ocean_profile_kernels_stats: bad argument");
     float ms[4] = {0.f, 0.f, 0.f, 0.f};
     return profile_kernels_impl(o, nsteps, iters, ms, stats_out, names_out, nkernels);
-}
-static mw_status profile_kernels_impl(mw_ocean* o, int32_t nsteps, int32_t iters, float* ms_out, float* stats_out, const char** names_out,
-                                      int32_t* nkernels) {
-    if (!o || !ms_out || !nkernels || iters < 1) return fail(MW_EINVAL, "mw_ocean_profile_kernels: bad argument");
-    if (nsteps < 1 || nsteps > MW_MAX_BATCH) return fail(MW_EINVAL, "nsteps out of range");
-    HIP_TRY(hipSetDevice(o->device));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    if (o->sem == MW_SEM_OCEANRENDERER) {
-        // nsteps frames per enqueue (1: the lone-frame plan), in situ: the launches of a call follow one another as in
-        // mw_ocean_generate_texture[_steps]_device, a HIP event between every two; the frames stay in the handle.  The phase ADVANCES.
-        if (nsteps > 1 && o->orr.tiles != 1) return fail(MW_ESTATE, "mw_ocean_profile_kernels: a batched handle advances one frame per call");
-        static const char* rnames[4] = {"k_or_pass1 (dispersion + spectrum + transform along py)", "k_or_pass2 (transform along px, height / displacement)",
-                                        "k_or_normal_white", "copies (k_or_copy_frame: the last frame becomes the handle's latest)"};
-        static const char* snames[4] = {"k_or_pass1_steps (phase chain + spectra + transform along py, all frames)", rnames[1], rnames[2], rnames[3]};
-        float dts[MW_OR_MAX_FRAMES];
-        for (int k = 0; k < MW_OR_MAX_FRAMES; k++) dts[k] = 1.0f / 60.0f;
-        frame_or_lone(o);
-        auto call = [&](hipEvent_t* ev) { return or_frames(o->orr, o->p.choppiness, dts, nsteps, false, {nullptr, nullptr, nullptr, nullptr}, o->stream, ev); };
-        mw_status s = MW_OK;
-        {
-            const auto t0 = std::chrono::steady_clock::now();
-            do {
-                for (int w = 0; w < 2 && s == MW_OK; w++) s = call(nullptr);
-                hipStreamSynchronize(o->stream);
-            } while (s == MW_OK && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < 0.12);
-        }
-        if (s != MW_OK) return s;
-        // events of one call, per chunk j of frames (one chunk in the lone-frame plan): [3j] before its spectrum launch, [3j + 1] after it,
-        // [3j + 2] after its pass 2, [3j + 3] after its normal / whitecap pass; [3 nch + 1] after the copies
-        const int nch = nsteps == 1 ? 1 : or_steps_chunks(o->orr.M, nsteps);
-        const size_t per_it = 2 + 3 * (size_t)nch;
-        std::vector<hipEvent_t> ev(per_it * (size_t)iters);
-        for (auto& e : ev) hipEventCreate(&e);
-        for (int it = 0; it < iters && s == MW_OK; it++) s = call(&ev[per_it * (size_t)it]);
-        hipStreamSynchronize(o->stream);
-        std::vector<float> per[4];
-        double acc[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int it = 0; it < iters && s == MW_OK; it++) {
-            hipEvent_t* e = &ev[per_it * (size_t)it];
-            float m[4] = {0.f, 0.f, 0.f, 0.f}, x = 0.f;
-            for (int j = 0; j < nch; j++)
-                for (int k = 0; k < 3; k++) { hipEventElapsedTime(&x, e[3 * j + k], e[3 * j + k + 1]); m[k] += x; }
-            hipEventElapsedTime(&m[3], e[3 * nch], e[3 * nch + 1]);
-            for (int k = 0; k < 4; k++) { acc[k] += m[k]; per[k].push_back(m[k]); }
-        }
-        for (auto& e : ev) hipEventDestroy(e);
-        if (s != MW_OK) return s;
-        for (int k = 0; k < 4; k++) {
-            ms_out[k] = (float)(acc[k] / iters);
-            if (names_out) names_out[k] = (nsteps == 1 ? rnames : snames)[k];
-            if (stats_out) launch_stats(per[k], stats_out + 6 * k);
-        }
-        *nkernels = 4;
-        const bool kept[4] = {true, true, true, true};
-        frame_or_steps(o, nsteps, kept, -1);  // the hook has always left the steps tail unset: mw_ocean_velocity takes frame -1 only after it
-        return MW_OK;
-    }
-    if (!o->use_fft) {  // direct-sum path: kernel 0 = the four GEMM launches of one step, kernel 1 = spectrum + assembly + whitecap
-        if (nsteps != 1) return fail(MW_EINVAL, "mw_ocean_profile_kernels: the direct-sum path evaluates one step per enqueue");
-        static const char* gnames[2] = {"k_gemm_f32_mfma (4 launches: z sum, x sum)", "k_direct_spec + k_direct_assemble + k_direct_white"};
-        static const char* znames[2] = {"k_czt (2 launches: spectrum + chirp-z along j, chirp-z along i)", "k_czt_assemble_white"};
-        static const char* fnames[2] = {"k_czt (spectrum + chirp-z along j)", "k_czt_rows_assemble (chirp-z along i + vertices, normals, whitecap: one launch)"};
-        static const char* onames[2] = {"(no separate launch)", "k_czt_one (both axes + vertices, normals, whitecap: one workgroup, one launch)"};
-        const char* const* dnames = gnames;
-        if (o->direct.use_czt) {  // the names follow the plan czt_evaluate runs (czt_plan: the one place that decides)
-            const CztPlan plan = czt_plan(o->direct.czt, o->N);
-            dnames = plan == CZT_PLAN_ONE ? onames : (plan == CZT_PLAN_TWO ? fnames : znames);
-        }
-        hipEvent_t ev[4];
-        for (auto& e : ev) hipEventCreate(&e);
-        frame_fftmesh_overwritten(o);  // by the launches below (whitecap scalar, stride 1)
-        hipError_t he = hipSuccess;
-        for (int w = 0; w < 5 && he == hipSuccess; w++)
-            he = direct_evaluate(o->direct, consts_of(o), o->h0, o->h0c, 1.0f, o->s_vert, o->s_norm, o->s_white, 1, o->stream);
-        double acc[2] = {0.0, 0.0};
-        std::vector<float> per[2];
-        for (int it = 0; it < iters && he == hipSuccess; it++) {
-            he = direct_evaluate(o->direct, consts_of(o), o->h0, o->h0c, 1.0f + (float)it / 60.f, o->s_vert, o->s_norm, o->s_white, 1, o->stream, ev);
-            hipEventRecord(ev[3], o->stream);
-            hipEventSynchronize(ev[3]);
-            float a = 0.f, g = 0.f, b = 0.f;
-            hipEventElapsedTime(&a, ev[0], ev[1]);
-            hipEventElapsedTime(&g, ev[1], ev[2]);
-            hipEventElapsedTime(&b, ev[2], ev[3]);
-            acc[0] += g;
-            acc[1] += a + b;
-            per[0].push_back(g);
-            per[1].push_back(a + b);
-        }
-        for (auto& e : ev) hipEventDestroy(e);
-        if (he != hipSuccess) return fail(MW_EDEVICE, std::string("direct-sum profile: ") + hipGetErrorString(he));
-        frame_fftmesh_made(o, 1.0f + (float)(iters - 1) / 60.f, 1);  // the chirp-z / direct kernels above wrote the host-API frame
-        for (int k = 0; k < 2; k++) {
-            ms_out[k] = (float)(acc[k] / iters);
-            if (names_out) names_out[k] = dnames[k];
-            if (stats_out) launch_stats(per[k], stats_out + 6 * k);
-        }
-        *nkernels = 2;
-        return MW_OK;
-    }
-    mw_status s = ensure_exchange(o, nsteps);
-    if (s != MW_OK) return s;
-    const size_t NN = (size_t)o->N * o->N;
-    float *dv = nullptr, *dn = nullptr, *dw = nullptr;
-    if (nsteps == 1) { dv = o->s_vert; dn = o->s_norm; dw = o->s_white; frame_fftmesh_overwritten(o); }  // by the launches below, whitecap stride 1
-    else {
-        if ((s = dmalloc(&dv, NN * 3 * nsteps)) != MW_OK || (s = dmalloc(&dn, NN * 3 * nsteps)) != MW_OK ||
-            (s = dmalloc(&dw, NN * nsteps)) != MW_OK) { hipFree(dv); hipFree(dn); hipFree(dw); return s; }
-    }
-    StepTimes tm;
-    for (int k = 0; k < nsteps; k++) tm.t[k] = 1.0f + (float)k / 60.f;
-    // In-situ timing: the two kernels alternate exactly as in mw_ocean_evaluate_device (pass 2 of a batch follows
-    // its pass 1), with a HIP event between every launch on the launch stream.
-    static const char* names[2] = {"k_pass1 (h~ + transform along i)", "k_pass2 (transform along j + epilogue)"};
-    std::vector<hipEvent_t> ev(2 * iters + 1);
-    for (auto& e : ev) hipEventCreate(&e);
-    // warm-up: the allocations above idle the device for milliseconds and the first ~10 ms after idle run at reduced
-    // clocks (bench.py preheats its timed region for the same reason): 120 ms of the same two kernels, at least 2 rounds
-    {
-        const auto t0 = std::chrono::steady_clock::now();
-        int rounds = 0;
-        do {
-            for (int w = 0; w < 2 && s == MW_OK; w++) {
-                s = launch_pass1(o, tm, nsteps, o->stream);
-                if (s == MW_OK) s = launch_pass2(o, nsteps, dv, dn, dw, 1);
-            }
-            hipStreamSynchronize(o->stream);
-            rounds++;
-        } while (s == MW_OK && (rounds < 1 || std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < 0.12));
-    }
-    hipEventRecord(ev[0], o->stream);
-    for (int it = 0; it < iters && s == MW_OK; it++) {
-        s = launch_pass1(o, tm, nsteps, o->stream);
-        hipEventRecord(ev[2 * it + 1], o->stream);
-        if (s == MW_OK) s = launch_pass2(o, nsteps, dv, dn, dw, 1);
-        hipEventRecord(ev[2 * it + 2], o->stream);
-    }
-    hipEventSynchronize(ev[2 * iters]);
-    double acc[2] = {0.0, 0.0};
-    std::vector<float> per[2];
-    for (int it = 0; it < iters && s == MW_OK; it++) {
-        float m1 = 0.f, m2 = 0.f;
-        hipEventElapsedTime(&m1, ev[2 * it], ev[2 * it + 1]);
-        hipEventElapsedTime(&m2, ev[2 * it + 1], ev[2 * it + 2]);
-        acc[0] += m1;
-        acc[1] += m2;
-        per[0].push_back(m1);
-        per[1].push_back(m2);
-    }
-    for (int k = 0; k < 2; k++) {
-        ms_out[k] = (float)(acc[k] / iters);
-        if (names_out) names_out[k] = names[k];
-        if (stats_out && s == MW_OK) launch_stats(per[k], stats_out + 6 * k);
-    }
-    for (auto& e : ev) hipEventDestroy(e);
-    if (nsteps != 1) { hipFree(dv); hipFree(dn); hipFree(dw); }
-    else if (s == MW_OK) frame_fftmesh_made(o, 1.0f, 1);  // the host-API frame is the profiled step (t = 1) now
-    *nkernels = 2;
-    return s;
 }
 
 // test hook: omega(i,j)*t exactly as the kernels form it (bit-exactness check vs the oracle)
@@ -1637,33 +937,21 @@ mw_status mw_debug_evaluate_hds(mw_ocean* o, float t, float* vertices_xyz, float
     if (o->sem != MW_SEM_FFTMESH) return fail(MW_ESTATE, "mw_debug_evaluate_hds: FFTMesh semantics only");
     HIP_TRY(hipSetDevice(o->device));
     const size_t NN = (size_t)o->N * o->N;
-    cf* dh = nullptr;
-    if (o->use_fft) {
-        mw_status s = scratch_reserve(o, NN * sizeof(cf));
-        if (s != MW_OK) return s;
+    FmState& f = o->fm;
+    cf* dh = o->direct.hds;  // the direct-sum kernels leave hds there
+    mw_status s = o->use_fft ? scratch_reserve(o, NN * sizeof(cf)) : mw_ocean_evaluate_device(o, &t, 1, f.s_vert, f.s_norm, f.s_white, MW_OUT_COLOR_RGBA);
+    if (s == MW_OK && o->use_fft) {
         dh = static_cast<cf*>(o->scratch.p);
-        if ((s = ensure_exchange(o, 1)) != MW_OK) return s;
-        StepTimes tm;
-        tm.t[0] = t;
-        if ((s = launch_pass1(o, tm, 1, o->stream)) != MW_OK) return s;
-        if ((s = launch_pass2(o, 1, o->s_vert, o->s_norm, o->s_white, 4, dh)) != MW_OK) return s;
-    } else {
-        mw_status s = mw_ocean_evaluate_device(o, &t, 1, o->s_vert, o->s_norm, o->s_white, MW_OUT_COLOR_RGBA);
-        if (s != MW_OK) return s;
-        dh = o->direct.hds;
+        s = fm_evaluate(f, f.sp, consts_of(o), &t, 1, f.s_vert, f.s_norm, f.s_white, 4, o->stream, false, dh);
     }
+    if (s != MW_OK) return s;
     frame_fftmesh_made(o, t, 4);
-    if (vertices_xyz) HIP_TRY(hipMemcpyAsync(vertices_xyz, o->s_vert, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    if (normals_xyz) HIP_TRY(hipMemcpyAsync(normals_xyz, o->s_norm, NN * 3 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    if (colors_rgba) HIP_TRY(hipMemcpyAsync(colors_rgba, o->s_white, NN * 4 * sizeof(float), hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipMemcpyAsync(hds_xy, dh, NN * sizeof(cf), hipMemcpyDeviceToHost, o->stream));
-    HIP_TRY(hipStreamSynchronize(o->stream));
-    return MW_OK;
+    return fm_frame_to_host(f, NN, vertices_xyz, normals_xyz, colors_rgba, dh, hds_xy, o->stream);
 }
 
 // measurement hook: the pass-1 time group an enqueue of nsteps uses (bench.py prints what it timed)
 int32_t mw_debug_pass1_time_group(mw_ocean* o, int32_t nsteps) {
-    return (o && o->sem == MW_SEM_FFTMESH && o->use_fft && nsteps >= 1 && nsteps <= MW_MAX_BATCH) ? p1_time_group(o, nsteps) : 0;
+    return (o && o->sem == MW_SEM_FFTMESH && o->use_fft && nsteps >= 1 && nsteps <= MW_MAX_BATCH) ? p1_time_group(o->fm, nsteps) : 0;
 }
 
 // test hooks: the stored omega table and the device sincos
@@ -1748,8 +1036,8 @@ mw_status mw_debug_stream_read(int64_t bytes, int32_t width, int32_t iters) {
 }
 
 mw_status mw_debug_get_omega(mw_ocean* o, float* out_host) {  // [j][i] layout
-    if (!o || !o->Om) return fail(MW_EINVAL, "no omega table");
-    HIP_TRY(hipMemcpy(out_host, o->Om, sizeof(float) * o->N * o->N, hipMemcpyDeviceToHost));
+    if (!o || !o->fm.sp.Om) return fail(MW_EINVAL, "no omega table");
+    HIP_TRY(hipMemcpy(out_host, o->fm.sp.Om, sizeof(float) * o->N * o->N, hipMemcpyDeviceToHost));
     return MW_OK;
 }
 

@@ -1,5 +1,5 @@
-// mw_host.h -- host-side helpers every part of the library shares (device build only): the error channel behind mw_last_error() and the
-// one list of transform sizes.  Everything here has internal linkage: nothing joins the library's exported symbols.
+// mw_host.h -- host-side helpers every part of the library shares (device build only): the error channel behind mw_last_error(), the
+// typed hipMalloc and the one list of transform sizes.  Everything here has internal linkage: nothing joins the library's exported symbols.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,6 +22,12 @@ static mw_status fail(mw_status s, const char* who, const std::string& m) { retu
         if (e_ != hipSuccess)                                                                           \
             return fail(MW_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
     } while (0)
+
+template <typename T>
+static mw_status dmalloc(T** p, size_t count) {
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
+    return MW_OK;
+}
 
 // The transform sizes the library has kernels for, named once.  The statement(s) after DEFAULT run with NN a constant expression equal
 // to N_; any other N_ runs DEFAULT (the caller's own message and status).

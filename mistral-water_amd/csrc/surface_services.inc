@@ -33,8 +33,8 @@ static mw_status query_prepare(mw_ocean* o, int32_t frame, int32_t mode, const v
     if (!(o->p.unit_width > 0.f)) return fail(MW_EINVAL, who, "the mesh needs unit_width > 0");
     m->unit_width = o->p.unit_width;
     if (o->sem == MW_SEM_FFTMESH) {
-        if (!o->s_have) return fail(MW_ESTATE, who, "no frame yet (mw_ocean_evaluate / mw_ocean_update first)");
-        m->vert = o->s_vert; m->norm = o->s_norm; m->white = o->s_white; m->R = o->N; m->wstride = o->s_wstride;
+        if (!o->fm.s_have) return fail(MW_ESTATE, who, "no frame yet (mw_ocean_evaluate / mw_ocean_update first)");
+        m->vert = o->fm.s_vert; m->norm = o->fm.s_norm; m->white = o->fm.s_white; m->R = o->N; m->wstride = o->fm.s_wstride;
         return MW_OK;
     }
     OrState& r = o->orr;
@@ -98,7 +98,7 @@ static mw_status velocity_check(mw_ocean* o, int32_t frame, const char* who) {
     if (o->sem == MW_SEM_OCEANRENDERER && frame != -1 && !(frame >= 0 && frame == o->or_steps_tail))
         return fail(MW_EINVAL, who, "the handle keeps only the latest phase: frame must be -1 or the last frame of the latest "
                                     "steps call");
-    if (o->sem == MW_SEM_FFTMESH && !o->s_have) return fail(MW_ESTATE, who, "no frame yet (mw_ocean_evaluate / mw_ocean_update first)");
+    if (o->sem == MW_SEM_FFTMESH && !o->fm.s_have) return fail(MW_ESTATE, who, "no frame yet (mw_ocean_evaluate / mw_ocean_update first)");
     if (o->sem == MW_SEM_OCEANRENDERER && !o->orr.have_frame) return fail(MW_ESTATE, who, "no GenerateTexture() yet");
     return MW_OK;
 }
@@ -112,38 +112,30 @@ static mw_status velocity_run(mw_ocean* o, float* d_vel) {
     const size_t NN = (size_t)N * N;
     mw_status s = MW_OK;
     if (!v.white) {  // the last buffer allocated: a failure half-way frees them all, and the next call starts again
-        if ((s = dmalloc(&v.h0, NN)) != MW_OK || (s = dmalloc(&v.h0c, NN)) != MW_OK || (s = dmalloc(&v.norm, 3 * NN)) != MW_OK ||
-            (o->use_fft && ((s = dmalloc(&v.PQt, NN)) != MW_OK || (s = dmalloc(&v.Om, NN)) != MW_OK ||
-                            (s = dmalloc(&v.dPQ_i0, (size_t)N)) != MW_OK || (s = dmalloc(&v.dPQ_j0, (size_t)N)) != MW_OK)) ||
-            (s = dmalloc(&v.white, NN)) != MW_OK) {
+        if ((s = fm_spectrum_alloc(v.sp, N, o->use_fft)) != MW_OK || (s = dmalloc(&v.norm, 3 * NN)) != MW_OK || (s = dmalloc(&v.white, NN)) != MW_OK) {
             vel_free(v);
             return s;
         }
     }
     const unsigned nb = (unsigned)((NN + 255) / 256);
     if (!v.ready) {  // (i w h0, -i w h0c) and, on the FFT path, its prep tables: once per spectrum
-        hipLaunchKernelGGL(k_velocity_spectrum, dim3(nb), dim3(256), 0, o->stream, N, o->p.length, o->p.gravity, o->h0, o->h0c, v.h0, v.h0c);
-        if (o->use_fft)
-            hipLaunchKernelGGL(k_prep, dim3(nb), dim3(256), 0, o->stream, N, o->p.length, o->p.gravity, v.h0, v.h0c, o->Wpre, v.PQt,
-                               v.dPQ_i0, v.dPQ_j0, v.Om);
+        hipLaunchKernelGGL(k_velocity_spectrum, dim3(nb), dim3(256), 0, o->stream, N, o->p.length, o->p.gravity, o->fm.sp.h0, o->fm.sp.h0c, v.sp.h0,
+                           v.sp.h0c);
         HIP_TRY(hipGetLastError());
+        if (o->use_fft && (s = fm_prep(v.sp, N, o->p.length, o->p.gravity, o->fm.Wpre, o->stream)) != MW_OK) return s;
         velocity_spectrum_built(o);
     }
     OceanConsts C = consts_of(o);
-    C.choppiness = o->s_chop;  // the frame's choppiness (mw_ocean_set_choppiness may have changed it since)
+    C.choppiness = o->fm.s_chop;  // the frame's choppiness (mw_ocean_set_choppiness may have changed it since)
     if (!o->use_fft) {
-        if (direct_evaluate(o->direct, C, v.h0, v.h0c, o->s_t, d_vel, v.norm, v.white, 1, o->stream) != hipSuccess)
+        if (direct_evaluate(o->direct, C, v.sp.h0, v.sp.h0c, o->fm.s_t, d_vel, v.norm, v.white, 1, o->stream) != hipSuccess)
             return fail(MW_EDEVICE, "velocity: direct-sum kernels failed to launch");
         hipLaunchKernelGGL(k_velocity_from_hds, dim3(nb), dim3(256), 0, o->stream, N, C.choppiness, o->direct.hds, d_vel);
         HIP_TRY(hipGetLastError());
         return MW_OK;
     }
-    if ((s = ensure_exchange(o, 1)) != MW_OK) return s;
-    StepTimes tm;
-    tm.t[0] = o->s_t;
-    if ((s = launch_pass1(o, tm, 1, o->stream, &v, &C)) != MW_OK) return s;
-    C.unit_width = 0.f;  // rest coordinate +-0: the vertex the epilogue writes is (-chop Dx, h, -chop Dz) of the weighted spectrum
-    return launch_pass2(o, 1, d_vel, v.norm, v.white, 1, nullptr, &C);
+    // pass 2 around a rest coordinate of +-0 (unit_width = 0): the vertex the epilogue writes is (-chop Dx, h, -chop Dz) of the weighted spectrum
+    return fm_evaluate(o->fm, v.sp, C, &o->fm.s_t, 1, d_vel, v.norm, v.white, 1, o->stream, true);
 }
 static size_t velocity_count(const mw_ocean* o) {  // floats of the per-vertex velocity [R*R][3]
     const int R = o->sem == MW_SEM_OCEANRENDERER ? o->p.resolution : o->N;

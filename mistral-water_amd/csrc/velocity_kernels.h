@@ -63,9 +63,7 @@ __global__ void k_velocity_from_hds(int N, float choppiness, const cf* hds, floa
 struct VelState {
     bool ready = false;
     // FFTMesh: the weighted spectrum, its k_prep tables (FFT path), and the normals / whitecap the frame kernels also write
-    cf *h0 = nullptr, *h0c = nullptr;
-    f4 *PQt = nullptr, *dPQ_i0 = nullptr, *dPQ_j0 = nullptr;
-    float* Om = nullptr;
+    FmSpectrum sp;
     float *norm = nullptr, *white = nullptr;
     // OceanRenderer: weighted initial spectrum and its (P, Q), the phase the spectrum kernel stores (unchanged: dt = 0), the exchange
     // buffer and the rate textures of pass 2
@@ -78,7 +76,7 @@ struct VelState {
     float* vert = nullptr;
 };
 static inline void vel_free(VelState& v) {
-    hipFree(v.h0); hipFree(v.h0c); hipFree(v.PQt); hipFree(v.dPQ_i0); hipFree(v.dPQ_j0); hipFree(v.Om); hipFree(v.norm); hipFree(v.white);
+    fm_spectrum_free(v.sp); hipFree(v.norm); hipFree(v.white);
     hipFree(v.initT); hipFree(v.PQT); hipFree(v.phase); hipFree(v.E); hipFree(v.height); hipFree(v.disp_g); hipFree(v.disp); hipFree(v.vert);
     v = VelState();
 }

@@ -855,3 +855,29 @@ def test_errors_on_gpu(mw):
     with pytest.raises(mw.MistralWaterError) as e:
         mw.Ocean(resolution=64, length=64.0, device=99)
     assert e.value.status == mw.MW_EINVAL
+
+
+FFT_KERNELS = ["k_pass1 (h~ + transform along i)", "k_pass2 (transform along j + epilogue)"]
+CZT_TWO_KERNELS = ["k_czt (spectrum + chirp-z along j)", "k_czt_rows_assemble (chirp-z along i + vertices, normals, whitecap: one launch)"]
+OR_KERNELS = ["k_or_pass1 (dispersion + spectrum + transform along py)", "k_or_pass2 (transform along px, height / displacement)",
+              "k_or_normal_white", "copies (k_or_copy_frame: the last frame becomes the handle's latest)"]
+OR_STEPS_KERNELS = ["k_or_pass1_steps (phase chain + spectra + transform along py, all frames)"] + OR_KERNELS[1:]
+
+
+def test_gpu_profile_kernels_stats_shape(mw):
+    """mw_ocean_profile_kernels_stats on the smallest handle of each path: the kernel count, the names (the literals of the hook, per path and
+    nsteps), ordered and finite statistics, and the same names from mw_ocean_profile_kernels.  Nothing about how long anything takes."""
+    fft = dict(resolution=64, unit_width=1.0, length=64.0)                   # FFTMesh, FFT path
+    direct = dict(resolution=50)                                              # FFTMesh, direct-sum path: chirp-z, two launches at this size
+    renderer = dict(resolution=8, length=64.0, semantics=mw.MW_SEM_OCEANRENDERER)  # a 64^2 texture
+    cases = [(fft, 1, FFT_KERNELS), (fft, 2, FFT_KERNELS), (direct, 1, CZT_TWO_KERNELS), (renderer, 1, OR_KERNELS),
+             (renderer, 2, OR_STEPS_KERNELS)]
+    for kw, nsteps, names in cases:
+        with mw.Ocean(**kw) as o:
+            stats = o.profile_kernels_stats(nsteps=nsteps, iters=3)
+            assert [k for k, _ in stats] == names, (kw, nsteps)
+            for k, s in stats:
+                assert all(np.isfinite(x) for x in s.values()), (k, s)
+                assert 0.0 <= s["min"] <= s["p10"] <= s["median"] <= s["p90"] <= s["max"], (k, s)
+                assert s["min"] <= s["mean"] <= s["max"], (k, s)
+            assert [k for k, _ in o.profile_kernels(nsteps=nsteps, iters=3)] == names, (kw, nsteps)
