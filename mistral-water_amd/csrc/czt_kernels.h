@@ -15,7 +15,7 @@
 //
 // Phase functions are MW_HD so that tests/emul steps the same code on the host (tests/test_emul.py::test_chirp_z_*).
 // STATUS (round 4): green on hardware at N = 12 ... 1500 and the default for every non-FFT grid with 2N <= 4096
-// (direct_alloc); the MFMA GEMM form (direct_kernels.h) serves larger grids and MW_DIRECT_CZT=0.
+// (direct_create); the MFMA GEMM form (direct_kernels.h) serves larger grids and MW_DIRECT_CZT=0.
 #pragma once
 #include "fftmesh_kernels.h"
 

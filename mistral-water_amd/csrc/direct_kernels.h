@@ -12,8 +12,12 @@
 //                    product with K = 2N:   Re: [Er^T | -Ei^T] [Tr_f ; Ti_f]      Im: [Ei^T | Er^T] [Tr_f ; Ti_f]
 // = 60 N^3 flop per step on v_mfma_f32_32x32x2_f32 (exact f32: the result is an fmaf chain in k order), instead of five
 // complex accumulators per thread walking global memory.  All operands are zero-padded to Np = a multiple of 64, so the
-// GEMM has no bounds checks and only aligned 16-byte loads.  E and the step-2 left factors are built ONCE per handle
-// (they do not depend on t); per step: the spectrum kernel, 4 GEMM launches, one assembly kernel, the whitecap kernel.
+// GEMM has no bounds checks and only aligned 16-byte loads.  E and the step-2 left factors are built when the handle is created and
+// when its length changes (direct_tables: they do not depend on t); per step: the spectrum kernel, 4 GEMM launches, one assembly
+// kernel, the whitecap kernel.
+//
+// The second half of this file is the host side of both forms: DirectState, direct_buffers / direct_create / direct_free,
+// direct_tables, czt_args, and direct_evaluate, the one step.
 #pragma once
 #include "mw_switches.h"
 #include "fftmesh_kernels.h"
@@ -21,20 +25,16 @@
 
 namespace mw {
 
-// chirp-z form (czt_kernels.h; the default for N <= 2048): tables + the two complex work arrays
-struct CztState {
-    int M = 0;
+// Host state of the direct-sum path: the buffers of the form the handle runs (the other form's stay NULL) and the stamp of its tables.
+struct DirectState {
+    bool use_czt = false;  // chirp-z form (czt_kernels.h; the default for N <= 2048), else the GEMM form
+    int M = 0;             // chirp-z: transform size (czt_size)
+    int Np = 0;            // GEMM: N padded to whole tiles
+    // chirp-z: tables + the two complex work arrays
     cf *w1 = nullptr, *w2 = nullptr, *Hh = nullptr, *TWf = nullptr, *TWi = nullptr;
     cf *TT = nullptr, *O = nullptr;  // packed planes (czt_packed_value): [3][N][N + 1] after the z sum (transposed), [3][N][N] after the x sum
     float *Om = nullptr, *K = nullptr;  // CztArgs::Om / K (k_czt_tables)
-    float table_gravity = -1.f;
-    float table_length = -1.f, table_unit_width = -1.f;
-};
-
-struct DirectState {
-    CztState czt;
-    bool use_czt = false;
-    int N = 0, Np = 0;
+    // GEMM
     float* A1 = nullptr;     // [5][Np][2Np]   (Fr_f | Fi_f), rebuilt every step
     float* T = nullptr;      // [5][2Np][Np]   (Tr_f ; Ti_f)
     float* B1re = nullptr;   // [2Np][Np]      [Er ; -Ei]
@@ -42,8 +42,8 @@ struct DirectState {
     float* A2re = nullptr;   // [Np][2Np]      [Er^T | -Ei^T]
     float* A2im = nullptr;   // [Np][2Np]      [Ei^T |  Er^T]
     float* out = nullptr;    // [5][Np][Np]    H, Dx, Dz, Sx, Sz
-    cf* hds = nullptr;       // [N*N]
-    float table_length = -1.f, table_unit_width = -1.f;  // what the E tables were built for
+    cf* hds = nullptr;       // [N*N], both forms
+    float table_length = -1.f, table_unit_width = -1.f, table_gravity = -1.f;  // what the tables were built for (direct_tables)
 };
 
 #if defined(__HIPCC__)
@@ -501,56 +501,91 @@ __global__ void k_czt_assemble_white(OceanConsts C, const cf* O, cf* hds, float*
     else { white[4 * idx] = xx; white[4 * idx + 1] = xx; white[4 * idx + 2] = xx; white[4 * idx + 3] = xx; }
 }
 
+// ---- host side: DirectState, its buffers and tables, one step -------------------------------------------------------------
 std::vector<cf> build_twiddle_table(int N, int P, int sgn);  // mistral_water.hip
 
-static inline void czt_free(CztState& z) {
-    hipFree(z.w1); hipFree(z.w2); hipFree(z.Hh); hipFree(z.TWf); hipFree(z.TWi); hipFree(z.TT); hipFree(z.O); hipFree(z.Om); hipFree(z.K);
-    z = CztState();
+// Every device buffer of a DirectState, named once: the rows direct_create allocates and direct_free frees.  The form decides which rows
+// have a size; zero: filled with 0 on the stream (the GEMM operands' padding); init: uploaded from the host (the two twiddle tables).
+struct DirectBuf { void** p; size_t bytes; bool zero; const void* init; };
+constexpr int DIRECT_NBUF = 17;
+static inline void direct_buffers(DirectState& d, int N, const std::vector<cf>& twf, const std::vector<cf>& twi, DirectBuf (&b)[DIRECT_NBUF]) {
+    const size_t z = d.use_czt ? 1 : 0, P2 = d.use_czt ? 0 : (size_t)d.Np * d.Np, NN = (size_t)N * N, N1 = (size_t)N + 1;
+    int n = 0;
+    auto row = [&](auto*& p, size_t count, bool zero = false, const void* init = nullptr) { b[n++] = DirectBuf{(void**)&p, sizeof(*p) * count, zero, init}; };
+    row(d.w1, z * N1); row(d.w2, z * N); row(d.Hh, z * d.M); row(d.TWf, twf.size(), false, twf.data()); row(d.TWi, twi.size(), false, twi.data());
+    row(d.TT, z * MW_CZT_PLANES * N * N1); row(d.O, z * MW_CZT_PLANES * NN); row(d.Om, z * N1 * N1); row(d.K, z * N1);
+    row(d.A1, 10 * P2, true); row(d.T, 10 * P2, true); row(d.B1re, 2 * P2, true); row(d.B1im, 2 * P2, true);
+    row(d.A2re, 2 * P2, true); row(d.A2im, 2 * P2, true); row(d.out, 5 * P2, true);
+    row(d.hds, NN);
 }
-static inline int czt_alloc(CztState& z, int N) {
-    z.M = czt_size(N);
-    if (!z.M) return 1;
-    const int P = czt_points(z.M);
-    const std::vector<cf> tf = build_twiddle_table(z.M, P, -1), ti = build_twiddle_table(z.M, P, +1);
-    const size_t NN = (size_t)N * N;
-    if (hipMalloc((void**)&z.w1, sizeof(cf) * (N + 1)) != hipSuccess || hipMalloc((void**)&z.w2, sizeof(cf) * N) != hipSuccess ||
-        hipMalloc((void**)&z.Hh, sizeof(cf) * z.M) != hipSuccess || hipMalloc((void**)&z.TWf, sizeof(cf) * tf.size()) != hipSuccess ||
-        hipMalloc((void**)&z.TWi, sizeof(cf) * ti.size()) != hipSuccess ||
-        hipMalloc((void**)&z.TT, sizeof(cf) * MW_CZT_PLANES * (size_t)N * (N + 1)) != hipSuccess ||
-        hipMalloc((void**)&z.O, sizeof(cf) * MW_CZT_PLANES * NN) != hipSuccess ||
-        hipMalloc((void**)&z.Om, sizeof(float) * (size_t)(N + 1) * (N + 1)) != hipSuccess || hipMalloc((void**)&z.K, sizeof(float) * (N + 1)) != hipSuccess ||
-        hipMemcpy(z.TWf, tf.data(), sizeof(cf) * tf.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(z.TWi, ti.data(), sizeof(cf) * ti.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        czt_free(z);
-        return 4;
-    }
-    return 0;
+static inline void direct_free(DirectState& d) {
+    DirectBuf b[DIRECT_NBUF];
+    direct_buffers(d, 0, {}, {}, b);
+    for (const DirectBuf& r : b) hipFree(*r.p);
+    d = DirectState();
 }
-// chirps and the transform of the wrapped kernel (f64 on the host): uploaded when the handle is created and when its length changes
-// (mw_ocean_create / mw_ocean_reinit_spectrum) -- an enqueue never synchronises or copies
+// chirp-z: the tables of CztArgs::Om / K
 __global__ void k_czt_tables(int N, float length, float gravity, float* Om, float* K) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < (N + 1) * (N + 1)) czt_table_element(N, length, gravity, e, Om, K);
 }
-static inline hipError_t czt_upload_tables(CztState& z, int N, float unit_width, float length, float gravity, hipStream_t st) {
-    std::vector<cf> w1, w2, Hh;
-    czt_build_tables(N, N + 1, z.M, unit_width, length, w1, w2, Hh);
-    z.table_length = z.table_unit_width = z.table_gravity = -1.f;  // half-written tables belong to no length: a failure below forces a rebuild
-    hipError_t e = hipStreamSynchronize(st);  // a step still in flight may be reading the old tables
-    if (e == hipSuccess) {
-        const unsigned ne = (unsigned)((N + 1) * (N + 1));
-        hipLaunchKernelGGL(k_czt_tables, dim3((ne + 255) / 256), dim3(256), 0, st, N, length, gravity, z.Om, z.K);
-        e = hipGetLastError();
+// The tables of the handle's form for (unit_width, length, gravity) -- none of them depends on t -- and their stamp; nothing to do where
+// the stamp already says so.  Chirp-z: k_czt_tables, and the chirps and the transform of the wrapped kernel formed in f64 on the host;
+// a step still in flight may be reading the old ones, so the stream is waited for.  GEMM: k_direct_tables on the stream.  Called by
+// direct_create and fm_reinit alone: an enqueue never builds tables, synchronises or copies.
+static inline mw_status direct_tables(DirectState& d, int N, float unit_width, float length, float gravity, hipStream_t st) {
+    if (d.table_length == length && d.table_unit_width == unit_width && d.table_gravity == gravity) return MW_OK;
+    d.table_length = d.table_unit_width = d.table_gravity = -1.f;  // half-written tables belong to no length
+    hipError_t e;
+    if (d.use_czt) {
+        std::vector<cf> w1, w2, Hh;
+        czt_build_tables(N, N + 1, d.M, unit_width, length, w1, w2, Hh);
+        e = hipStreamSynchronize(st);
+        if (e == hipSuccess) {
+            const unsigned ne = (unsigned)((N + 1) * (N + 1));
+            hipLaunchKernelGGL(k_czt_tables, dim3((ne + 255) / 256), dim3(256), 0, st, N, length, gravity, d.Om, d.K);
+            e = hipGetLastError();
+        }
         if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = hipMemcpy(d.w1, w1.data(), sizeof(cf) * (N + 1), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d.w2, w2.data(), sizeof(cf) * N, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d.Hh, Hh.data(), sizeof(cf) * d.M, hipMemcpyHostToDevice);
+    } else {
+        const unsigned nb = (unsigned)(((size_t)N * N + 127) / 128);
+        hipLaunchKernelGGL(k_direct_tables, dim3(nb), dim3(128), 0, st, N, d.Np, length, unit_width, d.B1re, d.B1im, d.A2re, d.A2im);
+        e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpy(z.w1, w1.data(), sizeof(cf) * (N + 1), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(z.w2, w2.data(), sizeof(cf) * N, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(z.Hh, Hh.data(), sizeof(cf) * z.M, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return e;
-    z.table_length = length;
-    z.table_unit_width = unit_width;
-    z.table_gravity = gravity;
-    return hipSuccess;
+    if (e != hipSuccess) return fail(MW_EDEVICE, std::string("direct path: chirp tables could not be uploaded: ") + hipGetErrorString(e));
+    d.table_length = length; d.table_unit_width = unit_width; d.table_gravity = gravity;
+    return MW_OK;
+}
+// The form, its buffers and its tables for an N^2 grid; the zero fill and the table kernels go to st.  A failure leaves what it did
+// allocate, for direct_free.
+// The chirp-z form is the default wherever one workgroup holds the transform (N + 1 inputs, N outputs: 2N <= 4096): first hardware
+// run in round 4 -- 2.4x (N = 100) to 5.8x (N = 1000) faster than the GEMM form and an order of magnitude more accurate on
+// grids with large phases (profiles/r04a_bench_direct_*).  MW_DIRECT_CZT=0 selects the GEMM form (A/B, and the path of larger N).
+static inline mw_status direct_create(DirectState& d, int N, float unit_width, float length, float gravity, hipStream_t st) {
+    d.M = sw(SW_DIRECT_CZT) != 0 ? czt_size(N) : 0;
+    d.use_czt = d.M != 0;
+    d.Np = d.use_czt ? 0 : (N + 63) / 64 * 64;
+    std::vector<cf> twf, twi;
+    if (d.use_czt) { twf = build_twiddle_table(d.M, czt_points(d.M), -1); twi = build_twiddle_table(d.M, czt_points(d.M), +1); }
+    DirectBuf b[DIRECT_NBUF];
+    direct_buffers(d, N, twf, twi, b);
+    for (const DirectBuf& r : b) {
+        if (!r.bytes) continue;
+        if (dmalloc(reinterpret_cast<char**>(r.p), r.bytes) != MW_OK) return fail(MW_ENOMEM, "direct path alloc failed: " + g_err);
+        // the zero padding, ordered on the handle's stream: the table / spectrum kernels that fill the live part run there later
+        // (a null-stream hipMemset is not ordered with a non-blocking stream)
+        if (r.zero) HIP_TRY(hipMemsetAsync(*r.p, 0, r.bytes, st));
+        if (r.init) HIP_TRY(hipMemcpy(*r.p, r.init, r.bytes, hipMemcpyHostToDevice));
+    }
+    return direct_tables(d, N, unit_width, length, gravity, st);
+}
+
+// ---- one step ----------------------------------------------------------------------------------------------------------
+static inline mw_status direct_launched(hipError_t e) {
+    return e == hipSuccess ? MW_OK : fail(MW_EDEVICE, std::string("direct-sum kernels failed to launch: ") + hipGetErrorString(e));
 }
 #ifndef MW_CZT_FUSED_MAX_M
 #define MW_CZT_FUSED_MAX_M 256  // grids whose second axis and assembly run in one launch (environment MW_CZT_FUSED=0: three launches, A/B)
@@ -566,15 +601,13 @@ static hipError_t czt_launch_rows_assemble(const CztArgs& A, cf* hds, float* dv,
     k_czt_rows_assemble<M, P, RW><<<dim3((A.rows + RW - 1) / RW), dim3(NG * M / P), LB, st>>>(A, hds, dv, dn, dw, white_stride);
     return hipGetLastError();
 }
-// N <= MW_CZT_ONE_MAX_N (transform size 64): one launch (MW_CZT_ONE=0, read per call: the two-launch plan, for A/B and the bit-identity test)
-static inline bool czt_one_launch(const CztState& z, int N) {
-    return z.M == 64 && N <= MW_CZT_ONE_MAX_N && sw(SW_CZT_ONE) != 0 && sw(SW_CZT_FUSED) != 0;
-}
-// which launches a chirp-z step is: the ONE place that decides (czt_evaluate and the measurement hook's kernel names both ask here)
+// which launches a chirp-z step is: the ONE place that decides (czt_evaluate and the measurement hook's kernel names both ask here).
+// N <= MW_CZT_ONE_MAX_N (transform size 64): one launch; M <= MW_CZT_FUSED_MAX_M: two; else three.  MW_CZT_ONE=0 / MW_CZT_FUSED=0, read
+// per call: the next plan down, for A/B and the bit-identity test.
 enum CztPlan { CZT_PLAN_ONE, CZT_PLAN_TWO, CZT_PLAN_THREE };
-static inline CztPlan czt_plan(const CztState& z, int N) {
-    if (czt_one_launch(z, N)) return CZT_PLAN_ONE;
-    return (sw(SW_CZT_FUSED) != 0 && z.M <= MW_CZT_FUSED_MAX_M) ? CZT_PLAN_TWO : CZT_PLAN_THREE;
+static inline CztPlan czt_plan(const DirectState& d, int N) {
+    if (sw(SW_CZT_FUSED) == 0 || d.M > MW_CZT_FUSED_MAX_M) return CZT_PLAN_THREE;
+    return (d.M == 64 && N <= MW_CZT_ONE_MAX_N && sw(SW_CZT_ONE) != 0) ? CZT_PLAN_ONE : CZT_PLAN_TWO;
 }
 static hipError_t czt_launch_one(const CztArgs& A, cf* hds, float* dv, float* dn, float* dw, int white_stride, hipStream_t st) {
     constexpr int M = 64, P = czt_points(M), T = M / P, BUF = FftGeom<M, P>::LBUF + 4;
@@ -597,97 +630,48 @@ static hipError_t czt_launch(const CztArgs& A, hipStream_t st) {
     k_czt<M, P, RW><<<dim3((A.rows + RW - 1) / RW, MW_CZT_PLANES), dim3(RW * M / P), LB, st>>>(A);
     return hipGetLastError();
 }
-// ev (measurement hook): ev[0], ev[1] before and ev[2] after the two k_czt launches (the spectrum is formed inside the first one)
-static inline hipError_t czt_evaluate(DirectState& d, OceanConsts C, const cf* h0, const cf* h0c, float t, float* dv, float* dn, float* dw,
-                                      int white_stride, hipStream_t st, hipEvent_t* ev = nullptr) {
-    CztState& z = d.czt;
+// The arguments of one axis.  pass 0, along j: rows i = 0 .. N formed from the spectrum -> TT[p][b][i] (N rows of N + 1); the one-launch
+// plan takes these too (it forms its lines from the spectrum and keeps both planes in LDS).  pass 1, along i: rows b of TT -> O[p][a][b].
+static inline CztArgs czt_args(const DirectState& d, const OceanConsts& C, const cf* h0, const cf* h0c, float t, int pass) {
     const int N = C.N;
-    const unsigned nb = (unsigned)(((size_t)N * N + 127) / 128);
-    if (z.table_length != C.length || z.table_unit_width != C.unit_width || z.table_gravity != C.gravity) {  // safety net only: the tables are uploaded at creation and at a
-        hipError_t e = czt_upload_tables(z, N, C.unit_width, C.length, C.gravity, st);    // length change (direct_prepare_tables), never inside an enqueue
-        if (e != hipSuccess) return e;
-    }
-    const CztPlan plan = czt_plan(z, N);
-    const bool fused = plan == CZT_PLAN_TWO;
-    if (ev) { hipEventRecord(ev[0], st); hipEventRecord(ev[1], st); }
     CztArgs A;
-    A.w1 = z.w1; A.w2 = z.w2; A.Hh = z.Hh; A.TWf = z.TWf; A.TWi = z.TWi; A.Om = z.Om; A.K = z.K;
+    A.w1 = d.w1; A.w2 = d.w2; A.Hh = d.Hh; A.TWf = d.TWf; A.TWi = d.TWi; A.Om = d.Om; A.K = d.K;
     A.nin = N + 1; A.nout = N;  // the packed planes live on the index set [0, N]^2 (czt_packed_value)
-    if (plan == CZT_PLAN_ONE) {  // tiny grids: both axes and the assembly in one workgroup (k_czt_one)
-        A.h0 = h0; A.h0c = h0c; A.t = t; A.C = C;
-        if (ev) hipEventRecord(ev[2], st);
-        return czt_launch_one(A, d.hds, dv, dn, dw, white_stride, st);
-    }
+    A.h0 = pass == 0 ? h0 : nullptr; A.h0c = h0c; A.t = t; A.C = C;
+    A.in = d.TT; A.in_ld = N + 1; A.in_plane = (long long)N * (N + 1);
+    A.rows = pass == 0 ? N + 1 : N;
+    if (pass == 0) { A.out = d.TT; A.out_ld = N + 1; A.out_plane = (long long)N * (N + 1); }
+    else { A.out = d.O; A.out_ld = N; A.out_plane = (long long)N * N; }
+    return A;
+}
+// one chirp-z step: plan, events, arguments, launches.  ev (measurement hook): ev[0], ev[1] before the k_czt launches (the spectrum is
+// formed inside the first one), ev[2] in front of the launch that assembles
+static inline mw_status czt_evaluate(DirectState& d, const OceanConsts& C, const cf* h0, const cf* h0c, float t, float* dv, float* dn, float* dw,
+                                     int white_stride, hipStream_t st, hipEvent_t* ev) {
+    const CztPlan plan = czt_plan(d, C.N);
     hipError_t e = hipSuccess;
-    for (int pass = 0; pass < 2 && e == hipSuccess; pass++) {
-        // along j: rows i = 0 .. N formed from the spectrum -> TT[p][b][i] (N rows of N + 1); along i: rows b -> O[p][a][b]
-        A.in = z.TT;
-        A.out = pass == 0 ? z.TT : z.O;
-        A.h0 = pass == 0 ? h0 : nullptr; A.h0c = h0c; A.t = t; A.C = C;
-        A.rows = pass == 0 ? N + 1 : N;
-        A.in_ld = N + 1; A.in_plane = (long long)N * (N + 1);
-        A.out_ld = pass == 0 ? N + 1 : N; A.out_plane = pass == 0 ? (long long)N * (N + 1) : (long long)N * N;
-        if (pass == 1 && fused) {  // small grids: the second axis and the assembly in one launch, no plane O
+    if (ev) { hipEventRecord(ev[0], st); hipEventRecord(ev[1], st); }
+    if (plan == CZT_PLAN_ONE) {  // tiny grids: both axes and the assembly in one workgroup (k_czt_one)
+        if (ev) hipEventRecord(ev[2], st);
+        return direct_launched(czt_launch_one(czt_args(d, C, h0, h0c, t, 0), d.hds, dv, dn, dw, white_stride, st));
+    }
+    for (int pass = 0; pass < 2; pass++) {
+        const CztArgs A = czt_args(d, C, h0, h0c, t, pass);
+        if (pass == 1 && plan == CZT_PLAN_TWO) {  // small grids: the second axis and the assembly in one launch, no plane O
             if (ev) hipEventRecord(ev[2], st);
-            switch (z.M) {
-                case 64: return czt_launch_rows_assemble<64>(A, d.hds, dv, dn, dw, white_stride, st);
-                case 128: return czt_launch_rows_assemble<128>(A, d.hds, dv, dn, dw, white_stride, st);
-                default: return czt_launch_rows_assemble<256>(A, d.hds, dv, dn, dw, white_stride, st);
-            }
+            MW_FOR_SIZE(d.M, return fail(MW_EINVAL, "unsupported FFT size"),
+                        if constexpr (NN <= MW_CZT_FUSED_MAX_M) e = czt_launch_rows_assemble<NN>(A, d.hds, dv, dn, dw, white_stride, st);
+                        else return fail(MW_EINVAL, "unsupported FFT size"));
+            return direct_launched(e);
         }
-        switch (z.M) {
-            case 64: e = czt_launch<64>(A, st); break;
-            case 128: e = czt_launch<128>(A, st); break;
-            case 256: e = czt_launch<256>(A, st); break;
-            case 512: e = czt_launch<512>(A, st); break;
-            case 1024: e = czt_launch<1024>(A, st); break;
-            case 2048: e = czt_launch<2048>(A, st); break;
-            case 4096: e = czt_launch<4096>(A, st); break;
-            default: return hipErrorInvalidValue;
-        }
+        MW_FOR_SIZE(d.M, return fail(MW_EINVAL, "unsupported FFT size"), e = czt_launch<NN>(A, st));
+        if (e != hipSuccess) return direct_launched(e);
     }
-    if (e != hipSuccess) return e;
     if (ev) hipEventRecord(ev[2], st);
-    hipLaunchKernelGGL(k_czt_assemble_white, dim3(nb), dim3(128), 0, st, C, z.O, d.hds, dv, dn, dw, white_stride);
-    return hipGetLastError();
+    const unsigned nb = (unsigned)(((size_t)C.N * C.N + 127) / 128);
+    hipLaunchKernelGGL(k_czt_assemble_white, dim3(nb), dim3(128), 0, st, C, d.O, d.hds, dv, dn, dw, white_stride);
+    return direct_launched(hipGetLastError());
 }
-
-static inline void direct_free(DirectState& d) {
-    hipFree(d.A1); hipFree(d.T); hipFree(d.B1re); hipFree(d.B1im); hipFree(d.A2re); hipFree(d.A2im); hipFree(d.out); hipFree(d.hds);
-    czt_free(d.czt);
-    d = DirectState();
-}
-static inline int direct_alloc(DirectState& d, int N, hipStream_t st) {
-    // The chirp-z form is the default wherever one workgroup holds the transform (N + 1 inputs, N outputs: 2N <= 4096): first hardware
-    // run in round 4 -- 2.4x (N = 100) to 5.8x (N = 1000) faster than the GEMM form and an order of magnitude more accurate on
-    // grids with large phases (profiles/r04a_bench_direct_*).  MW_DIRECT_CZT=0 selects the GEMM form (A/B, and the path of larger N).
-    if (sw(SW_DIRECT_CZT) != 0 && czt_size(N) != 0) {
-        if (czt_alloc(d.czt, N) != 0 || hipMalloc((void**)&d.hds, sizeof(cf) * (size_t)N * N) != hipSuccess) { direct_free(d); return 4; }
-        d.N = N;
-        d.use_czt = true;
-        return 0;
-    }
-    d.Np = (N + 63) / 64 * 64;
-    const size_t P2 = (size_t)d.Np * d.Np;
-    struct { float** p; size_t n; } bufs[] = {{&d.A1, 10 * P2}, {&d.T, 10 * P2}, {&d.B1re, 2 * P2}, {&d.B1im, 2 * P2},
-                                              {&d.A2re, 2 * P2}, {&d.A2im, 2 * P2}, {&d.out, 5 * P2}};
-    for (auto& b : bufs) {
-        if (hipMalloc((void**)b.p, sizeof(float) * b.n) != hipSuccess) { direct_free(d); return 4; }
-        // the zero padding, ordered on the handle's stream: the table / spectrum kernels that fill the live part run there later
-        // (a null-stream hipMemset is not ordered with a non-blocking stream)
-        if (hipMemsetAsync(*b.p, 0, sizeof(float) * b.n, st) != hipSuccess) { direct_free(d); return 4; }
-    }
-    if (hipMalloc((void**)&d.hds, sizeof(cf) * (size_t)N * N) != hipSuccess) { direct_free(d); return 4; }
-    d.N = N;
-    return 0;
-}
-// tables that depend on (unit_width, length) but not on t: built when the handle is created and when its length changes
-static inline hipError_t direct_prepare_tables(DirectState& d, int N, float unit_width, float length, float gravity, hipStream_t st) {
-    if (d.use_czt) return czt_upload_tables(d.czt, N, unit_width, length, gravity, st);
-    return hipSuccess;  // GEMM form: k_direct_tables runs on the stream, inside the first enqueue after a change (asynchronous)
-}
-// flop of one step as the GEMMs execute it (padded), and algorithmically (60 N^3)
-static inline double direct_flops_padded(const DirectState& d) { return 60.0 * (double)d.Np * d.Np * d.Np; }
 
 static inline hipError_t direct_gemm(const float* A, const float* B, float* C, int M, int Nc, int K, int lda, int ldb, int ldc,
                                      long long sA, long long sB, long long sC, int batch, hipStream_t st) {
@@ -697,32 +681,28 @@ static inline hipError_t direct_gemm(const float* A, const float* B, float* C, i
     return hipGetLastError();
 }
 
-// ev (measurement hook, mw_ocean_profile_kernels): three events recorded before the spectrum kernel, before and after the GEMMs
-static inline hipError_t direct_evaluate(DirectState& d, OceanConsts C, const cf* h0, const cf* h0c, float t, float* dv,
-                                         float* dn, float* dw, int white_stride, hipStream_t st, hipEvent_t* ev = nullptr) {
+// One step of the spectrum (h0, h0c) at time t into (dv, dn, dw) and d.hds, on st, from the tables direct_tables built for C.
+// ev (measurement hook, mw_ocean_profile_kernels): three events -- GEMM form: before the spectrum kernel, before and after the GEMMs
+static inline mw_status direct_evaluate(DirectState& d, const OceanConsts& C, const cf* h0, const cf* h0c, float t, float* dv, float* dn,
+                                        float* dw, int white_stride, hipStream_t st, hipEvent_t* ev = nullptr) {
     if (d.use_czt) return czt_evaluate(d, C, h0, h0c, t, dv, dn, dw, white_stride, st, ev);
     const int N = C.N, Np = d.Np;
     const unsigned nb = (unsigned)(((size_t)N * N + 127) / 128);
     const long long P2 = (long long)Np * Np;
-    if (d.table_length != C.length || d.table_unit_width != C.unit_width) {  // E does not depend on t: once per handle / length
-        hipLaunchKernelGGL(k_direct_tables, dim3(nb), dim3(128), 0, st, N, Np, C.length, C.unit_width, d.B1re, d.B1im, d.A2re, d.A2im);
-        d.table_length = C.length;
-        d.table_unit_width = C.unit_width;
-    }
     if (ev) hipEventRecord(ev[0], st);
     hipLaunchKernelGGL(k_direct_spec, dim3(nb), dim3(128), 0, st, C, Np, h0, h0c, t, d.A1);
     if (ev) hipEventRecord(ev[1], st);
     hipError_t e;
     // step 1: Tr_f = A1_f B1re, Ti_f = A1_f B1im   (5 fields per launch; T_f = [Tr_f ; Ti_f])
-    if ((e = direct_gemm(d.A1, d.B1re, d.T, Np, Np, 2 * Np, 2 * Np, Np, Np, 2 * P2, 0, 2 * P2, 5, st)) != hipSuccess) return e;
-    if ((e = direct_gemm(d.A1, d.B1im, d.T + P2, Np, Np, 2 * Np, 2 * Np, Np, Np, 2 * P2, 0, 2 * P2, 5, st)) != hipSuccess) return e;
+    if ((e = direct_gemm(d.A1, d.B1re, d.T, Np, Np, 2 * Np, 2 * Np, Np, Np, 2 * P2, 0, 2 * P2, 5, st)) != hipSuccess) return direct_launched(e);
+    if ((e = direct_gemm(d.A1, d.B1im, d.T + P2, Np, Np, 2 * Np, 2 * Np, Np, Np, 2 * P2, 0, 2 * P2, 5, st)) != hipSuccess) return direct_launched(e);
     // step 2: H = A2re T_0;  Dx, Dz, Sx, Sz = A2im T_1..4
-    if ((e = direct_gemm(d.A2re, d.T, d.out, Np, Np, 2 * Np, 2 * Np, Np, Np, 0, 0, 0, 1, st)) != hipSuccess) return e;
-    if ((e = direct_gemm(d.A2im, d.T + 2 * P2, d.out + P2, Np, Np, 2 * Np, 2 * Np, Np, Np, 0, 2 * P2, P2, 4, st)) != hipSuccess) return e;
+    if ((e = direct_gemm(d.A2re, d.T, d.out, Np, Np, 2 * Np, 2 * Np, Np, Np, 0, 0, 0, 1, st)) != hipSuccess) return direct_launched(e);
+    if ((e = direct_gemm(d.A2im, d.T + 2 * P2, d.out + P2, Np, Np, 2 * Np, 2 * Np, Np, Np, 0, 2 * P2, P2, 4, st)) != hipSuccess) return direct_launched(e);
     if (ev) hipEventRecord(ev[2], st);
     hipLaunchKernelGGL(k_direct_assemble, dim3(nb), dim3(128), 0, st, C, Np, d.out, d.hds, dv, dn);
     hipLaunchKernelGGL(k_direct_white, dim3(nb), dim3(128), 0, st, N, d.hds, dn, dw, white_stride);
-    return hipGetLastError();
+    return direct_launched(hipGetLastError());
 }
 #endif
 

@@ -618,6 +618,34 @@ static mw_status fm_create(FmState& f, const mw_params& p, int N, bool use_fft, 
     if (hipGetLastError() != hipSuccess) return fail(MW_EDEVICE, "k_spectrum launch failed");
     return use_fft ? fm_prep(f.sp, N, p.length, p.gravity, f.Wpre, st) : MW_OK;
 }
+// mw_ocean_reinit_spectrum on FFTMesh, transactional: the new spectrum is generated into buffers of its own and what is derived from it and
+// from the length is rebuilt from there -- the prep tables (FFT path), the direct-sum tables d of the new length (otherwise; here and
+// not inside the next enqueue).  The handle adopts the new buffers and frees the old ones only once every step has succeeded; otherwise
+// it keeps the old spectrum and puts the tables of the old length p.length back.  No staging in `scratch`: another host entry point
+// cannot clobber the new spectrum half-way.
+static mw_status fm_reinit(FmState& f, DirectState& d, const mw_params& p, int N, bool use_fft, float length, float wind_x, float wind_y,
+                           float amplitude, uint64_t seed, hipStream_t st) {
+    const size_t NN = (size_t)N * N;
+    cf *n0 = nullptr, *n0c = nullptr, *old0 = f.sp.h0, *old0c = f.sp.h0c;
+    mw_status s = dmalloc(&n0, NN);
+    if (s == MW_OK) s = dmalloc(&n0c, NN);
+    if (s != MW_OK) { hipFree(n0); hipFree(n0c); return s; }
+    auto tables = [&](float len) { return use_fft ? fm_prep(f.sp, N, len, p.gravity, f.Wpre, st) : direct_tables(d, N, p.unit_width, len, p.gravity, st); };
+    hipLaunchKernelGGL(k_spectrum, dim3((unsigned)((NN + 255) / 256)), dim3(256), 0, st, N, length, wind_x, wind_y, amplitude, p.gravity, seed, n0, n0c);
+    hipError_t e = hipGetLastError();
+    f.sp.h0 = n0; f.sp.h0c = n0c;
+    if (e == hipSuccess && use_fft) s = tables(length);
+    if (e == hipSuccess && s == MW_OK) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) s = fail(MW_EDEVICE, std::string("mw_ocean_reinit_spectrum: ") + hipGetErrorString(e));
+    if (s == MW_OK && !use_fft) s = tables(length);
+    if (s == MW_OK) { hipFree(old0); hipFree(old0c); return MW_OK; }
+    const std::string why = g_err;  // (the way back may fail() as well: if the device is gone, the handle is too)
+    f.sp.h0 = old0; f.sp.h0c = old0c;
+    (void)tables(p.length);
+    (void)hipStreamSynchronize(st);
+    hipFree(n0); hipFree(n0c);
+    return fail(s, why);
+}
 // the exchange buffers hold nsteps steps afterwards; growing waits for the work on st that may still read the old ones
 static mw_status ensure_exchange(FmState& f, int N, int nsteps, hipStream_t st) {
     if (f.e_cap >= nsteps) return MW_OK;

@@ -305,10 +305,8 @@ static mw_status ocean_create_impl(const mw_params* params, int tiles, mw_ocean*
         // FFT path precondition: power of two and unit_width == length / N exactly.
         o->use_fft = is_pow2(N) && N >= 64 && (params->unit_width * (float)N == params->length);
         if (N > 4096) s = fail(MW_EINVAL, "FFTMesh: resolution > 4096 unsupported");
-        else if (!o->use_fft && direct_alloc(o->direct, N, o->stream) != 0) s = fail(MW_ENOMEM, "direct path alloc failed");
-        else if (!o->use_fft && direct_prepare_tables(o->direct, N, params->unit_width, params->length, params->gravity, o->stream) != hipSuccess)
-            s = fail(MW_EDEVICE, "direct path: chirp tables could not be uploaded");
-        else s = fm_create(o->fm, *params, N, o->use_fft, o->stream);
+        else if (o->use_fft || (s = direct_create(o->direct, N, params->unit_width, params->length, params->gravity, o->stream)) == MW_OK)
+            s = fm_create(o->fm, *params, N, o->use_fft, o->stream);
     } else {
         const int M = params->resolution * 8;  // S/OceanRenderer.cs:136
         o->N = M;
@@ -437,45 +435,16 @@ mw_status mw_ocean_reinit_spectrum(mw_ocean* o, float length, float wind_x, floa
     if (!(length > 0.f)) return fail(MW_EINVAL, "mw_ocean_reinit_spectrum: length must be positive");
     HIP_TRY(hipSetDevice(o->device));
     frame_spectrum_changed(o, false);  // new spectrum and dispersion; the phase textures stay
+    mw_status s;
     if (o->sem == MW_SEM_OCEANRENDERER) {  // S/OceanRenderer.cs:98-109: RenderInitial() again, phase textures untouched
-        mw_status s = or_reinit(o->orr, length, wind_x, wind_y, amplitude, seed, o->stream);
-        if (s != MW_OK) return s;
+        s = or_reinit(o->orr, length, wind_x, wind_y, amplitude, seed, o->stream);
     } else {
-        const int N = o->N;
-        const bool fft = is_pow2(N) && N >= 64 && (o->p.unit_width * (float)N == length);
-        if (fft != o->use_fft)
+        if ((is_pow2(o->N) && o->N >= 64 && (o->p.unit_width * (float)o->N == length)) != o->use_fft)
             return fail(MW_ESTATE, "mw_ocean_reinit_spectrum: the new length moves the grid between the FFT and the direct-sum path; "
                                    "create a new handle");
-        const size_t NN = (size_t)N * N;
-        // Transactional: the new spectrum is generated into buffers of its own and the derived tables (PQt, omega) are rebuilt
-        // from there; the handle adopts the new buffers only once every step has succeeded (and frees the old ones), otherwise
-        // it keeps the old spectrum and rebuilds the tables from it with the old length.  No staging in `scratch`: another host
-        // entry point cannot clobber the new spectrum half-way.
-        cf *n0 = nullptr, *n0c = nullptr;
-        mw_status s = dmalloc(&n0, NN);
-        if (s == MW_OK) s = dmalloc(&n0c, NN);
-        if (s != MW_OK) { hipFree(n0); hipFree(n0c); return s; }
-        hipLaunchKernelGGL(k_spectrum, dim3((unsigned)((NN + 255) / 256)), dim3(256), 0, o->stream, N, length, wind_x, wind_y,
-                           amplitude, o->p.gravity, seed, n0, n0c);
-        hipError_t e = hipGetLastError();
-        const float old_length = o->p.length;
-        cf *old0 = o->fm.sp.h0, *old0c = o->fm.sp.h0c;
-        o->p.length = length;  // run_prep reads it (omega table, S/FFTMesh.cs:141-147)
-        o->fm.sp.h0 = n0; o->fm.sp.h0c = n0c;
-        if (e == hipSuccess) s = run_prep(o);
-        if (s == MW_OK && e == hipSuccess) e = hipStreamSynchronize(o->stream);
-        if (s == MW_OK && e == hipSuccess && !o->use_fft && length != old_length)  // chirp tables of the new length, here and not inside the next enqueue
-            e = direct_prepare_tables(o->direct, N, o->p.unit_width, length, o->p.gravity, o->stream);
-        if (s != MW_OK || e != hipSuccess) {
-            o->fm.sp.h0 = old0; o->fm.sp.h0c = old0c;
-            o->p.length = old_length;
-            (void)run_prep(o);  // tables back to (old spectrum, old length); if the device is gone, the handle is too (MW_EDEVICE)
-            (void)hipStreamSynchronize(o->stream);
-            hipFree(n0); hipFree(n0c);
-            return s != MW_OK ? s : fail(MW_EDEVICE, std::string("mw_ocean_reinit_spectrum: ") + hipGetErrorString(e));
-        }
-        hipFree(old0); hipFree(old0c);
+        s = fm_reinit(o->fm, o->direct, o->p, o->N, o->use_fft, length, wind_x, wind_y, amplitude, seed, o->stream);
     }
+    if (s != MW_OK) return s;
     o->p.length = length; o->p.wind_x = wind_x; o->p.wind_y = wind_y; o->p.amplitude = amplitude; o->p.seed = seed;
     HIP_TRY(hipStreamSynchronize(o->stream));
     return MW_OK;
@@ -568,7 +537,7 @@ mw_status mw_ocean_evaluate_device(mw_ocean* o, const float* t, int32_t nsteps, 
     const int white_stride = (flags & MW_OUT_COLOR_RGBA) ? 4 : 1;
     if (!o->use_fft)
         return direct_evaluate(o->direct, consts_of(o), o->fm.sp.h0, o->fm.sp.h0c, t[0], (float*)d_vertices, (float*)d_normals, (float*)d_white,
-                               white_stride, o->stream) == hipSuccess ? MW_OK : fail(MW_EDEVICE, "direct-sum kernels failed to launch");
+                               white_stride, o->stream);
     return fm_evaluate(o->fm, o->fm.sp, consts_of(o), t, nsteps, (float*)d_vertices, (float*)d_normals, (float*)d_white, white_stride, o->stream);
 }
 
@@ -829,7 +798,7 @@ static mw_status profile_direct(mw_ocean* o, int nsteps, int iters, KernelTimes&
     static const char* onames[2] = {"(no separate launch)", "k_czt_one (both axes + vertices, normals, whitecap: one workgroup, one launch)"};
     kt.n = 2; kt.names = gnames;
     if (o->direct.use_czt) {  // the names follow the plan czt_evaluate runs (czt_plan: the one place that decides)
-        const CztPlan plan = czt_plan(o->direct.czt, o->N);
+        const CztPlan plan = czt_plan(o->direct, o->N);
         kt.names = plan == CZT_PLAN_ONE ? onames : (plan == CZT_PLAN_TWO ? fnames : znames);
     }
     FmState& f = o->fm;
@@ -838,10 +807,10 @@ static mw_status profile_direct(mw_ocean* o, int nsteps, int iters, KernelTimes&
     };
     Events ev(4);
     frame_fftmesh_overwritten(o);  // by the launches below (whitecap scalar, stride 1)
-    hipError_t he = hipSuccess;
-    for (int w = 0; w < 5 && he == hipSuccess; w++) he = call(1.0f, nullptr);
-    for (int it = 0; it < iters && he == hipSuccess; it++) {
-        he = call(1.0f + (float)it / 60.f, &ev[0]);
+    mw_status s = MW_OK;
+    for (int w = 0; w < 5 && s == MW_OK; w++) s = call(1.0f, nullptr);
+    for (int it = 0; it < iters && s == MW_OK; it++) {
+        s = call(1.0f + (float)it / 60.f, &ev[0]);
         hipEventRecord(ev[3], o->stream);
         hipEventSynchronize(ev[3]);
         float d[3] = {0.f, 0.f, 0.f};
@@ -849,7 +818,7 @@ static mw_status profile_direct(mw_ocean* o, int nsteps, int iters, KernelTimes&
         const float m[2] = {d[1], d[0] + d[2]};
         kt.add(m);
     }
-    if (he != hipSuccess) return fail(MW_EDEVICE, std::string("direct-sum profile: ") + hipGetErrorString(he));
+    if (s != MW_OK) return s;
     frame_fftmesh_made(o, 1.0f + (float)(iters - 1) / 60.f, 1);  // the chirp-z / direct kernels above wrote the host-API frame
     return MW_OK;
 }

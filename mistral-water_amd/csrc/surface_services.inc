@@ -128,8 +128,7 @@ static mw_status velocity_run(mw_ocean* o, float* d_vel) {
     OceanConsts C = consts_of(o);
     C.choppiness = o->fm.s_chop;  // the frame's choppiness (mw_ocean_set_choppiness may have changed it since)
     if (!o->use_fft) {
-        if (direct_evaluate(o->direct, C, v.sp.h0, v.sp.h0c, o->fm.s_t, d_vel, v.norm, v.white, 1, o->stream) != hipSuccess)
-            return fail(MW_EDEVICE, "velocity: direct-sum kernels failed to launch");
+        if ((s = direct_evaluate(o->direct, C, v.sp.h0, v.sp.h0c, o->fm.s_t, d_vel, v.norm, v.white, 1, o->stream)) != MW_OK) return s;
         hipLaunchKernelGGL(k_velocity_from_hds, dim3(nb), dim3(256), 0, o->stream, N, C.choppiness, o->direct.hds, d_vel);
         HIP_TRY(hipGetLastError());
         return MW_OK;

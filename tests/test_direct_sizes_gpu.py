@@ -1,7 +1,7 @@
 """GPU tier: the separable direct sum (csrc/czt_kernels.h, csrc/direct_kernels.h) on the non-FFT grids users reach most easily --
 every size above 2048 and every power of two whose length is not N * unit_width -- at the sizes where its two forms change shape.
 
-direct_alloc picks the form.  Chirp-z runs where czt_size(N) != 0: the packed planes carry N + 1 inputs and N outputs per line, so the
+direct_create picks the form.  Chirp-z runs where czt_size(N) != 0: the packed planes carry N + 1 inputs and N outputs per line, so the
 cyclic convolution needs 2N lags and the transform size is M = the next power of two >= 2N (64 ... 4096, N <= 2048).  Two kinds of
 grid sit at its edges:
   * N = 256, 512, 1024, 2048 with an incommensurate length: 2N = M, the convolution is exactly full (the largest negative lag -N wraps
@@ -152,9 +152,9 @@ def test_surface_query_on_a_gemm_grid(mw, oracle):
 
 
 def test_reinit_spectrum_with_a_new_length_on_a_gemm_handle(mw, oracle):
-    """The GEMM form's E tables depend on (unit_width, length) and are rebuilt inside the first enqueue after a length change (the
-    table_length check of direct_evaluate).  After evaluate, reinit_spectrum(length = ...), evaluate the handle must be the handle a fresh
-    create with the new parameters gives, bit for bit, and match the oracle at the new length and spectrum."""
+    """The GEMM form's E tables depend on (unit_width, length) and are rebuilt by reinit_spectrum when the length changes (direct_tables,
+    on the handle's stream; no enqueue builds tables).  After evaluate, reinit_spectrum(length = ...), evaluate the handle must be the
+    handle a fresh create with the new parameters gives, bit for bit, and match the oracle at the new length and spectrum."""
     old = _params(oracle, 2049, 2049.0)
     L = 2300.0
     new = dataclasses.replace(old, length=L, wind_x=-3.0, wind_y=6.0, amplitude=1.5e-8 * (1024.0 / 2049) ** 2 * (L / 2049) ** 2)
@@ -170,3 +170,36 @@ def test_reinit_spectrum_with_a_new_length_on_a_gemm_handle(mw, oracle):
     assert (h0 == g0).all() and (h0c == g0c).all()
     assert all((x == y).all() for x, y in zip(a, b)), "reinit + evaluate must equal create + evaluate"
     _check_frame(oracle, new, a, h0, h0c, 1.25, "GEMM reinit N=2049")
+
+
+# (N, unit_width, length, amplitude, MW_DIRECT_CZT, kernel of the plan): the grids, winds and amplitudes of test_both_forms_of_the_direct_sum
+REINIT = [(12, 1.0, 12.39, 0.01, 1, "k_czt_one"),                # chirp-z, one launch
+          (65, 0.5, 40.0, 1e-5, 1, "k_czt_rows_assemble"),       # chirp-z, M = 256, two launches
+          (65, 0.5, 40.0, 1e-5, 0, GEMM_NAME)]                   # GEMM at Np = 128: two tiles per axis, 63 padding lines
+
+
+@pytest.mark.parametrize("N,u,L,amp,czt,kernel", REINIT, ids=["chirp-z-one-12", "chirp-z-two-65", "gemm-65"])
+def test_reinit_before_the_first_frame_on_both_forms(mw, oracle, N, u, L, amp, czt, kernel):
+    """The tables of both forms are built when the handle is created and replaced by reinit_spectrum, never by an enqueue (direct_tables).
+    A handle whose length changes before its first frame -- the tables of creation never used -- must then be the handle a fresh create
+    with the new length gives: spectrum, frame and velocity bit for bit, on the plan expected.  A handle at the original length is held
+    to the f64 oracle at the direct paths' 2e-5 first, so that what is compared bit for bit is a frame of the right sea."""
+    p = oracle.Params(N=N, unit_width=u, length=L, wind_x=5.0, wind_y=3.0, amplitude=amp, choppiness=0.8)
+    new = dataclasses.replace(p, length=1.3 * L)
+    try:
+        mw.set_switch("MW_DIRECT_CZT", czt)      # read when a handle is created
+        with _ocean(mw, p) as o:
+            h0, h0c = o.get_spectrum()
+            _check_frame(oracle, p, o.evaluate(1.25), h0, h0c, 1.25, f"reinit N={N} czt={czt} original length")
+        with _ocean(mw, p) as o:
+            o.reinit_spectrum(length=new.length, seed=9)      # no frame since creation
+            a = o.get_spectrum() + o.evaluate(1.25) + (o.velocity(),)
+            assert any(kernel in k for k in _plan(o)), kernel
+        with _ocean(mw, new, seed=9) as f:
+            b = f.get_spectrum() + f.evaluate(1.25) + (f.velocity(),)
+            assert any(kernel in k for k in _plan(f)), kernel
+    finally:
+        mw.set_switch("MW_DIRECT_CZT", 1)
+    assert len(a) == 6 and all(np.isfinite(x).all() for x in a) and np.abs(a[5]).max() > 0
+    for name, x, y in zip(("h0", "h0conj", "vertices", "normals", "colours", "velocity"), a, b):
+        assert (x == y).all(), f"reinit + evaluate differs from create + evaluate in {name}"
