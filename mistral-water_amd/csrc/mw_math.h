@@ -82,11 +82,14 @@ MW_HD float sdiv(float a, float b) {
 }
 MW_HD float ssqrt(float a) { return sqrtf(a); }
 
-// ---- sin/cos of a float32 phase, |x| <~ 1e5 rad ---------------------------------------------------
+// ---- sin/cos of a float32 phase ---------------------------------------------------------------------
+// Domains (tests/test_device_math_cpu.py, tests/test_device_math_gpu.py): sincos_f32 |x| <= 1e5 rad; sincos_fast_f32 |x| <= 5e5 rad at
+// its stated error (omega*t of the 256^2 test grid after a day reaches 5.7e5 rad and stays inside it), degrading slowly up to 2^23 revolutions (5.3e7 rad) and no reduction at all above.
 // The reference forms cos/sin of the FLOAT omega*t through double libm (Mathf.Cos, S/FFTMesh.cs:184-185).
 // Here: 3-term Cody-Waite reduction by pi/2 carried in FMAs (exact for |k| < 2^17) + the classic
 // degree-7/8 minimax polynomials on [-pi/4, pi/4]; absolute error <= ~1.5e-7 (about 1 ulp of a result
 // near 1), identical code on host (emulation) and device.  ~25 VALU ops, no branches, 6 live registers.
+// The reference form kept for the mw_debug_sincos hook, which pins it bit for bit against the host build: no longer the kernels' sine.
 MW_HD void sincos_f32(float x, float* sn, float* cs) {
     const float k = rintf(x * 0.63661977236758134308f);  // 2/pi
     float r = fmaf(-k, 1.5703125f, x);                    // pi/2 = 1.5703125 + 4.837512969970703125e-4 + 7.5497899e-8
@@ -106,18 +109,30 @@ MW_HD void sincos_f32(float x, float* sn, float* cs) {
     *cs = ((q + 1) & 2) ? -c0 : c0;
 }
 
-// sin/cos through the hardware's v_sin_f32 / v_cos_f32 (argument in revolutions, quarter-rate, ~1e-6 absolute) after a
-// two-constant reduction that keeps the revolution count exact: p = x/2pi rounded, e = the rounding error of that
-// product recovered by FMA plus the low part of 1/2pi, r = (p - rint(p)) + e in [-0.5, 0.5].  10 VALU issue slots
-// against ~25 for sincos_f32: used where a kernel is VALU-bound and 1e-6 is inside its stated tolerance (the pond: eight
-// sincos per vertex against 24 B).  The host (emulation) evaluates sin(2 pi r) in double: same r, correctly rounded
-// result -- host and device agree to the hardware's error, not bit for bit.
-MW_HD void sincos_fast_f32(float x, float* sn, float* cs) {
+// sin/cos through the hardware's v_sin_f32 / v_cos_f32 (argument in revolutions, quarter-rate) after a two-constant reduction that keeps
+// the revolution count exact: p = x/2pi rounded, e = the rounding error of that product recovered by FMA plus the low part of 1/2pi,
+// r = (p - rint(p)) + e.  r is NOT confined to [-0.5, 0.5]: p carries its own rounding error into rint, so near half revolutions r lands
+// just past +-0.5 (|r| reaches 0.507 for |x| <= 5e5 rad, 0.63 at 1e7) and the instruction is relied on slightly outside one revolution
+// centred on zero.  Error for |x| <= 5e5 rad, absolute, against float64 of the float32 argument:
+//   reduction alone (derived; reproduced on the host): the final rounding of r, 2 pi 2^-25 = 1.87e-7 in sin (|r| >= 0.5, where sin is
+//     steepest) and 2 pi 2^-26 = 9.4e-8 in cos; asserted as 1.9e-7 / 1.0e-7
+//   v_sin_f32 / v_cos_f32 on top of it (measured on an MI355X over r in [-0.5, 0.5]): 1.244e-7 / 1.191e-7 (no larger on the arguments that
+//     put r past +-0.5); the tests assert 1.5 x that, 1.866e-7 / 1.787e-7
+//   together at most 3.77e-7 (sin) / 2.79e-7 (cos) -- the largest total measured is 1.99e-7 / 1.77e-7; every consumer's tolerance is written against the looser 1e-6, which the tests hold as a
+//     hard cap.
+// Above 2^23 revolutions p has no fraction bits, rint(p) = p and r is the error term alone (|r| up to 14 at 1e9 rad).
+// 10 VALU issue slots against ~25 for sincos_f32: used where a kernel is VALU-bound (the pond: eight sincos per vertex against 24 B).
+// The host (emulation) evaluates sin(2 pi r) in double: same r, correctly rounded result -- host and device agree to the hardware's
+// error, not bit for bit.
+MW_HD float revolution_fraction_f32(float x) {  // the reduction alone: what tests/emul hands to the tests as the host's r
     const float hi = 0.15915494f, lo = 6.4206382e-09f;  // 1/(2 pi) = hi + lo (hi = the f32 nearest, lo = the rest)
     const float p = smul(x, hi);  // the ROUNDED product (a contracted x*hi - rint(p) would count its error twice)
     float e = fmaf(x, hi, -p);
     e = fmaf(x, lo, e);
-    const float r = sadd(ssub(p, rintf(p)), e);
+    return sadd(ssub(p, rintf(p)), e);
+}
+MW_HD void sincos_fast_f32(float x, float* sn, float* cs) {
+    const float r = revolution_fraction_f32(x);
 #if defined(__HIP_DEVICE_COMPILE__)
     *sn = __builtin_amdgcn_sinf(r);
     *cs = __builtin_amdgcn_cosf(r);

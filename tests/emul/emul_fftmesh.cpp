@@ -516,6 +516,19 @@ void emul_omega_t(int N, float length, float gravity, float t, float* out) {
     for (int i = 0; i < N; i++)
         for (int j = 0; j < N; j++) out[i * N + j] = omega_t_f32(N, length, gravity, i, j, t);
 }
+// the host build of the kernels' sine/cosine (mw_math.h): fast = 1 -> sincos_fast_f32 (what mw_sincos / mw_sincos_fast run) and, in
+// r_out (may be NULL), the revolution fraction its reduction hands to v_sin_f32 / v_cos_f32; fast = 0 -> the polynomial sincos_f32
+// (r_out untouched)
+void emul_sincos(const float* x, long n, float* s, float* c, float* r_out, int fast) {
+    for (long i = 0; i < n; i++) {
+        if (fast) {
+            sincos_fast_f32(x[i], &s[i], &c[i]);
+            if (r_out) r_out[i] = revolution_fraction_f32(x[i]);
+        } else {
+            sincos_f32(x[i], &s[i], &c[i]);
+        }
+    }
+}
 
 void emul_gerstner(const float* pos, long nverts, const float* waves, int nwaves, float amplitude, float frequency,
                    float steepness, float t, float* out) {

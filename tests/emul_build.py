@@ -87,6 +87,15 @@ class Emul:
         self.L.emul_omega_t(p.N, C.c_float(p.length), C.c_float(p.gravity), C.c_float(t), _p(out))
         return out
 
+    def sincos(self, x, fast=True):
+        """The host build of mw_math.h's sine/cosine on float32 x -> (sin, cos, r): fast=True is sincos_fast_f32 with r the revolution
+        fraction of its reduction (revolution_fraction_f32); fast=False is the polynomial sincos_f32 (finite x only), r is None."""
+        x = np.ascontiguousarray(x, np.float32)
+        s, c = np.empty_like(x), np.empty_like(x)
+        r = np.empty_like(x) if fast else None
+        self.L.emul_sincos(_p(x), C.c_long(x.size), _p(s), _p(c), _p(r) if fast else None, 1 if fast else 0)
+        return s, c, r
+
     def or_init(self, rp, seed):
         M = rp.M
         initT = np.empty((M, M, 4), np.float32)   # [px][py]
