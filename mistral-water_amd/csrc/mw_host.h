@@ -1,5 +1,5 @@
 // mw_host.h -- host-side helpers every part of the library shares (device build only): the error channel behind mw_last_error(), the
-// typed hipMalloc and the one list of transform sizes.  Everything here has internal linkage: nothing joins the library's exported symbols.
+// typed hipMalloc, its scoped form and the one list of transform sizes.  Everything here has internal linkage: nothing joins the library's exported symbols.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,6 +28,17 @@ static mw_status dmalloc(T** p, size_t count) {
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
     return MW_OK;
 }
+// a device allocation of one call (the test hooks): freed on every way out of its scope
+namespace {
+template <typename T>
+struct DevTmp {
+    T* p = nullptr;
+    DevTmp() = default;
+    DevTmp(const DevTmp&) = delete;
+    ~DevTmp() { hipFree(p); }
+    hipError_t alloc(size_t count) { return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)); }
+};
+}  // namespace
 
 // The transform sizes the library has kernels for, named once.  The statement(s) after DEFAULT run with NN a constant expression equal
 // to N_; any other N_ runs DEFAULT (the caller's own message and status).

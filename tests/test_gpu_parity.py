@@ -802,6 +802,34 @@ def test_pond_material_displacement_modes(mw, oracle):
     assert out.shape == (0, 3)
 
 
+def test_pond_staging_buffer_grows_and_is_reused(mw):
+    """The host forms stage in one grow-only buffer per device: 100, then 5000 (the buffer grows when the test runs first in its process;
+    after test_pond_material_displacement_modes, which stages a million vertices, it is only reused), then 100 vertices (the larger buffer
+    is reused), with and without normals (three regions or two) and mw_gerstner_displace calls (two regions of the same buffer) in between.
+    Every result is, bit for bit, the device form's on the same input."""
+    import torch
+    P = workloads.POND
+    mat = mw.PondMaterial(mode=mw.MW_POND_WAVE, **workloads.POND_MATERIAL)
+    st = torch.cuda.current_stream().cuda_stream
+    wv = np.ascontiguousarray(P["waves"], np.float32).reshape(-1, 3)
+    for k, n in enumerate((100, 5000, 100)):
+        pos = workloads.pond_lattice(71, y=0.25, seed=k)[:n]
+        t = 1.5 + k
+        dp = torch.from_numpy(pos).cuda()
+        do, dn, dg = torch.empty_like(dp), torch.empty_like(dp), torch.empty_like(dp)
+        mat.displace_device(dp.data_ptr(), n, t, do.data_ptr(), dn.data_ptr(), st)
+        assert mw.lib().mw_gerstner_displace_device(C.c_void_p(dp.data_ptr()), n, wv.ctypes.data_as(C.c_void_p), wv.shape[0], C.c_float(P["amplitude"]),
+                                                    C.c_float(P["frequency"]), C.c_float(P["steepness"]), C.c_float(t), C.c_void_p(dg.data_ptr()),
+                                                    C.c_void_p(st) if st else None) == mw.MW_OK
+        torch.cuda.synchronize()
+        want_o, want_n, want_g = do.cpu().numpy(), dn.cpu().numpy(), dg.cpu().numpy()
+        for normals in (True, False, True):
+            out, nrm = mat.displace(pos, t, normals=normals)
+            assert (out == want_o).all(), (n, normals)
+            assert (nrm == want_n).all() if normals else nrm is None, (n, normals)
+            assert (mw.gerstner_displace(pos, P["waves"], P["amplitude"], P["frequency"], P["steepness"], t) == want_g).all(), (n, normals)
+
+
 def test_batch_limits_and_empty_inputs(mw, oracle):
     """Maximum batch (32 steps per enqueue) equals single steps; one more is MW_EINVAL; empty pond input is a no-op."""
     import torch

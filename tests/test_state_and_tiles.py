@@ -177,6 +177,44 @@ def test_handles_give_their_device_memory_back(mw):
     assert before - after < (8 << 20), f"{(before - after) / 2**20:.1f} MiB did not come back after 20 create / destroy cycles"
 
 
+@pytest.mark.parametrize("semantics", ["fftmesh", "oceanrenderer"])
+@pytest.mark.parametrize("case", ["second_ordinal_out_of_range", "max_steps_above_the_limit"])
+def test_failed_tile_creation_gives_everything_back(mw, semantics, case):
+    """mw_tiles_create that fails after its first tile stands (the second device ordinal does not exist) or before any (max_steps one above
+    the limit of 32) reports the argument error and leaves nothing behind: the free device memory afterwards is the free memory before
+    (hipMemGetInfo, as in test_handles_give_their_device_memory_back).  Smallest grids: FFTMesh 64, OceanRenderer resolution 8."""
+    import torch
+    hip = C.CDLL("libamdhip64.so")
+    free, total = C.c_size_t(), C.c_size_t()
+
+    def free_bytes():
+        torch.cuda.synchronize()
+        assert hip.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
+        return free.value
+    if semantics == "fftmesh":
+        kw = dict(resolution=64, unit_width=1.0, length=64.0)
+    else:
+        kw = dict(resolution=8, length=27.155, wind=(14.45, 12.0), amplitude=0.41, choppiness=0.46, mult=1.5, semantics=mw.MW_SEM_OCEANRENDERER)
+    if case == "second_ordinal_out_of_range":
+        args, message = dict(ntiles=2, devices=[0, mw.lib().mw_device_count()], max_steps=2), "mw_tiles_create: bad device ordinal"
+    else:
+        args, message = dict(ntiles=2, devices=[0, 0], max_steps=33), "mw_tiles_create: max_steps out of range"
+
+    def fails():
+        with pytest.raises(mw.MistralWaterError) as e:
+            mw.Tiles(seed=3, **args, **kw)
+        assert e.value.status == mw.MW_EINVAL and str(e.value) == "MW_EINVAL: " + message
+    with mw.Tiles(ntiles=1, devices=[0], max_steps=2, seed=3, **kw):   # first use: one-time allocations of the runtime / RCCL itself
+        pass
+    fails()
+    before = free_bytes()
+    for _ in range(8):
+        fails()
+    after = free_bytes()
+    print(f"free device memory: before {before}, after {after}")
+    assert after == before, f"{(before - after) / 2**10:.0f} KiB did not come back after 8 failed mw_tiles_create calls"
+
+
 def test_two_host_threads_drive_two_handles_at_once(mw, oracle):
     """The library keeps no unguarded global state: two host threads (ctypes releases the GIL inside every call), each with its own handle on
     its own stream -- one alternating single steps and 5-step batches on a 512^2 FFT grid, the other stepping a non-FFT grid and the pond's
