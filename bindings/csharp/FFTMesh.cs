@@ -109,6 +109,14 @@ public class FFTMesh : MonoBehaviour
         mesh.colors = colors;
     }
 
+    /// Not in the reference: SampleSurface, hull forces and bodies read the infinite tiling of the mesh (period = resolution * unitWidth)
+    /// instead of the one footprint, so nothing that drifts off the patch is lost.  Throws unless unitWidth * resolution == length and the
+    /// resolution is even; raycasts refuse a periodic handle.
+    public void SetPeriodic(bool on = true)
+    {
+        Native.Check(Native.mw_ocean_set_periodic(ocean, on ? 1 : 0));
+    }
+
     /// Not in the reference: the displaced mesh's surface at horizontal points, xz = {x0, z0, x1, z1, ...} in the mesh's object space;
     /// result (8 floats per point) = position xyz, normal xyz, whitecap, residual.  world = true: xz lies on the displaced surface (the
     /// buoyancy question "how high is the water here?"); false: xz is a rest-plane position (NaN off the mesh).  Surface of the latest Update().

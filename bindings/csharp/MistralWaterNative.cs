@@ -75,6 +75,8 @@ public static class MistralWaterNative
     [DllImport(Lib)] public static extern IntPtr mw_ocean_get_stream(IntPtr ocean);
     [DllImport(Lib)] public static extern Status mw_ocean_synchronize(IntPtr ocean);
     [DllImport(Lib)] public static extern Status mw_ocean_set_choppiness(IntPtr ocean, float choppiness);
+    [DllImport(Lib)] public static extern Status mw_ocean_set_periodic(IntPtr ocean, int on);
+    [DllImport(Lib)] public static extern Status mw_ocean_get_periodic(IntPtr ocean, out int on, out float period);
 
     // ---- spectrum and state -------------------------------------------------------------------------------------
     [DllImport(Lib)] public static extern Status mw_ocean_set_spectrum(IntPtr ocean, Vector2[] h0, Vector2[] h0conj);

@@ -35,7 +35,8 @@ typedef enum {
     MW_OK = 0,
     MW_EINVAL = 1,           /* bad argument / NULL pointer / unsupported resolution */
     MW_ENOTPOW2 = 2,         /* OceanRenderer semantics needs a power-of-two texture size (S/OceanRenderer.cs:231) */
-    MW_ENOTCOMMENSURATE = 3, /* reserved: (unit_width != length/N is served by the direct-sum kernel instead) */
+    MW_ENOTCOMMENSURATE = 3, /* mw_ocean_set_periodic: the grid does not repeat (creation never returns it: unit_width != length/N is
+                                served by the direct-sum kernel instead) */
     MW_ENOMEM = 4,
     MW_EDEVICE = 5,          /* no usable HIP device / HIP runtime error */
     MW_ESTATE = 6            /* call order violation (e.g. evaluate before a spectrum exists) */
@@ -107,6 +108,46 @@ mw_status mw_ocean_synchronize(mw_ocean* o);
 /* choppiness / tDivision / mult may change between frames without regenerating the spectrum
  * (S/FFTMesh.cs:244-245 reads choppiness every frame; S/OceanRenderer.cs:96).                      */
 mw_status mw_ocean_set_choppiness(mw_ocean* o, float choppiness);
+
+/* ---- the periodic surface: the surface services on the infinite tiling of the frame ---------------------------------
+ * An FFTMesh frame on a grid that repeats -- unit_width * (float)N == length in float32 and N even, the chirp-z grids among them
+ * (N = 100, unit_width 1, length 100) -- is periodic with period P = (float)N * unit_width (one float32 multiply).  With the switch
+ * on, mw_ocean_query_surface, mw_ocean_query_velocity, mw_ocean_hull_forces and mw_ocean_step_bodies (host and device forms, both
+ * plans of the bodies) read that tiling instead of the one footprint.  Off by default; with it off every call returns the bits it
+ * always returned.  The switch is not part of the frame record: it needs no new frame and changes no output of mw_ocean_evaluate,
+ * mw_ocean_update or mw_ocean_velocity.
+ *   set_periodic(o, 1): MW_ENOTCOMMENSURATE on any other FFTMesh grid (the shipped N = 12, length 12.39 scene; an odd N, whose
+ *     sum is ANTI-periodic); MW_ESTATE on an OceanRenderer handle -- its mesh samples clamp-addressed textures half a texel inside
+ *     each edge, so vertex res-1 is not the image of vertex 0 and the mesh does not tile; MW_EINVAL on a batched handle, a NULL
+ *     handle, or `on` outside {0, 1}.  set_periodic(o, 0) is always allowed.
+ *   mw_ocean_reinit_spectrum to a length that breaks the condition turns the switch off.
+ *   get_periodic: the switch and P (either out-argument may be NULL); P is reported whether or not the switch is on, 0 where the
+ *     grid does not repeat.
+ * The tiled surface:
+ *   integer grid line g = k*N + a (floor division, 0 <= a < N) rests at rest(g) = rest_coord(a) + (float)k * P; for k = 0 this is
+ *     exactly the rest coordinate of mw_ocean_rest_mesh;
+ *   vertex (gi, gj) is vertex (ai, aj) of the frame displaced by (ki*P, 0, kj*P); its normal, whitecap and velocity are those of
+ *     (ai, aj);
+ *   every integer cell (gi, gj) exists and is split along the same diagonal; cell a = N-1, between the last grid line of a tile and
+ *     the first of the next, is the seam (it is in no index buffer).
+ *   Reduction first: a query (x, z) is reduced to (x', z') = (x - kx*P, z - kz*P) with x', z' in [rest(0), rest(0) + P], answered
+ *     in the frame of the base tile (where the neighbouring tiles sit at +-P, +-2P, ...), and kx*P, kz*P are added to px and pz
+ *     once, at the end.  The answer is a function of (x', z', kx, kz): its precision does not degrade with the distance from the
+ *     origin.  The residual is computed in the base frame.
+ *   MW_QUERY_REST: every finite point has an answer (no NaN off the footprint); a point inside the base footprint returns the same
+ *     8 floats, bit for bit, as with the switch off.
+ *   MW_QUERY_WORLD: the same walk (preconditioned step, 4-cell cap, in-triangle tolerance, best-so-far rule) but unclamped: it
+ *     crosses seams and tile boundaries freely.  Where the non-periodic walk never touches its clamp the periodic one returns the
+ *     same bits; folds still return the visited point of smallest residual.
+ *   Non-finite points, and points whose tile index exceeds 2^20 in magnitude, give NaN in every field (status MW_OK).
+ *   Hull vertices are located one by one, so a hull may straddle a seam; only eta, u and the residual come from the located point.
+ *   Arithmetic: the tiled services run in strict float32 (no fused multiply-adds), so a g++ build of the same functions equals them
+ *     bit for bit, as it does the raycasts; the one-footprint services keep the contracted arithmetic their bits have always come
+ *     from.  The two "same bits" statements above hold between the two forms under one arithmetic; on the device a periodic answer
+ *     inside the base footprint agrees with the switch-off answer to rounding, not bit for bit.
+ * mw_ocean_raycast on a handle with the switch on returns MW_ESTATE: raycasts do not tile yet.                              */
+mw_status mw_ocean_set_periodic(mw_ocean* o, int32_t on);                     /* 0 / 1 */
+mw_status mw_ocean_get_periodic(mw_ocean* o, int32_t* on, float* period);     /* either out-argument may be NULL */
 
 /* Inject / read back verttilde and vertConj (S/FFTMesh.cs:35-36,114-116), N*N*2 floats each,
  * idx = i*N + j.  Injection is how a caller reproduces a Unity-generated spectrum exactly, and

@@ -53,7 +53,10 @@ MW_HD void hull_transform(const float body[16], const float h[3], float x[3]) {
 // The vertex step: one instance vertex -> slab[8] = (x, y, z, d, ux, uy, uz, residual).  eta, u and the residual come from the one
 // sq_locate of the world-mode surface query at (x.x, x.z), accumulated as sq_query_point / sq_velocity_point accumulate them (eta is
 // query_surface's py bit for bit).  vel == nullptr (drag off): u = 0.  A non-finite vertex has no answer: all eight are NaN.
-MW_HD void hull_vertex(const SqMesh& m, const float* vel, float vscale, int iters, const float body[16], const float h[3],
+// Mesh = SqTiled (a periodic handle): every vertex is located on the tiling on its own, so a hull may straddle a seam; x stays the world
+// position, eta and u are those of the located point, the residual is taken in the base tile's frame.
+template <typename Mesh>
+MW_HD void hull_vertex(const Mesh& m, const float* vel, float vscale, int iters, const float body[16], const float h[3],
                        float slab[8]) {
     float x[3];
     hull_transform(body, h, x);
@@ -62,7 +65,7 @@ MW_HD void hull_vertex(const SqMesh& m, const float* vel, float vscale, int iter
         for (int k = 0; k < 8; k++) slab[k] = NAN;
         return;
     }
-    sq_locate(m, MW_SQ_WORLD, x[0], x[2], iters, [&] { for (int k = 0; k < 8; k++) slab[k] = NAN; }, [&](const int v[3], const float w[3]) {
+    sq_locate(m, MW_SQ_WORLD, x[0], x[2], iters, [&] { for (int k = 0; k < 8; k++) slab[k] = NAN; }, [&](const int v[3], const float w[3], const SqTile& t) {
         float eta = 0.f, u[3] = {0.f, 0.f, 0.f};
         for (int k = 0; k < 3; k++) eta += w[k] * m.vert[3 * v[k] + 1];
         if (vel)
@@ -71,7 +74,7 @@ MW_HD void hull_vertex(const SqMesh& m, const float* vel, float vscale, int iter
         slab[0] = x[0]; slab[1] = x[1]; slab[2] = x[2];
         slab[3] = eta - x[1];
         slab[4] = u[0] * vscale; slab[5] = u[1] * vscale; slab[6] = u[2] * vscale;
-        slab[7] = sq_residual(m, v, w, x[0], x[2]);
+        slab[7] = sq_residual(m, v, w, t);
     });
 }
 
@@ -214,8 +217,9 @@ MW_HD void hull_row(const float acc[7], float res, float out[8]) {
 }
 
 #if defined(__HIPCC__)
-struct HullArgs {
-    SqMesh m;
+template <typename Mesh>
+struct HullArgsT {
+    Mesh m;
     const float* vel;  // per-vertex water velocity [R*R][3] (drag on), else nullptr
     float vscale;
     int iters;
@@ -229,6 +233,12 @@ struct HullArgs {
     float4* part;   // [nbodies * nchunks][2]
     float4* out;    // [nbodies][2]
 };
+using HullArgs = HullArgsT<SqMesh>;
+// the same call with its mesh read as the tiling (a periodic handle: the kernels' SqTiled instantiations, surface_tiled.hip)
+inline HullArgsT<SqTiled> hull_args_tiled(const HullArgs& a) {
+    return HullArgsT<SqTiled>{SqTiled{a.m}, a.vel, a.vscale, a.iters, a.cf, a.hull, a.tris, a.bodies, a.nverts, a.ntris, a.nchunks, a.nbodies,
+                              a.vslab, a.part, a.out};
+}
 
 MW_HD void hull_load_body(const float4* b, float body[16]) {
     for (int k = 0; k < 4; k++) {
@@ -239,7 +249,8 @@ MW_HD void hull_load_body(const float4* b, float body[16]) {
 
 // One lane per instance vertex (n = nbodies * nverts < 2^31): the body's 64 B (shared by the lanes of a body: cache hits), the walk's
 // gathers, two 16-byte stores.
-__global__ __launch_bounds__(256) void k_hull_vertices(HullArgs a) {
+template <typename Mesh>
+__global__ __launch_bounds__(256) void k_hull_vertices(HullArgsT<Mesh> a) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.nbodies * a.nverts) return;
     const unsigned b = (unsigned)k / (unsigned)a.nverts;  // k < 2^31
@@ -256,7 +267,8 @@ __global__ __launch_bounds__(256) void k_hull_vertices(HullArgs a) {
 // counted once, referenced or not).  The 8 values are reduced in a fixed order: a shuffle tree inside each wave, then lane 0 adds the
 // four waves' sums in wave order.  Workgroups stride over the chunks (a 1-D grid of at most 2^20 workgroups); each chunk is done by one
 // workgroup start to finish.
-__global__ __launch_bounds__(256) void k_hull_triangles(HullArgs a) {
+template <typename Mesh>
+__global__ __launch_bounds__(256) void k_hull_triangles(HullArgsT<Mesh> a) {
     __shared__ float red[MW_HULL_CHUNK / 64][8];
     const int l = threadIdx.x, lane = l & 63, wave = l >> 6;
     const int64_t total = a.nbodies * a.nchunks;
@@ -299,7 +311,8 @@ __global__ __launch_bounds__(256) void k_hull_triangles(HullArgs a) {
 
 // One wave per body: lane l sums chunks l, l + 64, ... in order, a fixed shuffle tree sums the lanes, lane 0 writes the row.  Waves
 // stride over the bodies (a 1-D grid of at most 2^20 workgroups).
-__global__ __launch_bounds__(256) void k_hull_reduce(HullArgs a) {
+template <typename Mesh>
+__global__ __launch_bounds__(256) void k_hull_reduce(HullArgsT<Mesh> a) {
     const int l = threadIdx.x & 63;
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
     for (int64_t b = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; b < a.nbodies; b += nwaves) {  // wave-uniform

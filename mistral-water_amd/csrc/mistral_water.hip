@@ -32,6 +32,7 @@
 #include "velocity_kernels.h"
 #include "hull_forces.h"
 #include "rigid_bodies.h"
+#include "surface_tiled.h"
 #include "raycast.h"
 static_assert(MW_SQ_REST == MW_QUERY_REST && MW_SQ_WORLD == MW_QUERY_WORLD, "surface_query.h and the ABI name the modes alike");
 
@@ -63,6 +64,7 @@ struct mw_ocean {
     FmState fm;  // FFTMesh state: spectrum, tables, exchange buffers and the host-API frame (fftmesh_device.h)
     int or_steps_tail = -1;  // OceanRenderer: the last frame of the latest steps call while the phase is still that frame's, else -1
     bool frame_behind = false;  // the spectrum or the phase changed after the latest frame was made (mw_ocean_query_velocity refuses)
+    bool periodic = false;      // mw_ocean_set_periodic: the surface services read the tiling of the frame (not part of the frame record)
     VelState vel;            // mw_ocean_velocity: the weighted spectrum and the velocity buffers (velocity_kernels.h)
     // four separate buffers: the host forms keep their staged inputs in scratch while hull, bodies and rc_tree are in use
     GrowBuf hull;     // mw_ocean_hull_forces: vertex slab + chunk partials (hull_forces.h)
@@ -188,6 +190,13 @@ namespace mw {
 int plan_points_host(int N) { return N >= 2048 ? 16 : MW_PT; }
 std::vector<cf> build_twiddle_table(int N, int P, int sgn) { return build_twiddle_table_host(N, P, sgn); }
 }  // namespace mw
+
+// The period of the handle's surface, or 0 where it does not repeat.  An FFTMesh frame tiles where the grid is commensurate and N is even
+// (an odd N is anti-periodic); an OceanRenderer mesh samples clamp-addressed textures and never does.
+static float grid_period(const mw_ocean* o) {
+    if (o->sem != MW_SEM_FFTMESH || o->N % 2 != 0 || !(o->p.unit_width * (float)o->N == o->p.length)) return 0.f;
+    return (float)o->N * o->p.unit_width;
+}
 
 static OceanConsts consts_of(const mw_ocean* o) { return OceanConsts{o->N, o->p.length, o->p.gravity, o->p.unit_width, o->p.choppiness}; }
 
@@ -370,6 +379,28 @@ mw_status mw_ocean_set_choppiness(mw_ocean* o, float c) {
     return MW_OK;
 }
 
+mw_status mw_ocean_set_periodic(mw_ocean* o, int32_t on) {
+    const char* who = "mw_ocean_set_periodic";
+    if (!o) return fail(MW_EINVAL, who, "NULL handle");
+    if (on != 0 && on != 1) return fail(MW_EINVAL, who, "on must be 0 or 1");
+    if (on) {
+        if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
+            return fail(MW_EINVAL, who, "a batched handle (mw_ocean_create_batch) has no single surface");
+        if (o->sem != MW_SEM_FFTMESH)
+            return fail(MW_ESTATE, who, "an OceanRenderer mesh does not tile (its edge vertices sample half a texel inside the texture): FFTMesh handles only");
+        if (grid_period(o) == 0.f)
+            return fail(MW_ENOTCOMMENSURATE, who, "the frame repeats only where unit_width * resolution == length and the resolution is even");
+    }
+    o->periodic = on != 0;
+    return MW_OK;
+}
+mw_status mw_ocean_get_periodic(mw_ocean* o, int32_t* on, float* period) {
+    if (!o) return fail(MW_EINVAL, "mw_ocean_get_periodic", "NULL handle");
+    if (on) *on = o->periodic ? 1 : 0;
+    if (period) *period = grid_period(o);
+    return MW_OK;
+}
+
 int32_t mw_ocean_grid_size(const mw_ocean* o) { return o ? o->N : 0; }
 int64_t mw_ocean_index_count(const mw_ocean* o) {
     if (!o) return 0;
@@ -450,6 +481,7 @@ mw_status mw_ocean_reinit_spectrum(mw_ocean* o, float length, float wind_x, floa
     }
     if (s != MW_OK) return s;
     o->p.length = length; o->p.wind_x = wind_x; o->p.wind_y = wind_y; o->p.amplitude = amplitude; o->p.seed = seed;
+    if (grid_period(o) == 0.f) o->periodic = false;  // the new length no longer repeats with the grid: the tiling is gone
     HIP_TRY(hipStreamSynchronize(o->stream));
     return MW_OK;
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <mutex>
 #include <string>
 
 #include "../../include/mistral_water.h"
@@ -39,6 +40,22 @@ struct DevTmp {
     hipError_t alloc(size_t count) { return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)); }
 };
 }  // namespace
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device), safe from any number of host threads
+namespace mw {
+struct AttrOnce {
+    std::once_flag once[64];
+    hipError_t res[64];
+    hipError_t set(const void* fn, int bytes) {
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return e;
+        const int d = dev & 63;
+        std::call_once(once[d], [&] { res[d] = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); });
+        return res[d];
+    }
+};
+}  // namespace mw
 
 // The transform sizes the library has kernels for, named once.  The statement(s) after DEFAULT run with NN a constant expression equal
 // to N_; any other N_ runs DEFAULT (the caller's own message and status).

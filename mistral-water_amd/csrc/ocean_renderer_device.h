@@ -13,20 +13,6 @@
 
 namespace mw {
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device), safe from any number of host threads
-struct AttrOnce {
-    std::once_flag once[64];
-    hipError_t res[64];
-    hipError_t set(const void* fn, int bytes) {
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        const int d = dev & 63;
-        std::call_once(once[d], [&] { res[d] = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); });
-        return res[d];
-    }
-};
-
 // One set of the seven arrays a frame is made of.  The handle holds two: `out`, the latest frame (tile-major on a batched handle), and
 // `fr`, the frame buffers of a steps call ([frames_cap] frames each).  A set whose height_g / disp_a are NULL is a planar frame.
 struct OrTex {

@@ -99,8 +99,9 @@ MW_HD bool body_integrate(float body[16], const float row[8], const float mass[8
 }
 
 #if defined(__HIPCC__)
-struct BodiesArgs {
-    HullArgs h;            // the hull-forces arguments of the call (h.bodies = bodies, h.out = the per-substep rows)
+template <typename Mesh>
+struct BodiesArgsT {
+    HullArgsT<Mesh> h;            // the hull-forces arguments of the call (h.bodies = bodies, h.out = the per-substep rows)
     float4* bodies;        // [nbodies][4] float4, updated in place
     const float4* mass;    // [nbodies][2]
     const float4* rows;    // per-substep plan: hull_launch's rows of this substep [nbodies][2]
@@ -109,6 +110,10 @@ struct BodiesArgs {
     int substeps;
     int last;              // k_bodies_integrate: this is the call's last substep (write out)
 };
+using BodiesArgs = BodiesArgsT<SqMesh>;
+inline BodiesArgsT<SqTiled> bodies_args_tiled(const BodiesArgs& a) {
+    return BodiesArgsT<SqTiled>{hull_args_tiled(a.h), a.bodies, a.mass, a.rows, a.out, a.g, a.dt, a.substeps, a.last};
+}
 
 MW_HD void body_load_mass(const float4* p, float mass[8]) {
     const float4 a = p[0], b = p[1];
@@ -117,7 +122,8 @@ MW_HD void body_load_mass(const float4* p, float mass[8]) {
 }
 
 // Per-substep plan, after hull_launch: one lane per body integrates its row; the last substep also writes out.
-__global__ __launch_bounds__(256) void k_bodies_integrate(BodiesArgs a) {
+template <typename Mesh>
+__global__ __launch_bounds__(256) void k_bodies_integrate(BodiesArgsT<Mesh> a) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= a.h.nbodies) return;
     float body[16], mass[8], row[8];
@@ -143,12 +149,13 @@ inline size_t bodies_step_lds(int nverts, int nchunks) { return ((size_t)nverts 
 // One-launch plan: one 256-lane workgroup per body runs every substep.  Per substep: the vertex phase (k_hull_vertices per lane, into
 // the LDS slab), the triangle phase (k_hull_triangles per chunk, in chunk order, into the LDS partials), the reduce (k_hull_reduce in
 // wave 0) and, in lane 0, the integration; the new pose goes to every lane through LDS.
-__global__ __launch_bounds__(MW_HULL_CHUNK) void k_bodies_step(BodiesArgs a) {
+template <typename Mesh>
+__global__ __launch_bounds__(MW_HULL_CHUNK) void k_bodies_step(BodiesArgsT<Mesh> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ float red[MW_HULL_CHUNK / 64][8];
     __shared__ float pose[16];
     __shared__ int stop;
-    const HullArgs& ha = a.h;
+    const HullArgsT<Mesh>& ha = a.h;
     float4* slab = reinterpret_cast<float4*>(smem);  // [nverts][2]
     float4* part = slab + 2 * (size_t)ha.nverts;     // [nchunks][2]
     const float* vs = reinterpret_cast<const float*>(slab);

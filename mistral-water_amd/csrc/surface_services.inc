@@ -16,6 +16,8 @@ static bool triangles_in_range(const int32_t* triangles, int32_t ntris, int32_t 
 // ---- surface queries (csrc/surface_query.h) -------------------------------------------------------------------
 // Validates the call and names the vertex arrays of the queried frame.  OceanRenderer: the material's vertex stage of that frame
 // (k_or_displace_mesh, so the vertices are those of mw_ocean_displace_mesh bit for bit) runs into the handle's q_mesh first.
+// This is the one place an SqMesh is filled: a periodic handle (mw_ocean_set_periodic) gets its period here, every other mesh 0, and the
+// launches below pick the kernels' SqTiled instantiations (surface_tiled.h) from m.period != 0.
 static mw_status query_prepare(mw_ocean* o, int32_t frame, int32_t mode, const void* xz, int64_t n, int32_t iterations, const void* out,
                                const char* who, SqMesh* m) {
     if (!o) return fail(MW_EINVAL, who, "NULL handle");
@@ -32,6 +34,7 @@ static mw_status query_prepare(mw_ocean* o, int32_t frame, int32_t mode, const v
         return fail(MW_EINVAL, who, "frame out of range (-1, or a frame of the latest steps call)");
     if (!(o->p.unit_width > 0.f)) return fail(MW_EINVAL, who, "the mesh needs unit_width > 0");
     m->unit_width = o->p.unit_width;
+    m->period = o->periodic ? grid_period(o) : 0.f;
     if (o->sem == MW_SEM_FFTMESH) {
         if (!o->fm.s_have) return fail(MW_ESTATE, who, "no frame yet (mw_ocean_evaluate / mw_ocean_update first)");
         m->vert = o->fm.s_vert; m->norm = o->fm.s_norm; m->white = o->fm.s_white; m->R = o->N; m->wstride = o->fm.s_wstride;
@@ -55,8 +58,10 @@ static mw_status query_prepare(mw_ocean* o, int32_t frame, int32_t mode, const v
     return MW_OK;
 }
 static mw_status query_launch(mw_ocean* o, const SqMesh& m, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
-    k_query_surface<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, mode, sq_iters(iterations), static_cast<const float2*>(d_xz),
-                                                                                   n, static_cast<float4*>(d_out));
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    const float2* xz = static_cast<const float2*>(d_xz);
+    if (m.period != 0.f) HIP_TRY(tiled_query_surface(grid, o->stream, m, mode, sq_iters(iterations), xz, n, static_cast<float4*>(d_out)));
+    else k_query_surface<<<grid, block, 0, o->stream>>>(m, mode, sq_iters(iterations), xz, n, static_cast<float4*>(d_out));
     HIP_TRY(hipGetLastError());
     return MW_OK;
 }
@@ -184,8 +189,10 @@ static mw_status query_velocity_prepare(mw_ocean* o, int32_t frame, int32_t mode
 static mw_status query_velocity_launch(mw_ocean* o, const SqMesh& m, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
     mw_status s = velocity_to_handle(o);
     if (s != MW_OK) return s;
-    k_query_velocity<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, o->vel.vert, mode, sq_iters(iterations),
-                                                                                    static_cast<const float2*>(d_xz), n, static_cast<float4*>(d_out));
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    const float2* xz = static_cast<const float2*>(d_xz);
+    if (m.period != 0.f) HIP_TRY(tiled_query_velocity(grid, o->stream, m, o->vel.vert, mode, sq_iters(iterations), xz, n, static_cast<float4*>(d_out)));
+    else k_query_velocity<<<grid, block, 0, o->stream>>>(m, o->vel.vert, mode, sq_iters(iterations), xz, n, static_cast<float4*>(d_out));
     HIP_TRY(hipGetLastError());
     return MW_OK;
 }
@@ -277,9 +284,15 @@ static mw_status hull_launch(mw_ocean* o, const HullPlan& p, const HullCall& c, 
     a.part = reinterpret_cast<float4*>(static_cast<char*>(o->hull.p) + bslab);
     a.out = static_cast<float4*>(c.out);
     const int64_t nv = (int64_t)c.nbodies * c.nverts, nblk = (int64_t)c.nbodies * nchunks;
-    k_hull_vertices<<<dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, o->stream>>>(a);
-    k_hull_triangles<<<dim3((unsigned)std::min<int64_t>(nblk, (int64_t)1 << 20)), dim3(MW_HULL_CHUNK), 0, o->stream>>>(a);
-    k_hull_reduce<<<dim3((unsigned)std::min<int64_t>(((int64_t)c.nbodies + 3) / 4, (int64_t)1 << 20)), dim3(256), 0, o->stream>>>(a);
+    const dim3 gv((unsigned)((nv + 255) / 256)), gt((unsigned)std::min<int64_t>(nblk, (int64_t)1 << 20)),
+        gr((unsigned)std::min<int64_t>(((int64_t)c.nbodies + 3) / 4, (int64_t)1 << 20));
+    if (a.m.period != 0.f) {
+        HIP_TRY(tiled_hull_forces(gv, gt, gr, o->stream, a));
+        return MW_OK;
+    }
+    k_hull_vertices<<<gv, dim3(256), 0, o->stream>>>(a);
+    k_hull_triangles<<<gt, dim3(MW_HULL_CHUNK), 0, o->stream>>>(a);
+    k_hull_reduce<<<gr, dim3(256), 0, o->stream>>>(a);
     HIP_TRY(hipGetLastError());
     return MW_OK;
 }
@@ -400,8 +413,12 @@ static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c
     const size_t lds = bodies_step_lds(c.nverts, nchunks);
     const int plan = sw(SW_BODIES_PLAN);
     if (lds <= MW_BODIES_LDS_MAX && (plan == 1 || (plan < 0 && bodies_one_launch_rule(nchunks)))) {
+        if (a.h.m.period != 0.f) {
+            HIP_TRY(tiled_bodies_step(dim3((unsigned)c.nbodies), lds, MW_BODIES_LDS_MAX, o->stream, a));
+            return MW_OK;
+        }
         static AttrOnce attr;
-        HIP_TRY(attr.set(reinterpret_cast<const void*>(k_bodies_step), MW_BODIES_LDS_MAX));
+        HIP_TRY(attr.set(reinterpret_cast<const void*>(k_bodies_step<SqMesh>), MW_BODIES_LDS_MAX));
         k_bodies_step<<<dim3((unsigned)c.nbodies), dim3(MW_HULL_CHUNK), lds, o->stream>>>(a);
         HIP_TRY(hipGetLastError());
         return MW_OK;
@@ -413,7 +430,9 @@ static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c
     for (int k = 0; k < c.substeps; k++) {
         if ((s = hull_launch(o, p, rows, false)) != MW_OK) return s;
         a.last = k == c.substeps - 1;
-        k_bodies_integrate<<<dim3((unsigned)(((int64_t)c.nbodies + 255) / 256)), dim3(256), 0, o->stream>>>(a);
+        const dim3 gi((unsigned)(((int64_t)c.nbodies + 255) / 256));
+        if (a.h.m.period != 0.f) HIP_TRY(tiled_bodies_integrate(gi, o->stream, a));
+        else k_bodies_integrate<<<gi, dim3(256), 0, o->stream>>>(a);
         HIP_TRY(hipGetLastError());
     }
     return MW_OK;
@@ -465,6 +484,13 @@ mw_status mw_ocean_step_bodies(mw_ocean* o, int32_t frame, const float* hull_xyz
 // ---- raycasts (csrc/raycast.h) -------------------------------------------------------------------------------------
 // The surface query's validation and mesh (query_prepare, world mode), then the hierarchy of that mesh into the handle's tree buffer
 // (k_rc_build_leaves, and k_rc_build_top for trees deeper than 4 levels) and one lane per ray (k_raycast), all on the handle's stream.
+// A periodic handle is refused: a ray can cross any number of tiles, and ordering hits across displaced tiles is not built yet.
+static mw_status raycast_prepare(mw_ocean* o, int32_t frame, const void* rays, int64_t n, const void* out, const char* who, SqMesh* m) {
+    mw_status s = query_prepare(o, frame, MW_QUERY_WORLD, rays, n, 0, out, who, m);
+    if (s == MW_OK && m->period != 0.f)
+        return fail(MW_ESTATE, who, "raycasts do not tile yet: the handle is periodic (mw_ocean_set_periodic(o, 0) first)");
+    return s;
+}
 static mw_status raycast_launch(mw_ocean* o, const SqMesh& m, const void* d_rays, int64_t n, void* d_out, void* d_hit) {
     int B = sw(SW_RC_BLOCK);
     if (B <= 0) B = MW_RC_DEFAULT_BLOCK;
@@ -488,7 +514,7 @@ mw_status mw_ocean_raycast_device(mw_ocean* o, int32_t frame, const void* d_rays
     if (n > 0 && (misaligned(d_rays, 16) || misaligned(d_out, 16) || misaligned(d_hit, 8)))
         return fail(MW_EINVAL, who, "d_rays and d_out must be 16-byte and d_hit 8-byte aligned");
     SqMesh m{};
-    mw_status s = query_prepare(o, frame, MW_QUERY_WORLD, d_rays, n, 0, d_out, who, &m);
+    mw_status s = raycast_prepare(o, frame, d_rays, n, d_out, who, &m);
     if (s != MW_OK || n == 0) return s;
     return raycast_launch(o, m, d_rays, n, d_out, d_hit);
 }
@@ -497,7 +523,7 @@ mw_status mw_ocean_raycast(mw_ocean* o, int32_t frame, const float* rays, int64_
     const char* who = "mw_ocean_raycast";
     if (o) HIP_TRY(hipSetDevice(o->device));
     SqMesh m{};
-    mw_status s = query_prepare(o, frame, MW_QUERY_WORLD, rays, n, 0, out, who, &m);
+    mw_status s = raycast_prepare(o, frame, rays, n, out, who, &m);
     if (s != MW_OK || n == 0) return s;
     void *d_rays, *d_out, *d_hit;
     Stage st(o);

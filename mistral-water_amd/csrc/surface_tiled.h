@@ -1,0 +1,22 @@
+// surface_tiled.h -- how the host code launches the SqTiled instantiations of the surface services' kernels (a periodic handle,
+// mw_ocean_set_periodic).  They are instantiated in a translation unit of their own, surface_tiled.hip, which compiles the MW_HD
+// functions of surface_query.h, hull_forces.h and rigid_bodies.h without floating-point contraction: the tiled services are the
+// strict float32 the g++ build of the same functions computes (tests/periodic_shim.cpp), bit for bit, as raycast.h is.  The SqMesh
+// instantiations stay in mistral_water.hip, compiled as they always were, so a handle with the switch off keeps its bits.
+//
+// Each function enqueues on `s` with the grids the caller worked out (surface_services.inc: the same as for SqMesh) and returns
+// hipGetLastError().  Internal to the library: hidden from its exported symbols.
+#pragma once
+#include "rigid_bodies.h"
+
+namespace mw {
+#define MW_INTERNAL __attribute__((visibility("hidden")))
+MW_INTERNAL hipError_t tiled_query_surface(dim3 grid, hipStream_t s, const SqMesh& m, int mode, int iters, const float2* xz, int64_t n, float4* out);
+MW_INTERNAL hipError_t tiled_query_velocity(dim3 grid, hipStream_t s, const SqMesh& m, const float* vel, int mode, int iters, const float2* xz,
+                                            int64_t n, float4* out);
+// k_hull_vertices, k_hull_triangles, k_hull_reduce on their three grids
+MW_INTERNAL hipError_t tiled_hull_forces(dim3 vertices, dim3 triangles, dim3 reduce, hipStream_t s, const HullArgs& a);
+MW_INTERNAL hipError_t tiled_bodies_integrate(dim3 grid, hipStream_t s, const BodiesArgs& a);
+// k_bodies_step with `lds` bytes of dynamic LDS, at most lds_max (set as the kernel's attribute once per device)
+MW_INTERNAL hipError_t tiled_bodies_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const BodiesArgs& a);
+}  // namespace mw

@@ -1,0 +1,45 @@
+// surface_tiled.hip -- the SqTiled instantiations of the surface services' kernels (surface_tiled.h), compiled without floating-point
+// contraction.  The pragma stands after mw_math.h, which ends by setting its own, and before the headers whose MW_HD functions the
+// kernels run: every multiply and add of the walk, the hull integrals and the integrator keeps its own rounding here.
+#include <hip/hip_runtime.h>
+
+#include "mw_host.h"  // AttrOnce
+#include "mw_math.h"
+#pragma clang fp contract(off)
+#include "surface_tiled.h"
+
+namespace mw {
+
+hipError_t tiled_query_surface(dim3 grid, hipStream_t s, const SqMesh& m, int mode, int iters, const float2* xz, int64_t n, float4* out) {
+    k_query_surface<<<grid, dim3(256), 0, s>>>(SqTiled{m}, mode, iters, xz, n, out);
+    return hipGetLastError();
+}
+
+hipError_t tiled_query_velocity(dim3 grid, hipStream_t s, const SqMesh& m, const float* vel, int mode, int iters, const float2* xz, int64_t n,
+                                float4* out) {
+    k_query_velocity<<<grid, dim3(256), 0, s>>>(SqTiled{m}, vel, mode, iters, xz, n, out);
+    return hipGetLastError();
+}
+
+hipError_t tiled_hull_forces(dim3 vertices, dim3 triangles, dim3 reduce, hipStream_t s, const HullArgs& a) {
+    const HullArgsT<SqTiled> t = hull_args_tiled(a);
+    k_hull_vertices<<<vertices, dim3(256), 0, s>>>(t);
+    k_hull_triangles<<<triangles, dim3(MW_HULL_CHUNK), 0, s>>>(t);
+    k_hull_reduce<<<reduce, dim3(256), 0, s>>>(t);
+    return hipGetLastError();
+}
+
+hipError_t tiled_bodies_integrate(dim3 grid, hipStream_t s, const BodiesArgs& a) {
+    k_bodies_integrate<<<grid, dim3(256), 0, s>>>(bodies_args_tiled(a));
+    return hipGetLastError();
+}
+
+hipError_t tiled_bodies_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const BodiesArgs& a) {
+    static AttrOnce attr;
+    const hipError_t e = attr.set(reinterpret_cast<const void*>(k_bodies_step<SqTiled>), lds_max);
+    if (e != hipSuccess) return e;
+    k_bodies_step<<<grid, dim3(MW_HULL_CHUNK), lds, s>>>(bodies_args_tiled(a));
+    return hipGetLastError();
+}
+
+}  // namespace mw

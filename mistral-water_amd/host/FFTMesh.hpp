@@ -154,6 +154,9 @@ public:
         check(mw_ocean_set_choppiness(ocean_, choppiness));
         check(mw_ocean_evaluate(ocean_, t, &mesh.vertices[0].x, &mesh.normals[0].x, &mesh.colors[0].r));
     }
+    // Not in the reference: the surface services read the infinite tiling of the frame (include/mistral_water.h, the periodic surface);
+    // throws unless unitWidth * resolution == length with an even resolution
+    void SetPeriodic(bool on = true) { check(mw_ocean_set_periodic(ocean_, on ? 1 : 0)); }
     // Not in the reference: the surface of the latest EvaluateWaves() at horizontal points (include/mistral_water.h, surface queries)
     void QuerySurface(const std::vector<Vector2>& xz, std::vector<SurfaceSample>& out, bool world = true, int32_t iterations = 0) {
         query_surface(ocean_, -1, xz, out, world, iterations);

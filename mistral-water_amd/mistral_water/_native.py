@@ -62,6 +62,9 @@ BUILD_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-Xclang", "-target-feature", "-Xclang", "-load-store-opt"]
 
 
+TRANSLATION_UNITS = ["mistral_water.hip", "surface_tiled.hip"]
+
+
 def csrc_files():
     """The kernel sources (csrc/*.hip, *.h, *.inc), sorted: what the library is built from and what source_hash() covers."""
     return sorted(os.path.join(CSRC_DIR, f) for f in os.listdir(CSRC_DIR) if f.endswith((".hip", ".h", ".inc")))
@@ -111,7 +114,8 @@ def build_native(force: bool = False, verbose: bool = False, out: str | None = N
         cmd.append('-DMW_BUILD_TAG="%s"' % tag)
     if resource_report:
         cmd.append("-Rpass-analysis=kernel-resource-usage")
-    cmd += ["-o", target, os.path.join(CSRC_DIR, "mistral_water.hip")]
+    # two translation units: the library, and the tiled surface services, which set their own floating-point mode (csrc/surface_tiled.hip)
+    cmd += ["-o", target] + [os.path.join(CSRC_DIR, f) for f in TRANSLATION_UNITS]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if resource_report:
         open(resource_report, "w").write(r.stderr)
@@ -172,6 +176,8 @@ def lib():
         "mw_ocean_get_stream": (vp, [vp]),
         "mw_ocean_synchronize": (C.c_int, [vp]),
         "mw_ocean_set_choppiness": (C.c_int, [vp, C.c_float]),
+        "mw_ocean_set_periodic": (C.c_int, [vp, C.c_int32]),
+        "mw_ocean_get_periodic": (C.c_int, [vp, vp, vp]),
         "mw_ocean_set_spectrum": (C.c_int, [vp, f32p, f32p]),
         "mw_ocean_get_spectrum": (C.c_int, [vp, f32p, f32p]),
         "mw_ocean_rest_mesh": (C.c_int, [vp, f32p, f32p, f32p, i32p]),
@@ -248,6 +254,7 @@ ABI_SYMBOLS = [
     "mw_abi_version", "mw_build_id", "mw_last_error", "mw_device_count", "mw_params_default", "mw_ocean_create", "mw_ocean_destroy",
     "mw_ocean_create_batch", "mw_ocean_batch_size",
     "mw_ocean_set_stream", "mw_ocean_use_own_stream", "mw_ocean_get_stream", "mw_ocean_synchronize", "mw_ocean_set_choppiness",
+    "mw_ocean_set_periodic", "mw_ocean_get_periodic",
     "mw_ocean_set_spectrum", "mw_ocean_get_spectrum", "mw_ocean_reinit_spectrum", "mw_ocean_get_phase", "mw_ocean_set_phase",
     "mw_ocean_set_timer", "mw_ocean_normal_length", "mw_ocean_set_normal_length", "mw_comm_unique_id", "mw_tiles_create",
     "mw_tiles_create_rank", "mw_tiles_destroy", "mw_tiles_count",

@@ -92,6 +92,26 @@ class Ocean:
     def set_choppiness(self, c: float):
         nat.check(nat.lib().mw_ocean_set_choppiness(self._h, C.c_float(c)))
 
+    def set_periodic(self, on: bool = True):
+        """The surface services (query_surface, query_velocity, hull_forces, step_bodies) read the infinite tiling of the FFTMesh
+        frame instead of the one footprint (mw_ocean_set_periodic).  MW_ENOTCOMMENSURATE unless unit_width * N == length with N even;
+        MW_ESTATE on an OceanRenderer handle; raycasts refuse a periodic handle."""
+        nat.check(nat.lib().mw_ocean_set_periodic(self._h, 1 if on else 0))
+
+    def _get_periodic(self):
+        on, period = C.c_int32(0), C.c_float(0.0)
+        nat.check(nat.lib().mw_ocean_get_periodic(self._h, C.byref(on), C.byref(period)))
+        return bool(on.value), float(period.value)
+
+    @property
+    def periodic(self) -> bool:
+        return self._get_periodic()[0]
+
+    @property
+    def period(self) -> float:
+        """P = float32(N) * unit_width where the grid repeats (whether or not the switch is on), else 0."""
+        return self._get_periodic()[1]
+
     # -- spectrum ----------------------------------------------------------------------------
     def set_spectrum(self, h0, h0conj):
         h0 = np.ascontiguousarray(h0, np.float32)

@@ -1,0 +1,311 @@
+"""CPU tier of the periodic surface (mw_ocean_set_periodic, include/mistral_water.h; csrc/surface_query.h, SqTiled).
+
+* the period is real: the reference's direct sum, restated here in float64, repeats after N grid lines on a commensurate even grid and
+  does not on an odd or a non-commensurate one -- the grids mw_ocean_set_periodic refuses;
+* the MW_HD functions compiled with g++ over a tiled mesh (tests/periodic_shim.cpp): bit identities with the one-footprint functions
+  (tests/surface_query_shim.cpp) inside the base footprint, exact translation by whole tiles, and the float64 brute force of
+  tests/surface_ref.py, tests/hull_ref.py and tests/body_ref.py over the explicit replication of the mesh;
+* the two entry points are exported, declared and refuse a NULL handle."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import body_ref as B
+import hull_ref as H
+import periodic_ref as PR
+import surface_ref as S
+import test_surface_query_cpu as TS  # its shim builder and query wrapper: the one-footprint functions
+
+RHO, G = 1000.0, 9.81
+bits = PR.bits
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    return PR.build_shim(str(tmp_path_factory.mktemp("ps") / "libperiodic_shim.so"))
+
+
+@pytest.fixture(scope="module")
+def plain(tmp_path_factory):
+    return TS.build_shim(str(tmp_path_factory.mktemp("ps_sq") / "libsq_shim.so"))
+
+
+# ---- the period is real ---------------------------------------------------------------------------------------------------
+def _direct_sum(N, uw, length, lines_x, lines_z, seed=0):
+    """The reference's sum, in this test's words: field(a, b) = sum_ij F(i, j) exp(i (k_i x_a + k_j z_b)) with k_i = 2 pi (i - N/2) / length
+    (N/2 a real number: a half-integer shift for odd N) and x_a = (a - N div 2) unit_width, plus unit_width / 2 for even N -- for ANY
+    integer grid line a, also past the mesh.  Three fields: the height F = h, and the two displacements F = (k_x / |k|) h, (-k_z / |k|) h.
+    Returns [3, len(lines_x), len(lines_z)] complex128 and the scale sum |F| of each field."""
+    rng = np.random.default_rng(seed)
+    h = rng.standard_normal((N, N)) + 1j * rng.standard_normal((N, N))
+    i = np.arange(N, dtype=np.float64)
+    k = 2 * np.pi * (i - N / 2.0) / length
+    kx, kz = np.meshgrid(k, k, indexing="ij")
+    kl = np.hypot(kx, kz)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ux, uz = np.where(kl < 1e-4, 0, kx / kl), np.where(kl < 1e-4, 0, -kz / kl)
+    pos = lambda lines: (np.asarray(lines, np.float64) - N // 2) * uw + (uw / 2 if N % 2 == 0 else 0.0)  # noqa: E731
+    Ex, Ez = np.exp(1j * np.outer(k, pos(lines_x))), np.exp(1j * np.outer(k, pos(lines_z)))
+    fields = [h, ux * h, uz * h]
+    return np.stack([Ex.T @ (f @ Ez) for f in fields]), np.array([np.abs(f).sum() for f in fields])
+
+
+def test_the_field_repeats_after_n_grid_lines_on_the_grids_the_switch_accepts_only():
+    def gap(N, uw, length):
+        a = np.arange(N)
+        here, scale = _direct_sum(N, uw, length, a, a)
+        there, _ = _direct_sum(N, uw, length, a + N, a)   # one tile further along x
+        assert np.abs(_direct_sum(N, uw, length, a, a + N)[0] - there).max() <= 1e3 * scale.max()  # (z alike: the sum is symmetric)
+        anti = np.abs(here + there).max(axis=(1, 2)) / scale
+        return np.abs(here - there).max(axis=(1, 2)) / scale, anti, np.abs(here).max(axis=(1, 2)) / scale
+    d, _, size = gap(8, 1.0, 8.0)
+    print("N = 8, L = 8: |f(a + N) - f(a)| / scale =", d)
+    assert (d <= 1e-12).all() and (size > 1e-3).all()
+    d, anti, size = gap(9, 1.0, 9.0)  # odd N: k_i x_(a+N) - k_i x_a = 2 pi (i - 4.5): every term changes sign
+    print("N = 9, L = 9: difference", d, "sum", anti)
+    assert (d > 0.5 * size).all() and (anti <= 1e-12).all()
+    d, _, size = gap(12, 1.0, 12.39)  # the shipped scene: N unit_width != length
+    print("N = 12, L = 12.39: difference", d)
+    assert (d > 0.05 * size).all()
+
+
+# ---- bit identities with the one-footprint functions ----------------------------------------------------------------------
+@pytest.mark.parametrize("R", [16, 64, 128])
+def test_rest_mode_inside_the_base_footprint_has_the_bits_of_the_one_mesh(shim, plain, R):
+    uw = 1.0
+    vert, norm, white = S.synth_mesh(R, uw, 0.8, seed=R)
+    rc = S.rest_coords(R, uw)
+    rng = np.random.default_rng(R)
+    xz = np.concatenate([rng.uniform(float(rc[0]), float(rc[-1]), (3000, 2)).astype(np.float32), S.rest_plane(R, uw),
+                         np.array([[rc[0], rc[-1]], [rc[-1], rc[0]], [rc[-1], rc[-1]]], np.float32)])
+    a = TS.query(plain, R, uw, vert, norm, white, 4, 0, xz)
+    b = PR.query(shim, R, uw, PR.period(R, uw), vert, norm, white, 4, 0, xz)
+    assert np.isfinite(a).all() and np.array_equal(bits(a), bits(b))
+    # and with no period the new shim IS the one-footprint function
+    assert np.array_equal(bits(PR.query(shim, R, uw, 0.0, vert, norm, white, 4, 0, xz)), bits(a))
+
+
+@pytest.mark.parametrize("fold", [0.5, 0.95])
+def test_world_mode_away_from_the_edges_has_the_bits_of_the_one_mesh(shim, plain, fold):
+    """8 steps of at most 4 cells reach 32 cells: from 33 cells inside, the one-mesh walk never meets its clamp"""
+    R, uw = 128, 1.0
+    vert, norm, white = S.synth_mesh(R, uw, fold, seed=7 + R)
+    rc = S.rest_coords(R, uw)
+    xz = np.random.default_rng(3).uniform(float(rc[0]) + 33 * uw, float(rc[-1]) - 33 * uw, (4000, 2)).astype(np.float32)
+    a = TS.query(plain, R, uw, vert, norm, white, 1, 1, xz)
+    b = PR.query(shim, R, uw, PR.period(R, uw), vert, norm, white, 1, 1, xz)
+    assert np.isfinite(a).all() and (a[:, 7] > 0).any() and np.array_equal(bits(a), bits(b))
+
+
+@pytest.mark.parametrize("uw", [1.0, 0.5])
+@pytest.mark.parametrize("mode", [0, 1])
+def test_translation_by_whole_tiles_is_exact(shim, uw, mode):
+    """P a power of two and coordinates multiples of 2^-8: q + k P is exact, so result(q + (kx P, kz P)) must be result(q) with exactly
+    kx P and kz P added to px and pz (one float32 addition each) and every other field bit for bit -- seam strips and corners included"""
+    R = 64
+    P = PR.period(R, uw)
+    assert P == 2.0 ** round(np.log2(P))
+    vert, norm, white, vel = PR.periodic_synth(R, uw, 0.8, seed=5)
+    q = PR.base_points(R, uw, 400, np.random.default_rng(11), step=2.0 ** -8)
+    rc = S.rest_coords(R, uw)
+    assert (q[:, 0] > rc[-1]).sum() > 50 and (q[:, 1] > rc[-1]).sum() > 50   # the seam strips are covered
+    base = PR.query(shim, R, uw, P, vert, norm, white, 4, mode, q)
+    vbase = PR.velocity(shim, R, uw, P, vert, vel, mode, q)
+    assert np.isfinite(base).all()
+    for kx in range(-3, 4):
+        for kz in range(-3, 4):
+            sh = np.array([kx * P, kz * P], np.float32)
+            moved = (q + sh).astype(np.float32)
+            assert np.array_equal(moved.astype(np.float64), q.astype(np.float64) + sh.astype(np.float64))
+            out = PR.query(shim, R, uw, P, vert, norm, white, 4, mode, moved)
+            want = base.copy()
+            want[:, 0] = base[:, 0] + sh[0]
+            want[:, 2] = base[:, 2] + sh[1]
+            assert np.array_equal(bits(out), bits(want)), (kx, kz)
+            assert np.array_equal(bits(PR.velocity(shim, R, uw, P, vert, vel, mode, moved)), bits(vbase)), (kx, kz)
+
+
+def test_non_finite_points_and_tiles_past_2_to_the_20_have_no_answer(shim):
+    R, uw = 16, 1.0
+    P = PR.period(R, uw)
+    vert, norm, white, vel = PR.periodic_synth(R, uw, 0.5, seed=1)
+    far = float(P) * 2 ** 20
+    xz = np.array([[np.nan, 0], [0, np.inf], [-np.inf, 0], [far + 2 * P, 0], [0, -far - 2 * P], [3e38, 0]], np.float32)
+    near = np.array([[far - 2 * P, 0], [0, -far + 2 * P]], np.float32)
+    for mode in (0, 1):
+        assert np.isnan(PR.query(shim, R, uw, P, vert, norm, white, 1, mode, xz)).all()
+        assert np.isnan(PR.velocity(shim, R, uw, P, vert, vel, mode, xz)).all()
+        out = PR.query(shim, R, uw, P, vert, norm, white, 1, mode, near)
+        assert np.isfinite(out).all() and (out[:, 7] <= 1e-4).all()
+        assert abs(out[0, 0] - near[0, 0]) <= 2 * P and abs(out[1, 2] - near[1, 1]) <= 2 * P
+
+
+# ---- against the explicit tiling ------------------------------------------------------------------------------------------
+def _tiled_case(R=16, uw=1.0, fold=0.7, reps=1, seed=2):
+    vert, norm, white, vel = PR.periodic_synth(R, uw, fold, seed=seed)
+    Rb, rest, bvert, bnorm, bwhite, bvel = PR.tiling(R, uw, reps, vert, norm, white, vel)
+    return dict(R=R, uw=uw, P=PR.period(R, uw), vert=vert, norm=norm, white=white, vel=vel, Rb=Rb, rest=rest, bvert=bvert, bnorm=bnorm,
+                bwhite=bwhite, bvel=bvel, tris=S.grid_triangles(Rb))
+
+
+def _seam_points(c, n, rng):
+    """points of the centre tile, of its four seams (the strips on both sides of the base footprint) and of the corner seam cells"""
+    rc = S.rest_coords(c["R"], c["uw"])
+    x0, hi, P, uw = float(rc[0]), float(rc[-1]), c["P"], c["uw"]
+    inside = rng.uniform(x0, hi, (n, 2))
+    strip = np.concatenate([rng.uniform(hi, x0 + P, n), rng.uniform(x0 - uw, x0, n)])
+    along = rng.uniform(x0 - uw, x0 + P, 2 * n)
+    corner = np.stack([np.where(rng.random(n) < 0.5, rng.uniform(hi, x0 + P, n), rng.uniform(x0 - uw, x0, n)),
+                       np.where(rng.random(n) < 0.5, rng.uniform(hi, x0 + P, n), rng.uniform(x0 - uw, x0, n))], 1)
+    return np.concatenate([inside, np.stack([strip, along], 1), np.stack([along, strip], 1), corner]).astype(np.float32)
+
+
+def test_rest_mode_equals_the_brute_force_over_the_explicit_tiling(shim):
+    c = _tiled_case()
+    xz = _seam_points(c, 150, np.random.default_rng(4))
+    out = PR.query(shim, c["R"], c["uw"], c["P"], c["vert"], c["norm"], c["white"], 4, 0, xz)
+    hits = S.containing(xz[:, 0], xz[:, 1], c["rest"], c["tris"], 1e-9)
+    scale = float(np.abs(c["bvert"]).max())
+    assert np.isfinite(out).all() and (out[:, 7] == 0).all()
+    for k, (t, w) in enumerate(hits):
+        assert len(t) >= 1, xz[k]
+        p, n, wh = S._interp(c["tris"][t[0]], w[0], c["bvert"], c["bnorm"], c["bwhite"])
+        assert np.abs(out[k, :3] - p).max() <= 1e-5 * scale, (k, xz[k], out[k], p)
+        assert np.abs(out[k, 3:6] - n).max() <= 1e-5
+        assert abs(out[k, 6] - wh) <= 1e-5 * max(1.0, float(c["white"].max()))
+    # the vertices of the tiling themselves, closing row and column included, come back exactly (weights 0 and 1)
+    Rb = c["Rb"]
+    ring = np.array([i * Rb + j for i in range(Rb) for j in range(Rb) if abs(i - Rb // 2) <= c["R"] and abs(j - Rb // 2) <= c["R"]])
+    at = PR.query(shim, c["R"], c["uw"], c["P"], c["vert"], c["norm"], c["white"], 4, 0, c["rest"][ring])
+    assert np.array_equal(at[:, :3], c["bvert"][ring].astype(np.float32)) and np.array_equal(at[:, 6], c["bwhite"][ring])
+
+
+@pytest.mark.parametrize("fold", [0.7, 0.95])
+def test_world_mode_equals_the_brute_force_over_the_explicit_tiling(shim, fold):
+    c = _tiled_case(fold=fold, seed=3)
+    xz = _seam_points(c, 60, np.random.default_rng(5))
+    out = PR.query(shim, c["R"], c["uw"], c["P"], c["vert"], c["norm"], c["white"], 1, 1, xz)
+    bv32 = c["bvert"].astype(np.float32)
+    nuniq, nfold, _ = S.check_world(out, xz, bv32, c["bnorm"], c["bwhite"], c["uw"], lambda x, z: c["tris"])
+    assert nfold == 0 and nuniq >= 0.9 * len(xz), (nuniq, nfold)
+    # the velocity query locates the same points: the same residuals, bit for bit, and the velocity of the explicit tiling there
+    vq = PR.velocity(shim, c["R"], c["uw"], c["P"], c["vert"], c["vel"], 1, xz)
+    assert np.array_equal(bits(vq[:, 3]), bits(out[:, 7]))
+    eta, nhit, u = PR.water_on(xz, c["bvert"], c["tris"], c["bvel"])
+    one = nhit == 1
+    assert one.sum() >= 0.9 * len(xz)
+    assert np.abs(vq[one, :3] - u[one]).max() <= 1e-4 * float(np.abs(c["vel"]).max())
+    assert np.abs(out[one, 1] - eta[one]).max() <= 1e-5 * float(np.abs(c["vert"][:, 1]).max())
+
+
+# ---- hull forces and bodies -----------------------------------------------------------------------------------------------
+def _bodies(p, v=None):
+    b = np.zeros((len(p), 16), np.float32)
+    b[:, 0:3] = p
+    b[:, 7] = 1.0
+    if v is not None:
+        b[:, 8:11] = v
+    return b
+
+
+@pytest.mark.parametrize("drag", [False, True])
+def test_hull_rows_across_a_seam_and_two_tiles_away_equal_the_reference_on_the_explicit_tiling(shim, drag):
+    c = _tiled_case(reps=2, seed=6)
+    rc = S.rest_coords(c["R"], c["uw"])
+    hi, P = float(rc[-1]), c["P"]
+    hull, tris = H.box(2.0, 1.0, 1.6)
+    pos = [[hi + 0.5, 0.1, 1.3],            # straddles the x seam: vertices on both sides of the last grid line and in the strip
+           [2.2, -0.1, hi + 0.6],           # the z seam
+           [hi + 0.4, 0.0, hi + 0.5],       # the corner seam cell
+           [1.7 + 2 * P, 0.1, -2.4 - 2 * P]]  # two tiles away on both axes
+    pos = np.array(pos)
+    pos[:, 1] += PR.water_on(pos[:, [0, 2]], c["bvert"], c["tris"])[0]   # afloat: the centre near the water's height there
+    bodies = _bodies(pos, v=[[0.5, 0.1, -0.3]] * 4)
+    lin, quad = (30.0, 60.0) if drag else (0.0, 0.0)
+    cf = np.array([RHO, G, lin, quad, 1.0], np.float32)
+    slab, rows = PR.hull_forces(shim, c["R"], c["uw"], P, c["vert"], c["vel"], hull, tris, bodies, cf)
+    assert np.isfinite(rows).all() and (rows[:, 7] <= 1e-4).all() and (rows[:, 3] > 0).all()
+    x = H.transform(bodies, hull).astype(np.float32)
+    assert (x[0, :, 0] < hi).any() and (x[0, :, 0] > hi).any()
+    for b in range(len(bodies)):
+        eta, nhit, u = PR.water_on(x[b][:, [0, 2]], c["bvert"], c["tris"], c["bvel"])
+        assert (nhit >= 1).all()
+        ref = H.forces(x[b], eta - x[b][:, 1], u if drag else np.zeros_like(u), tris, bodies[b], RHO, G, lin, quad)
+        scale = RHO * G * H.volume(x[b].astype(np.float64), tris) + (lin + quad) * 4 * np.abs(ref[3]) * 10
+        assert np.abs(rows[b, 0:3] - ref[0:3]).max() <= 1e-4 * scale, (b, rows[b], ref)
+        assert abs(rows[b, 3] - ref[3]) <= 1e-4 * max(ref[3], 1.0)
+        assert np.abs(rows[b, 4:7] - ref[4:7]).max() <= 1e-4 * scale * (1 + np.abs(hull).max()), (b, rows[b], ref)
+    # off: the same bodies leave the one footprint and clamp at its edge (residuals of the order of a cell) -- what the feature is for
+    _, off = PR.hull_forces(shim, c["R"], c["uw"], 0.0, c["vert"], c["vel"], hull, tris, bodies, cf)
+    assert (off[:, 7] > 0.3).all()
+
+
+@pytest.mark.parametrize("drag", [False, True])
+def test_a_buoy_crosses_the_seam_within_8_substeps(shim, drag):
+    c = _tiled_case(seed=8)
+    rc = S.rest_coords(c["R"], c["uw"])
+    hi, x0, P = float(rc[-1]), float(rc[0]), c["P"]
+    hull, tris = H.icosphere(0.6, 1)
+    m, cen, I = B.mass_properties(hull, tris, 500.0)
+    hull = (hull - cen).astype(np.float32)
+    mass = np.array([[m, I[0, 0], I[1, 1], I[2, 2], I[0, 1], I[0, 2], I[1, 2], 0.0]], np.float32)
+    start = _bodies([[hi - 0.3, 0.0, 2.0]], v=[[4.0, 0.0, 0.5]])
+    lin, quad = (20.0, 40.0) if drag else (0.0, 0.0)
+    cf = np.array([RHO, G, lin, quad, 1.0], np.float32)
+    dt, K = np.float32(0.5), 8
+    args = (shim, c["R"], c["uw"], P, c["vert"], c["vel"], hull, tris)
+    a, ra = PR.step_bodies(*args, start, mass, cf, dt, K, plan=0)
+    b, rb = PR.step_bodies(*args, start, mass, cf, dt, K, plan=1)
+    assert np.array_equal(bits(a), bits(b)) and np.array_equal(bits(ra), bits(rb))      # the two plans' order: the same bits
+    assert np.isfinite(a).all() and np.isfinite(ra).all() and a[0, 0] > x0 + P            # it left the tile through the seam
+    # one substep at a time: the same chain bit for bit, each row the hull forces of that state (checked against the explicit tiling
+    # above), each new state tests/body_ref.py's step of it
+    h = float(dt / np.float32(K))
+    state = start.copy()
+    xs = [float(state[0, 0])]
+    for _ in range(K):
+        _, row = PR.hull_forces(*args, state, cf)
+        nxt, r1 = PR.step_bodies(*args, state, mass, cf, h, 1, plan=1)
+        assert np.array_equal(bits(r1), bits(row)) and row[0, 7] <= 1e-4
+        ref = B.step(state[0], row[0], mass[0].astype(np.float64), G, h)
+        for sl in (slice(0, 3), slice(4, 8), slice(8, 11), slice(12, 15)):
+            assert np.abs(nxt[0, sl] - ref[sl]).max() <= 2e-5 * (1 + np.abs(ref[sl]).max()), (sl, nxt[0, sl], ref[sl])
+        state = nxt
+        xs.append(float(state[0, 0]))
+    assert xs[0] < hi < xs[-1] and any(hi <= x <= x0 + P for x in xs)                     # a substep stood in the seam strip
+    assert np.array_equal(bits(state), bits(a)) and np.array_equal(bits(r1), bits(ra))
+    # off: the same buoy runs off the footprint; the walk clamps at the edge and reports how far away the body is
+    _, roff = PR.step_bodies(shim, c["R"], c["uw"], 0.0, c["vert"], c["vel"], hull, tris, start, mass, cf, dt, K, plan=1)
+    assert roff[0, 7] > 0.5
+
+
+# ---- exports and statuses without a GPU -----------------------------------------------------------------------------------
+def test_periodic_symbols_are_exported_declared_and_refuse_a_null_handle(mw):
+    from mistral_water import _native
+    L = C.CDLL(_native.LIB_PATH)
+    hdr = open(_native.HEADER_PATH).read()
+    for s in ("mw_ocean_set_periodic", "mw_ocean_get_periodic"):
+        assert hasattr(L, s) and s in _native.ABI_SYMBOLS and s + "(" in hdr
+    on, period = C.c_int32(7), C.c_float(7.0)
+    assert mw.lib().mw_ocean_set_periodic(None, 1) == mw.MW_EINVAL and b"NULL handle" in mw.lib().mw_last_error()
+    assert mw.lib().mw_ocean_set_periodic(None, 0) == mw.MW_EINVAL
+    assert mw.lib().mw_ocean_get_periodic(None, C.byref(on), C.byref(period)) == mw.MW_EINVAL
+    assert on.value == 7 and period.value == 7.0
+    assert mw.MW_ENOTCOMMENSURATE == 3 and mw.lib().mw_abi_version() == 4
+
+
+def test_the_tiled_kernels_run_the_functions_the_shim_runs():
+    """one source text for both mesh types: the kernels are templates over the mesh, the tiled forms are reached inside sq_locate, and the
+    tiled instantiations are compiled with contraction off, as g++ compiles the shim"""
+    import os
+    from conftest import REPO
+    csrc = os.path.join(REPO, "mistral-water_amd", "csrc")
+    sq = open(os.path.join(csrc, "surface_query.h")).read()
+    loc = sq[sq.index("MW_HD void sq_locate("):sq.index("// one query:")]
+    assert "sq_cell_of(m, ux, &fa)" in loc and "sq_triangle_of(m, ti, tj, tu, ta, tb, v, w, &t)" in loc and "sq_reduce(" in loc
+    assert "template <typename Mesh>\n__global__ __launch_bounds__(256) void k_query_surface(Mesh m" in sq
+    tu = open(os.path.join(csrc, "surface_tiled.hip")).read()
+    assert tu.index('#include "mw_math.h"') < tu.index("#pragma clang fp contract(off)") < tu.index('#include "surface_tiled.h"')
+    for k in ("k_query_surface", "k_query_velocity", "k_hull_vertices", "k_hull_triangles", "k_hull_reduce", "k_bodies_integrate", "k_bodies_step"):
+        assert k + "<<<" in tu or k + "<SqTiled>" in tu
