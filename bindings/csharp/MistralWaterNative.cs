@@ -25,6 +25,7 @@ public static class MistralWaterNative
     public const int QueryRest = 0, QueryWorld = 1;
     public const int HullNCoeffs = 5;
     public const int BodyNMass = 8;
+    public const int RcDefaultReach = 16, RcMaxReach = 1024;
 
     [StructLayout(LayoutKind.Sequential)]   // mw_params: 56 bytes
     public struct Params
@@ -137,6 +138,10 @@ public static class MistralWaterNative
     // (triangle, facing) or null; a miss: t = +infinity, an invalid ray: NaN
     [DllImport(Lib)] public static extern Status mw_ocean_raycast(IntPtr ocean, int frame, float[] rays, long n, [Out] float[] result, [Out] int[] hit);
     [DllImport(Lib)] public static extern Status mw_ocean_raycast_device(IntPtr ocean, int frame, IntPtr dRays, long n, IntPtr dResult, IntPtr dHit);
+    // tiled raycasts (the periodic surface, whatever the switch says): the (2 reach + 1)^2 tiles around the origin's; hit [n][4] =
+    // (tiled triangle id, facing, tile x, tile z) or null; id -1: a miss, -2: the ray left the window's reach unhit
+    [DllImport(Lib)] public static extern Status mw_ocean_raycast_tiled(IntPtr ocean, int frame, float[] rays, long n, int reach, [Out] float[] result, [Out] int[] hit);
+    [DllImport(Lib)] public static extern Status mw_ocean_raycast_tiled_device(IntPtr ocean, int frame, IntPtr dRays, long n, int reach, IntPtr dResult, IntPtr dHit);
 
     // ---- page-locked output arrays ------------------------------------------------------------------------------
     [DllImport(Lib)] public static extern Status mw_host_register(IntPtr ptr, UIntPtr bytes);

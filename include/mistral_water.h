@@ -145,7 +145,8 @@ mw_status mw_ocean_set_choppiness(mw_ocean* o, float choppiness);
  *     bit for bit, as it does the raycasts; the one-footprint services keep the contracted arithmetic their bits have always come
  *     from.  The two "same bits" statements above hold between the two forms under one arithmetic; on the device a periodic answer
  *     inside the base footprint agrees with the switch-off answer to rounding, not bit for bit.
- * mw_ocean_raycast on a handle with the switch on returns MW_ESTATE: raycasts do not tile yet.                              */
+ * mw_ocean_raycast on a handle with the switch on returns MW_ESTATE: it reads the one footprint and does not tile.  The tiled surface
+ *   has a cast of its own, mw_ocean_raycast_tiled (below), which does not read the switch.                                       */
 mw_status mw_ocean_set_periodic(mw_ocean* o, int32_t on);                     /* 0 / 1 */
 mw_status mw_ocean_get_periodic(mw_ocean* o, int32_t* on, float* period);     /* either out-argument may be NULL */
 
@@ -475,6 +476,51 @@ mw_status mw_ocean_step_bodies_device(mw_ocean* o, int32_t frame, const void* d_
 mw_status mw_ocean_raycast(mw_ocean* o, int32_t frame, const float* rays, int64_t n, float* out, int32_t* hit);
 /* device arrays, asynchronous on the handle's stream */
 mw_status mw_ocean_raycast_device(mw_ocean* o, int32_t frame, const void* d_rays, int64_t n, void* d_out, void* d_hit);
+
+/* ---- tiled raycasts: first hit of rays on the periodic ocean surface ------------------------------------------------
+ * mw_ocean_raycast on the tiled surface of "the periodic surface" above.  The entry point names its surface: it does not read the
+ *   periodic switch, gives the same bits with the switch on or off and leaves the switch and all other handle state alone.  It needs a
+ *   grid that repeats: mw_ocean_get_periodic reporting P > 0.
+ * Surface: vertex (gi, gj) of the integer grid, g = k*N + a (floor division), is vertex (ai, aj) of the frame displaced by
+ *   (ki*P, 0, kj*P): x + (float)k * P in float32, k = 0 leaving the bits alone.  Every integer cell exists, the seam cells a = N-1
+ *   (between the frame's last grid line and the next tile's first) included, split along the same diagonal as mw_ocean_raycast's cells.
+ *   Tile (kx, kz) owns the N x N cells whose lower grid lines are its own.  Tiled triangle id = 2 * (ai*N + aj) + upper, in [0, 2 N^2);
+ *   for ai, aj < N-1 it is mw_ocean_raycast's id of the same triangle + 2*ai.
+ * rays [n][8]: the layout and the validity rule of mw_ocean_raycast.  A ray is also invalid when its origin lies more than 2^20 tiles
+ *   from the base tile on x or z.  An invalid ray gives NaN in all 8 floats and hit (-1, 0, 0, 0).
+ * Reduction first: K0 = the tile of the origin, ox = ox' + K0x*P with ox' in the base tile [rest(0), rest(0) + P] (likewise z).  The ray
+ *   is cast from o' = (ox', oy, oz') in the frame of K0, where relative tile k has its vertices displaced by k*P; p = o' + t d, and
+ *   K0x*P and K0z*P are added to px and pz once, at the end.  Precision therefore falls off with the distance the ray travels, not with
+ *   the distance from the world origin: moving the origin by whole tiles (where that is exact in float32) leaves t, id, facing, normal
+ *   and whitecap bit-identical.  A vertex of a seam has one expression, in terms of its global grid line, so its sheared coordinates are
+ *   the same bits from both sides and no ray slips through a seam.
+ * Window: the ray sees the (2*reach + 1)^2 tiles within `reach` of K0 on each axis, reach in [0, MW_RC_MAX_REACH].  Geometry of tiles
+ *   outside the window is NOT seen, not even where it overhangs into the window: a caller that needs the answer of the infinite tiling
+ *   picks reach one larger than the distance (in tiles) it cares about.
+ * First hit: the smallest accepted t over every triangle of every window tile; ties go to the smallest relative tile x, then tile z,
+ *   then id.  A pure function of (frame, ray, reach): independent of n, of the ray's place in the batch and of the acceleration
+ *   structure.  The intersection arithmetic is mw_ocean_raycast's: strict float32, the float64 fallback for a zero edge value.
+ * out [n][8] = t px py pz nx ny nz white, as mw_ocean_raycast: normal and whitecap from the (wrapped) vertices with the hit's weights.
+ * hit [n][4] int32 (optional, NULL allowed) = id, facing, tile_x, tile_z: the tiled id, the facing of mw_ocean_raycast, and the ABSOLUTE
+ *   tile of the triangle's cell (K0 plus its relative tile).
+ *   A miss: t = +inf, NaN in the other 7 floats, hit (-1, 0, 0, 0): nothing in the window was hit, and the ray ended (tmax) or left the
+ *     height range of the surface before it left the columns the window's tiles reach.
+ *   Out of reach: the same row with id -2: nothing in the window was hit, and the ray left those columns -- the window's own and as
+ *     many beyond them as a tile's geometry overhangs its footprint, one for any sane ocean -- while still inside [tmin, tmax] and the
+ *     surface's height range.  The infinite tiling may or may not be hit further on.
+ * MW_EINVAL for a batched handle; MW_ESTATE for an OceanRenderer handle; MW_EINVAL for reach outside [0, MW_RC_MAX_REACH];
+ *   MW_ENOTCOMMENSURATE where the grid does not repeat (the shipped N = 12 scene, an odd N); then MW_EINVAL for frame != -1, a NULL rays
+ *   or out with n > 0, n < 0 or n > 2^32 - 256, and in the device form d_rays, d_out or d_hit not 16-byte aligned; MW_ESTATE before the
+ *   first frame.  n == 0 does nothing.  Caller arrays are untouched on failure.
+ * Every call builds the bounds hierarchy of one tile in the buffer mw_ocean_raycast uses; the call changes
+ *   nothing of the handle's state.  A horizontal displacement of more than 7 periods is not followed.                          */
+#define MW_RC_DEFAULT_REACH 16
+#define MW_RC_MAX_REACH 1024
+/* host arrays, synchronous */
+mw_status mw_ocean_raycast_tiled(mw_ocean* o, int32_t frame, const float* rays, int64_t n, int32_t reach, float* out, int32_t* hit);
+/* device arrays (d_rays, d_out, d_hit 16-byte aligned), asynchronous on the handle's stream */
+mw_status mw_ocean_raycast_tiled_device(mw_ocean* o, int32_t frame, const void* d_rays, int64_t n, int32_t reach, void* d_out,
+                                        void* d_hit);
 
 /* ---- independent tiles on several devices (BASELINE configs[2]) ------------------------------------
  * Tiles are independent units in both semantics: tile k is the ocean of `params` with seed params->seed + k on its own

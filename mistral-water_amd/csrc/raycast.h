@@ -363,6 +363,7 @@ __device__ __forceinline__ void rc_reduce_lds(const float4* s_lo, const float4* 
             hi->x = fmaxf(hi->x, ch.x); hi->y = fmaxf(hi->y, ch.y); hi->z = fmaxf(hi->z, ch.z);
         }
 }
+#if !defined(MW_RC_NO_KERNELS)  // a second translation unit takes the functions above without defining the kernels again
 // Leaves and the levels above them up to level D - 4: one workgroup per T x T tile of leaves (T = min(16, 2^D)), one lane per leaf
 // gathering its (B+1)^2 vertices, then the tile reduced 2 x 2 in LDS up to its own root; every level is written out.
 __global__ __launch_bounds__(256) void k_rc_build_leaves(SqMesh m, RcTree tr) {
@@ -435,6 +436,7 @@ __global__ __launch_bounds__(256) void k_raycast(SqMesh m, RcTree tr, const floa
     out[2 * k + 1] = make_float4(o[4], o[5], o[6], o[7]);
     if (hit) hit[k] = make_int2(h[0], h[1]);
 }
+#endif  // MW_RC_NO_KERNELS
 #endif
 
 }  // namespace mw

@@ -484,11 +484,12 @@ mw_status mw_ocean_step_bodies(mw_ocean* o, int32_t frame, const float* hull_xyz
 // ---- raycasts (csrc/raycast.h) -------------------------------------------------------------------------------------
 // The surface query's validation and mesh (query_prepare, world mode), then the hierarchy of that mesh into the handle's tree buffer
 // (k_rc_build_leaves, and k_rc_build_top for trees deeper than 4 levels) and one lane per ray (k_raycast), all on the handle's stream.
-// A periodic handle is refused: a ray can cross any number of tiles, and ordering hits across displaced tiles is not built yet.
+// A periodic handle is refused: this cast reads the one footprint.  The tiled surface has its own entry point, mw_ocean_raycast_tiled.
 static mw_status raycast_prepare(mw_ocean* o, int32_t frame, const void* rays, int64_t n, const void* out, const char* who, SqMesh* m) {
     mw_status s = query_prepare(o, frame, MW_QUERY_WORLD, rays, n, 0, out, who, m);
     if (s == MW_OK && m->period != 0.f)
-        return fail(MW_ESTATE, who, "raycasts do not tile yet: the handle is periodic (mw_ocean_set_periodic(o, 0) first)");
+        return fail(MW_ESTATE, who, "raycasts do not tile yet: the handle is periodic (mw_ocean_set_periodic(o, 0) first, or mw_ocean_raycast_tiled "
+                                    "for the tiled surface)");
     return s;
 }
 static mw_status raycast_launch(mw_ocean* o, const SqMesh& m, const void* d_rays, int64_t n, void* d_out, void* d_hit) {
@@ -531,5 +532,67 @@ mw_status mw_ocean_raycast(mw_ocean* o, int32_t frame, const float* rays, int64_
     st.out(&d_out, out, (size_t)n * 8 * sizeof(float));
     st.out(&d_hit, hit, (size_t)n * 2 * sizeof(int32_t));  // optional
     if ((s = st.begin()) != MW_OK || (s = raycast_launch(o, m, d_rays, n, d_out, d_hit)) != MW_OK) return s;
+    return st.finish();
+}
+
+// ---- tiled raycasts (csrc/raycast_tiled.h) ------------------------------------------------------------------------------
+// The entry point names its surface: the handle's periodic switch is neither read nor changed.  Handle rules first (batched, OceanRenderer,
+// a grid that does not repeat), then the arguments and the frame (query_prepare), and the mesh carries the grid's period whatever the switch
+// says.  The hierarchy of one tile goes into the same tree buffer as mw_ocean_raycast's (k_rct_build_leaves in surface_tiled.hip, then
+// k_rc_build_top for trees deeper than 4 levels), then one lane per ray (k_raycast_tiled), all on the handle's stream.
+static mw_status raycast_tiled_prepare(mw_ocean* o, int32_t frame, const void* rays, int64_t n, int32_t reach, const void* out, const char* who,
+                                       SqMesh* m) {
+    if (!o) return fail(MW_EINVAL, who, "NULL handle");
+    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
+        return fail(MW_EINVAL, who, "a batched handle (mw_ocean_create_batch) has no single surface");
+    if (o->sem != MW_SEM_FFTMESH) return fail(MW_ESTATE, who, "an OceanRenderer mesh does not tile (mw_ocean_set_periodic)");
+    if (reach < 0 || reach > MW_RC_MAX_REACH) return fail(MW_EINVAL, who, "reach must be in [0, MW_RC_MAX_REACH]");
+    const float P = grid_period(o);
+    if (P == 0.f)
+        return fail(MW_ENOTCOMMENSURATE, who, "the frame repeats only where unit_width * resolution == length and the resolution is even");
+    mw_status s = query_prepare(o, frame, MW_QUERY_WORLD, rays, n, 0, out, who, m);
+    m->period = P;
+    return s;
+}
+static mw_status raycast_tiled_launch(mw_ocean* o, const SqMesh& m, const void* d_rays, int64_t n, int32_t reach, void* d_out, void* d_hit) {
+    int B = sw(SW_RC_BLOCK);
+    if (B <= 0) B = MW_RC_DEFAULT_BLOCK;
+    const int minB = (m.R - 1) / (1 << MW_RC_MAX_LEVEL) + 1;  // at most 2^MW_RC_MAX_LEVEL leaves per side
+    RcTree tr = rc_tree(nullptr, m.R + 1, B < minB ? minB : B);  // rct_tree: the N x N cells of one tile, grid line N the wrapped line 0
+    mw_status s = grow_reserve(o, o->rc_tree, (size_t)rc_nodes(tr.D) * 8 * sizeof(float), "the raycast hierarchy");
+    if (s != MW_OK) return s;
+    tr.box = static_cast<float*>(o->rc_tree.p);
+    const int T = tr.D >= 4 ? 16 : (1 << tr.D), tiles = (1 << tr.D) / T;
+    HIP_TRY(tiled_raycast_build_leaves(dim3((unsigned)(tiles * tiles)), o->stream, m, tr));
+    if (tr.D > 4) k_rc_build_top<<<dim3(1), dim3(256), 0, o->stream>>>(tr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(tiled_raycast(dim3((unsigned)((n + 255) / 256)), o->stream, m, tr, static_cast<const float4*>(d_rays), n, reach,
+                          static_cast<float4*>(d_out), static_cast<int4*>(d_hit)));
+    return MW_OK;
+}
+
+mw_status mw_ocean_raycast_tiled_device(mw_ocean* o, int32_t frame, const void* d_rays, int64_t n, int32_t reach, void* d_out, void* d_hit) {
+    const char* who = "mw_ocean_raycast_tiled_device";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (n > 0 && (misaligned(d_rays, 16) || misaligned(d_out, 16) || misaligned(d_hit, 16)))
+        return fail(MW_EINVAL, who, "d_rays, d_out and d_hit must be 16-byte aligned");
+    SqMesh m{};
+    mw_status s = raycast_tiled_prepare(o, frame, d_rays, n, reach, d_out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    return raycast_tiled_launch(o, m, d_rays, n, reach, d_out, d_hit);
+}
+
+mw_status mw_ocean_raycast_tiled(mw_ocean* o, int32_t frame, const float* rays, int64_t n, int32_t reach, float* out, int32_t* hit) {
+    const char* who = "mw_ocean_raycast_tiled";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    SqMesh m{};
+    mw_status s = raycast_tiled_prepare(o, frame, rays, n, reach, out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    void *d_rays, *d_out, *d_hit;
+    Stage st(o);
+    st.in(&d_rays, rays, (size_t)n * 8 * sizeof(float));
+    st.out(&d_out, out, (size_t)n * 8 * sizeof(float));
+    st.out(&d_hit, hit, (size_t)n * 4 * sizeof(int32_t));  // optional
+    if ((s = st.begin()) != MW_OK || (s = raycast_tiled_launch(o, m, d_rays, n, reach, d_out, d_hit)) != MW_OK) return s;
     return st.finish();
 }

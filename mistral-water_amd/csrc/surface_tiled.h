@@ -3,11 +3,14 @@
 // functions of surface_query.h, hull_forces.h and rigid_bodies.h without floating-point contraction: the tiled services are the
 // strict float32 the g++ build of the same functions computes (tests/periodic_shim.cpp), bit for bit, as raycast.h is.  The SqMesh
 // instantiations stay in mistral_water.hip, compiled as they always were, so a handle with the switch off keeps its bits.
+// The tiled raycast (raycast_tiled.h, mw_ocean_raycast_tiled) has its kernels here for the same reason: sq_shift, sq_reduce and the
+// column planes of its walk must round as the g++ build rounds them (tests/raycast_tiled_shim.cpp).
 //
 // Each function enqueues on `s` with the grids the caller worked out (surface_services.inc: the same as for SqMesh) and returns
 // hipGetLastError().  Internal to the library: hidden from its exported symbols.
 #pragma once
 #include "rigid_bodies.h"
+#include "raycast.h"  // RcTree
 
 namespace mw {
 #define MW_INTERNAL __attribute__((visibility("hidden")))
@@ -19,4 +22,9 @@ MW_INTERNAL hipError_t tiled_hull_forces(dim3 vertices, dim3 triangles, dim3 red
 MW_INTERNAL hipError_t tiled_bodies_integrate(dim3 grid, hipStream_t s, const BodiesArgs& a);
 // k_bodies_step with `lds` bytes of dynamic LDS, at most lds_max (set as the kernel's attribute once per device)
 MW_INTERNAL hipError_t tiled_bodies_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const BodiesArgs& a);
+// k_rct_build_leaves: the leaf boxes of one tile and the levels above them up to D - 4 (k_rc_build_top, launched by the caller, does the
+// rest); k_raycast_tiled: one lane per ray.  m.period is the tiling's P.
+MW_INTERNAL hipError_t tiled_raycast_build_leaves(dim3 grid, hipStream_t s, const SqMesh& m, const RcTree& tr);
+MW_INTERNAL hipError_t tiled_raycast(dim3 grid, hipStream_t s, const SqMesh& m, const RcTree& tr, const float4* rays, int64_t n, int reach,
+                                     float4* out, int4* hit);
 }  // namespace mw

@@ -6,7 +6,9 @@
 #include "mw_host.h"  // AttrOnce
 #include "mw_math.h"
 #pragma clang fp contract(off)
+#define MW_RC_NO_KERNELS  // k_raycast and the two build kernels are mistral_water.hip's
 #include "surface_tiled.h"
+#include "raycast_tiled.h"
 
 namespace mw {
 
@@ -39,6 +41,17 @@ hipError_t tiled_bodies_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, 
     const hipError_t e = attr.set(reinterpret_cast<const void*>(k_bodies_step<SqTiled>), lds_max);
     if (e != hipSuccess) return e;
     k_bodies_step<<<grid, dim3(MW_HULL_CHUNK), lds, s>>>(bodies_args_tiled(a));
+    return hipGetLastError();
+}
+
+hipError_t tiled_raycast_build_leaves(dim3 grid, hipStream_t s, const SqMesh& m, const RcTree& tr) {
+    k_rct_build_leaves<<<grid, dim3(256), 0, s>>>(m, tr);
+    return hipGetLastError();
+}
+
+hipError_t tiled_raycast(dim3 grid, hipStream_t s, const SqMesh& m, const RcTree& tr, const float4* rays, int64_t n, int reach, float4* out,
+                         int4* hit) {
+    k_raycast_tiled<<<grid, dim3(256), 0, s>>>(m, tr, rays, n, reach, out, hit);
     return hipGetLastError();
 }
 

@@ -23,6 +23,7 @@ MW_OUT_WHITE_SCALAR, MW_OUT_COLOR_RGBA = 0, 1
 MW_QUERY_REST, MW_QUERY_WORLD = 0, 1
 MW_HULL_NCOEFFS = 5
 MW_BODY_NMASS = 8
+MW_RC_DEFAULT_REACH, MW_RC_MAX_REACH = 16, 1024
 STATUS_NAMES = {0: "MW_OK", 1: "MW_EINVAL", 2: "MW_ENOTPOW2", 3: "MW_ENOTCOMMENSURATE", 4: "MW_ENOMEM",
                 5: "MW_EDEVICE", 6: "MW_ESTATE"}
 
@@ -219,6 +220,8 @@ def lib():
                                                   C.c_int32, C.c_int32, vp]),
         "mw_ocean_raycast": (C.c_int, [vp, C.c_int32, f32p, C.c_int64, f32p, i32p]),
         "mw_ocean_raycast_device": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, vp]),
+        "mw_ocean_raycast_tiled": (C.c_int, [vp, C.c_int32, f32p, C.c_int64, C.c_int32, f32p, i32p]),
+        "mw_ocean_raycast_tiled_device": (C.c_int, [vp, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp]),
         "mw_ocean_profile_kernels": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
         "mw_ocean_profile_kernels_stats": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
         "mw_gerstner_displace": (C.c_int, [f32p, C.c_int64, f32p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
@@ -269,7 +272,7 @@ ABI_SYMBOLS = [
     "mw_ocean_displace_mesh", "mw_ocean_displace_mesh_device", "mw_ocean_query_surface", "mw_ocean_query_surface_device",
     "mw_ocean_velocity", "mw_ocean_velocity_device", "mw_ocean_query_velocity", "mw_ocean_query_velocity_device",
     "mw_ocean_hull_forces", "mw_ocean_hull_forces_device", "mw_hull_mass_properties", "mw_ocean_step_bodies", "mw_ocean_step_bodies_device",
-    "mw_ocean_raycast", "mw_ocean_raycast_device",
+    "mw_ocean_raycast", "mw_ocean_raycast_device", "mw_ocean_raycast_tiled", "mw_ocean_raycast_tiled_device",
     "mw_gerstner_displace",
     "mw_gerstner_displace_device", "mw_gerstner_displace_steps_device", "mw_gerstner_max_steps", "mw_pond_displace", "mw_pond_displace_device",
 ]

@@ -95,7 +95,8 @@ class Ocean:
     def set_periodic(self, on: bool = True):
         """The surface services (query_surface, query_velocity, hull_forces, step_bodies) read the infinite tiling of the FFTMesh
         frame instead of the one footprint (mw_ocean_set_periodic).  MW_ENOTCOMMENSURATE unless unit_width * N == length with N even;
-        MW_ESTATE on an OceanRenderer handle; raycasts refuse a periodic handle."""
+        MW_ESTATE on an OceanRenderer handle.  raycast() reads the one footprint and refuses a periodic handle; raycast_tiled() casts
+        on the tiling whatever the switch says."""
         nat.check(nat.lib().mw_ocean_set_periodic(self._h, 1 if on else 0))
 
     def _get_periodic(self):
@@ -416,6 +417,25 @@ class Ocean:
         asynchronous on the handle's stream (synchronize() or the stream before reading d_out)."""
         nat.check(nat.lib().mw_ocean_raycast_device(self._h, int(frame), C.c_void_p(d_rays), int(n), C.c_void_p(d_out),
                                                      C.c_void_p(d_hit) if d_hit else None))
+
+    # -- tiled raycasts (mw_ocean_raycast_tiled) -------------------------------------------------
+    def raycast_tiled(self, origins, directions, tmin=0.0, tmax=np.inf, reach: int = nat.MW_RC_DEFAULT_REACH, frame: int = -1):
+        """First hit of the rays on the infinite tiling of the FFTMesh frame (the surface of set_periodic, whatever the switch says),
+        among the (2 reach + 1)^2 tiles around the tile of each ray's origin -> (out [n, 8] float32 rows (t, px, py, pz, nx, ny, nz,
+        white), hit [n, 4] int32 rows (tiled triangle id = 2 (ai N + aj) + upper, facing, tile x, tile z)).  A miss: t = +inf, NaN,
+        (-1, 0, 0, 0); out of reach (nothing hit and the ray left the window's reach inside [tmin, tmax] and the surface's height range):
+        the same with id -2; an invalid ray: NaN, (-1, 0, 0, 0).  MW_ENOTCOMMENSURATE unless the grid repeats (period > 0)."""
+        rays = self.pack_rays(origins, directions, tmin, tmax)
+        out = np.empty((rays.shape[0], 8), np.float32)
+        hit = np.empty((rays.shape[0], 4), np.int32)
+        nat.check(nat.lib().mw_ocean_raycast_tiled(self._h, int(frame), _p(rays), rays.shape[0], int(reach), _p(out), _p(hit)))
+        return out, hit
+
+    def raycast_tiled_device(self, d_rays: int, n: int, d_out: int, d_hit: int = 0, reach: int = nat.MW_RC_DEFAULT_REACH, frame: int = -1):
+        """Device-pointer form: d_rays [n][8] and d_out [n][8] float32, d_hit [n][4] int32 (0 = none), all 16-byte aligned; asynchronous
+        on the handle's stream (synchronize() or the stream before reading d_out)."""
+        nat.check(nat.lib().mw_ocean_raycast_tiled_device(self._h, int(frame), C.c_void_p(d_rays), int(n), int(reach), C.c_void_p(d_out),
+                                                           C.c_void_p(d_hit) if d_hit else None))
 
     # -- floating bodies (mw_ocean_step_bodies) --------------------------------------------------
     def step_bodies(self, hull_xyz, triangles, bodies, mass, dt, substeps: int = 1, density=1000.0, gravity=9.81, linear_drag=0.0,
