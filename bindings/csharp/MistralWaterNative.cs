@@ -26,6 +26,7 @@ public static class MistralWaterNative
     public const int HullNCoeffs = 5;
     public const int BodyNMass = 8;
     public const int RcDefaultReach = 16, RcMaxReach = 1024;
+    public const int FleetMaxHulls = 32, FleetNHull = 5;
 
     [StructLayout(LayoutKind.Sequential)]   // mw_params: 56 bytes
     public struct Params
@@ -134,6 +135,13 @@ public static class MistralWaterNative
     [DllImport(Lib)] public static extern Status mw_hull_mass_properties(float[] hullXyz, int nverts, int[] triangles, int ntris, float density, [Out] float[] massProperties);
     [DllImport(Lib)] public static extern Status mw_ocean_step_bodies(IntPtr ocean, int frame, float[] hullXyz, int nverts, int[] triangles, int ntris, [In] [Out] float[] bodies, float[] mass, int nbodies, float[] coeffs, float dt, int substeps, int iterations, [Out] float[] result);
     [DllImport(Lib)] public static extern Status mw_ocean_step_bodies_device(IntPtr ocean, int frame, IntPtr dHullXyz, int nverts, IntPtr dTriangles, int ntris, IntPtr dBodies, IntPtr dMass, int nbodies, float[] coeffs, float dt, int substeps, int iterations, IntPtr dResult);
+    // mixed fleets: every hull's geometry concatenated (triangle indices local to their hull), hulls [nhulls][FleetNHull] = (vertFirst, nverts,
+    // triFirst, ntris, nbodies), coeffs [nhulls][HullNCoeffs]; bodies, mass, wrench [totalBodies][8] = (Fx, Fy, Fz, _, tx, ty, tz, _) or null
+    // and result hull after hull in table order; a body's row and state have the bits of the single-hull call on its hull alone
+    [DllImport(Lib)] public static extern Status mw_ocean_fleet_forces(IntPtr ocean, int frame, float[] hullXyz, int totalVerts, int[] triangles, int totalTris, int[] hulls, int nhulls, float[] bodies, int totalBodies, float[] coeffs, int iterations, [Out] float[] result);
+    [DllImport(Lib)] public static extern Status mw_ocean_fleet_forces_device(IntPtr ocean, int frame, IntPtr dHullXyz, int totalVerts, IntPtr dTriangles, int totalTris, int[] hulls, int nhulls, IntPtr dBodies, int totalBodies, float[] coeffs, int iterations, IntPtr dResult);
+    [DllImport(Lib)] public static extern Status mw_ocean_step_fleet(IntPtr ocean, int frame, float[] hullXyz, int totalVerts, int[] triangles, int totalTris, int[] hulls, int nhulls, [In] [Out] float[] bodies, float[] mass, float[] wrench, int totalBodies, float[] coeffs, float dt, int substeps, int iterations, [Out] float[] result);
+    [DllImport(Lib)] public static extern Status mw_ocean_step_fleet_device(IntPtr ocean, int frame, IntPtr dHullXyz, int totalVerts, IntPtr dTriangles, int totalTris, int[] hulls, int nhulls, IntPtr dBodies, IntPtr dMass, IntPtr dWrench, int totalBodies, float[] coeffs, float dt, int substeps, int iterations, IntPtr dResult);
     // raycasts: rays [n][8] = (ox, oy, oz, tmin, dx, dy, dz, tmax) -> result [n][8] = (t, px, py, pz, nx, ny, nz, white), hit [n][2] =
     // (triangle, facing) or null; a miss: t = +infinity, an invalid ray: NaN
     [DllImport(Lib)] public static extern Status mw_ocean_raycast(IntPtr ocean, int frame, float[] rays, long n, [Out] float[] result, [Out] int[] hit);

@@ -443,6 +443,65 @@ mw_status mw_ocean_step_bodies_device(mw_ocean* o, int32_t frame, const void* d_
                                       int32_t ntris, void* d_bodies, const void* d_mass, int32_t nbodies, const float* coeffs,
                                       float dt, int32_t substeps, int32_t iterations, void* d_out);
 
+/* ---- mixed fleets: forces and stepping for many hull shapes in one call ---------------------------------------------
+ * mw_ocean_fleet_forces and mw_ocean_step_fleet are mw_ocean_hull_forces and mw_ocean_step_bodies for a whole scene: up to
+ *   MW_FLEET_MAX_HULLS hull shapes, each with its own coefficients and its own bodies, in one call.  The velocity field (drag on) is
+ *   computed once per call and every substep takes one set of launches, whatever the number of shapes.
+ * Geometry: hull_xyz [total_verts][3] and triangles [total_tris][3] hold every hull's geometry, concatenated.  Triangle indices are
+ *   local to their hull, in [0, nverts_h).  Two hulls may share a vertex or a triangle range.
+ * hulls [nhulls][MW_FLEET_NHULL] = vert_first, nverts, tri_first, ntris, nbodies: a HOST array in both forms, like coeffs.  nhulls in
+ *   [1, MW_FLEET_MAX_HULLS]; each range inside its array; nverts >= 3, ntris >= 1; nbodies >= 0 (a hull without bodies is allowed); the
+ *   hulls' nbodies add up to total_bodies.
+ * Per-body arrays: the bodies lie hull after hull in table order in bodies [total_bodies][16], mass [total_bodies][MW_BODY_NMASS],
+ *   wrench [total_bodies][8] and out [total_bodies][8]; a row means what it means in the single-hull entry points (out of step_fleet is
+ *   optional, NULL allowed).
+ * coeffs [nhulls][MW_HULL_NCOEFFS]: a HOST array, one row of density, gravity, linear_drag, quadratic_drag, velocity_scale per hull.
+ *   Drag is on for the call when any hull's row has drag: the frame and state rules are then mw_ocean_query_velocity's, MW_ESTATE
+ *   included, otherwise mw_ocean_query_surface's.  A hull whose own row has no drag reads no velocity.
+ * The defining property: the out row of a body, and after step_fleet its state, has the bits mw_ocean_hull_forces or
+ *   mw_ocean_step_bodies gives on that body's hull alone with that hull's coeffs row and the same frame, iterations, dt and substeps --
+ *   in the host and device forms, on periodic and non-periodic handles, in both semantics.  A row therefore does not depend on which
+ *   other hulls and bodies are in the fleet, or on their order.
+ * wrench (step_fleet; optional, NULL = none): per body Fx Fy Fz _ tx ty tz _, an external force and a torque about p in world axes,
+ *   constant over the call's substeps.  It is added to the water row before steps 2 and 3 of the integrator (F[k] + wrench[k] and
+ *   tau[k] + wrench[4+k], one float32 add each); out still reports the water row alone.  With wrench == NULL there is no addition and
+ *   the bits are mw_ocean_step_bodies'; an all-zero wrench promises nothing (-0 + 0 changes a sign).  A non-finite wrench row is
+ *   treated like an invalid mass row: the host form returns MW_EINVAL naming the body, the device form gives that body a NaN out row
+ *   and leaves its state unchanged.
+ * Failures stay local: the NaN-row rule and the invalid-mass rule of mw_ocean_step_bodies apply per body.  In the device forms a
+ *   triangle index outside [0, nverts_h) makes NaN rows for the bodies of that hull only; the host forms check every hull's indices
+ *   and return MW_EINVAL naming the hull.  A body off the one footprint of a non-periodic handle is NOT a NaN row: as in the
+ *   single-hull calls the world-mode walk clamps to the mesh's edge, the row is that of the edge's water and its residual is the
+ *   distance to it; the other bodies are not affected.  On a periodic handle the body is in another tile.
+ * Plans: on a periodic handle mw_ocean_step_fleet follows mw_ocean_step_bodies' plan rule hull by hull (hulls of fewer than 4 chunks
+ *   of 256 triangles and vertices in one launch for all substeps, the others per substep).  On a non-periodic handle it always
+ *   steps per substep, whatever the library's plan switch says: the bits are the same, but for a fleet of one or two small hull
+ *   shapes the call is slower than mw_ocean_step_bodies on each (DESIGN.md section 7i has the figures).
+ * MW_EINVAL for a broken hull-table rule; total_bodies, sum nbodies_h * nverts_h or sum nbodies_h * ntris_h above 2^31 - 256; a NULL
+ *   array with total_bodies > 0 (hulls and coeffs always); a negative or non-finite coefficient; a batched handle; and the substeps,
+ *   dt, frame, iterations and alignment rules of the single-hull calls (d_wrench 16-byte aligned).  total_bodies == 0 does nothing.
+ *   Caller arrays are untouched on failure; nothing of the handle's state changes.  The calls share the single-hull calls' buffers. */
+#define MW_FLEET_MAX_HULLS 32
+#define MW_FLEET_NHULL 5   /* hull row: vert_first, nverts, tri_first, ntris, nbodies */
+/* host arrays, synchronous */
+mw_status mw_ocean_fleet_forces(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t total_verts, const int32_t* triangles,
+                                int32_t total_tris, const int32_t* hulls, int32_t nhulls, const float* bodies, int32_t total_bodies,
+                                const float* coeffs, int32_t iterations, float* out);
+/* device arrays, asynchronous on the handle's stream; hulls and coeffs host */
+mw_status mw_ocean_fleet_forces_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t total_verts, const void* d_triangles,
+                                       int32_t total_tris, const int32_t* hulls, int32_t nhulls, const void* d_bodies,
+                                       int32_t total_bodies, const float* coeffs, int32_t iterations, void* d_out);
+/* host arrays, synchronous */
+mw_status mw_ocean_step_fleet(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t total_verts, const int32_t* triangles,
+                              int32_t total_tris, const int32_t* hulls, int32_t nhulls, float* bodies, const float* mass,
+                              const float* wrench, int32_t total_bodies, const float* coeffs, float dt, int32_t substeps,
+                              int32_t iterations, float* out);
+/* device arrays, asynchronous on the handle's stream; hulls and coeffs host */
+mw_status mw_ocean_step_fleet_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t total_verts, const void* d_triangles,
+                                     int32_t total_tris, const int32_t* hulls, int32_t nhulls, void* d_bodies, const void* d_mass,
+                                     const void* d_wrench, int32_t total_bodies, const float* coeffs, float dt, int32_t substeps,
+                                     int32_t iterations, void* d_out);
+
 /* ---- raycasts: where does this ray hit the water? -----------------------------------------------------------------
  * The first hit of each of n rays on the surface mw_ocean_query_surface reads, under its frame rules: FFTMesh frame -1 (the latest
  *   frame); OceanRenderer -1 or frame k of the latest steps call.  Triangles: rest cell (i, j), i along x and j along z, holds the lower

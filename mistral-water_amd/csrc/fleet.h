@@ -1,0 +1,407 @@
+// fleet.h -- mixed fleets: hull forces and floating bodies for many hull shapes in one call (mw_ocean_fleet_forces, mw_ocean_step_fleet,
+// include/mistral_water.h).
+//
+// Up to MW_FLEET_HULLS hulls, their geometry concatenated (hull_xyz [total_verts][3], triangles [total_tris][3] with indices local to
+// their hull), each with its own coefficients and its own count of bodies; the per-body arrays hold the bodies hull after hull.  A
+// body's row and state are those of the single-hull kernels (hull_forces.h, rigid_bodies.h) on its hull alone, bit for bit: every
+// kernel here is its single-hull counterpart with (nverts, ntris, nchunks, coefficients, array offsets) read per work item from the
+// hull table, the same MW_HD functions in the same order (256-triangle chunks in chunk order, the 64-lane shuffle tree, the waves in
+// wave order, the reduce's chunks l, l + 64, ... per lane, the lane tree, hull_row).
+//
+// The table travels by value in the kernel arguments (FleetTable, under 2 KiB): nothing to upload, so a second call enqueued before
+// the first has run reads its own table.  A work index (instance vertex, (body, chunk) or body) maps to (hull, body, item) through
+// the per-hull starts of that space: fleet_map, a loop over the hulls with a uniform index and compare-and-select, so that a lane-varying
+// work index never indexes the table (which would copy it to scratch).
+//
+//   k_fleet_vertices   one lane per instance vertex over all hulls               (k_hull_vertices)
+//   k_fleet_triangles  one 256-lane workgroup per (body, chunk) over all hulls   (k_hull_triangles)
+//   k_fleet_reduce     one wave per body                                         (k_hull_reduce)
+//   k_fleet_integrate  one lane per body, with the wrench                        (k_bodies_integrate)
+//   k_fleet_step       one 256-lane workgroup per body runs every substep        (k_bodies_step; SqTiled only, see below)
+//
+// Operand order.  The SqTiled instantiations are compiled without contraction (surface_tiled.hip), where equal operations give equal
+// bits.  The SqMesh instantiations are compiled with contraction, and there the compiler fuses the FIRST product of a sum of two
+// products, a * b + c * d -> fma(a, b, c * d), after an earlier pass has put the two products in an order of its own: the one defined
+// from values that appear earlier in the kernel comes first.  hull_transform's R[3c] * h[0] + R[3c+1] * h[1] came out as
+// fma(R[3c], h[0], R[3c+1] * h[1]) in a kernel that loads the pose before the hull vertex with the table's values read in between, and
+// as fma(R[3c+1], h[1], R[3c] * h[0]) in k_hull_vertices: rows differed in the last bits.  So the kernels here load in the order that
+// reproduces the single-hull kernels' operand order (checked on the optimised IR: the same sums of products, the same operand first).
+// For two kernels no order of loads reproduced the single-hull sums (hull_transform's, and body_integrate's R^T tau and R dw):
+// k_fleet_step is instantiated for SqTiled only, and on the one footprint a call without a wrench integrates with k_bodies_integrate
+// itself, launched per hull (surface_services.inc: fleet_launch).  There every hull steps through the per-substep kernels, whose bits
+// are those of both of mw_ocean_step_bodies' plans; k_fleet_integrate<SqMesh> runs only with a wrench, where no single-hull call
+// defines the bits.
+//
+// Everything but the __global__ wrappers is MW_HD: tests/fleet_shim.cpp compiles the same functions with g++.
+#pragma once
+#include "rigid_bodies.h"
+
+namespace mw {
+
+#define MW_FLEET_HULLS 32  // MW_FLEET_MAX_HULLS of the ABI
+
+// the three work spaces of a table
+#define MW_FLEET_VERTS 0   // nbodies * nverts:  one item per instance vertex
+#define MW_FLEET_CHUNKS 1  // nbodies * nchunks: one item per (body, chunk)
+#define MW_FLEET_BODIES 2  // nbodies
+
+// one hull as the kernels read it
+struct FleetHull {
+    int vert_first, nverts, tri_first, ntris;  // its ranges of hull_xyz and triangles
+    int nchunks;                               // ceil(max(ntris, nverts) / MW_HULL_CHUNK)
+    int body_first;                            // its first body in the call's per-body arrays (bodies, mass, wrench, out, rows)
+    int first[3];                              // where its work starts in each space of this table
+    HullCoeffs cf;
+    float vscale, g;
+};
+// The hulls of one group of launches.  Every hull of the call has its row; a hull that is not in the group (or has no bodies) has no
+// work: first[s] of the next hull equals its own.
+struct FleetTable {
+    int nhulls;
+    int total[3];  // the size of each space
+    FleetHull hull[MW_FLEET_HULLS];
+};
+
+MW_HD int fleet_chunks(int nverts, int ntris) { return ((ntris > nverts ? ntris : nverts) + MW_HULL_CHUNK - 1) / MW_HULL_CHUNK; }
+
+// Fills the geometry, body_first, first[] and total[] of t from a hull table hulls [nhulls][5] = vert_first, nverts, tri_first, ntris,
+// nbodies (validated by the caller: nhulls in [1, MW_FLEET_HULLS], every sum below 2^31); hull h has work in t only when bit h of
+// `take` is set.  The coefficients are the caller's to fill.
+MW_HD void fleet_table(const int32_t* hulls, int nhulls, uint32_t take, FleetTable* t) {
+    t->nhulls = nhulls;
+    int body = 0, first[3] = {0, 0, 0};
+    for (int h = 0; h < nhulls; h++) {
+        const int32_t* r = hulls + 5 * h;
+        FleetHull& f = t->hull[h];
+        f.vert_first = r[0]; f.nverts = r[1]; f.tri_first = r[2]; f.ntris = r[3];
+        f.nchunks = fleet_chunks(r[1], r[3]);
+        f.body_first = body;
+        for (int s = 0; s < 3; s++) f.first[s] = first[s];
+        const int nb = ((take >> h) & 1u) ? r[4] : 0;
+        first[MW_FLEET_VERTS] += nb * f.nverts;
+        first[MW_FLEET_CHUNKS] += nb * f.nchunks;
+        first[MW_FLEET_BODIES] += nb;
+        body += r[4];
+    }
+    for (int s = 0; s < 3; s++) t->total[s] = first[s];
+}
+
+// Work item w of a space (0 <= w < t.total[space]): its hull, the body within that hull, the item within that body (vertex, chunk, 0)
+// and the hull's row.  The starts are non-decreasing and a hull without work shares its start with the next one, so the last hull
+// whose start is <= w is the one that holds w.  The table is only ever indexed by h, which is uniform.
+struct FleetItem {
+    int hull, body, item;
+    FleetHull row;
+};
+static_assert(sizeof(FleetHull) == 15 * 4, "fleet_map selects FleetHull field by field: a new field needs its line there");
+MW_HD FleetItem fleet_map(const FleetTable& t, int space, int w) {
+    FleetItem it;
+    it.hull = 0;
+    it.row = t.hull[0];
+    for (int h = 1; h < t.nhulls; h++) {
+        const FleetHull r = t.hull[h];
+        const bool in = w >= r.first[space];
+        it.hull = in ? h : it.hull;
+        // field by field: a select of the whole struct goes through memory (136 B of scratch in every kernel)
+        it.row.vert_first = in ? r.vert_first : it.row.vert_first; it.row.nverts = in ? r.nverts : it.row.nverts;
+        it.row.tri_first = in ? r.tri_first : it.row.tri_first;    it.row.ntris = in ? r.ntris : it.row.ntris;
+        it.row.nchunks = in ? r.nchunks : it.row.nchunks;          it.row.body_first = in ? r.body_first : it.row.body_first;
+        for (int s = 0; s < 3; s++) it.row.first[s] = in ? r.first[s] : it.row.first[s];
+        it.row.cf.rho_g = in ? r.cf.rho_g : it.row.cf.rho_g; it.row.cf.lin = in ? r.cf.lin : it.row.cf.lin;
+        it.row.cf.quad = in ? r.cf.quad : it.row.cf.quad;    it.row.cf.drag = in ? r.cf.drag : it.row.cf.drag;
+        it.row.vscale = in ? r.vscale : it.row.vscale;       it.row.g = in ? r.g : it.row.g;
+    }
+    const unsigned per = space == MW_FLEET_VERTS ? (unsigned)it.row.nverts : space == MW_FLEET_CHUNKS ? (unsigned)it.row.nchunks : 1u;
+    const unsigned local = (unsigned)(w - it.row.first[space]);
+    it.body = (int)(local / per);
+    it.item = (int)(local - (unsigned)it.body * per);
+    return it;
+}
+
+// a usable wrench row (Fx Fy Fz _ tx ty tz _): the six entries finite
+MW_HD bool fleet_wrench_valid(const float wrench[8]) {
+    for (int k = 0; k < 3; k++)
+        if (!(fabsf(wrench[k]) <= 3.4e38f && fabsf(wrench[4 + k]) <= 3.4e38f)) return false;
+    return true;
+}
+
+// The row steps 2 and 3 of the integrator see: the water row, and when wrench != nullptr the external force and torque added to it,
+// F[k] + wrench[k] and tau[k] + wrench[4 + k], one float32 add each.  wrench == nullptr: the water row itself, no addition.
+MW_HD void fleet_pushed_row(const float row[8], const float* wrench, float r[8]) {
+    for (int k = 0; k < 8; k++) r[k] = row[k];
+    if (!wrench) return;
+    for (int k = 0; k < 3; k++) {
+        r[k] = row[k] + wrench[k];
+        r[4 + k] = row[4 + k] + wrench[4 + k];
+    }
+}
+// One substep of a body under its water row and its wrench (nullptr: none, and then this is body_integrate on the row).
+MW_HD bool fleet_integrate(float body[16], const float row[8], const float mass[8], const float* wrench, float g, float h) {
+    float r[8];
+    fleet_pushed_row(row, wrench, r);
+    return body_integrate(body, r, mass, g, h);
+}
+
+#if defined(__HIPCC__)
+template <typename Mesh>
+struct FleetArgsT {
+    Mesh m;
+    const float* vel;  // per-vertex water velocity [R*R][3] (some hull has drag), else nullptr
+    int iters;
+    const float* hull;      // [total_verts][3]
+    const int* tris;        // [total_tris][3], indices local to their hull
+    float4* bodies;         // [total_bodies][4] float4; updated in place by the stepping kernels
+    const float4* mass;     // [total_bodies][2]
+    const float4* wrench;   // [total_bodies][2] or nullptr
+    float4* vslab;          // [total[VERTS]][2]
+    float4* part;           // [total[CHUNKS]][2]
+    float4* rows;           // [total_bodies][2]: k_fleet_reduce writes them, k_fleet_integrate reads them
+    float4* out;            // [total_bodies][2] or nullptr (stepping): the row of the last substep
+    float dt;               // h = dt / substeps
+    int substeps;
+    int last;               // k_fleet_integrate: this is the call's last substep (write out)
+    FleetTable t;
+};
+using FleetArgs = FleetArgsT<SqMesh>;
+inline FleetArgsT<SqTiled> fleet_args_tiled(const FleetArgs& a) {
+    return FleetArgsT<SqTiled>{SqTiled{a.m}, a.vel, a.iters, a.hull, a.tris, a.bodies, a.mass, a.wrench, a.vslab, a.part, a.rows, a.out, a.dt,
+                               a.substeps, a.last, a.t};
+}
+
+// One lane per instance vertex of the table (k_hull_vertices per lane): slab row k is vertex `item` of body `body` of its hull.
+template <typename Mesh>
+__global__ __launch_bounds__(256) void k_fleet_vertices(FleetArgsT<Mesh> a) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.t.total[MW_FLEET_VERTS]) return;
+    const FleetItem it = fleet_map(a.t, MW_FLEET_VERTS, (int)k);
+    float body[16], h[3], s[8];
+    // the hull vertex before the pose, and every table value before both: see "operand order" at the top of this file
+    const float* vel = it.row.cf.drag ? a.vel : nullptr;
+    const float vscale = it.row.vscale;
+    for (int c = 0; c < 3; c++) h[c] = a.hull[3 * (size_t)(it.row.vert_first + it.item) + c];
+    hull_load_body(a.bodies + 4 * (size_t)(it.row.body_first + it.body), body);
+    hull_vertex(a.m, vel, vscale, a.iters, body, h, s);
+    a.vslab[2 * k] = make_float4(s[0], s[1], s[2], s[3]);
+    a.vslab[2 * k + 1] = make_float4(s[4], s[5], s[6], s[7]);
+}
+
+// One 256-lane workgroup per (body, chunk) of the table (k_hull_triangles per chunk); workgroups stride over them.
+template <typename Mesh>
+__global__ __launch_bounds__(256) void k_fleet_triangles(FleetArgsT<Mesh> a) {
+    __shared__ float red[MW_HULL_CHUNK / 64][8];
+    const int l = threadIdx.x, lane = l & 63, wave = l >> 6;
+    const int total = a.t.total[MW_FLEET_CHUNKS];
+    for (int blk = blockIdx.x; blk < total; blk += gridDim.x) {
+        const FleetItem it = fleet_map(a.t, MW_FLEET_CHUNKS, blk);
+        const int nverts = it.row.nverts, ntris = it.row.ntris;
+        const size_t b = (size_t)(it.row.body_first + it.body);
+        const float* vs = reinterpret_cast<const float*>(a.vslab + 2 * ((size_t)it.row.first[MW_FLEET_VERTS] + (size_t)it.body * nverts));
+        const int* tris = a.tris + 3 * (size_t)it.row.tri_first;
+        float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float res = 0.f;
+        const int t = it.item * MW_HULL_CHUNK + l;
+        if (t < ntris) {
+            float body[16];
+            hull_load_body(a.bodies + 4 * b, body);
+            const int idx[3] = {tris[3 * (size_t)t], tris[3 * (size_t)t + 1], tris[3 * (size_t)t + 2]};
+            if (!hull_triangle(idx, nverts, vs, body, it.row.cf, acc)) res = NAN;
+        }
+        if (t < nverts) res = hull_max(res, vs[8 * (size_t)t + 7]);
+        for (int off = 32; off > 0; off >>= 1) {
+            for (int k = 0; k < 7; k++) acc[k] += __shfl_down(acc[k], off, 64);
+            res = hull_max(res, __shfl_down(res, off, 64));
+        }
+        if (lane == 0) {
+            for (int k = 0; k < 7; k++) red[wave][k] = acc[k];
+            red[wave][7] = res;
+        }
+        __syncthreads();
+        if (l == 0) {
+            float o[8];
+            for (int k = 0; k < 8; k++) o[k] = red[0][k];
+            for (int w = 1; w < MW_HULL_CHUNK / 64; w++) {
+                for (int k = 0; k < 7; k++) o[k] += red[w][k];
+                o[7] = hull_max(o[7], red[w][7]);
+            }
+            a.part[2 * (size_t)blk] = make_float4(o[0], o[1], o[2], o[3]);
+            a.part[2 * (size_t)blk + 1] = make_float4(o[4], o[5], o[6], o[7]);
+        }
+        __syncthreads();  // red is reused by the next chunk
+    }
+}
+
+// One wave per body of the table (k_hull_reduce per wave): the row goes to rows[body] (fleet forces: rows is the call's out).
+template <typename Mesh>
+__global__ __launch_bounds__(256) void k_fleet_reduce(FleetArgsT<Mesh> a) {
+    const int l = threadIdx.x & 63;
+    const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < a.t.total[MW_FLEET_BODIES]; w += nwaves) {  // wave-uniform
+        const FleetItem it = fleet_map(a.t, MW_FLEET_BODIES, (int)w);
+        const int nchunks = it.row.nchunks;
+        const size_t p = (size_t)it.row.first[MW_FLEET_CHUNKS] + (size_t)it.body * nchunks;
+        float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, res = 0.f;
+        for (int c = l; c < nchunks; c += 64) {
+            const float4 p0 = a.part[2 * (p + c)], p1 = a.part[2 * (p + c) + 1];
+            acc[0] += p0.x; acc[1] += p0.y; acc[2] += p0.z; acc[3] += p0.w;
+            acc[4] += p1.x; acc[5] += p1.y; acc[6] += p1.z;
+            res = hull_max(res, p1.w);
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            for (int k = 0; k < 7; k++) acc[k] += __shfl_down(acc[k], off, 64);
+            res = hull_max(res, __shfl_down(res, off, 64));
+        }
+        if (l == 0) {
+            float o[8];
+            hull_row(acc, res, o);
+            const size_t b = (size_t)(it.row.body_first + it.body);
+            a.rows[2 * b] = make_float4(o[0], o[1], o[2], o[3]);
+            a.rows[2 * b + 1] = make_float4(o[4], o[5], o[6], o[7]);
+        }
+    }
+}
+
+MW_HD void fleet_load_row(const float4* p, float row[8]) {
+    const float4 a = p[0], b = p[1];
+    row[0] = a.x; row[1] = a.y; row[2] = a.z; row[3] = a.w;
+    row[4] = b.x; row[5] = b.y; row[6] = b.z; row[7] = b.w;
+}
+
+// Per-substep plan, after the three kernels above: one lane per body of the table integrates its row (k_bodies_integrate per lane);
+// the last substep also writes out.  Wrench is a template argument, not a branch on a.wrench: the kernel of a call without a wrench
+// holds no trace of one, so that its body_integrate is k_bodies_integrate's operand for operand (see "operand order").
+template <typename Mesh, bool Wrench>
+__global__ __launch_bounds__(256) void k_fleet_integrate(FleetArgsT<Mesh> a) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= a.t.total[MW_FLEET_BODIES]) return;
+    const FleetItem it = fleet_map(a.t, MW_FLEET_BODIES, (int)w);
+    const size_t b = (size_t)(it.row.body_first + it.body);
+    float body[16], mass[8], row[8], wr[8];
+    hull_load_body(a.bodies + 4 * b, body);
+    body_load_mass(a.mass + 2 * b, mass);
+    fleet_load_row(a.rows + 2 * b, row);
+    bool valid = body_mass_valid(mass);
+    if (Wrench) {
+        fleet_load_row(a.wrench + 2 * b, wr);
+        valid = valid && fleet_wrench_valid(wr);
+    }
+    if (!valid) {
+        for (int k = 0; k < 8; k++) row[k] = NAN;
+    } else if (Wrench ? fleet_integrate(body, row, mass, wr, it.row.g, a.dt) : body_integrate(body, row, mass, it.row.g, a.dt)) {
+        for (int k = 0; k < 4; k++) a.bodies[4 * b + k] = make_float4(body[4 * k], body[4 * k + 1], body[4 * k + 2], body[4 * k + 3]);
+    }
+    if (a.last && a.out) {
+        a.out[2 * b] = make_float4(row[0], row[1], row[2], row[3]);
+        a.out[2 * b + 1] = make_float4(row[4], row[5], row[6], row[7]);
+    }
+}
+
+// One-launch plan: one 256-lane workgroup per body of the table runs every substep (k_bodies_step per workgroup, with the wrench).
+// Dynamic LDS: the largest bodies_step_lds of the table's hulls; each workgroup lays out its own hull's slab and partials in it.
+template <typename Mesh>
+__global__ __launch_bounds__(MW_HULL_CHUNK) void k_fleet_step(FleetArgsT<Mesh> a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ float red[MW_HULL_CHUNK / 64][8];
+    __shared__ float pose[16];
+    __shared__ int stop;
+    const FleetItem it = fleet_map(a.t, MW_FLEET_BODIES, (int)blockIdx.x);
+    const int nverts = it.row.nverts, ntris = it.row.ntris, nchunks = it.row.nchunks;
+    const float* hull = a.hull + 3 * (size_t)it.row.vert_first;
+    const int* tris = a.tris + 3 * (size_t)it.row.tri_first;
+    const float* vel = it.row.cf.drag ? a.vel : nullptr;
+    float4* slab = reinterpret_cast<float4*>(smem);  // [nverts][2]
+    float4* part = slab + 2 * (size_t)nverts;        // [nchunks][2]
+    const float* vs = reinterpret_cast<const float*>(slab);
+    const int l = threadIdx.x, lane = l & 63, wave = l >> 6;
+    const size_t b = (size_t)(it.row.body_first + it.body);
+    float body[16], mass[8], row[8], wr[8];
+    hull_load_body(a.bodies + 4 * b, body);
+    body_load_mass(a.mass + 2 * b, mass);
+    bool valid = body_mass_valid(mass);
+    if (a.wrench) {
+        fleet_load_row(a.wrench + 2 * b, wr);
+        valid = valid && fleet_wrench_valid(wr);
+    }
+    if (!valid) {  // uniform over the workgroup
+        if (l == 0 && a.out) {
+            a.out[2 * b] = make_float4(NAN, NAN, NAN, NAN);
+            a.out[2 * b + 1] = make_float4(NAN, NAN, NAN, NAN);
+        }
+        return;
+    }
+    for (int s = 0; s < a.substeps; s++) {
+        // vertices (k_hull_vertices)
+        for (int v = l; v < nverts; v += MW_HULL_CHUNK) {
+            float h[3], sl[8];
+            for (int c = 0; c < 3; c++) h[c] = hull[3 * (size_t)v + c];
+            hull_vertex(a.m, vel, it.row.vscale, a.iters, body, h, sl);
+            slab[2 * v] = make_float4(sl[0], sl[1], sl[2], sl[3]);
+            slab[2 * v + 1] = make_float4(sl[4], sl[5], sl[6], sl[7]);
+        }
+        __syncthreads();
+        // triangles (k_hull_triangles), chunk by chunk
+        for (int c = 0; c < nchunks; c++) {
+            float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            float res = 0.f;
+            const int t = c * MW_HULL_CHUNK + l;
+            if (t < ntris) {
+                const int idx[3] = {tris[3 * (size_t)t], tris[3 * (size_t)t + 1], tris[3 * (size_t)t + 2]};
+                if (!hull_triangle(idx, nverts, vs, body, it.row.cf, acc)) res = NAN;
+            }
+            if (t < nverts) res = hull_max(res, vs[8 * (size_t)t + 7]);
+            for (int off = 32; off > 0; off >>= 1) {
+                for (int k = 0; k < 7; k++) acc[k] += __shfl_down(acc[k], off, 64);
+                res = hull_max(res, __shfl_down(res, off, 64));
+            }
+            if (lane == 0) {
+                for (int k = 0; k < 7; k++) red[wave][k] = acc[k];
+                red[wave][7] = res;
+            }
+            __syncthreads();
+            if (l == 0) {
+                float o[8];
+                for (int k = 0; k < 8; k++) o[k] = red[0][k];
+                for (int w = 1; w < MW_HULL_CHUNK / 64; w++) {
+                    for (int k = 0; k < 7; k++) o[k] += red[w][k];
+                    o[7] = hull_max(o[7], red[w][7]);
+                }
+                part[2 * c] = make_float4(o[0], o[1], o[2], o[3]);
+                part[2 * c + 1] = make_float4(o[4], o[5], o[6], o[7]);
+            }
+            __syncthreads();
+        }
+        // the row (k_hull_reduce) and the integration, in wave 0
+        if (l < 64) {
+            float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, res = 0.f;
+            for (int c = l; c < nchunks; c += 64) {
+                const float4 p0 = part[2 * c], p1 = part[2 * c + 1];
+                acc[0] += p0.x; acc[1] += p0.y; acc[2] += p0.z; acc[3] += p0.w;
+                acc[4] += p1.x; acc[5] += p1.y; acc[6] += p1.z;
+                res = hull_max(res, p1.w);
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                for (int k = 0; k < 7; k++) acc[k] += __shfl_down(acc[k], off, 64);
+                res = hull_max(res, __shfl_down(res, off, 64));
+            }
+            if (l == 0) {
+                hull_row(acc, res, row);
+                const bool ok = a.wrench ? fleet_integrate(body, row, mass, wr, it.row.g, a.dt) : body_integrate(body, row, mass, it.row.g, a.dt);
+                for (int k = 0; k < 16; k++) pose[k] = body[k];
+                stop = ok ? 0 : 1;
+            }
+        }
+        __syncthreads();
+        for (int k = 0; k < 16; k++) body[k] = pose[k];
+        if (stop) break;  // a NaN row: the state stays, and so would every later row
+        __syncthreads();  // pose and stop are written again by the next substep
+    }
+    if (l == 0) {
+        for (int k = 0; k < 4; k++) a.bodies[4 * b + k] = make_float4(body[4 * k], body[4 * k + 1], body[4 * k + 2], body[4 * k + 3]);
+        if (a.out) {
+            a.out[2 * b] = make_float4(row[0], row[1], row[2], row[3]);
+            a.out[2 * b + 1] = make_float4(row[4], row[5], row[6], row[7]);
+        }
+    }
+}
+#endif
+
+}  // namespace mw

@@ -32,6 +32,7 @@
 #include "velocity_kernels.h"
 #include "hull_forces.h"
 #include "rigid_bodies.h"
+#include "fleet.h"
 #include "surface_tiled.h"
 #include "raycast.h"
 static_assert(MW_SQ_REST == MW_QUERY_REST && MW_SQ_WORLD == MW_QUERY_WORLD, "surface_query.h and the ABI name the modes alike");
@@ -102,7 +103,7 @@ static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 namespace {  // internal linkage: at file scope Stage::begin / finish would join the library's exported symbols
 struct Stage {
     struct Region { void** dev; const void* in; void* out; size_t bytes, off; };
-    static constexpr int MAX = 5;
+    static constexpr int MAX = 6;
     mw_ocean* o;
     Region r[MAX];
     int n = 0;
@@ -111,7 +112,7 @@ struct Stage {
     void add(void** dev, const void* in, void* out, size_t bytes) {
         *dev = nullptr;
         if (!in && !out) return;
-        if (n == MAX) std::abort();  // a sixth region is a mistake in this file, never a caller's: stop before writing past r[]
+        if (n == MAX) std::abort();  // a seventh region is a mistake in this file, never a caller's: stop before writing past r[]
         const size_t off = align256(total);
         r[n++] = Region{dev, in, out, bytes, off};
         total = off + bytes;

@@ -1,5 +1,5 @@
 // surface_services.inc -- the host code of the services that read the displaced surface: surface queries, surface velocity, hull
-// forces, floating bodies, raycasts.  Included by mistral_water.hip inside its extern "C" block (one translation unit: the handle, fail,
+// forces, floating bodies, mixed fleets, raycasts.  Included by mistral_water.hip inside its extern "C" block (one translation unit: the handle, fail,
 // HIP_TRY, dmalloc, grow_reserve, Stage and the frame record are file-static there).  Every service is a pair of entry points over a
 // shared prepare (validate, name the mesh of the queried frame) and launch (the kernels, on the handle's stream): the device form
 // checks alignment and launches on the caller's arrays, the host form stages its arrays in the handle's scratch buffer (Stage).
@@ -479,6 +479,248 @@ mw_status mw_ocean_step_bodies(mw_ocean* o, int32_t frame, const float* hull_xyz
     d.hull = d_hull; d.tris = d_tris; d.bodies = d_bodies; d.mass = d_mass; d.out = d_out;
     if ((s = bodies_launch(o, p, d)) != MW_OK) return s;
     return st.finish();
+}
+
+// ---- mixed fleets (csrc/fleet.h) ----------------------------------------------------------------------------------
+static_assert(MW_FLEET_MAX_HULLS == MW_FLEET_HULLS && MW_FLEET_NHULL == 5, "fleet.h and the ABI size the hull table alike");
+// The arguments of a fleet-forces or step-fleet call; as HullCall, the host and the device form differ only in whose pointers it holds.
+// hulls and coeffs are host arrays in both.
+struct FleetCall {
+    const void *hull, *tris; void* bodies; const void *mass, *wrench; void* out;
+    const int32_t* hulls; const float* coeffs;
+    int32_t total_verts, total_tris, nhulls, total_bodies, iterations; float dt; int32_t substeps;
+    bool step;  // mw_ocean_step_fleet: mass is required, out is optional, dt and substeps are read
+};
+// what prepare derives: the mesh of the queried frame, the table of every hull with its coefficients, whether any hull has drag
+struct FleetPlan { SqMesh m; FleetTable all; bool drag; };
+
+// Validates a fleet call (the hull table, the sums, the arrays, every hull's coefficients, the stepping arguments) and names the surface
+// as hull_prepare does: the velocity query's rules when any hull's row has drag, the surface query's otherwise.
+static mw_status fleet_prepare(mw_ocean* o, int32_t frame, const FleetCall& c, const char* who, FleetPlan* p) {
+    if (!o) return fail(MW_EINVAL, who, "NULL handle");
+    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
+        return fail(MW_EINVAL, who, "a batched handle (mw_ocean_create_batch) has no single surface");
+    if (c.step && !(c.substeps >= 1 && c.substeps <= 64)) return fail(MW_EINVAL, who, "substeps must be in [1, 64]");
+    if (c.step && !(c.dt >= 0.f && c.dt <= 3.4e38f)) return fail(MW_EINVAL, who, "dt must be finite and >= 0");
+    if (c.nhulls < 1 || c.nhulls > MW_FLEET_MAX_HULLS) return fail(MW_EINVAL, who, "nhulls must be in [1, MW_FLEET_MAX_HULLS]");
+    if (!c.hulls || !c.coeffs) return fail(MW_EINVAL, who, "NULL hulls or coeffs");
+    if (c.total_bodies < 0 || c.total_verts < 0 || c.total_tris < 0) return fail(MW_EINVAL, who, "total_bodies, total_verts or total_tris < 0");
+    const int64_t lim = ((int64_t)1 << 31) - 256;
+    int64_t nb = 0, nv = 0, nt = 0;
+    for (int h = 0; h < c.nhulls; h++) {
+        const int32_t* r = c.hulls + MW_FLEET_NHULL * h;
+        const std::string hull = "hull " + std::to_string(h);
+        if (r[1] < 3 || r[3] < 1) return fail(MW_EINVAL, who, hull + " needs nverts >= 3 and ntris >= 1");
+        if (r[0] < 0 || (int64_t)r[0] + r[1] > c.total_verts) return fail(MW_EINVAL, who, hull + ": its vertex range lies outside hull_xyz");
+        if (r[2] < 0 || (int64_t)r[2] + r[3] > c.total_tris) return fail(MW_EINVAL, who, hull + ": its triangle range lies outside triangles");
+        if (r[4] < 0) return fail(MW_EINVAL, who, hull + ": nbodies < 0");
+        nb += r[4];
+        nv += (int64_t)r[4] * r[1];
+        nt += (int64_t)r[4] * r[3];
+    }
+    if (nb != c.total_bodies) return fail(MW_EINVAL, who, "the hulls' nbodies must add up to total_bodies");
+    if (nb > lim || nv > lim || nt > lim)
+        return fail(MW_EINVAL, who, "total_bodies and the sums of nbodies * nverts and nbodies * ntris must not exceed 2^31 - 256");
+    if (c.total_bodies > 0 && (!c.hull || !c.tris || !c.bodies || (c.step ? !c.mass : !c.out))) return fail(MW_EINVAL, who, "NULL array");
+    for (int k = 0; k < c.nhulls * MW_HULL_NCOEFFS; k++)
+        if (!(c.coeffs[k] >= 0.f && c.coeffs[k] <= 3.4e38f)) return fail(MW_EINVAL, who, "coefficients must be finite and >= 0");
+    fleet_table(c.hulls, c.nhulls, ~0u, &p->all);
+    p->drag = false;
+    for (int h = 0; h < c.nhulls; h++) {
+        const float* k = c.coeffs + MW_HULL_NCOEFFS * h;
+        FleetHull& f = p->all.hull[h];
+        f.cf.rho_g = k[0] * k[1];
+        f.cf.lin = k[2];
+        f.cf.quad = k[3];
+        f.cf.drag = (k[2] > 0.f || k[3] > 0.f) ? 1 : 0;
+        f.g = k[1];
+        f.vscale = k[4];
+        p->drag = p->drag || f.cf.drag;
+    }
+    const void* mark = c.total_bodies > 0 ? c.bodies : nullptr;
+    return p->drag ? query_velocity_prepare(o, frame, MW_QUERY_WORLD, mark, c.total_bodies, c.iterations, mark, who, &p->m)
+                   : query_prepare(o, frame, MW_QUERY_WORLD, mark, c.total_bodies, c.iterations, mark, who, &p->m);
+}
+// the checks only a host form can make: every hull's triangle indices, and for stepping every mass and wrench row
+static mw_status fleet_check_host(const FleetCall& c, const char* who) {
+    for (int h = 0; h < c.nhulls; h++) {
+        const int32_t* r = c.hulls + MW_FLEET_NHULL * h;
+        if (!triangles_in_range(static_cast<const int32_t*>(c.tris) + 3 * (size_t)r[2], r[3], r[1]))
+            return fail(MW_EINVAL, who, "hull " + std::to_string(h) + ": triangle index outside [0, nverts)");
+    }
+    if (!c.step) return MW_OK;
+    for (int32_t b = 0; b < c.total_bodies; b++) {
+        if (!body_mass_valid(static_cast<const float*>(c.mass) + 8 * (size_t)b))
+            return fail(MW_EINVAL, who, "the mass row of body " + std::to_string(b) +
+                                            " is invalid (m <= 0 or not finite, or I_b not positive definite)");
+        if (c.wrench && !fleet_wrench_valid(static_cast<const float*>(c.wrench) + 8 * (size_t)b))
+            return fail(MW_EINVAL, who, "the wrench row of body " + std::to_string(b) + " is not finite");
+    }
+    return MW_OK;
+}
+
+// the table of the hulls in `take`, with the coefficients prepare worked out
+static FleetTable fleet_group(const FleetPlan& p, const FleetCall& c, uint32_t take) {
+    FleetTable t = p.all;
+    fleet_table(c.hulls, c.nhulls, take, &t);
+    return t;
+}
+// k_fleet_vertices, k_fleet_triangles and k_fleet_reduce over a.t (which has bodies), the slab and the partials in the handle's
+// hull-forces buffer, the rows into a.rows
+static mw_status fleet_rows(mw_ocean* o, FleetArgs& a) {
+    const int64_t nv = a.t.total[MW_FLEET_VERTS], nblk = a.t.total[MW_FLEET_CHUNKS], nb = a.t.total[MW_FLEET_BODIES];
+    const size_t bslab = align256((size_t)nv * 8 * sizeof(float)), bpart = (size_t)nblk * 8 * sizeof(float);
+    mw_status s = grow_reserve(o, o->hull, bslab + bpart, "the hull-forces buffer");
+    if (s != MW_OK) return s;
+    a.vslab = static_cast<float4*>(o->hull.p);
+    a.part = reinterpret_cast<float4*>(static_cast<char*>(o->hull.p) + bslab);
+    const dim3 gv((unsigned)((nv + 255) / 256)), gt((unsigned)std::min<int64_t>(nblk, (int64_t)1 << 20)),
+        gr((unsigned)std::min<int64_t>((nb + 3) / 4, (int64_t)1 << 20));
+    if (a.m.period != 0.f) {
+        HIP_TRY(tiled_fleet_forces(gv, gt, gr, o->stream, a));
+        return MW_OK;
+    }
+    k_fleet_vertices<<<gv, dim3(256), 0, o->stream>>>(a);
+    k_fleet_triangles<<<gt, dim3(MW_HULL_CHUNK), 0, o->stream>>>(a);
+    k_fleet_reduce<<<gr, dim3(256), 0, o->stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return MW_OK;
+}
+// The call on the handle's stream (total_bodies > 0): the velocity field once (some hull has drag); forces: the three kernels over
+// every hull; stepping: the plan rule of bodies_launch per hull -- the hulls of the one-launch plan in one k_fleet_step launch over all
+// their bodies (a periodic handle only), the others through the per-substep launches together.  Bodies do not interact and the surface is frozen, so the two
+// groups are independent.
+static mw_status fleet_launch(mw_ocean* o, const FleetPlan& p, const FleetCall& c) {
+    mw_status s;
+    if (p.drag && (s = velocity_to_handle(o)) != MW_OK) return s;
+    FleetArgs a{};
+    a.m = p.m;
+    a.vel = p.drag ? o->vel.vert : nullptr;
+    a.iters = sq_iters(c.iterations);
+    a.hull = static_cast<const float*>(c.hull); a.tris = static_cast<const int32_t*>(c.tris); a.bodies = static_cast<float4*>(c.bodies);
+    a.mass = static_cast<const float4*>(c.mass); a.wrench = static_cast<const float4*>(c.wrench);
+    a.out = static_cast<float4*>(c.out);
+    if (!c.step) {
+        a.t = p.all;
+        a.rows = a.out;
+        return fleet_rows(o, a);
+    }
+    a.dt = c.dt / (float)c.substeps;
+    a.substeps = c.substeps;
+    const int plan = sw(SW_BODIES_PLAN);
+    uint32_t one = 0;
+    size_t lds = 0;
+    for (int h = 0; h < c.nhulls; h++) {
+        const FleetHull& f = p.all.hull[h];
+        const size_t l = bodies_step_lds(f.nverts, f.nchunks);
+        if (l <= MW_BODIES_LDS_MAX && (plan == 1 || (plan < 0 && bodies_one_launch_rule(f.nchunks)))) {
+            one |= 1u << h;
+            if (c.hulls[MW_FLEET_NHULL * h + 4] > 0) lds = std::max(lds, l);
+        }
+    }
+    // k_fleet_step exists for the tiled surface only (fleet.h, "operand order"): on the one footprint every hull steps per substep,
+    // which has the bits of both of mw_ocean_step_bodies' plans
+    if (a.m.period == 0.f) one = 0;
+    a.t = fleet_group(p, c, one);
+    if (a.t.total[MW_FLEET_BODIES] > 0)
+        HIP_TRY(tiled_fleet_step(dim3((unsigned)a.t.total[MW_FLEET_BODIES]), lds, MW_BODIES_LDS_MAX, o->stream, a));
+    a.t = fleet_group(p, c, ~one);
+    if (a.t.total[MW_FLEET_BODIES] == 0) return MW_OK;
+    if ((s = grow_reserve(o, o->bodies, (size_t)c.total_bodies * 8 * sizeof(float), "the step-bodies row buffer")) != MW_OK) return s;
+    a.rows = static_cast<float4*>(o->bodies.p);
+    for (int k = 0; k < c.substeps; k++) {
+        if ((s = fleet_rows(o, a)) != MW_OK) return s;
+        a.last = k == c.substeps - 1;
+        const dim3 gi((unsigned)(((int64_t)a.t.total[MW_FLEET_BODIES] + 255) / 256));
+        if (a.m.period != 0.f) {
+            HIP_TRY(tiled_fleet_integrate(gi, o->stream, a));
+        } else if (a.wrench) {
+            k_fleet_integrate<SqMesh, true><<<gi, dim3(256), 0, o->stream>>>(a);
+        } else {
+            // the one footprint, no wrench: k_bodies_integrate itself over each hull's bodies -- mw_ocean_step_bodies' bits by
+            // construction, where no k_fleet_integrate reproduced them (fleet.h, "operand order")
+            for (int h = 0; h < a.t.nhulls; h++) {
+                const FleetHull& f = a.t.hull[h];
+                const int64_t nb = (h + 1 < a.t.nhulls ? a.t.hull[h + 1].first[MW_FLEET_BODIES] : a.t.total[MW_FLEET_BODIES]) - f.first[MW_FLEET_BODIES];
+                if (nb == 0) continue;
+                BodiesArgs ba{};
+                ba.h.nbodies = nb;
+                ba.bodies = a.bodies + 4 * (size_t)f.body_first;
+                ba.mass = a.mass + 2 * (size_t)f.body_first;
+                ba.rows = a.rows + 2 * (size_t)f.body_first;
+                ba.out = a.out ? a.out + 2 * (size_t)f.body_first : nullptr;
+                ba.g = f.g; ba.dt = a.dt; ba.substeps = a.substeps; ba.last = a.last;
+                k_bodies_integrate<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, o->stream>>>(ba);
+            }
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return MW_OK;
+}
+
+// the host form of both entry points: validate, stage, launch, copy back
+static mw_status fleet_host(mw_ocean* o, int32_t frame, const FleetCall& c, const char* who) {
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    FleetPlan p{};
+    mw_status s = fleet_prepare(o, frame, c, who, &p);
+    if (s != MW_OK || c.total_bodies == 0) return s;
+    if ((s = fleet_check_host(c, who)) != MW_OK) return s;
+    const size_t nb = (size_t)c.total_bodies;
+    void *d_hull, *d_tris, *d_bodies, *d_mass, *d_wrench, *d_out;
+    Stage st(o);
+    st.in(&d_hull, c.hull, (size_t)c.total_verts * 3 * sizeof(float));
+    st.in(&d_tris, c.tris, (size_t)c.total_tris * 3 * sizeof(int32_t));
+    if (c.step) st.inout(&d_bodies, c.bodies, nb * 16 * sizeof(float));
+    else st.in(&d_bodies, c.bodies, nb * 16 * sizeof(float));
+    st.in(&d_mass, c.mass, nb * 8 * sizeof(float));
+    st.in(&d_wrench, c.wrench, nb * 8 * sizeof(float));  // optional
+    st.out(&d_out, c.out, nb * 8 * sizeof(float));       // optional when stepping
+    if ((s = st.begin()) != MW_OK) return s;
+    FleetCall d = c;
+    d.hull = d_hull; d.tris = d_tris; d.bodies = d_bodies; d.mass = d_mass; d.wrench = d_wrench; d.out = d_out;
+    if ((s = fleet_launch(o, p, d)) != MW_OK) return s;
+    return st.finish();
+}
+// the device form: alignment, validate, launch on the caller's arrays; never waits for the stream
+static mw_status fleet_device(mw_ocean* o, int32_t frame, const FleetCall& c, const char* who) {
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (c.total_bodies > 0 && (misaligned(c.hull, 4) || misaligned(c.tris, 4) || misaligned(c.bodies, 16) || misaligned(c.mass, 16) ||
+                               misaligned(c.wrench, 16) || misaligned(c.out, 16)))
+        return fail(MW_EINVAL, who, "d_hull_xyz and d_triangles must be 4-byte, d_bodies, d_mass, d_wrench and d_out 16-byte aligned");
+    FleetPlan p{};
+    mw_status s = fleet_prepare(o, frame, c, who, &p);
+    if (s != MW_OK || c.total_bodies == 0) return s;
+    return fleet_launch(o, p, c);
+}
+
+mw_status mw_ocean_fleet_forces(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t total_verts, const int32_t* triangles,
+                                int32_t total_tris, const int32_t* hulls, int32_t nhulls, const float* bodies, int32_t total_bodies,
+                                const float* coeffs, int32_t iterations, float* out) {
+    const FleetCall c{hull_xyz, triangles, const_cast<float*>(bodies), nullptr, nullptr, out, hulls, coeffs, total_verts, total_tris, nhulls,
+                      total_bodies, iterations, 0.f, 1, false};
+    return fleet_host(o, frame, c, "mw_ocean_fleet_forces");
+}
+mw_status mw_ocean_fleet_forces_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t total_verts, const void* d_triangles,
+                                       int32_t total_tris, const int32_t* hulls, int32_t nhulls, const void* d_bodies,
+                                       int32_t total_bodies, const float* coeffs, int32_t iterations, void* d_out) {
+    const FleetCall c{d_hull_xyz, d_triangles, const_cast<void*>(d_bodies), nullptr, nullptr, d_out, hulls, coeffs, total_verts, total_tris,
+                      nhulls, total_bodies, iterations, 0.f, 1, false};
+    return fleet_device(o, frame, c, "mw_ocean_fleet_forces_device");
+}
+mw_status mw_ocean_step_fleet(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t total_verts, const int32_t* triangles,
+                              int32_t total_tris, const int32_t* hulls, int32_t nhulls, float* bodies, const float* mass, const float* wrench,
+                              int32_t total_bodies, const float* coeffs, float dt, int32_t substeps, int32_t iterations, float* out) {
+    const FleetCall c{hull_xyz, triangles, bodies, mass, wrench, out, hulls, coeffs, total_verts, total_tris, nhulls, total_bodies, iterations,
+                      dt, substeps, true};
+    return fleet_host(o, frame, c, "mw_ocean_step_fleet");
+}
+mw_status mw_ocean_step_fleet_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t total_verts, const void* d_triangles,
+                                     int32_t total_tris, const int32_t* hulls, int32_t nhulls, void* d_bodies, const void* d_mass,
+                                     const void* d_wrench, int32_t total_bodies, const float* coeffs, float dt, int32_t substeps,
+                                     int32_t iterations, void* d_out) {
+    const FleetCall c{d_hull_xyz, d_triangles, d_bodies, d_mass, d_wrench, d_out, hulls, coeffs, total_verts, total_tris, nhulls, total_bodies,
+                      iterations, dt, substeps, true};
+    return fleet_device(o, frame, c, "mw_ocean_step_fleet_device");
 }
 
 // ---- raycasts (csrc/raycast.h) -------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 // hipGetLastError().  Internal to the library: hidden from its exported symbols.
 #pragma once
 #include "rigid_bodies.h"
+#include "fleet.h"
 #include "raycast.h"  // RcTree
 
 namespace mw {
@@ -22,6 +23,11 @@ MW_INTERNAL hipError_t tiled_hull_forces(dim3 vertices, dim3 triangles, dim3 red
 MW_INTERNAL hipError_t tiled_bodies_integrate(dim3 grid, hipStream_t s, const BodiesArgs& a);
 // k_bodies_step with `lds` bytes of dynamic LDS, at most lds_max (set as the kernel's attribute once per device)
 MW_INTERNAL hipError_t tiled_bodies_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const BodiesArgs& a);
+// the fleet kernels (fleet.h): k_fleet_vertices, k_fleet_triangles, k_fleet_reduce on their three grids; k_fleet_integrate; k_fleet_step
+// with `lds` bytes of dynamic LDS, as tiled_bodies_step
+MW_INTERNAL hipError_t tiled_fleet_forces(dim3 vertices, dim3 triangles, dim3 reduce, hipStream_t s, const FleetArgs& a);
+MW_INTERNAL hipError_t tiled_fleet_integrate(dim3 grid, hipStream_t s, const FleetArgs& a);
+MW_INTERNAL hipError_t tiled_fleet_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const FleetArgs& a);
 // k_rct_build_leaves: the leaf boxes of one tile and the levels above them up to D - 4 (k_rc_build_top, launched by the caller, does the
 // rest); k_raycast_tiled: one lane per ray.  m.period is the tiling's P.
 MW_INTERNAL hipError_t tiled_raycast_build_leaves(dim3 grid, hipStream_t s, const SqMesh& m, const RcTree& tr);

@@ -44,6 +44,28 @@ hipError_t tiled_bodies_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, 
     return hipGetLastError();
 }
 
+hipError_t tiled_fleet_forces(dim3 vertices, dim3 triangles, dim3 reduce, hipStream_t s, const FleetArgs& a) {
+    const FleetArgsT<SqTiled> t = fleet_args_tiled(a);
+    k_fleet_vertices<<<vertices, dim3(256), 0, s>>>(t);
+    k_fleet_triangles<<<triangles, dim3(MW_HULL_CHUNK), 0, s>>>(t);
+    k_fleet_reduce<<<reduce, dim3(256), 0, s>>>(t);
+    return hipGetLastError();
+}
+
+hipError_t tiled_fleet_integrate(dim3 grid, hipStream_t s, const FleetArgs& a) {
+    if (a.wrench) k_fleet_integrate<SqTiled, true><<<grid, dim3(256), 0, s>>>(fleet_args_tiled(a));
+    else k_fleet_integrate<SqTiled, false><<<grid, dim3(256), 0, s>>>(fleet_args_tiled(a));
+    return hipGetLastError();
+}
+
+hipError_t tiled_fleet_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const FleetArgs& a) {
+    static AttrOnce attr;
+    const hipError_t e = attr.set(reinterpret_cast<const void*>(k_fleet_step<SqTiled>), lds_max);
+    if (e != hipSuccess) return e;
+    k_fleet_step<<<grid, dim3(MW_HULL_CHUNK), lds, s>>>(fleet_args_tiled(a));
+    return hipGetLastError();
+}
+
 hipError_t tiled_raycast_build_leaves(dim3 grid, hipStream_t s, const SqMesh& m, const RcTree& tr) {
     k_rct_build_leaves<<<grid, dim3(256), 0, s>>>(m, tr);
     return hipGetLastError();

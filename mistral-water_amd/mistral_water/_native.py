@@ -24,6 +24,7 @@ MW_QUERY_REST, MW_QUERY_WORLD = 0, 1
 MW_HULL_NCOEFFS = 5
 MW_BODY_NMASS = 8
 MW_RC_DEFAULT_REACH, MW_RC_MAX_REACH = 16, 1024
+MW_FLEET_MAX_HULLS, MW_FLEET_NHULL = 32, 5
 STATUS_NAMES = {0: "MW_OK", 1: "MW_EINVAL", 2: "MW_ENOTPOW2", 3: "MW_ENOTCOMMENSURATE", 4: "MW_ENOMEM",
                 5: "MW_EDEVICE", 6: "MW_ESTATE"}
 
@@ -218,6 +219,14 @@ def lib():
                                            C.c_int32, C.c_int32, f32p]),
         "mw_ocean_step_bodies_device": (C.c_int, [vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, f32p, C.c_float,
                                                   C.c_int32, C.c_int32, vp]),
+        "mw_ocean_fleet_forces": (C.c_int, [vp, C.c_int32, f32p, C.c_int32, i32p, C.c_int32, i32p, C.c_int32, f32p, C.c_int32, f32p, C.c_int32,
+                                            f32p]),
+        "mw_ocean_fleet_forces_device": (C.c_int, [vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, i32p, C.c_int32, vp, C.c_int32, f32p,
+                                                   C.c_int32, vp]),
+        "mw_ocean_step_fleet": (C.c_int, [vp, C.c_int32, f32p, C.c_int32, i32p, C.c_int32, i32p, C.c_int32, f32p, f32p, f32p, C.c_int32,
+                                          f32p, C.c_float, C.c_int32, C.c_int32, f32p]),
+        "mw_ocean_step_fleet_device": (C.c_int, [vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, i32p, C.c_int32, vp, vp, vp, C.c_int32, f32p,
+                                                 C.c_float, C.c_int32, C.c_int32, vp]),
         "mw_ocean_raycast": (C.c_int, [vp, C.c_int32, f32p, C.c_int64, f32p, i32p]),
         "mw_ocean_raycast_device": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, vp]),
         "mw_ocean_raycast_tiled": (C.c_int, [vp, C.c_int32, f32p, C.c_int64, C.c_int32, f32p, i32p]),
@@ -272,6 +281,7 @@ ABI_SYMBOLS = [
     "mw_ocean_displace_mesh", "mw_ocean_displace_mesh_device", "mw_ocean_query_surface", "mw_ocean_query_surface_device",
     "mw_ocean_velocity", "mw_ocean_velocity_device", "mw_ocean_query_velocity", "mw_ocean_query_velocity_device",
     "mw_ocean_hull_forces", "mw_ocean_hull_forces_device", "mw_hull_mass_properties", "mw_ocean_step_bodies", "mw_ocean_step_bodies_device",
+    "mw_ocean_fleet_forces", "mw_ocean_fleet_forces_device", "mw_ocean_step_fleet", "mw_ocean_step_fleet_device",
     "mw_ocean_raycast", "mw_ocean_raycast_device", "mw_ocean_raycast_tiled", "mw_ocean_raycast_tiled_device",
     "mw_gerstner_displace",
     "mw_gerstner_displace_device", "mw_gerstner_displace_steps_device", "mw_gerstner_max_steps", "mw_pond_displace", "mw_pond_displace_device",

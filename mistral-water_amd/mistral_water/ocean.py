@@ -468,6 +468,104 @@ class Ocean:
                                                          int(ntris), C.c_void_p(d_bodies), C.c_void_p(d_mass), int(nbodies), _p(cf),
                                                          float(dt), int(substeps), int(iterations), C.c_void_p(d_out or None)))
 
+    # -- mixed fleets (mw_ocean_fleet_forces, mw_ocean_step_fleet) --------------------------------
+    def _fleet_coeffs(self, nhulls, coeffs):
+        """[nhulls, 5] float32 rows (density, gravity, linear_drag, quadratic_drag, velocity_scale): None = water at rest drag (1000,
+        9.81, 0, 0, the default velocity scale) for every hull; one row is broadcast; a NaN velocity_scale means the default."""
+        default = self._hull_coeffs(1000.0, 9.81, 0.0, 0.0, None)
+        if coeffs is None:
+            return np.ascontiguousarray(np.broadcast_to(default, (nhulls, nat.MW_HULL_NCOEFFS)))
+        cf = np.asarray(coeffs, np.float32)
+        cf = np.array(np.broadcast_to(cf.reshape(-1, nat.MW_HULL_NCOEFFS), (nhulls, nat.MW_HULL_NCOEFFS)), np.float32, order="C")  # rows, hull by hull
+        cf[:, 4] = np.where(np.isnan(cf[:, 4]), default[4], cf[:, 4])
+        return cf
+
+    @staticmethod
+    def _fleet_arrays(hull_xyz, triangles, hulls):
+        hull = np.ascontiguousarray(hull_xyz, np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+        table = np.ascontiguousarray(hulls, np.int32).reshape(-1, nat.MW_FLEET_NHULL)
+        return hull, tris, table
+
+    def fleet_forces(self, hull_xyz, triangles, hulls, bodies, coeffs=None, frame: int = -1, iterations: int = 0):
+        """hull_forces for a mixed fleet in one call -> [total_bodies, 8] float32 rows.  hull_xyz, triangles and hulls as pack_fleet
+        makes them (every hull's geometry concatenated, indices local to their hull, hulls [nhulls, 5] = vert_first, nverts, tri_first,
+        ntris, nbodies); bodies [total_bodies, 16] hull after hull in table order; coeffs [nhulls, 5] rows of (density, gravity,
+        linear_drag, quadratic_drag, velocity_scale), one row for all, or None.  A body's row has the bits hull_forces gives on its hull
+        alone; the velocity field is computed once, and only when some hull has drag."""
+        hull, tris, table = self._fleet_arrays(hull_xyz, triangles, hulls)
+        b = np.ascontiguousarray(bodies, np.float32).reshape(-1, 16)
+        cf = self._fleet_coeffs(table.shape[0], coeffs)
+        out = np.empty((b.shape[0], 8), np.float32)
+        nat.check(nat.lib().mw_ocean_fleet_forces(self._h, int(frame), _p(hull), hull.shape[0], _p(tris), tris.shape[0], _p(table),
+                                                   table.shape[0], _p(b), b.shape[0], _p(cf), int(iterations), _p(out)))
+        return out
+
+    def fleet_forces_device(self, d_hull_xyz: int, total_verts: int, d_triangles: int, total_tris: int, hulls, d_bodies: int,
+                            total_bodies: int, d_out: int, coeffs=None, frame: int = -1, iterations: int = 0):
+        """Device-pointer form: the geometry, d_bodies [total_bodies][16] and d_out [total_bodies][8] on the device (16-byte aligned), hulls
+        and coeffs host arrays; asynchronous on the handle's stream.  A triangle index outside its hull's [0, nverts) makes the rows of
+        that hull's bodies NaN."""
+        table = np.ascontiguousarray(hulls, np.int32).reshape(-1, nat.MW_FLEET_NHULL)
+        cf = self._fleet_coeffs(table.shape[0], coeffs)
+        nat.check(nat.lib().mw_ocean_fleet_forces_device(self._h, int(frame), C.c_void_p(d_hull_xyz), int(total_verts),
+                                                          C.c_void_p(d_triangles), int(total_tris), _p(table), table.shape[0],
+                                                          C.c_void_p(d_bodies), int(total_bodies), _p(cf), int(iterations),
+                                                          C.c_void_p(d_out)))
+
+    def step_fleet(self, hull_xyz, triangles, hulls, bodies, mass, dt, substeps: int = 1, wrench=None, coeffs=None, frame: int = -1,
+                   iterations: int = 0, return_forces: bool = False):
+        """step_bodies for a mixed fleet in one call -> bodies [total_bodies, 16] (updated in place when it is a C-contiguous float32
+        array), and with return_forces the water rows [total_bodies, 8] of the last substep.  wrench [total_bodies, 8] = (Fx, Fy, Fz, _,
+        tx, ty, tz, _) or None: an external force and torque about p in world axes, constant over the call, added to the water row of
+        every substep (the returned rows stay the water's alone).  Everything else as fleet_forces and step_bodies; a body's state has
+        the bits step_bodies gives on its hull alone."""
+        hull, tris, table = self._fleet_arrays(hull_xyz, triangles, hulls)
+        b = np.ascontiguousarray(bodies, np.float32).reshape(-1, 16)
+        m = np.ascontiguousarray(mass, np.float32).reshape(-1, nat.MW_BODY_NMASS)
+        w = None if wrench is None else np.ascontiguousarray(wrench, np.float32).reshape(-1, 8)
+        if m.shape[0] != b.shape[0] or (w is not None and w.shape[0] != b.shape[0]):
+            raise ValueError(f"step_fleet: {b.shape[0]} bodies but {m.shape[0]} mass rows"
+                             + ("" if w is None else f" and {w.shape[0]} wrench rows"))
+        cf = self._fleet_coeffs(table.shape[0], coeffs)
+        out = np.empty((b.shape[0], 8), np.float32) if return_forces else None
+        nat.check(nat.lib().mw_ocean_step_fleet(self._h, int(frame), _p(hull), hull.shape[0], _p(tris), tris.shape[0], _p(table),
+                                                 table.shape[0], _p(b), _p(m), _p(w), b.shape[0], _p(cf), float(dt), int(substeps),
+                                                 int(iterations), _p(out)))
+        return (b, out) if return_forces else b
+
+    def step_fleet_device(self, d_hull_xyz: int, total_verts: int, d_triangles: int, total_tris: int, hulls, d_bodies: int, d_mass: int,
+                          total_bodies: int, dt, substeps: int = 1, d_wrench: int = 0, d_out: int = 0, coeffs=None, frame: int = -1,
+                          iterations: int = 0):
+        """Device-pointer form: d_bodies [total_bodies][16] updated in place, d_mass, d_wrench (0 = none) and d_out (0 = none)
+        [total_bodies][8], 16-byte aligned; hulls and coeffs host arrays; asynchronous on the handle's stream.  An invalid mass row or a
+        non-finite wrench row gives that body a NaN row and leaves it unchanged."""
+        table = np.ascontiguousarray(hulls, np.int32).reshape(-1, nat.MW_FLEET_NHULL)
+        cf = self._fleet_coeffs(table.shape[0], coeffs)
+        nat.check(nat.lib().mw_ocean_step_fleet_device(self._h, int(frame), C.c_void_p(d_hull_xyz), int(total_verts),
+                                                        C.c_void_p(d_triangles), int(total_tris), _p(table), table.shape[0],
+                                                        C.c_void_p(d_bodies), C.c_void_p(d_mass), C.c_void_p(d_wrench or None),
+                                                        int(total_bodies), _p(cf), float(dt), int(substeps), int(iterations),
+                                                        C.c_void_p(d_out or None)))
+
+
+def pack_fleet(hulls):
+    """(hull_xyz [total_verts, 3] float32, triangles [total_tris, 3] int32, table [nhulls, 5] int32) of Ocean.fleet_forces / step_fleet
+    from (hull_xyz, triangles, nbodies) triples: the geometry concatenated in order, triangle indices left local to their hull, table
+    rows (vert_first, nverts, tri_first, ntris, nbodies)."""
+    xs, ts, rows = [], [], []
+    v0 = t0 = 0
+    for hull_xyz, triangles, nbodies in hulls:
+        x = np.asarray(hull_xyz, np.float32).reshape(-1, 3)
+        t = np.asarray(triangles, np.int32).reshape(-1, 3)
+        xs.append(x); ts.append(t)
+        rows.append((v0, x.shape[0], t0, t.shape[0], int(nbodies)))
+        v0 += x.shape[0]; t0 += t.shape[0]
+    if not rows:
+        raise ValueError("pack_fleet: no hulls")
+    return (np.ascontiguousarray(np.concatenate(xs)), np.ascontiguousarray(np.concatenate(ts)),
+            np.asarray(rows, np.int32).reshape(-1, nat.MW_FLEET_NHULL))
+
 
 def hull_mass_properties(hull_xyz, triangles, density=1000.0):
     """(mass, centroid [3], inertia [3, 3]) of the closed hull (outward winding) of uniform density: the inertia tensor about the
