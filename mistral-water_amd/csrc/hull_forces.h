@@ -25,6 +25,9 @@ namespace mw {
 
 #define MW_HULL_CHUNK 256  // triangles (and vertices) per k_hull_triangles workgroup
 
+// the chunks of a hull: every triangle and every vertex is in one
+MW_HD int hull_chunks(int nverts, int ntris) { return ((ntris > nverts ? ntris : nverts) + MW_HULL_CHUNK - 1) / MW_HULL_CHUNK; }
+
 // NaN-propagating max: once either side is NaN the result is NaN, whatever the order
 MW_HD float hull_max(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }
 

@@ -98,6 +98,11 @@ MW_HD bool body_integrate(float body[16], const float row[8], const float mass[8
     return true;
 }
 
+// LDS of k_bodies_step beyond its static arrays: the vertex slab and the chunk partials, 32 B each
+inline size_t bodies_step_lds(int nverts, int nchunks) { return ((size_t)nverts + (size_t)nchunks) * 8 * sizeof(float); }
+// dynamic LDS k_bodies_step may take: one MI355X CU's 160 KiB less 1 KiB for its static arrays
+#define MW_BODIES_LDS_MAX (160 * 1024 - 1024)
+
 #if defined(__HIPCC__)
 template <typename Mesh>
 struct BodiesArgsT {
@@ -142,9 +147,6 @@ __global__ __launch_bounds__(256) void k_bodies_integrate(BodiesArgsT<Mesh> a) {
         a.out[2 * b + 1] = make_float4(row[4], row[5], row[6], row[7]);
     }
 }
-
-// LDS of k_bodies_step beyond its static arrays: the vertex slab and the chunk partials, 32 B each
-inline size_t bodies_step_lds(int nverts, int nchunks) { return ((size_t)nverts + (size_t)nchunks) * 8 * sizeof(float); }
 
 // One-launch plan: one 256-lane workgroup per body runs every substep.  Per substep: the vertex phase (k_hull_vertices per lane, into
 // the LDS slab), the triangle phase (k_hull_triangles per chunk, in chunk order, into the LDS partials), the reduce (k_hull_reduce in

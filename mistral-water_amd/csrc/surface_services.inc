@@ -257,7 +257,7 @@ static mw_status hull_prepare(mw_ocean* o, int32_t frame, const HullCall& c, con
     return p->cf.drag ? query_velocity_prepare(o, frame, MW_QUERY_WORLD, mark, c.nbodies, c.iterations, mark, who, &p->m)
                       : query_prepare(o, frame, MW_QUERY_WORLD, mark, c.nbodies, c.iterations, mark, who, &p->m);
 }
-static int hull_chunks(const HullCall& c) { return (std::max(c.ntris, c.nverts) + MW_HULL_CHUNK - 1) / MW_HULL_CHUNK; }
+static int hull_chunks(const HullCall& c) { return hull_chunks(c.nverts, c.ntris); }
 // the kernels' view of a call on device pointers; vslab, part and out are the launch's own (hull_launch)
 static HullArgs hull_args(const mw_ocean* o, const HullPlan& p, const HullCall& c) {
     HullArgs a{};
@@ -335,8 +335,6 @@ mw_status mw_ocean_hull_forces(mw_ocean* o, int32_t frame, const float* hull_xyz
 
 // ---- floating bodies (csrc/rigid_bodies.h) ------------------------------------------------------------------------
 static_assert(MW_BODY_NMASS == 8, "rigid_bodies.h reads 8 floats per mass row");
-// dynamic LDS k_bodies_step may take: one MI355X CU's 160 KiB less 1 KiB for its static arrays
-#define MW_BODIES_LDS_MAX (160 * 1024 - 1024)
 
 mw_status mw_hull_mass_properties(const float* hull_xyz, int32_t nverts, const int32_t* triangles, int32_t ntris, float density,
                                   float* out) {

@@ -11,6 +11,9 @@
 
 using namespace mw;
 
+// the chunks of one hull of a table
+extern "C" int fs_chunks(int nverts, int ntris) { return fleet_chunks(nverts, ntris); }
+
 // fleet_table of hulls [nhulls][5] with the hulls of `take`: total[3] = the sizes of the vertex, chunk and body spaces
 extern "C" void fs_totals(const int32_t* hulls, int nhulls, uint32_t take, int* total) {
     FleetTable t{};

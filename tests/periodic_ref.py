@@ -30,6 +30,10 @@ def build_shim(path):
     L.ps_velocity.argtypes = [i, f, f, vp, vp, i, vp, C.c_int64, i, vp]
     L.ps_hull_forces.argtypes = [i, f, f, vp, vp, i, vp, i, vp, i, vp, i, vp, vp, vp]
     L.ps_step_bodies.argtypes = [i, f, f, vp, vp, i, vp, i, vp, i, vp, vp, i, vp, f, i, i, vp]
+    L.ps_hull_chunks.argtypes = [i, i]
+    L.ps_bodies_step_lds.restype = L.ps_bodies_lds_max.restype = C.c_int64
+    L.ps_bodies_step_lds.argtypes = [i, i]
+    L.ps_bodies_lds_max.argtypes = []
     return L
 
 

@@ -127,6 +127,11 @@ void step_bodies(const Mesh& m, const Call& c, int plan, float* bodies, const fl
 extern "C" float ps_period(int N, float unit_width) { return (float)N * unit_width; }
 extern "C" float ps_rest(int N, float unit_width, int g) { return sq_tiled_rest(N, unit_width, (float)N * unit_width, g); }
 
+// the launch arithmetic of a hull call: its chunks, the dynamic LDS of the one-launch plan and that plan's limit
+extern "C" int ps_hull_chunks(int nverts, int ntris) { return hull_chunks(nverts, ntris); }
+extern "C" int64_t ps_bodies_step_lds(int nverts, int nchunks) { return (int64_t)bodies_step_lds(nverts, nchunks); }
+extern "C" int64_t ps_bodies_lds_max() { return MW_BODIES_LDS_MAX; }
+
 // sq_query_point over n points; period == 0: the one footprint
 extern "C" int ps_query(int R, float unit_width, float period, const float* vert, const float* norm, const float* white, int wstride, int mode,
                         const float* xz, int64_t n, int iters, float* out) {
