@@ -4,9 +4,9 @@
 // Up to MW_FLEET_HULLS hulls, their geometry concatenated (hull_xyz [total_verts][3], triangles [total_tris][3] with indices local to
 // their hull), each with its own coefficients and its own count of bodies; the per-body arrays hold the bodies hull after hull.  A
 // body's row and state are those of the single-hull kernels (hull_forces.h, rigid_bodies.h) on its hull alone, bit for bit: every
-// kernel here is its single-hull counterpart with (nverts, ntris, nchunks, coefficients, array offsets) read per work item from the
-// hull table, the same MW_HD functions in the same order (256-triangle chunks in chunk order, the 64-lane shuffle tree, the waves in
-// wave order, the reduce's chunks l, l + 64, ... per lane, the lane tree, hull_row).
+// kernel here reads (nverts, ntris, nchunks, coefficients, array offsets) per work item from the hull table and then calls what its
+// single-hull counterpart calls: hull_vertex, hull_triangle, hull_chunk_partial, hull_body_sum, hull_row, body_integrate.  The order
+// of a row's sum is hull_forces.h's alone; k_fleet_step repeats only k_bodies_step's phases around those calls.
 //
 // The table travels by value in the kernel arguments (FleetTable, under 2 KiB): nothing to upload, so a second call enqueued before
 // the first has run reads its own table.  A work index (instance vertex, (body, chunk) or body) maps to (hull, body, item) through
@@ -62,7 +62,8 @@ struct FleetTable {
     FleetHull hull[MW_FLEET_HULLS];
 };
 
-MW_HD int fleet_chunks(int nverts, int ntris) { return ((ntris > nverts ? ntris : nverts) + MW_HULL_CHUNK - 1) / MW_HULL_CHUNK; }
+// the chunks of one hull of a table: a fleet's hull is chunked as a single hull is
+MW_HD int fleet_chunks(int nverts, int ntris) { return hull_chunks(nverts, ntris); }
 
 // Fills the geometry, body_first, first[] and total[] of t from a hull table hulls [nhulls][5] = vert_first, nverts, tri_first, ntris,
 // nbodies (validated by the caller: nhulls in [1, MW_FLEET_HULLS], every sum below 2^31); hull h has work in t only when bit h of
@@ -181,15 +182,13 @@ __global__ __launch_bounds__(256) void k_fleet_vertices(FleetArgsT<Mesh> a) {
     for (int c = 0; c < 3; c++) h[c] = a.hull[3 * (size_t)(it.row.vert_first + it.item) + c];
     hull_load_body(a.bodies + 4 * (size_t)(it.row.body_first + it.body), body);
     hull_vertex(a.m, vel, vscale, a.iters, body, h, s);
-    a.vslab[2 * k] = make_float4(s[0], s[1], s[2], s[3]);
-    a.vslab[2 * k + 1] = make_float4(s[4], s[5], s[6], s[7]);
+    hull_store_row(a.vslab + 2 * k, s);
 }
 
 // One 256-lane workgroup per (body, chunk) of the table (k_hull_triangles per chunk); workgroups stride over them.
 template <typename Mesh>
 __global__ __launch_bounds__(256) void k_fleet_triangles(FleetArgsT<Mesh> a) {
-    __shared__ float red[MW_HULL_CHUNK / 64][8];
-    const int l = threadIdx.x, lane = l & 63, wave = l >> 6;
+    const int l = threadIdx.x;
     const int total = a.t.total[MW_FLEET_CHUNKS];
     for (int blk = blockIdx.x; blk < total; blk += gridDim.x) {
         const FleetItem it = fleet_map(a.t, MW_FLEET_CHUNKS, blk);
@@ -207,26 +206,7 @@ __global__ __launch_bounds__(256) void k_fleet_triangles(FleetArgsT<Mesh> a) {
             if (!hull_triangle(idx, nverts, vs, body, it.row.cf, acc)) res = NAN;
         }
         if (t < nverts) res = hull_max(res, vs[8 * (size_t)t + 7]);
-        for (int off = 32; off > 0; off >>= 1) {
-            for (int k = 0; k < 7; k++) acc[k] += __shfl_down(acc[k], off, 64);
-            res = hull_max(res, __shfl_down(res, off, 64));
-        }
-        if (lane == 0) {
-            for (int k = 0; k < 7; k++) red[wave][k] = acc[k];
-            red[wave][7] = res;
-        }
-        __syncthreads();
-        if (l == 0) {
-            float o[8];
-            for (int k = 0; k < 8; k++) o[k] = red[0][k];
-            for (int w = 1; w < MW_HULL_CHUNK / 64; w++) {
-                for (int k = 0; k < 7; k++) o[k] += red[w][k];
-                o[7] = hull_max(o[7], red[w][7]);
-            }
-            a.part[2 * (size_t)blk] = make_float4(o[0], o[1], o[2], o[3]);
-            a.part[2 * (size_t)blk + 1] = make_float4(o[4], o[5], o[6], o[7]);
-        }
-        __syncthreads();  // red is reused by the next chunk
+        hull_chunk_partial(acc, res, a.part + 2 * (size_t)blk);
     }
 }
 
@@ -239,31 +219,14 @@ __global__ __launch_bounds__(256) void k_fleet_reduce(FleetArgsT<Mesh> a) {
         const FleetItem it = fleet_map(a.t, MW_FLEET_BODIES, (int)w);
         const int nchunks = it.row.nchunks;
         const size_t p = (size_t)it.row.first[MW_FLEET_CHUNKS] + (size_t)it.body * nchunks;
-        float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, res = 0.f;
-        for (int c = l; c < nchunks; c += 64) {
-            const float4 p0 = a.part[2 * (p + c)], p1 = a.part[2 * (p + c) + 1];
-            acc[0] += p0.x; acc[1] += p0.y; acc[2] += p0.z; acc[3] += p0.w;
-            acc[4] += p1.x; acc[5] += p1.y; acc[6] += p1.z;
-            res = hull_max(res, p1.w);
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            for (int k = 0; k < 7; k++) acc[k] += __shfl_down(acc[k], off, 64);
-            res = hull_max(res, __shfl_down(res, off, 64));
-        }
+        float acc[7], res;
+        hull_body_sum(a.part, p, nchunks, l, acc, res);
         if (l == 0) {
             float o[8];
             hull_row(acc, res, o);
-            const size_t b = (size_t)(it.row.body_first + it.body);
-            a.rows[2 * b] = make_float4(o[0], o[1], o[2], o[3]);
-            a.rows[2 * b + 1] = make_float4(o[4], o[5], o[6], o[7]);
+            hull_store_row(a.rows + 2 * (size_t)(it.row.body_first + it.body), o);
         }
     }
-}
-
-MW_HD void fleet_load_row(const float4* p, float row[8]) {
-    const float4 a = p[0], b = p[1];
-    row[0] = a.x; row[1] = a.y; row[2] = a.z; row[3] = a.w;
-    row[4] = b.x; row[5] = b.y; row[6] = b.z; row[7] = b.w;
 }
 
 // Per-substep plan, after the three kernels above: one lane per body of the table integrates its row (k_bodies_integrate per lane);
@@ -277,11 +240,11 @@ __global__ __launch_bounds__(256) void k_fleet_integrate(FleetArgsT<Mesh> a) {
     const size_t b = (size_t)(it.row.body_first + it.body);
     float body[16], mass[8], row[8], wr[8];
     hull_load_body(a.bodies + 4 * b, body);
-    body_load_mass(a.mass + 2 * b, mass);
-    fleet_load_row(a.rows + 2 * b, row);
+    hull_load_row(a.mass + 2 * b, mass);
+    hull_load_row(a.rows + 2 * b, row);
     bool valid = body_mass_valid(mass);
     if (Wrench) {
-        fleet_load_row(a.wrench + 2 * b, wr);
+        hull_load_row(a.wrench + 2 * b, wr);
         valid = valid && fleet_wrench_valid(wr);
     }
     if (!valid) {
@@ -289,10 +252,7 @@ __global__ __launch_bounds__(256) void k_fleet_integrate(FleetArgsT<Mesh> a) {
     } else if (Wrench ? fleet_integrate(body, row, mass, wr, it.row.g, a.dt) : body_integrate(body, row, mass, it.row.g, a.dt)) {
         for (int k = 0; k < 4; k++) a.bodies[4 * b + k] = make_float4(body[4 * k], body[4 * k + 1], body[4 * k + 2], body[4 * k + 3]);
     }
-    if (a.last && a.out) {
-        a.out[2 * b] = make_float4(row[0], row[1], row[2], row[3]);
-        a.out[2 * b + 1] = make_float4(row[4], row[5], row[6], row[7]);
-    }
+    if (a.last && a.out) hull_store_row(a.out + 2 * b, row);
 }
 
 // One-launch plan: one 256-lane workgroup per body of the table runs every substep (k_bodies_step per workgroup, with the wrench).
@@ -300,7 +260,6 @@ __global__ __launch_bounds__(256) void k_fleet_integrate(FleetArgsT<Mesh> a) {
 template <typename Mesh>
 __global__ __launch_bounds__(MW_HULL_CHUNK) void k_fleet_step(FleetArgsT<Mesh> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ float red[MW_HULL_CHUNK / 64][8];
     __shared__ float pose[16];
     __shared__ int stop;
     const FleetItem it = fleet_map(a.t, MW_FLEET_BODIES, (int)blockIdx.x);
@@ -311,21 +270,19 @@ __global__ __launch_bounds__(MW_HULL_CHUNK) void k_fleet_step(FleetArgsT<Mesh> a
     float4* slab = reinterpret_cast<float4*>(smem);  // [nverts][2]
     float4* part = slab + 2 * (size_t)nverts;        // [nchunks][2]
     const float* vs = reinterpret_cast<const float*>(slab);
-    const int l = threadIdx.x, lane = l & 63, wave = l >> 6;
+    const int l = threadIdx.x;
     const size_t b = (size_t)(it.row.body_first + it.body);
     float body[16], mass[8], row[8], wr[8];
     hull_load_body(a.bodies + 4 * b, body);
-    body_load_mass(a.mass + 2 * b, mass);
+    hull_load_row(a.mass + 2 * b, mass);
     bool valid = body_mass_valid(mass);
     if (a.wrench) {
-        fleet_load_row(a.wrench + 2 * b, wr);
+        hull_load_row(a.wrench + 2 * b, wr);
         valid = valid && fleet_wrench_valid(wr);
     }
     if (!valid) {  // uniform over the workgroup
-        if (l == 0 && a.out) {
-            a.out[2 * b] = make_float4(NAN, NAN, NAN, NAN);
-            a.out[2 * b + 1] = make_float4(NAN, NAN, NAN, NAN);
-        }
+        for (int k = 0; k < 8; k++) row[k] = NAN;
+        if (l == 0 && a.out) hull_store_row(a.out + 2 * b, row);
         return;
     }
     for (int s = 0; s < a.substeps; s++) {
@@ -334,8 +291,7 @@ __global__ __launch_bounds__(MW_HULL_CHUNK) void k_fleet_step(FleetArgsT<Mesh> a
             float h[3], sl[8];
             for (int c = 0; c < 3; c++) h[c] = hull[3 * (size_t)v + c];
             hull_vertex(a.m, vel, it.row.vscale, a.iters, body, h, sl);
-            slab[2 * v] = make_float4(sl[0], sl[1], sl[2], sl[3]);
-            slab[2 * v + 1] = make_float4(sl[4], sl[5], sl[6], sl[7]);
+            hull_store_row(slab + 2 * v, sl);
         }
         __syncthreads();
         // triangles (k_hull_triangles), chunk by chunk
@@ -348,40 +304,12 @@ __global__ __launch_bounds__(MW_HULL_CHUNK) void k_fleet_step(FleetArgsT<Mesh> a
                 if (!hull_triangle(idx, nverts, vs, body, it.row.cf, acc)) res = NAN;
             }
             if (t < nverts) res = hull_max(res, vs[8 * (size_t)t + 7]);
-            for (int off = 32; off > 0; off >>= 1) {
-                for (int k = 0; k < 7; k++) acc[k] += __shfl_down(acc[k], off, 64);
-                res = hull_max(res, __shfl_down(res, off, 64));
-            }
-            if (lane == 0) {
-                for (int k = 0; k < 7; k++) red[wave][k] = acc[k];
-                red[wave][7] = res;
-            }
-            __syncthreads();
-            if (l == 0) {
-                float o[8];
-                for (int k = 0; k < 8; k++) o[k] = red[0][k];
-                for (int w = 1; w < MW_HULL_CHUNK / 64; w++) {
-                    for (int k = 0; k < 7; k++) o[k] += red[w][k];
-                    o[7] = hull_max(o[7], red[w][7]);
-                }
-                part[2 * c] = make_float4(o[0], o[1], o[2], o[3]);
-                part[2 * c + 1] = make_float4(o[4], o[5], o[6], o[7]);
-            }
-            __syncthreads();
+            hull_chunk_partial(acc, res, part + 2 * c);
         }
         // the row (k_hull_reduce) and the integration, in wave 0
         if (l < 64) {
-            float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, res = 0.f;
-            for (int c = l; c < nchunks; c += 64) {
-                const float4 p0 = part[2 * c], p1 = part[2 * c + 1];
-                acc[0] += p0.x; acc[1] += p0.y; acc[2] += p0.z; acc[3] += p0.w;
-                acc[4] += p1.x; acc[5] += p1.y; acc[6] += p1.z;
-                res = hull_max(res, p1.w);
-            }
-            for (int off = 32; off > 0; off >>= 1) {
-                for (int k = 0; k < 7; k++) acc[k] += __shfl_down(acc[k], off, 64);
-                res = hull_max(res, __shfl_down(res, off, 64));
-            }
+            float acc[7], res;
+            hull_body_sum(part, 0, nchunks, l, acc, res);
             if (l == 0) {
                 hull_row(acc, res, row);
                 const bool ok = a.wrench ? fleet_integrate(body, row, mass, wr, it.row.g, a.dt) : body_integrate(body, row, mass, it.row.g, a.dt);
@@ -396,10 +324,7 @@ __global__ __launch_bounds__(MW_HULL_CHUNK) void k_fleet_step(FleetArgsT<Mesh> a
     }
     if (l == 0) {
         for (int k = 0; k < 4; k++) a.bodies[4 * b + k] = make_float4(body[4 * k], body[4 * k + 1], body[4 * k + 2], body[4 * k + 3]);
-        if (a.out) {
-            a.out[2 * b] = make_float4(row[0], row[1], row[2], row[3]);
-            a.out[2 * b + 1] = make_float4(row[4], row[5], row[6], row[7]);
-        }
+        if (a.out) hull_store_row(a.out + 2 * b, row);
     }
 }
 #endif

@@ -13,11 +13,13 @@
 // Three launches, no atomics, every sum in a fixed order, so a body's row depends on nothing but its own inputs (bitwise the same
 // alone or in a batch of any size):
 //   k_hull_vertices   one lane per instance vertex: pose, sq_locate once, 32 B to the vertex slab (x y z d | ux uy uz residual)
-//   k_hull_triangles  one 256-lane workgroup per (body, chunk of 256 triangles and 256 vertices): per-lane terms, a shuffle tree per
-//                     wave and the four waves in order to one partial row (7 sums, NaN-propagating max residual) per chunk
-//   k_hull_reduce     one wave per body: its chunks in order, a fixed shuffle tree, the row with the NaN rule applied
+//   k_hull_triangles  one 256-lane workgroup per (body, chunk of 256 triangles and 256 vertices): per-lane terms, then
+//                     hull_chunk_partial: one partial row (7 sums, NaN-propagating max residual) per chunk
+//   k_hull_reduce     one wave per body: hull_body_sum over its chunks, the row with the NaN rule applied (hull_row)
+// The order of the sum is written once, in hull_wave_sum, hull_chunk_partial and hull_body_sum below; k_bodies_step (rigid_bodies.h)
+// and the k_fleet_* kernels (fleet.h) call the same three, which is why their rows are these kernels' bit for bit.
 //
-// Everything but the __global__ wrappers is MW_HD: tests/hull_forces_shim.cpp compiles the same functions with g++.
+// Everything but the __global__ wrappers and the three sums is MW_HD: tests/hull_forces_shim.cpp compiles the same functions with g++.
 #pragma once
 #include "surface_query.h"
 
@@ -135,6 +137,12 @@ struct HullCoeffs {
     float rho_g, lin, quad;
     int drag;
 };
+// from the five coefficients of the ABI, k = (density, gravity, linear_drag, quadratic_drag, velocity_scale)
+MW_HD void hull_coeffs(const float k[5], HullCoeffs* cf, float* g, float* vscale) {
+    *cf = HullCoeffs{k[0] * k[1], k[2], k[3], (k[2] > 0.f || k[3] > 0.f) ? 1 : 0};
+    *g = k[1];
+    *vscale = k[4];
+}
 
 // pressure and drag of one submerged sub-triangle about p, added to acc[7] = (Fx, Fy, Fz, area, tx, ty, tz); body[16] as above
 MW_HD void hull_subtriangle(const HullCorner& s0, const HullCorner& s1, const HullCorner& s2, const float body[16], const HullCoeffs& cf,
@@ -249,6 +257,64 @@ MW_HD void hull_load_body(const float4* b, float body[16]) {
         body[4 * k] = v.x; body[4 * k + 1] = v.y; body[4 * k + 2] = v.z; body[4 * k + 3] = v.w;
     }
 }
+// an 8-float row (slab entry, partial, output, mass or wrench row) as two float4
+MW_HD void hull_load_row(const float4* p, float r[8]) {
+    const float4 a = p[0], b = p[1];
+    r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w;
+    r[4] = b.x; r[5] = b.y; r[6] = b.z; r[7] = b.w;
+}
+MW_HD void hull_store_row(float4* p, const float r[8]) {
+    p[0] = make_float4(r[0], r[1], r[2], r[3]);
+    p[1] = make_float4(r[4], r[5], r[6], r[7]);
+}
+
+// The ordered sum of a body's row, the one definition every kernel of hull_forces.h, rigid_bodies.h and fleet.h calls.
+// The shuffle tree of one wave: lane 0 ends with the seven sums and the NaN-propagating max of the 64 lanes.
+__device__ inline void hull_wave_sum(float acc[7], float& res) {
+    for (int off = 32; off > 0; off >>= 1) {
+        for (int k = 0; k < 7; k++) acc[k] += __shfl_down(acc[k], off, 64);
+        res = hull_max(res, __shfl_down(res, off, 64));
+    }
+}
+// The partial row of one chunk from the per-lane terms of a MW_HULL_CHUNK-lane workgroup: the tree of each wave, then thread 0 adds
+// the waves in wave order and stores the row at dst (global memory or LDS).  The waves meet in 128 B of static LDS, free again on
+// return; its rows are float4 pairs, so that each is written and read as two 16-byte accesses however this is inlined.
+__device__ inline void hull_chunk_partial(float acc[7], float res, float4* dst) {
+    __shared__ float4 red[MW_HULL_CHUNK / 64][2];
+    const int l = threadIdx.x;
+    hull_wave_sum(acc, res);
+    if ((l & 63) == 0) {
+        const float o[8] = {acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], acc[6], res};
+        hull_store_row(red[l >> 6], o);
+    }
+    __syncthreads();
+    if (l == 0) {
+        float o[8], r[8];
+        hull_load_row(red[0], o);
+        for (int w = 1; w < MW_HULL_CHUNK / 64; w++) {
+            hull_load_row(red[w], r);
+            for (int k = 0; k < 7; k++) o[k] += r[k];
+            o[7] = hull_max(o[7], r[7]);
+        }
+        hull_store_row(dst, o);
+    }
+    __syncthreads();
+}
+// The sums of one body from its partials, rows first ... first + nchunks - 1 of part, by one wave: lane l takes chunks l, l + 64, ...
+// in order, then the tree.  Lane 0 holds what hull_row takes.
+__device__ inline void hull_body_sum(const float4* part, size_t first, int nchunks, int l, float acc[7], float& res) {
+    for (int k = 0; k < 7; k++) acc[k] = 0.f;
+    res = 0.f;
+    for (int c = l; c < nchunks; c += 64) {
+        float r[8];
+        hull_load_row(part + 2 * (first + c), r);
+        for (int k = 0; k < 7; k++) acc[k] += r[k];
+        res = hull_max(res, r[7]);
+    }
+    hull_wave_sum(acc, res);
+}
+// The per-lane terms before these sums stay in the kernels: k_hull_triangles and k_fleet_triangles load the body only where
+// t < ntris, the one-launch kernels hold it in registers, and one function for both would cost the first two a load or take a functor.
 
 // One lane per instance vertex (n = nbodies * nverts < 2^31): the body's 64 B (shared by the lanes of a body: cache hits), the walk's
 // gathers, two 16-byte stores.
@@ -262,18 +328,15 @@ __global__ __launch_bounds__(256) void k_hull_vertices(HullArgsT<Mesh> a) {
     hull_load_body(a.bodies + 4 * (size_t)b, body);
     for (int c = 0; c < 3; c++) h[c] = a.hull[3 * (size_t)v + c];
     hull_vertex(a.m, a.vel, a.vscale, a.iters, body, h, s);
-    a.vslab[2 * k] = make_float4(s[0], s[1], s[2], s[3]);
-    a.vslab[2 * k + 1] = make_float4(s[4], s[5], s[6], s[7]);
+    hull_store_row(a.vslab + 2 * k, s);
 }
 
 // One 256-lane workgroup per (body, chunk): lane l takes triangle c*256 + l and the residual of vertex c*256 + l (every vertex is
-// counted once, referenced or not).  The 8 values are reduced in a fixed order: a shuffle tree inside each wave, then lane 0 adds the
-// four waves' sums in wave order.  Workgroups stride over the chunks (a 1-D grid of at most 2^20 workgroups); each chunk is done by one
-// workgroup start to finish.
+// counted once, referenced or not); hull_chunk_partial reduces the 8 values.  Workgroups stride over the chunks (a 1-D grid of at most
+// 2^20 workgroups); each chunk is done by one workgroup start to finish.
 template <typename Mesh>
 __global__ __launch_bounds__(256) void k_hull_triangles(HullArgsT<Mesh> a) {
-    __shared__ float red[MW_HULL_CHUNK / 64][8];
-    const int l = threadIdx.x, lane = l & 63, wave = l >> 6;
+    const int l = threadIdx.x;
     const int64_t total = a.nbodies * a.nchunks;
     for (int64_t blk = blockIdx.x; blk < total; blk += gridDim.x) {
         const int64_t b = blk / a.nchunks;
@@ -289,52 +352,22 @@ __global__ __launch_bounds__(256) void k_hull_triangles(HullArgsT<Mesh> a) {
             if (!hull_triangle(idx, a.nverts, vs, body, a.cf, acc)) res = NAN;
         }
         if (t < a.nverts) res = hull_max(res, vs[8 * (size_t)t + 7]);
-        for (int off = 32; off > 0; off >>= 1) {
-            for (int k = 0; k < 7; k++) acc[k] += __shfl_down(acc[k], off, 64);
-            res = hull_max(res, __shfl_down(res, off, 64));
-        }
-        if (lane == 0) {
-            for (int k = 0; k < 7; k++) red[wave][k] = acc[k];
-            red[wave][7] = res;
-        }
-        __syncthreads();
-        if (l == 0) {
-            float o[8];
-            for (int k = 0; k < 8; k++) o[k] = red[0][k];
-            for (int w = 1; w < MW_HULL_CHUNK / 64; w++) {
-                for (int k = 0; k < 7; k++) o[k] += red[w][k];
-                o[7] = hull_max(o[7], red[w][7]);
-            }
-            a.part[2 * blk] = make_float4(o[0], o[1], o[2], o[3]);
-            a.part[2 * blk + 1] = make_float4(o[4], o[5], o[6], o[7]);
-        }
-        __syncthreads();  // red is reused by the next chunk
+        hull_chunk_partial(acc, res, a.part + 2 * blk);
     }
 }
 
-// One wave per body: lane l sums chunks l, l + 64, ... in order, a fixed shuffle tree sums the lanes, lane 0 writes the row.  Waves
-// stride over the bodies (a 1-D grid of at most 2^20 workgroups).
+// One wave per body: hull_body_sum, then lane 0 writes the row.  Waves stride over the bodies (a 1-D grid of at most 2^20 workgroups).
 template <typename Mesh>
 __global__ __launch_bounds__(256) void k_hull_reduce(HullArgsT<Mesh> a) {
     const int l = threadIdx.x & 63;
     const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
     for (int64_t b = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; b < a.nbodies; b += nwaves) {  // wave-uniform
-        float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, res = 0.f;
-        for (int c = l; c < a.nchunks; c += 64) {
-            const float4 p0 = a.part[2 * (b * a.nchunks + c)], p1 = a.part[2 * (b * a.nchunks + c) + 1];
-            acc[0] += p0.x; acc[1] += p0.y; acc[2] += p0.z; acc[3] += p0.w;
-            acc[4] += p1.x; acc[5] += p1.y; acc[6] += p1.z;
-            res = hull_max(res, p1.w);
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            for (int k = 0; k < 7; k++) acc[k] += __shfl_down(acc[k], off, 64);
-            res = hull_max(res, __shfl_down(res, off, 64));
-        }
+        float acc[7], res;
+        hull_body_sum(a.part, b * a.nchunks, a.nchunks, l, acc, res);
         if (l == 0) {
             float o[8];
             hull_row(acc, res, o);
-            a.out[2 * b] = make_float4(o[0], o[1], o[2], o[3]);
-            a.out[2 * b + 1] = make_float4(o[4], o[5], o[6], o[7]);
+            hull_store_row(a.out + 2 * b, o);
         }
     }
 }

@@ -16,9 +16,10 @@
 // Two plans with the same bits (surface_services.inc: bodies_launch, switch MW_BODIES_PLAN):
 //   per substep   hull_launch's three kernels, then k_bodies_integrate (one lane per body), once per substep
 //   one launch    k_bodies_step: one workgroup per body runs every substep; the vertex slab (32 B per vertex), the per-chunk partial
-//                 rows and the pose stay in LDS.  Each phase repeats k_hull_vertices, k_hull_triangles and k_hull_reduce's arithmetic
-//                 and summation order (256-triangle chunks, a shuffle tree per wave, waves in order, chunks per lane in order, the
-//                 same lane tree), so its rows are hull_launch's bit for bit.
+//                 rows and the pose stay in LDS.  Its phases call what k_hull_vertices, k_hull_triangles and k_hull_reduce call
+//                 (hull_vertex, hull_triangle, hull_chunk_partial, hull_body_sum, hull_row), so its rows are hull_launch's bit for
+//                 bit.  k_fleet_step (fleet.h) is the same loop with the hull read from a table and a wrench; the two stay apart
+//                 because k_bodies_step<SqMesh> built from a routine shared with it lost those bits.
 //                 Only workgroup barriers: no flags, no atomics, nothing between workgroups.
 //
 // Everything but the __global__ wrappers is MW_HD: tests/bodies_shim.cpp compiles the same functions with g++.
@@ -120,12 +121,6 @@ inline BodiesArgsT<SqTiled> bodies_args_tiled(const BodiesArgs& a) {
     return BodiesArgsT<SqTiled>{hull_args_tiled(a.h), a.bodies, a.mass, a.rows, a.out, a.g, a.dt, a.substeps, a.last};
 }
 
-MW_HD void body_load_mass(const float4* p, float mass[8]) {
-    const float4 a = p[0], b = p[1];
-    mass[0] = a.x; mass[1] = a.y; mass[2] = a.z; mass[3] = a.w;
-    mass[4] = b.x; mass[5] = b.y; mass[6] = b.z; mass[7] = b.w;
-}
-
 // Per-substep plan, after hull_launch: one lane per body integrates its row; the last substep also writes out.
 template <typename Mesh>
 __global__ __launch_bounds__(256) void k_bodies_integrate(BodiesArgsT<Mesh> a) {
@@ -133,44 +128,36 @@ __global__ __launch_bounds__(256) void k_bodies_integrate(BodiesArgsT<Mesh> a) {
     if (b >= a.h.nbodies) return;
     float body[16], mass[8], row[8];
     hull_load_body(a.bodies + 4 * b, body);
-    body_load_mass(a.mass + 2 * b, mass);
-    const float4 r0 = a.rows[2 * b], r1 = a.rows[2 * b + 1];
-    row[0] = r0.x; row[1] = r0.y; row[2] = r0.z; row[3] = r0.w;
-    row[4] = r1.x; row[5] = r1.y; row[6] = r1.z; row[7] = r1.w;
+    hull_load_row(a.mass + 2 * b, mass);
+    hull_load_row(a.rows + 2 * b, row);
     if (!body_mass_valid(mass)) {
         for (int k = 0; k < 8; k++) row[k] = NAN;
     } else if (body_integrate(body, row, mass, a.g, a.dt)) {
         for (int k = 0; k < 4; k++) a.bodies[4 * b + k] = make_float4(body[4 * k], body[4 * k + 1], body[4 * k + 2], body[4 * k + 3]);
     }
-    if (a.last && a.out) {
-        a.out[2 * b] = make_float4(row[0], row[1], row[2], row[3]);
-        a.out[2 * b + 1] = make_float4(row[4], row[5], row[6], row[7]);
-    }
+    if (a.last && a.out) hull_store_row(a.out + 2 * b, row);
 }
 
 // One-launch plan: one 256-lane workgroup per body runs every substep.  Per substep: the vertex phase (k_hull_vertices per lane, into
-// the LDS slab), the triangle phase (k_hull_triangles per chunk, in chunk order, into the LDS partials), the reduce (k_hull_reduce in
-// wave 0) and, in lane 0, the integration; the new pose goes to every lane through LDS.
+// the LDS slab), the triangle phase (k_hull_triangles per chunk, in chunk order, into the LDS partials), the row (k_hull_reduce) in
+// wave 0 and, in lane 0, the integration; the new pose goes to every lane through LDS.
 template <typename Mesh>
 __global__ __launch_bounds__(MW_HULL_CHUNK) void k_bodies_step(BodiesArgsT<Mesh> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ float red[MW_HULL_CHUNK / 64][8];
     __shared__ float pose[16];
     __shared__ int stop;
     const HullArgsT<Mesh>& ha = a.h;
     float4* slab = reinterpret_cast<float4*>(smem);  // [nverts][2]
     float4* part = slab + 2 * (size_t)ha.nverts;     // [nchunks][2]
     const float* vs = reinterpret_cast<const float*>(slab);
-    const int l = threadIdx.x, lane = l & 63, wave = l >> 6;
+    const int l = threadIdx.x;
     const int64_t b = blockIdx.x;
     float body[16], mass[8], row[8];
     hull_load_body(a.bodies + 4 * b, body);
-    body_load_mass(a.mass + 2 * b, mass);
+    hull_load_row(a.mass + 2 * b, mass);
     if (!body_mass_valid(mass)) {  // uniform over the workgroup
-        if (l == 0 && a.out) {
-            a.out[2 * b] = make_float4(NAN, NAN, NAN, NAN);
-            a.out[2 * b + 1] = make_float4(NAN, NAN, NAN, NAN);
-        }
+        for (int k = 0; k < 8; k++) row[k] = NAN;
+        if (l == 0 && a.out) hull_store_row(a.out + 2 * b, row);
         return;
     }
     for (int s = 0; s < a.substeps; s++) {
@@ -179,8 +166,7 @@ __global__ __launch_bounds__(MW_HULL_CHUNK) void k_bodies_step(BodiesArgsT<Mesh>
             float h[3], sl[8];
             for (int c = 0; c < 3; c++) h[c] = ha.hull[3 * (size_t)v + c];
             hull_vertex(ha.m, ha.vel, ha.vscale, ha.iters, body, h, sl);
-            slab[2 * v] = make_float4(sl[0], sl[1], sl[2], sl[3]);
-            slab[2 * v + 1] = make_float4(sl[4], sl[5], sl[6], sl[7]);
+            hull_store_row(slab + 2 * v, sl);
         }
         __syncthreads();
         // triangles (k_hull_triangles), chunk by chunk
@@ -193,40 +179,12 @@ __global__ __launch_bounds__(MW_HULL_CHUNK) void k_bodies_step(BodiesArgsT<Mesh>
                 if (!hull_triangle(idx, ha.nverts, vs, body, ha.cf, acc)) res = NAN;
             }
             if (t < ha.nverts) res = hull_max(res, vs[8 * (size_t)t + 7]);
-            for (int off = 32; off > 0; off >>= 1) {
-                for (int k = 0; k < 7; k++) acc[k] += __shfl_down(acc[k], off, 64);
-                res = hull_max(res, __shfl_down(res, off, 64));
-            }
-            if (lane == 0) {
-                for (int k = 0; k < 7; k++) red[wave][k] = acc[k];
-                red[wave][7] = res;
-            }
-            __syncthreads();
-            if (l == 0) {
-                float o[8];
-                for (int k = 0; k < 8; k++) o[k] = red[0][k];
-                for (int w = 1; w < MW_HULL_CHUNK / 64; w++) {
-                    for (int k = 0; k < 7; k++) o[k] += red[w][k];
-                    o[7] = hull_max(o[7], red[w][7]);
-                }
-                part[2 * c] = make_float4(o[0], o[1], o[2], o[3]);
-                part[2 * c + 1] = make_float4(o[4], o[5], o[6], o[7]);
-            }
-            __syncthreads();
+            hull_chunk_partial(acc, res, part + 2 * c);
         }
         // the row (k_hull_reduce) and the integration, in wave 0
         if (l < 64) {
-            float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, res = 0.f;
-            for (int c = l; c < ha.nchunks; c += 64) {
-                const float4 p0 = part[2 * c], p1 = part[2 * c + 1];
-                acc[0] += p0.x; acc[1] += p0.y; acc[2] += p0.z; acc[3] += p0.w;
-                acc[4] += p1.x; acc[5] += p1.y; acc[6] += p1.z;
-                res = hull_max(res, p1.w);
-            }
-            for (int off = 32; off > 0; off >>= 1) {
-                for (int k = 0; k < 7; k++) acc[k] += __shfl_down(acc[k], off, 64);
-                res = hull_max(res, __shfl_down(res, off, 64));
-            }
+            float acc[7], res;
+            hull_body_sum(part, 0, ha.nchunks, l, acc, res);
             if (l == 0) {
                 hull_row(acc, res, row);
                 const bool ok = body_integrate(body, row, mass, a.g, a.dt);
@@ -241,10 +199,7 @@ __global__ __launch_bounds__(MW_HULL_CHUNK) void k_bodies_step(BodiesArgsT<Mesh>
     }
     if (l == 0) {
         for (int k = 0; k < 4; k++) a.bodies[4 * b + k] = make_float4(body[4 * k], body[4 * k + 1], body[4 * k + 2], body[4 * k + 3]);
-        if (a.out) {
-            a.out[2 * b] = make_float4(row[0], row[1], row[2], row[3]);
-            a.out[2 * b + 1] = make_float4(row[4], row[5], row[6], row[7]);
-        }
+        if (a.out) hull_store_row(a.out + 2 * b, row);
     }
 }
 #endif

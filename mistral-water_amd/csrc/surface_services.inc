@@ -246,12 +246,7 @@ static mw_status hull_prepare(mw_ocean* o, int32_t frame, const HullCall& c, con
         return fail(MW_EINVAL, who, "nbodies * nverts and nbodies * ntris must not exceed 2^31 - 256");
     for (int k = 0; k < MW_HULL_NCOEFFS; k++)
         if (!(c.coeffs[k] >= 0.f && c.coeffs[k] <= 3.4e38f)) return fail(MW_EINVAL, who, "coefficients must be finite and >= 0");
-    p->cf.rho_g = c.coeffs[0] * c.coeffs[1];
-    p->cf.lin = c.coeffs[2];
-    p->cf.quad = c.coeffs[3];
-    p->cf.drag = (c.coeffs[2] > 0.f || c.coeffs[3] > 0.f) ? 1 : 0;
-    p->g = c.coeffs[1];
-    p->vscale = c.coeffs[4];
+    hull_coeffs(c.coeffs, &p->cf, &p->g, &p->vscale);
     // the surface (and, with drag on, the velocity) of the frame; the markers stand for the query's arrays, checked above
     const void* mark = c.nbodies > 0 ? c.bodies : nullptr;
     return p->cf.drag ? query_velocity_prepare(o, frame, MW_QUERY_WORLD, mark, c.nbodies, c.iterations, mark, who, &p->m)
@@ -270,29 +265,38 @@ static HullArgs hull_args(const mw_ocean* o, const HullPlan& p, const HullCall& 
     a.nverts = c.nverts; a.ntris = c.ntris; a.nchunks = hull_chunks(c); a.nbodies = c.nbodies;
     return a;
 }
-// the three launches on the handle's stream (nbodies > 0), the rows into c.out; the vertex slab and the chunk partials live in the
-// handle's grow-only buffer.
+// The work space of the three hull kernels over nv instance vertices, nblk (body, chunk) items and nb bodies, for hull_launch and
+// fleet_rows: the vertex slab and, 256-byte aligned behind it, the chunk partials in the handle's grow-only buffer, and the three grids
+struct HullWork { float4 *vslab, *part; dim3 gv, gt, gr; };
+static mw_status hull_reserve(mw_ocean* o, int64_t nv, int64_t nblk, int64_t nb, HullWork* w) {
+    const size_t bslab = align256((size_t)nv * 8 * sizeof(float)), bpart = (size_t)nblk * 8 * sizeof(float);
+    mw_status s = grow_reserve(o, o->hull, bslab + bpart, "the hull-forces buffer");
+    if (s != MW_OK) return s;
+    w->vslab = static_cast<float4*>(o->hull.p);
+    w->part = reinterpret_cast<float4*>(static_cast<char*>(o->hull.p) + bslab);
+    w->gv = dim3((unsigned)((nv + 255) / 256));
+    w->gt = dim3((unsigned)std::min<int64_t>(nblk, (int64_t)1 << 20));
+    w->gr = dim3((unsigned)std::min<int64_t>((nb + 3) / 4, (int64_t)1 << 20));
+    return MW_OK;
+}
+// the three launches on the handle's stream (nbodies > 0), the rows into c.out
 // velocity = false: the velocity field of this frame is already in o->vel.vert (mw_ocean_step_bodies computes it once per call)
 static mw_status hull_launch(mw_ocean* o, const HullPlan& p, const HullCall& c, bool velocity = true) {
-    const int nchunks = hull_chunks(c);
-    const size_t bslab = align256((size_t)c.nbodies * c.nverts * 8 * sizeof(float)), bpart = (size_t)c.nbodies * nchunks * 8 * sizeof(float);
-    mw_status s = grow_reserve(o, o->hull, bslab + bpart, "the hull-forces buffer");
+    HullWork w;
+    mw_status s = hull_reserve(o, (int64_t)c.nbodies * c.nverts, (int64_t)c.nbodies * hull_chunks(c), c.nbodies, &w);
     if (s != MW_OK) return s;
     if (velocity && p.cf.drag && (s = velocity_to_handle(o)) != MW_OK) return s;
     HullArgs a = hull_args(o, p, c);
-    a.vslab = static_cast<float4*>(o->hull.p);
-    a.part = reinterpret_cast<float4*>(static_cast<char*>(o->hull.p) + bslab);
+    a.vslab = w.vslab;
+    a.part = w.part;
     a.out = static_cast<float4*>(c.out);
-    const int64_t nv = (int64_t)c.nbodies * c.nverts, nblk = (int64_t)c.nbodies * nchunks;
-    const dim3 gv((unsigned)((nv + 255) / 256)), gt((unsigned)std::min<int64_t>(nblk, (int64_t)1 << 20)),
-        gr((unsigned)std::min<int64_t>(((int64_t)c.nbodies + 3) / 4, (int64_t)1 << 20));
     if (a.m.period != 0.f) {
-        HIP_TRY(tiled_hull_forces(gv, gt, gr, o->stream, a));
+        HIP_TRY(tiled_hull_forces(w.gv, w.gt, w.gr, o->stream, a));
         return MW_OK;
     }
-    k_hull_vertices<<<gv, dim3(256), 0, o->stream>>>(a);
-    k_hull_triangles<<<gt, dim3(MW_HULL_CHUNK), 0, o->stream>>>(a);
-    k_hull_reduce<<<gr, dim3(256), 0, o->stream>>>(a);
+    k_hull_vertices<<<w.gv, dim3(256), 0, o->stream>>>(a);
+    k_hull_triangles<<<w.gt, dim3(MW_HULL_CHUNK), 0, o->stream>>>(a);
+    k_hull_reduce<<<w.gr, dim3(256), 0, o->stream>>>(a);
     HIP_TRY(hipGetLastError());
     return MW_OK;
 }
@@ -393,6 +397,17 @@ static mw_status bodies_prepare(mw_ocean* o, int32_t frame, const HullCall& c, c
 // The plan rule (MW_BODIES_PLAN = -1), DESIGN.md section 7e: one launch for hulls of at most 3 chunks (768 triangles and vertices),
 // per substep above.  Measured: 1024 icospheres (2 chunks) 0.49x the per-substep time; 64 barges (22 chunks) 1.8x.
 static bool bodies_one_launch_rule(int nchunks) { return nchunks < 4; }
+// a hull steps in one launch (k_bodies_step, k_fleet_step): its slab and partials fit in LDS, and the switch asks for it or the rule does
+static bool bodies_one_launch(int nverts, int nchunks) {
+    const int plan = sw(SW_BODIES_PLAN);
+    return bodies_step_lds(nverts, nchunks) <= MW_BODIES_LDS_MAX && (plan == 1 || (plan < 0 && bodies_one_launch_rule(nchunks)));
+}
+// row b of a host array of mass rows, as both host forms of stepping check and report it
+static mw_status mass_row_check(const void* mass, int32_t b, const char* who) {
+    if (body_mass_valid(static_cast<const float*>(mass) + 8 * (size_t)b)) return MW_OK;
+    return fail(MW_EINVAL, who, "the mass row of body " + std::to_string(b) +
+                                    " is invalid (m <= 0 or not finite, or I_b not positive definite)");
+}
 
 // every substep of the call on the handle's stream (nbodies > 0): the velocity field once (drag on), then one k_bodies_step launch, or
 // per substep hull_launch and k_bodies_integrate
@@ -408,9 +423,8 @@ static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c
     a.g = p.g;
     a.dt = c.dt / (float)c.substeps;
     a.substeps = c.substeps;
-    const size_t lds = bodies_step_lds(c.nverts, nchunks);
-    const int plan = sw(SW_BODIES_PLAN);
-    if (lds <= MW_BODIES_LDS_MAX && (plan == 1 || (plan < 0 && bodies_one_launch_rule(nchunks)))) {
+    if (bodies_one_launch(c.nverts, nchunks)) {
+        const size_t lds = bodies_step_lds(c.nverts, nchunks);
         if (a.h.m.period != 0.f) {
             HIP_TRY(tiled_bodies_step(dim3((unsigned)c.nbodies), lds, MW_BODIES_LDS_MAX, o->stream, a));
             return MW_OK;
@@ -462,9 +476,7 @@ mw_status mw_ocean_step_bodies(mw_ocean* o, int32_t frame, const float* hull_xyz
     if (s != MW_OK || nbodies == 0) return s;
     if (!triangles_in_range(triangles, ntris, nverts)) return fail(MW_EINVAL, who, "triangle index outside [0, nverts)");
     for (int32_t b = 0; b < nbodies; b++)
-        if (!body_mass_valid(mass + 8 * (size_t)b))
-            return fail(MW_EINVAL, who, "the mass row of body " + std::to_string(b) +
-                                            " is invalid (m <= 0 or not finite, or I_b not positive definite)");
+        if ((s = mass_row_check(mass, b, who)) != MW_OK) return s;
     void *d_hull, *d_tris, *d_bodies, *d_mass, *d_out;
     Stage st(o);
     st.in(&d_hull, hull_xyz, (size_t)nverts * 3 * sizeof(float));
@@ -525,14 +537,8 @@ static mw_status fleet_prepare(mw_ocean* o, int32_t frame, const FleetCall& c, c
     fleet_table(c.hulls, c.nhulls, ~0u, &p->all);
     p->drag = false;
     for (int h = 0; h < c.nhulls; h++) {
-        const float* k = c.coeffs + MW_HULL_NCOEFFS * h;
         FleetHull& f = p->all.hull[h];
-        f.cf.rho_g = k[0] * k[1];
-        f.cf.lin = k[2];
-        f.cf.quad = k[3];
-        f.cf.drag = (k[2] > 0.f || k[3] > 0.f) ? 1 : 0;
-        f.g = k[1];
-        f.vscale = k[4];
+        hull_coeffs(c.coeffs + MW_HULL_NCOEFFS * h, &f.cf, &f.g, &f.vscale);
         p->drag = p->drag || f.cf.drag;
     }
     const void* mark = c.total_bodies > 0 ? c.bodies : nullptr;
@@ -548,9 +554,8 @@ static mw_status fleet_check_host(const FleetCall& c, const char* who) {
     }
     if (!c.step) return MW_OK;
     for (int32_t b = 0; b < c.total_bodies; b++) {
-        if (!body_mass_valid(static_cast<const float*>(c.mass) + 8 * (size_t)b))
-            return fail(MW_EINVAL, who, "the mass row of body " + std::to_string(b) +
-                                            " is invalid (m <= 0 or not finite, or I_b not positive definite)");
+        const mw_status s = mass_row_check(c.mass, b, who);
+        if (s != MW_OK) return s;
         if (c.wrench && !fleet_wrench_valid(static_cast<const float*>(c.wrench) + 8 * (size_t)b))
             return fail(MW_EINVAL, who, "the wrench row of body " + std::to_string(b) + " is not finite");
     }
@@ -566,21 +571,18 @@ static FleetTable fleet_group(const FleetPlan& p, const FleetCall& c, uint32_t t
 // k_fleet_vertices, k_fleet_triangles and k_fleet_reduce over a.t (which has bodies), the slab and the partials in the handle's
 // hull-forces buffer, the rows into a.rows
 static mw_status fleet_rows(mw_ocean* o, FleetArgs& a) {
-    const int64_t nv = a.t.total[MW_FLEET_VERTS], nblk = a.t.total[MW_FLEET_CHUNKS], nb = a.t.total[MW_FLEET_BODIES];
-    const size_t bslab = align256((size_t)nv * 8 * sizeof(float)), bpart = (size_t)nblk * 8 * sizeof(float);
-    mw_status s = grow_reserve(o, o->hull, bslab + bpart, "the hull-forces buffer");
+    HullWork w;
+    mw_status s = hull_reserve(o, a.t.total[MW_FLEET_VERTS], a.t.total[MW_FLEET_CHUNKS], a.t.total[MW_FLEET_BODIES], &w);
     if (s != MW_OK) return s;
-    a.vslab = static_cast<float4*>(o->hull.p);
-    a.part = reinterpret_cast<float4*>(static_cast<char*>(o->hull.p) + bslab);
-    const dim3 gv((unsigned)((nv + 255) / 256)), gt((unsigned)std::min<int64_t>(nblk, (int64_t)1 << 20)),
-        gr((unsigned)std::min<int64_t>((nb + 3) / 4, (int64_t)1 << 20));
+    a.vslab = w.vslab;
+    a.part = w.part;
     if (a.m.period != 0.f) {
-        HIP_TRY(tiled_fleet_forces(gv, gt, gr, o->stream, a));
+        HIP_TRY(tiled_fleet_forces(w.gv, w.gt, w.gr, o->stream, a));
         return MW_OK;
     }
-    k_fleet_vertices<<<gv, dim3(256), 0, o->stream>>>(a);
-    k_fleet_triangles<<<gt, dim3(MW_HULL_CHUNK), 0, o->stream>>>(a);
-    k_fleet_reduce<<<gr, dim3(256), 0, o->stream>>>(a);
+    k_fleet_vertices<<<w.gv, dim3(256), 0, o->stream>>>(a);
+    k_fleet_triangles<<<w.gt, dim3(MW_HULL_CHUNK), 0, o->stream>>>(a);
+    k_fleet_reduce<<<w.gr, dim3(256), 0, o->stream>>>(a);
     HIP_TRY(hipGetLastError());
     return MW_OK;
 }
@@ -605,16 +607,13 @@ static mw_status fleet_launch(mw_ocean* o, const FleetPlan& p, const FleetCall& 
     }
     a.dt = c.dt / (float)c.substeps;
     a.substeps = c.substeps;
-    const int plan = sw(SW_BODIES_PLAN);
     uint32_t one = 0;
     size_t lds = 0;
     for (int h = 0; h < c.nhulls; h++) {
         const FleetHull& f = p.all.hull[h];
-        const size_t l = bodies_step_lds(f.nverts, f.nchunks);
-        if (l <= MW_BODIES_LDS_MAX && (plan == 1 || (plan < 0 && bodies_one_launch_rule(f.nchunks)))) {
-            one |= 1u << h;
-            if (c.hulls[MW_FLEET_NHULL * h + 4] > 0) lds = std::max(lds, l);
-        }
+        if (!bodies_one_launch(f.nverts, f.nchunks)) continue;
+        one |= 1u << h;
+        if (c.hulls[MW_FLEET_NHULL * h + 4] > 0) lds = std::max(lds, bodies_step_lds(f.nverts, f.nchunks));
     }
     // k_fleet_step exists for the tiled surface only (fleet.h, "operand order"): on the one footprint every hull steps per substep,
     // which has the bits of both of mw_ocean_step_bodies' plans

@@ -12,6 +12,15 @@
 
 using namespace mw;
 
+// the kernels' coefficients, as the library derives them from the ABI's five (velocity_scale is not read here)
+static HullCoeffs coeffs_of(float density, float gravity, float linear_drag, float quadratic_drag) {
+    const float k[5] = {density, gravity, linear_drag, quadratic_drag, 1.f};
+    HullCoeffs cf;
+    float g, vscale;
+    hull_coeffs(k, &cf, &g, &vscale);
+    return cf;
+}
+
 // slab [nbodies][nverts][8] of hull_vertex over a synthetic mesh vert [R*R][3] (vel [R*R][3] or NULL: drag off)
 extern "C" int hs_vertices(int R, float unit_width, const float* vert, const float* vel, float vscale, int iters, const float* hull,
                            int nverts, const float* bodies, int nbodies, float* slab) {
@@ -27,7 +36,7 @@ extern "C" int hs_vertices(int R, float unit_width, const float* vert, const flo
 // terms [nbodies][ntris][8] of hull_triangle: (Fx, Fy, Fz, area, tx, ty, tz, ok) per triangle, ok = 0 for a bad index
 extern "C" void hs_triangles(const int* tris, int ntris, int nverts, const float* slab, const float* bodies, int nbodies, float density,
                              float gravity, float linear_drag, float quadratic_drag, float* terms) {
-    HullCoeffs cf{density * gravity, linear_drag, quadratic_drag, (linear_drag > 0.f || quadratic_drag > 0.f) ? 1 : 0};
+    const HullCoeffs cf = coeffs_of(density, gravity, linear_drag, quadratic_drag);
     for (int b = 0; b < nbodies; b++)
         for (int t = 0; t < ntris; t++) {
             float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -61,7 +70,7 @@ extern "C" int hs_clip(const float* in, float* sub) {
 // index order (the kernels sum the same terms in a fixed tree order), then hull_row -- the NaN rule of the output
 extern "C" void hs_rows(const int* tris, int ntris, int nverts, const float* slab, const float* bodies, int nbodies, float density,
                         float gravity, float linear_drag, float quadratic_drag, float* rows) {
-    HullCoeffs cf{density * gravity, linear_drag, quadratic_drag, (linear_drag > 0.f || quadratic_drag > 0.f) ? 1 : 0};
+    const HullCoeffs cf = coeffs_of(density, gravity, linear_drag, quadratic_drag);
     for (int b = 0; b < nbodies; b++) {
         const float* vs = slab + 8 * (size_t)b * nverts;
         float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, res = 0.f;

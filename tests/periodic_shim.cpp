@@ -162,12 +162,14 @@ extern "C" int ps_hull_forces(int R, float unit_width, float period, const float
                               const int* tris, int ntris, const float* bodies, int nbodies, const float* coeffs, float* slab, float* rows) {
     if (bad(R, unit_width, iters)) return 1;
     const SqMesh m = mesh_of(R, unit_width, period, vert, vert, vert, 3);
-    const HullCoeffs cf{coeffs[0] * coeffs[1], coeffs[2], coeffs[3], (coeffs[2] > 0.f || coeffs[3] > 0.f) ? 1 : 0};
+    HullCoeffs cf;
+    float g, vscale;
+    hull_coeffs(coeffs, &cf, &g, &vscale);
     const float* u = cf.drag ? vel : nullptr;
     for (int b = 0; b < nbodies; b++) {
         float* s = slab + 8 * (size_t)b * nverts;
-        if (period != 0.f) vertices(SqTiled{m}, u, coeffs[4], its(iters), hull, nverts, bodies + 16 * b, s);
-        else vertices(m, u, coeffs[4], its(iters), hull, nverts, bodies + 16 * b, s);
+        if (period != 0.f) vertices(SqTiled{m}, u, vscale, its(iters), hull, nverts, bodies + 16 * b, s);
+        else vertices(m, u, vscale, its(iters), hull, nverts, bodies + 16 * b, s);
         body_row(tris, ntris, nverts, s, bodies + 16 * b, cf, rows + 8 * b);
     }
     return 0;
@@ -179,8 +181,10 @@ extern "C" int ps_step_bodies(int R, float unit_width, float period, const float
                               int substeps, int plan, float* out) {
     if (bad(R, unit_width, iters) || substeps < 1) return 1;
     const SqMesh m = mesh_of(R, unit_width, period, vert, vert, vert, 3);
-    const HullCoeffs cf{coeffs[0] * coeffs[1], coeffs[2], coeffs[3], (coeffs[2] > 0.f || coeffs[3] > 0.f) ? 1 : 0};
-    const Call c{cf.drag ? vel : nullptr, hull, tris, nverts, ntris, coeffs[4], its(iters), cf, coeffs[1], dt / (float)substeps, substeps};
+    HullCoeffs cf;
+    float g, vscale;
+    hull_coeffs(coeffs, &cf, &g, &vscale);
+    const Call c{cf.drag ? vel : nullptr, hull, tris, nverts, ntris, vscale, its(iters), cf, g, dt / (float)substeps, substeps};
     if (period != 0.f) step_bodies(SqTiled{m}, c, plan, bodies, mass, nbodies, out);
     else step_bodies(m, c, plan, bodies, mass, nbodies, out);
     return 0;

@@ -225,13 +225,24 @@ def test_step_bodies_bad_arguments_are_statuses(mw):
 
 
 def test_kernels_use_the_hd_functions():
-    """both plans integrate with body_integrate and sum with the hull-forces functions; nothing between workgroups"""
+    """both plans integrate with body_integrate and sum with the hull-forces functions; the one-launch kernels of a single hull and of a
+    fleet call the same ordered sums; the summation order has one definition; nothing between workgroups"""
     src = open(HDR).read()
+    csrc = os.path.dirname(HDR)
+    hull, fleet = open(os.path.join(csrc, "hull_forces.h")).read(), open(os.path.join(csrc, "fleet.h")).read()
     step = src[src.index("void k_bodies_step"):]
     assert "hull_vertex(ha.m, ha.vel, ha.vscale, ha.iters, body, h, sl)" in step
     assert "hull_triangle(idx, ha.nverts, vs, body, ha.cf, acc)" in step
     assert "hull_row(acc, res, row)" in step and "body_integrate(body, row, mass, a.g, a.dt)" in step
     integ = src[src.index("void k_bodies_integrate"):src.index("void k_bodies_step")]
     assert "body_integrate(body, row, mass, a.g, a.dt)" in integ
+    # the two one-launch kernels sum through the shared functions: no tree and no wave loop of their own
+    for text in (step, fleet[fleet.index("void k_fleet_step"):]):
+        assert "hull_chunk_partial(acc, res, part + 2 * c)" in text and "hull_body_sum(part, 0, " in text
+        assert "red[" not in text and "off >>= 1" not in text
+    # the order of the sum is written once: the shuffle tree stands in hull_wave_sum and nowhere else
+    wave = hull[hull.index("void hull_wave_sum("):hull.index("void hull_chunk_partial(")]
+    assert hull.count("__shfl_down") == wave.count("__shfl_down") == 2
+    assert "__shfl_down" not in src and "__shfl_down" not in fleet
     code = re.sub(r"//[^\n]*", "", src)
     assert "atomic" not in code and "__threadfence" not in code and "volatile" not in code
