@@ -137,6 +137,24 @@ public class FFTMesh : MonoBehaviour
             for (int c = 0; c < 3; c++) result[4 * k + c] /= tDivision;
     }
 
+    /// Not in the reference: the water below the surface.  SetColumn names the rest depths of the layers (depths[0] == 0, strictly increasing,
+    /// 2 to 16 of them; null releases them); SampleColumn then answers at points xyz_ = {x, y, z, unused, ...} (4 floats per point) of the
+    /// latest Update(): result (12 floats per point) = velocity xyz PER SECOND of Update's deltaTime, rest depth (density * gravity * rest
+    /// depth is the pressure), position xyz, layer coordinate, rest point x0 z0, surface height over the point, residual.  world = false:
+    /// the point is a particle's label (x0, rest depth, z0).
+    public void SetColumn(float[] depths)
+    {
+        Native.Check(Native.mw_ocean_set_column(ocean, depths, depths == null ? 0 : depths.Length));
+    }
+
+    public void SampleColumn(float[] xyz_, float[] result, bool world = true)
+    {
+        if (result.Length < xyz_.Length * 3) throw new ArgumentException("result needs 12 floats per point");
+        Native.Check(Native.mw_ocean_query_column(ocean, -1, world ? Native.QueryWorld : Native.QueryRest, xyz_, xyz_.Length / 4, 0, result));
+        for (int k = 0; k < xyz_.Length / 4; k++)
+            for (int c = 0; c < 3; c++) result[12 * k + c] /= tDivision;
+    }
+
     /// Not in the reference: the first hit of rays on the displaced surface of the latest Update() (mw_ocean_raycast), in the mesh's
     /// object space.  rays (8 floats per ray) = origin xyz, tmin, direction xyz, tmax: t is in units of the direction, a segment
     /// p0 -> p1 is (p0, 0, p1 - p0, 1).  result (8 floats per ray) = t, point xyz, normal xyz, whitecap; t = +infinity on a miss, NaN

@@ -27,6 +27,7 @@ public static class MistralWaterNative
     public const int BodyNMass = 8;
     public const int RcDefaultReach = 16, RcMaxReach = 1024;
     public const int FleetMaxHulls = 32, FleetNHull = 5;
+    public const int ColumnMaxLayers = 16;
 
     [StructLayout(LayoutKind.Sequential)]   // mw_params: 56 bytes
     public struct Params
@@ -150,6 +151,14 @@ public static class MistralWaterNative
     // (tiled triangle id, facing, tile x, tile z) or null; id -1: a miss, -2: the ray left the window's reach unhit
     [DllImport(Lib)] public static extern Status mw_ocean_raycast_tiled(IntPtr ocean, int frame, float[] rays, long n, int reach, [Out] float[] result, [Out] int[] hit);
     [DllImport(Lib)] public static extern Status mw_ocean_raycast_tiled_device(IntPtr ocean, int frame, IntPtr dRays, long n, int reach, IntPtr dResult, IntPtr dHit);
+
+    // the water column (FFTMesh handles): layers at rest depths 0 = d_0 < d_1 < ...; xyz [n][4] (fourth float ignored), result [n][12] =
+    // ux uy uz rest_depth | px py pz lambda | x0 z0 eta residual; rho g rest_depth is the pressure at the point
+    [DllImport(Lib)] public static extern Status mw_ocean_set_column(IntPtr ocean, float[] depths, int nlayers);
+    [DllImport(Lib)] public static extern Status mw_ocean_get_column(IntPtr ocean, [Out] float[] depths, out int nlayers);
+    [DllImport(Lib)] public static extern Status mw_ocean_column_layers(IntPtr ocean, int frame, int layer, out IntPtr dPositions, out IntPtr dVelocities);
+    [DllImport(Lib)] public static extern Status mw_ocean_query_column(IntPtr ocean, int frame, int mode, float[] xyz, long n, int iterations, [Out] float[] result);
+    [DllImport(Lib)] public static extern Status mw_ocean_query_column_device(IntPtr ocean, int frame, int mode, IntPtr dXyz, long n, int iterations, IntPtr dResult);
 
     // ---- page-locked output arrays ------------------------------------------------------------------------------
     [DllImport(Lib)] public static extern Status mw_host_register(IntPtr ptr, UIntPtr bytes);

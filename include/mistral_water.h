@@ -581,6 +581,70 @@ mw_status mw_ocean_raycast_tiled(mw_ocean* o, int32_t frame, const float* rays, 
 mw_status mw_ocean_raycast_tiled_device(mw_ocean* o, int32_t frame, const void* d_rays, int64_t n, int32_t reach, void* d_out,
                                         void* d_hit);
 
+/* ---- the water column: water velocity and rest depth below the surface -------------------------------------------------
+ * FFTMesh handles, every grid path.  A deep-water component of wave number k decays as e^{-k d} at rest depth d, and every output of a
+ *   frame is linear in the spectrum: the water resting at depth d is one more frame, on the spectrum (A h0, A h0c) with A = e^{-k d},
+ *   and its velocity one more velocity field, on (i w A h0, -i w A h0c).  In this Lagrangian first-order model the pressure on a
+ *   material surface is rho g times its rest depth (exact for one trochoidal wave, first order for the sum), so the rest depth of the
+ *   particle at a world point is the pressure there, under a crest or a trough alike.
+ * A column is L layers, 2 <= L <= MW_COLUMN_MAX_LAYERS, at rest depths d_0 = 0 < d_1 < ... < d_{L-1}, all finite.  Layer 0 is not
+ *   computed: it is the latest frame's mesh and mw_ocean_velocity's field, so the column agrees with the surface services by
+ *   construction.  Layer l >= 1 of the latest frame (its t, its choppiness) is two [N*N][3] arrays: the frame's vertices on the
+ *   attenuated spectrum, whose y holds the layer's height h_l above its own rest level (the layer's height is h_l - d_l), and its
+ *   velocity in the units of mw_ocean_velocity.  Between layers every quantity is interpolated linearly, (1 - s) a + s b in strict
+ *   float32; e^{-k d} is convex, so put the layers closer where the motion is large (geometric depths), and put the deepest layer where
+ *   the motion the caller cares about has died out: below it the deepest layer's velocity is returned unchanged.
+ * Memory: per layer below the surface two spectra (16 B per bin each; with their prep tables on the FFT path, 36 B per bin each) plus
+ *   24 B per grid point, and once per column 16 B per grid point; allocated by the first column call after mw_ocean_set_column, freed by
+ *   mw_ocean_set_column(o, NULL, 0) and mw_ocean_destroy.  The weighted spectra are rebuilt after mw_ocean_set_spectrum,
+ *   mw_ocean_reinit_spectrum or mw_ocean_set_column, the layer arrays by the first column call after each frame.
+ * mw_ocean_set_column: depths is a host array; nlayers == 0 (depths may be NULL) releases the column.  mw_ocean_get_column: either
+ *   argument may be NULL; depths receives nlayers floats.
+ * mw_ocean_column_layers: builds the layers if they are stale and returns the handle-owned device pointers of one layer, on the
+ *   handle's stream, valid until the next frame, the next column or spectrum change, or destroy.  Layer 0 returns the surface mesh's
+ *   vertex array and the handle's surface-velocity array.  Either output may be NULL.
+ * mw_ocean_query_column: xyz_ [n][4] (the fourth float is ignored), out [n][12] =
+ *     ux uy uz rest_depth | px py pz lambda | x0 z0 eta residual
+ *   MW_QUERY_WORLD: (x, y, z) is a position in the water.  The layers are scanned from the top: in layer l, (x, z) is located exactly as
+ *     mw_ocean_query_surface locates it on that layer's vertices (the caller's iterations, the same rules), which gives the layer's
+ *     height y_l there, its velocity, the located rest point and a residual.  The scan stops at the first l with y > y_{l+1}; then
+ *     y_{l+1} < y <= y_l and s = (y_l - y) / (y_l - y_{l+1}).  u, p (the reconstructed position) and the rest point (x0, z0) are blended
+ *     between the two layers, rest_depth = (1 - s) d_l + s d_{l+1}, lambda = l + s, eta = y_0 (the surface height over the point),
+ *     residual = the largest residual of the layers visited.  Layers below l + 1 are not located.  A point exactly on layer l
+ *     (y == y_l, for instance py of mw_ocean_query_surface fed back) is that layer's sample: s = 0, lambda = l, rest_depth = d_l, and
+ *     layer l + 1 is not located, so on the surface the residual is the surface's own.
+ *       In the air (y > y_0): u = 0, rest_depth = y_0 - y (negative), lambda = 0; p, x0, z0, eta and residual are layer 0's.
+ *       At or below the deepest layer (y <= y_{L-1}): the deepest layer's u, p, x0, z0; rest_depth = d_{L-1} + (y_{L-1} - y), the
+ *         hydrostatic continuation; lambda = L - 1.
+ *       A non-finite coordinate, or a layer whose locate has no answer, gives a row of NaN.
+ *   MW_QUERY_REST: (x0, d, z0) is a particle's label: its rest-plane position and rest depth.  One rest-mode locate (the cell and the
+ *     weights are the same in every layer); l is the last layer with d_l <= d, capped at L - 2, s = (d - d_l) / (d_{l+1} - d_l); p and u
+ *     are blended between the two layers (p.y from h - d per layer), rest_depth = d, lambda = l + s, eta is layer 0's height at the
+ *     label, residual = 0, and (x0, z0) come back as located.  d < 0, d > d_{L-1}, a label off the footprint or a non-finite input
+ *     gives a row of NaN.  A label at a vertex's rest position with d = d_l returns that layer's vertex (y - d_l) and velocity bit for bit.
+ *   A periodic handle (mw_ocean_set_periodic; the switch is read per call) reads every layer as the tiling: the point is reduced to the
+ *     base tile, every layer gets the same tile indices, and the tile offset is added to px, pz, x0, z0 last.
+ *   Arithmetic: strict float32 throughout, on every handle.  On a periodic handle eta and residual have the bits of
+ *     mw_ocean_query_surface and, where lambda == 0, u the bits of mw_ocean_query_velocity; on a non-periodic handle they agree to
+ *     rounding only, because those older kernels contract multiply-adds there.
+ * MW_EINVAL: a NULL handle; an OceanRenderer or batched handle, which has no column (its mesh samples clamp-addressed textures);
+ *   frame != -1; a bad mode; iterations outside [0, 64]; a NULL array with n > 0; n < 0 or n > 2^32 - 256; in the device form d_xyz_ or
+ *   d_out not 16-byte aligned; nlayers outside {0} and [2, 16]; depths[0] != 0, or depths that are not strictly increasing or not
+ *   finite; a layer out of range.
+ * MW_ESTATE: no column set; no frame yet; the spectrum or phase moved past the latest frame (the rule of mw_ocean_query_velocity).
+ * MW_ENOMEM: an allocation failed; a half-built column frees its buffers and the next call starts again.
+ * n == 0 does nothing.  Caller arrays are untouched on failure.  No column call changes the timer, the phase, the frame, the periodic
+ *   switch or anything another service reads.                                                                              */
+#define MW_COLUMN_MAX_LAYERS 16
+mw_status mw_ocean_set_column(mw_ocean* o, const float* depths, int32_t nlayers);
+mw_status mw_ocean_get_column(mw_ocean* o, float* depths, int32_t* nlayers);
+mw_status mw_ocean_column_layers(mw_ocean* o, int32_t frame, int32_t layer, void** d_positions, void** d_velocities);
+/* host arrays, synchronous */
+mw_status mw_ocean_query_column(mw_ocean* o, int32_t frame, int32_t mode, const float* xyz_, int64_t n, int32_t iterations, float* out);
+/* device arrays (both 16-byte aligned), asynchronous on the handle's stream */
+mw_status mw_ocean_query_column_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xyz_, int64_t n, int32_t iterations,
+                                       void* d_out);
+
 /* ---- independent tiles on several devices (BASELINE configs[2]) ------------------------------------
  * Tiles are independent units in both semantics: tile k is the ocean of `params` with seed params->seed + k on its own
  * device, compute stream and output buffers; there is no data-path collective.  FFTMesh tiles advance up to max_steps

@@ -35,6 +35,8 @@
 #include "fleet.h"
 #include "surface_tiled.h"
 #include "raycast.h"
+#include "water_column.h"
+static_assert(MW_COL_MAX_LAYERS == MW_COLUMN_MAX_LAYERS, "water_column.h and the ABI size the layer table alike");
 static_assert(MW_SQ_REST == MW_QUERY_REST && MW_SQ_WORLD == MW_QUERY_WORLD, "surface_query.h and the ABI name the modes alike");
 
 #ifndef MW_WAVES_P1
@@ -53,6 +55,29 @@ using namespace mw;
 // ------------------------------------------------------------------------------------------------
 // a grow-only device buffer of the handle: allocated at the largest size asked for so far, not per call (grow_reserve)
 struct GrowBuf { void* p = nullptr; size_t cap = 0; };
+// The water column of a handle (mw_ocean_set_column, water_column.h): the depths, and per layer below the surface the attenuated spectrum,
+// its velocity-weighted twin (each with its k_prep tables on the FFT path) and the two vertex arrays of the latest frame.  Allocated on
+// the first build, freed as a whole (col_release) when an allocation fails half-way, the column is replaced or the handle destroyed.
+// ready: the weighted spectra belong to the handle's current spectrum; built: pos / vel belong to the latest frame -- both cleared by the
+// frame-record functions below and set by column_spectra_built / column_layers_built.
+struct ColLayer { FmSpectrum psp, vsp; float *pos = nullptr, *vel = nullptr; };
+struct ColState {
+    int L = 0;  // 0: no column
+    float depth[MW_COL_MAX_LAYERS] = {};
+    ColLayer layer[MW_COL_MAX_LAYERS];  // layer[0] stays empty: layer 0 is the surface mesh and vel.vert
+    float *norm = nullptr, *white = nullptr;  // the normals / whitecap the frame kernels also write (unused)
+    bool ready = false, built = false;
+};
+// frees every buffer, keeps the depths: the next build allocates again
+static void col_release(ColState& c) {
+    for (ColLayer& y : c.layer) {
+        fm_spectrum_free(y.psp); fm_spectrum_free(y.vsp); hipFree(y.pos); hipFree(y.vel);
+        y = ColLayer();
+    }
+    hipFree(c.norm); hipFree(c.white);
+    c.norm = c.white = nullptr;
+    c.ready = c.built = false;
+}
 struct mw_ocean {
     mw_params p;
     int N = 0;          // synthesis grid size
@@ -67,6 +92,7 @@ struct mw_ocean {
     bool frame_behind = false;  // the spectrum or the phase changed after the latest frame was made (mw_ocean_query_velocity refuses)
     bool periodic = false;      // mw_ocean_set_periodic: the surface services read the tiling of the frame (not part of the frame record)
     VelState vel;            // mw_ocean_velocity: the weighted spectrum and the velocity buffers (velocity_kernels.h)
+    ColState col;            // mw_ocean_set_column: the layers below the surface (water_column.h)
     // four separate buffers: the host forms keep their staged inputs in scratch while hull, bodies and rc_tree are in use
     GrowBuf hull;     // mw_ocean_hull_forces: vertex slab + chunk partials (hull_forces.h)
     GrowBuf bodies;   // mw_ocean_step_bodies, per-substep plan: the rows of a substep [nbodies][8]
@@ -142,12 +168,15 @@ struct Stage {
 // orr.fr_have -- is written by the functions below and nowhere else: every entry point that makes a frame, moves the phase or changes
 // the spectrum calls the one that states what it did.
 // velocity_spectrum_built below is the seventh writer: the only place vel.ready turns true (or_velocity sets its own for OceanRenderer).
+// The water column hangs on the same record: a new or overwritten frame makes its layer arrays stale (col.built), a new spectrum its weighted
+// spectra too (col.ready); column_spectra_built and column_layers_built are the only places the two turn true.
 // an FFTMesh frame evaluated at time t now stands in s_vert / s_norm / s_white, its whitecap at stride wstride (4: RGBA colours, 1: scalar)
 static void frame_fftmesh_made(mw_ocean* o, float t, int wstride) {
     o->fm.s_have = true; o->fm.s_wstride = wstride; o->fm.s_t = t; o->fm.s_chop = o->p.choppiness; o->frame_behind = false;
+    o->col.built = false;
 }
 // the launches that follow overwrite s_vert / s_norm / s_white: they hold no frame until frame_fftmesh_made says so (profiling hook)
-static void frame_fftmesh_overwritten(mw_ocean* o) { o->fm.s_have = false; }
+static void frame_fftmesh_overwritten(mw_ocean* o) { o->fm.s_have = false; o->col.built = false; }
 // an OceanRenderer lone frame is being made: the latest frame is the phase's, and no frame of a steps call is
 static void frame_or_lone(mw_ocean* o) { o->or_steps_tail = -1; o->frame_behind = false; }
 // an OceanRenderer steps call made n frames and kept[k] says whether kind k (height, displacement, normal, whitecap) stayed in the
@@ -162,10 +191,15 @@ static void frame_phase_moved(mw_ocean* o) { o->or_steps_tail = -1; o->frame_beh
 // phase_restarts: the OceanRenderer phase went back to 0 with it, so no frame of a steps call is the phase's either
 static void frame_spectrum_changed(mw_ocean* o, bool phase_restarts) {
     o->vel.ready = false; o->frame_behind = true;
+    o->col.ready = false; o->col.built = false;
     if (phase_restarts) o->or_steps_tail = -1;
 }
 // the velocity spectrum was rebuilt from the current spectrum (velocity_run; or_velocity does the same for OceanRenderer)
 static void velocity_spectrum_built(mw_ocean* o) { o->vel.ready = true; }
+// the column's weighted spectra were rebuilt from the current spectrum and depths; its layer arrays were built from the latest frame's
+// time and choppiness (column_build)
+static void column_spectra_built(mw_ocean* o) { o->col.ready = true; }
+static void column_layers_built(mw_ocean* o) { o->col.built = true; }
 
 // The four arrays that hold OceanRenderer frame k: the latest frame (k = -1), frame k of the latest steps call otherwise -- the handle's
 // latest-frame textures too when that call made one frame (it ran the lone-frame plan), else slot k of the frame buffers.  A kind the
@@ -273,6 +307,7 @@ void mw_ocean_destroy(mw_ocean* o) {
     hipFree(o->q_mesh);
     for (GrowBuf* b : {&o->scratch, &o->hull, &o->bodies, &o->rc_tree}) hipFree(b->p);
     vel_free(o->vel);
+    col_release(o->col);
     direct_free(o->direct);
     fm_free(o->fm);
     or_free(o->orr);

@@ -1,5 +1,5 @@
 // surface_services.inc -- the host code of the services that read the displaced surface: surface queries, surface velocity, hull
-// forces, floating bodies, mixed fleets, raycasts.  Included by mistral_water.hip inside its extern "C" block (one translation unit: the handle, fail,
+// forces, floating bodies, mixed fleets, raycasts, the water column.  Included by mistral_water.hip inside its extern "C" block (one translation unit: the handle, fail,
 // HIP_TRY, dmalloc, grow_reserve, Stage and the frame record are file-static there).  Every service is a pair of entry points over a
 // shared prepare (validate, name the mesh of the queried frame) and launch (the kernels, on the handle's stream): the device form
 // checks alignment and launches on the caller's arrays, the host form stages its arrays in the handle's scratch buffer (Stage).
@@ -833,5 +833,163 @@ mw_status mw_ocean_raycast_tiled(mw_ocean* o, int32_t frame, const float* rays, 
     st.out(&d_out, out, (size_t)n * 8 * sizeof(float));
     st.out(&d_hit, hit, (size_t)n * 4 * sizeof(int32_t));  // optional
     if ((s = st.begin()) != MW_OK || (s = raycast_tiled_launch(o, m, d_rays, n, reach, d_out, d_hit)) != MW_OK) return s;
+    return st.finish();
+}
+
+// ---- the water column (csrc/water_column.h) -----------------------------------------------------------------------------
+// FFTMesh handles only: an OceanRenderer mesh samples clamp-addressed textures (DESIGN.md section 7g) and has no column.
+static mw_status column_handle_check(mw_ocean* o, const char* who) {
+    if (!o) return fail(MW_EINVAL, who, "NULL handle");
+    if (o->sem != MW_SEM_FFTMESH)
+        return fail(MW_EINVAL, who, "an OceanRenderer or batched handle has no column (its mesh samples clamp-addressed textures): FFTMesh handles only");
+    return MW_OK;
+}
+
+mw_status mw_ocean_set_column(mw_ocean* o, const float* depths, int32_t nlayers) {
+    const char* who = "mw_ocean_set_column";
+    mw_status s = column_handle_check(o, who);
+    if (s != MW_OK) return s;
+    if (nlayers != 0 && (nlayers < 2 || nlayers > MW_COLUMN_MAX_LAYERS)) return fail(MW_EINVAL, who, "nlayers must be 0 or in [2, MW_COLUMN_MAX_LAYERS]");
+    if (nlayers > 0) {
+        if (!depths) return fail(MW_EINVAL, who, "NULL depths");
+        if (depths[0] != 0.f) return fail(MW_EINVAL, who, "depths[0] must be 0 (layer 0 is the surface)");
+        for (int l = 1; l < nlayers; l++)
+            if (!(depths[l] > depths[l - 1] && depths[l] <= 3.4e38f)) return fail(MW_EINVAL, who, "depths must be finite and strictly increasing");
+    }
+    HIP_TRY(hipSetDevice(o->device));
+    HIP_TRY(hipStreamSynchronize(o->stream));  // work on the stream may still read the old layers
+    col_release(o->col);
+    o->col.L = nlayers;
+    for (int l = 0; l < MW_COL_MAX_LAYERS; l++) o->col.depth[l] = l < nlayers ? depths[l] : 0.f;
+    return MW_OK;
+}
+
+mw_status mw_ocean_get_column(mw_ocean* o, float* depths, int32_t* nlayers) {
+    mw_status s = column_handle_check(o, "mw_ocean_get_column");
+    if (s != MW_OK) return s;
+    if (nlayers) *nlayers = o->col.L;
+    if (depths) for (int l = 0; l < o->col.L; l++) depths[l] = o->col.depth[l];
+    return MW_OK;
+}
+
+// Validates a column call: the handle, then the surface query's argument and frame rules (query_prepare), then the state -- a column, and
+// a frame that is still the spectrum's (the frame_behind rule of mw_ocean_query_velocity).  Names the surface mesh, period included.
+static mw_status column_prepare(mw_ocean* o, int32_t frame, int32_t mode, const void* xyz, int64_t n, int32_t iterations, const void* out,
+                                const char* who, SqMesh* m) {
+    mw_status s = column_handle_check(o, who);
+    if (s == MW_OK) s = query_prepare(o, frame, mode, xyz, n, iterations, out, who, m);
+    if (s != MW_OK) return s;
+    if (o->col.L == 0) return fail(MW_ESTATE, who, "no column set (mw_ocean_set_column first)");
+    if (o->frame_behind)
+        return fail(MW_ESTATE, who, "the spectrum or phase changed after the latest frame: the surface and the layers would belong to "
+                                    "different instants (make a frame first)");
+    return MW_OK;
+}
+// The layers of the latest frame, on the handle's stream: buffers on first use, the weighted spectra once per spectrum and column (one
+// k_column_weight per layer and, on the FFT path, two k_prep), the layer arrays once per frame -- per layer the frame passes on the
+// attenuated spectrum and the velocity passes on its weighted twin, exactly as velocity_run runs them.  Layer 0's velocity (vel.vert)
+// is made current here too.  Writes only the column's buffers, the handle's velocity buffers and the frame pipeline's work space.
+static mw_status column_build(mw_ocean* o) {
+    ColState& c = o->col;
+    const int N = o->N;
+    const size_t NN = (size_t)N * N;
+    mw_status s = MW_OK;
+    if (!c.white) {  // the last buffer allocated: a failure half-way frees them all, and the next call starts again
+        for (int l = 1; l < c.L && s == MW_OK; l++) {
+            ColLayer& y = c.layer[l];
+            if ((s = fm_spectrum_alloc(y.psp, N, o->use_fft)) != MW_OK || (s = fm_spectrum_alloc(y.vsp, N, o->use_fft)) != MW_OK ||
+                (s = dmalloc(&y.pos, 3 * NN)) != MW_OK)
+                break;
+            s = dmalloc(&y.vel, 3 * NN);
+        }
+        if (s != MW_OK || (s = dmalloc(&c.norm, 3 * NN)) != MW_OK || (s = dmalloc(&c.white, NN)) != MW_OK) {
+            col_release(c);
+            return s;
+        }
+    }
+    if (!c.ready) {
+        for (int l = 1; l < c.L; l++) {
+            ColLayer& y = c.layer[l];
+            HIP_TRY(column_weight_launch(o->stream, N, o->p.length, o->p.gravity, c.depth[l], o->fm.sp.h0, o->fm.sp.h0c, y.psp.h0, y.psp.h0c, y.vsp.h0,
+                                         y.vsp.h0c));
+            if (o->use_fft && ((s = fm_prep(y.psp, N, o->p.length, o->p.gravity, o->fm.Wpre, o->stream)) != MW_OK ||
+                               (s = fm_prep(y.vsp, N, o->p.length, o->p.gravity, o->fm.Wpre, o->stream)) != MW_OK))
+                return s;
+        }
+        column_spectra_built(o);
+    }
+    if (c.built && o->vel.vert) return MW_OK;
+    if ((s = velocity_to_handle(o)) != MW_OK) return s;
+    OceanConsts C = consts_of(o);
+    C.choppiness = o->fm.s_chop;  // the frame's choppiness, as velocity_run
+    const unsigned nb = (unsigned)((NN + 255) / 256);
+    for (int l = 1; l < c.L; l++) {
+        ColLayer& y = c.layer[l];
+        if (!o->use_fft) {
+            if ((s = direct_evaluate(o->direct, C, y.psp.h0, y.psp.h0c, o->fm.s_t, y.pos, c.norm, c.white, 1, o->stream)) != MW_OK) return s;
+            if ((s = direct_evaluate(o->direct, C, y.vsp.h0, y.vsp.h0c, o->fm.s_t, y.vel, c.norm, c.white, 1, o->stream)) != MW_OK) return s;
+            hipLaunchKernelGGL(k_velocity_from_hds, dim3(nb), dim3(256), 0, o->stream, N, C.choppiness, o->direct.hds, y.vel);
+            HIP_TRY(hipGetLastError());
+            continue;
+        }
+        if ((s = fm_evaluate(o->fm, y.psp, C, &o->fm.s_t, 1, y.pos, c.norm, c.white, 1, o->stream)) != MW_OK) return s;
+        if ((s = fm_evaluate(o->fm, y.vsp, C, &o->fm.s_t, 1, y.vel, c.norm, c.white, 1, o->stream, true)) != MW_OK) return s;
+    }
+    column_layers_built(o);
+    return MW_OK;
+}
+static ColTable column_table(const mw_ocean* o, const SqMesh& m) {
+    ColTable tb{};
+    tb.L = o->col.L;
+    for (int l = 0; l < tb.L; l++) {
+        tb.depth[l] = o->col.depth[l];
+        tb.pos[l] = l ? o->col.layer[l].pos : m.vert;
+        tb.vel[l] = l ? o->col.layer[l].vel : o->vel.vert;
+    }
+    return tb;
+}
+static mw_status column_launch(mw_ocean* o, const SqMesh& m, int32_t mode, const void* d_xyz, int64_t n, int32_t iterations, void* d_out) {
+    mw_status s = column_build(o);
+    if (s != MW_OK) return s;
+    HIP_TRY(column_query_launch(o->stream, m, column_table(o, m), mode, sq_iters(iterations), static_cast<const float4*>(d_xyz), n,
+                                static_cast<float4*>(d_out)));
+    return MW_OK;
+}
+
+mw_status mw_ocean_column_layers(mw_ocean* o, int32_t frame, int32_t layer, void** d_positions, void** d_velocities) {
+    const char* who = "mw_ocean_column_layers";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    SqMesh m{};
+    mw_status s = column_handle_check(o, who);
+    if (s != MW_OK) return s;
+    if (layer < 0 || layer >= MW_COLUMN_MAX_LAYERS || (o->col.L > 0 && layer >= o->col.L)) return fail(MW_EINVAL, who, "layer out of range");
+    if ((s = column_prepare(o, frame, MW_QUERY_WORLD, nullptr, 0, 0, nullptr, who, &m)) != MW_OK || (s = column_build(o)) != MW_OK) return s;
+    const ColTable tb = column_table(o, m);
+    if (d_positions) *d_positions = const_cast<float*>(tb.pos[layer]);
+    if (d_velocities) *d_velocities = const_cast<float*>(tb.vel[layer]);
+    return MW_OK;
+}
+
+mw_status mw_ocean_query_column_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xyz_, int64_t n, int32_t iterations, void* d_out) {
+    const char* who = "mw_ocean_query_column_device";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (n > 0 && (misaligned(d_xyz_, 16) || misaligned(d_out, 16))) return fail(MW_EINVAL, who, "d_xyz_ and d_out must be 16-byte aligned");
+    SqMesh m{};
+    mw_status s = column_prepare(o, frame, mode, d_xyz_, n, iterations, d_out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    return column_launch(o, m, mode, d_xyz_, n, iterations, d_out);
+}
+
+mw_status mw_ocean_query_column(mw_ocean* o, int32_t frame, int32_t mode, const float* xyz_, int64_t n, int32_t iterations, float* out) {
+    const char* who = "mw_ocean_query_column";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    SqMesh m{};
+    mw_status s = column_prepare(o, frame, mode, xyz_, n, iterations, out, who, &m);
+    if (s != MW_OK || n == 0) return s;
+    void *d_xyz, *d_out;
+    Stage st(o);
+    st.in(&d_xyz, xyz_, (size_t)n * 4 * sizeof(float));
+    st.out(&d_out, out, (size_t)n * MW_COL_NOUT * sizeof(float));
+    if ((s = st.begin()) != MW_OK || (s = column_launch(o, m, mode, d_xyz, n, iterations, d_out)) != MW_OK) return s;
     return st.finish();
 }

@@ -16,7 +16,8 @@
 // IS -chop Dx, rounded once -- no position is subtracted afterwards, which would cancel the digits the velocity is made of.
 #pragma once
 #include "mw_math.h"
-#if defined(__HIPCC__)
+// MW_VEL_NO_KERNELS: a second translation unit (water_column.hip) wants velocity_weight alone; the kernels and VelState are mistral_water.hip's
+#if defined(__HIPCC__) && !defined(MW_VEL_NO_KERNELS)
 #include "direct_kernels.h"
 #include "ocean_renderer_device.h"
 #endif
@@ -29,7 +30,7 @@ MW_HD void velocity_weight(float w, cf a, cf b, cf* va, cf* vb) {
     *vb = mk(w * b.y, -(w * b.x));
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(MW_VEL_NO_KERNELS)
 // FFTMesh: the weighted spectrum, w = omega_f32 of the same index -- the value the frame kernels' Om table and omega_t_f32 hold
 __global__ void k_velocity_spectrum(int N, float length, float gravity, const cf* h0, const cf* h0c, cf* vh0, cf* vh0c) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;

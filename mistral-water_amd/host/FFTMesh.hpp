@@ -53,6 +53,12 @@ inline void query_velocity(mw_ocean* o, int32_t frame, const std::vector<Vector2
                                   iterations, out.empty() ? nullptr : &out[0].velocity.x));
 }
 
+// mw_ocean_query_column: a point in the water (or a particle's label (x0, rest depth, z0)) and its answer
+struct ColumnPoint { Vector3 point; float unused = 0.f; };
+static_assert(sizeof(ColumnPoint) == 16, "[n][4] floats of mw_ocean_query_column");
+struct ColumnSample { Vector3 velocity; float restDepth = 0.f; Vector3 position; float lambda = 0.f; float x0 = 0.f, z0 = 0.f, eta = 0.f, residual = 0.f; };
+static_assert(sizeof(ColumnSample) == 48, "[n][12] floats of mw_ocean_query_column");
+
 // mw_ocean_raycast: one ray (t in units of direction; a segment p0 -> p1 is {p0, 0, p1 - p0, 1}) and its first hit on the surface
 // (t = +inf on a miss, NaN for an invalid ray); facing +1: the ray met the water from above, -1: from below; triangle -1: no hit
 struct Ray { Vector3 origin; float tmin = 0.f; Vector3 direction; float tmax = std::numeric_limits<float>::infinity(); };
@@ -171,6 +177,16 @@ public:
     // ... and at horizontal points, located as QuerySurface locates them (per second, as Velocity)
     void QueryVelocity(const std::vector<Vector2>& xz, std::vector<VelocitySample>& out, bool world = true, int32_t iterations = 0) {
         query_velocity(ocean_, -1, xz, out, world, iterations);
+        for (auto& s : out) { s.velocity.x /= tDivision; s.velocity.y /= tDivision; s.velocity.z /= tDivision; }
+    }
+    // Not in the reference: the water below the surface of the latest EvaluateWaves() at points in the water (world) or particle labels
+    // (x0, rest depth, z0); SetColumn names the layers' rest depths (depths[0] == 0, strictly increasing, 2 to 16; empty releases them).
+    // Velocity per second, as Velocity
+    void SetColumn(const std::vector<float>& depths) { check(mw_ocean_set_column(ocean_, depths.empty() ? nullptr : depths.data(), (int32_t)depths.size())); }
+    void SampleColumn(const std::vector<ColumnPoint>& xyz, std::vector<ColumnSample>& out, bool world = true, int32_t iterations = 0) {
+        out.resize(xyz.size());
+        check(mw_ocean_query_column(ocean_, -1, world ? MW_QUERY_WORLD : MW_QUERY_REST, xyz.empty() ? nullptr : &xyz[0].point.x, (int64_t)xyz.size(),
+                                    iterations, out.empty() ? nullptr : &out[0].velocity.x));
         for (auto& s : out) { s.velocity.x /= tDivision; s.velocity.y /= tDivision; s.velocity.z /= tDivision; }
     }
     // Not in the reference: the first hit of rays on the surface of the latest EvaluateWaves() (mouse picking, projectile segments, ...)

@@ -25,6 +25,7 @@ MW_HULL_NCOEFFS = 5
 MW_BODY_NMASS = 8
 MW_RC_DEFAULT_REACH, MW_RC_MAX_REACH = 16, 1024
 MW_FLEET_MAX_HULLS, MW_FLEET_NHULL = 32, 5
+MW_COLUMN_MAX_LAYERS = 16
 STATUS_NAMES = {0: "MW_OK", 1: "MW_EINVAL", 2: "MW_ENOTPOW2", 3: "MW_ENOTCOMMENSURATE", 4: "MW_ENOMEM",
                 5: "MW_EDEVICE", 6: "MW_ESTATE"}
 
@@ -64,7 +65,7 @@ BUILD_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-Xclang", "-target-feature", "-Xclang", "-load-store-opt"]
 
 
-TRANSLATION_UNITS = ["mistral_water.hip", "surface_tiled.hip"]
+TRANSLATION_UNITS = ["mistral_water.hip", "surface_tiled.hip", "water_column.hip"]
 
 
 def csrc_files():
@@ -116,7 +117,8 @@ def build_native(force: bool = False, verbose: bool = False, out: str | None = N
         cmd.append('-DMW_BUILD_TAG="%s"' % tag)
     if resource_report:
         cmd.append("-Rpass-analysis=kernel-resource-usage")
-    # two translation units: the library, and the tiled surface services, which set their own floating-point mode (csrc/surface_tiled.hip)
+    # three translation units: the library, and the tiled surface services and the water column, which set their own floating-point mode
+    # (csrc/surface_tiled.hip, csrc/water_column.hip)
     cmd += ["-o", target] + [os.path.join(CSRC_DIR, f) for f in TRANSLATION_UNITS]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if resource_report:
@@ -231,6 +233,11 @@ def lib():
         "mw_ocean_raycast_device": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, vp]),
         "mw_ocean_raycast_tiled": (C.c_int, [vp, C.c_int32, f32p, C.c_int64, C.c_int32, f32p, i32p]),
         "mw_ocean_raycast_tiled_device": (C.c_int, [vp, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp]),
+        "mw_ocean_set_column": (C.c_int, [vp, f32p, C.c_int32]),
+        "mw_ocean_get_column": (C.c_int, [vp, f32p, i32p]),
+        "mw_ocean_column_layers": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(vp), C.POINTER(vp)]),
+        "mw_ocean_query_column": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, C.c_int32, f32p]),
+        "mw_ocean_query_column_device": (C.c_int, [vp, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int32, vp]),
         "mw_ocean_profile_kernels": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
         "mw_ocean_profile_kernels_stats": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
         "mw_gerstner_displace": (C.c_int, [f32p, C.c_int64, f32p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
@@ -283,6 +290,7 @@ ABI_SYMBOLS = [
     "mw_ocean_hull_forces", "mw_ocean_hull_forces_device", "mw_hull_mass_properties", "mw_ocean_step_bodies", "mw_ocean_step_bodies_device",
     "mw_ocean_fleet_forces", "mw_ocean_fleet_forces_device", "mw_ocean_step_fleet", "mw_ocean_step_fleet_device",
     "mw_ocean_raycast", "mw_ocean_raycast_device", "mw_ocean_raycast_tiled", "mw_ocean_raycast_tiled_device",
+    "mw_ocean_set_column", "mw_ocean_get_column", "mw_ocean_column_layers", "mw_ocean_query_column", "mw_ocean_query_column_device",
     "mw_gerstner_displace",
     "mw_gerstner_displace_device", "mw_gerstner_displace_steps_device", "mw_gerstner_max_steps", "mw_pond_displace", "mw_pond_displace_device",
 ]

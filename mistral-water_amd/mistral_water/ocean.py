@@ -353,6 +353,50 @@ class Ocean:
         nat.check(nat.lib().mw_ocean_query_velocity_device(self._h, int(frame), self._QUERY_MODES[mode], C.c_void_p(d_xz), int(n),
                                                             int(iterations), C.c_void_p(d_out)))
 
+    # -- the water column (mw_ocean_set_column) --------------------------------------------------
+    def set_column(self, depths):
+        """The rest depths of the column's layers, depths[0] == 0 < depths[1] < ... (2 to MW_COLUMN_MAX_LAYERS of them); None or an
+        empty sequence releases the column.  FFTMesh handles only."""
+        d = np.ascontiguousarray([] if depths is None else depths, np.float32).reshape(-1)
+        nat.check(nat.lib().mw_ocean_set_column(self._h, _p(d) if d.size else None, int(d.size)))
+
+    @property
+    def column(self):
+        """The depths of the column's layers, [L] float32 (empty: no column)."""
+        n, d = C.c_int32(0), np.zeros(nat.MW_COLUMN_MAX_LAYERS, np.float32)
+        nat.check(nat.lib().mw_ocean_get_column(self._h, _p(d), C.byref(n)))
+        return d[:n.value].copy()
+
+    def column_layers(self, layer: int, frame: int = -1):
+        """Device pointers (ints) of one layer of the latest frame: (positions [N*N][3], velocities [N*N][3]); layer 0 is the surface mesh
+        and the surface velocity.  Valid until the next frame, column or spectrum change."""
+        pos, vel = C.c_void_p(), C.c_void_p()
+        nat.check(nat.lib().mw_ocean_column_layers(self._h, int(frame), int(layer), C.byref(pos), C.byref(vel)))
+        return pos.value, vel.value
+
+    def column_layer_arrays(self, layer: int):
+        """column_layers(layer) copied to the host: (positions [N*N, 3], velocities [N*N, 3]) float32."""
+        pos, vel = self.column_layers(layer)
+        self.synchronize()
+        n = self.N * self.N
+        return _d2h(pos, (n, 3)), _d2h(vel, (n, 3))
+
+    def query_column(self, xyz, mode: str = "world", frame: int = -1, iterations: int = 0):
+        """The water at points xyz [n, 3] (or [n, 4], the fourth float ignored) -> [n, 12] float32 rows
+        (ux, uy, uz, rest_depth, px, py, pz, lambda, x0, z0, eta, residual).  mode "world": (x, y, z) is a position in the water;
+        "rest": (x0, d, z0) a particle's rest-plane position and rest depth.  rho * g * rest_depth is the pressure there."""
+        a = np.asarray(xyz, np.float32)
+        a = a.reshape(-1, a.shape[-1] if a.ndim > 1 and a.shape[-1] in (3, 4) else 3)
+        q = np.zeros((a.shape[0], 4), np.float32)
+        q[:, :a.shape[1]] = a
+        out = np.empty((q.shape[0], 12), np.float32)
+        nat.check(nat.lib().mw_ocean_query_column(self._h, int(frame), self._QUERY_MODES[mode], _p(q), q.shape[0], int(iterations), _p(out)))
+        return out
+
+    def query_column_device(self, d_xyz: int, n: int, d_out: int, mode: str = "world", frame: int = -1, iterations: int = 0):
+        """Device-pointer form: d_xyz [n][4], d_out [n][12] float32, both 16-byte aligned; asynchronous on the handle's stream."""
+        nat.check(nat.lib().mw_ocean_query_column_device(self._h, int(frame), self._QUERY_MODES[mode], C.c_void_p(d_xyz), int(n),
+                                                          int(iterations), C.c_void_p(d_out)))
 
     # -- hull forces (mw_ocean_hull_forces) ----------------------------------------------------
     def _hull_coeffs(self, density, gravity, linear_drag, quadratic_drag, velocity_scale):
@@ -667,6 +711,11 @@ class FFTMesh:
     def SampleSurface(self, xz, world: bool = True, iterations: int = 0):
         """Not in the reference: the mesh's surface at horizontal points xz [n, 2] of the latest EvaluateWaves (Ocean.query_surface)."""
         return self._ocean.query_surface(xz, mode="world" if world else "rest", iterations=iterations)
+
+    def SampleColumn(self, xyz, world: bool = True):
+        """Not in the reference: the water below the surface at points xyz [n, 3] of the latest EvaluateWaves (Ocean.query_column; set
+        the layers with ocean.set_column first)."""
+        return self._ocean.query_column(xyz, mode="world" if world else "rest")
 
     @property
     def timer(self):
