@@ -155,6 +155,13 @@ public class FFTMesh : MonoBehaviour
             for (int c = 0; c < 3; c++) result[12 * k + c] /= tDivision;
     }
 
+    /// Not in the reference: HullForces and StepBodies read the water column (SetColumn) under every hull vertex instead of the surface
+    /// above it: the pressure at the vertex's rest depth and the water's velocity down there.  For keels, spar buoys and deep hulls.
+    public void SetDraught(bool on = true)
+    {
+        Native.Check(Native.mw_ocean_set_draught(ocean, on ? 1 : 0));
+    }
+
     /// Not in the reference: the first hit of rays on the displaced surface of the latest Update() (mw_ocean_raycast), in the mesh's
     /// object space.  rays (8 floats per ray) = origin xyz, tmin, direction xyz, tmax: t is in units of the direction, a segment
     /// p0 -> p1 is (p0, 0, p1 - p0, 1).  result (8 floats per ray) = t, point xyz, normal xyz, whitecap; t = +infinity on a miss, NaN

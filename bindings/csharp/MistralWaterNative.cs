@@ -160,6 +160,11 @@ public static class MistralWaterNative
     [DllImport(Lib)] public static extern Status mw_ocean_query_column(IntPtr ocean, int frame, int mode, float[] xyz, long n, int iterations, [Out] float[] result);
     [DllImport(Lib)] public static extern Status mw_ocean_query_column_device(IntPtr ocean, int frame, int mode, IntPtr dXyz, long n, int iterations, IntPtr dResult);
 
+    // draught (FFTMesh handles): with it on, mw_ocean_hull_forces and mw_ocean_step_bodies read the water column under every hull vertex
+    // (rest depth for the pressure, the column's velocity for the drag); needs a column by the time of the call; the fleet calls refuse it
+    [DllImport(Lib)] public static extern Status mw_ocean_set_draught(IntPtr ocean, int on);
+    [DllImport(Lib)] public static extern Status mw_ocean_get_draught(IntPtr ocean, out int on);
+
     // ---- page-locked output arrays ------------------------------------------------------------------------------
     [DllImport(Lib)] public static extern Status mw_host_register(IntPtr ptr, UIntPtr bytes);
     [DllImport(Lib)] public static extern Status mw_host_unregister(IntPtr ptr);

@@ -645,6 +645,30 @@ mw_status mw_ocean_query_column(mw_ocean* o, int32_t frame, int32_t mode, const 
 mw_status mw_ocean_query_column_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xyz_, int64_t n, int32_t iterations,
                                        void* d_out);
 
+/* ---- draught: hull forces and bodies read the water column below them ---------------------------------------------
+ * Without draught every hull vertex gets the depth eta - y and the surface particle's velocity, however deep it lies: right for a barge,
+ *   wrong for a keel, a spar buoy or a ship whose bottom sits a sizeable fraction of a wavelength down (the wave pressure under a hull
+ *   of draught T is overstated by e^{kT}, the Smith effect, and the drag acts against water that does not move that fast down there).
+ * mw_ocean_set_draught(o, 1) is a switch on the handle, like mw_ocean_set_periodic: read per call, default 0, and the entry points and
+ *   array layouts of the hull family do not change.  With it on, mw_ocean_hull_forces, mw_ocean_step_bodies and their _device forms
+ *   take every instance vertex as a world point of the column (the MW_QUERY_WORLD rules of mw_ocean_query_column, the caller's
+ *   iterations): its depth is the point's rest_depth, so the pressure is rho g rest_depth, its water velocity (drag on) the column's u
+ *   times velocity_scale, its residual the column's.  A vertex in the air carries eta - y and no velocity as before, so the waterline is
+ *   still cut at depth 0; below the deepest layer the depth continues hydrostatically and the velocity is the deepest layer's.  A vertex
+ *   the column has no answer for makes the body's row NaN.  The clip, the integrals, the order of the sum, the substep chain and every
+ *   NaN rule are those of the calls without draught.  Periodic and draught combine: the layers are read as the tiling.
+ *   Arithmetic: strict float32 throughout, on every handle (the column's).  On flat water the rows are Archimedes' as before.
+ *   Stepping builds the layers once per call and runs every hull per substep (MW_BODIES_PLAN is not read).
+ * With draught on the four calls take, after their own argument checks, the column's state rules whether drag is on or off:
+ *   MW_ESTATE when no column is set (mw_ocean_set_column) or the spectrum or phase moved past the latest frame.
+ * With draught on mw_ocean_fleet_forces, mw_ocean_step_fleet and their _device forms return MW_ESTATE before any other work: fleets do
+ *   not read the column yet.  Queries, velocity, raycasts and the column query ignore the switch.
+ * With draught off every call behaves, and launches, exactly as if the switch did not exist.
+ * mw_ocean_set_draught: MW_EINVAL for a NULL handle, on outside {0, 1}, or a handle mw_ocean_set_column refuses (OceanRenderer,
+ *   batched).  No column has to be set yet.  mw_ocean_get_draught: on may be NULL.                                              */
+mw_status mw_ocean_set_draught(mw_ocean* o, int32_t on);                      /* 0 / 1; default 0 */
+mw_status mw_ocean_get_draught(mw_ocean* o, int32_t* on);
+
 /* ---- independent tiles on several devices (BASELINE configs[2]) ------------------------------------
  * Tiles are independent units in both semantics: tile k is the ocean of `params` with seed params->seed + k on its own
  * device, compute stream and output buffers; there is no data-path collective.  FFTMesh tiles advance up to max_steps

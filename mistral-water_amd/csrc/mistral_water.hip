@@ -36,6 +36,7 @@
 #include "surface_tiled.h"
 #include "raycast.h"
 #include "water_column.h"
+#include "hull_draught.h"
 static_assert(MW_COL_MAX_LAYERS == MW_COLUMN_MAX_LAYERS, "water_column.h and the ABI size the layer table alike");
 static_assert(MW_SQ_REST == MW_QUERY_REST && MW_SQ_WORLD == MW_QUERY_WORLD, "surface_query.h and the ABI name the modes alike");
 
@@ -91,6 +92,7 @@ struct mw_ocean {
     int or_steps_tail = -1;  // OceanRenderer: the last frame of the latest steps call while the phase is still that frame's, else -1
     bool frame_behind = false;  // the spectrum or the phase changed after the latest frame was made (mw_ocean_query_velocity refuses)
     bool periodic = false;      // mw_ocean_set_periodic: the surface services read the tiling of the frame (not part of the frame record)
+    bool draught = false;       // mw_ocean_set_draught: hull forces and bodies read the water column (hull_draught.h; not part of the frame record)
     VelState vel;            // mw_ocean_velocity: the weighted spectrum and the velocity buffers (velocity_kernels.h)
     ColState col;            // mw_ocean_set_column: the layers below the surface (water_column.h)
     // four separate buffers: the host forms keep their staged inputs in scratch while hull, bodies and rc_tree are in use

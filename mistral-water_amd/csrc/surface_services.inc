@@ -231,8 +231,16 @@ struct HullCall {
 // what prepare derives from the call and the handle: the mesh of the queried frame and the coefficients as the kernels take them
 struct HullPlan { SqMesh m; HullCoeffs cf; float vscale, g; };  // vscale = coeffs[4]; g = coeffs[1], gravity (step bodies)
 
+// the water column's host code (below), as the hull family calls it with draught on (mw_ocean_set_draught, csrc/hull_draught.h)
+static mw_status column_prepare(mw_ocean* o, int32_t frame, int32_t mode, const void* xyz, int64_t n, int32_t iterations, const void* out,
+                                const char* who, SqMesh* m);
+static mw_status column_build(mw_ocean* o);
+static ColTable column_table(const mw_ocean* o, const SqMesh& m);
+
 // Validates a hull-forces call and names the surface it reads: the surface query's rules and mesh (query_prepare) with drag off, the
 // velocity query's (query_velocity_prepare: frame rules of the velocity, MW_ESTATE once the spectrum or phase moved on) with drag on.
+// With draught on, drag on or off, the column's (column_prepare: the same mesh, MW_ESTATE without a column or once the spectrum or phase
+// moved on) after the call's own argument checks.
 static mw_status hull_prepare(mw_ocean* o, int32_t frame, const HullCall& c, const char* who, HullPlan* p) {
     if (!o) return fail(MW_EINVAL, who, "NULL handle");
     if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
@@ -249,6 +257,7 @@ static mw_status hull_prepare(mw_ocean* o, int32_t frame, const HullCall& c, con
     hull_coeffs(c.coeffs, &p->cf, &p->g, &p->vscale);
     // the surface (and, with drag on, the velocity) of the frame; the markers stand for the query's arrays, checked above
     const void* mark = c.nbodies > 0 ? c.bodies : nullptr;
+    if (o->draught) return column_prepare(o, frame, MW_QUERY_WORLD, mark, c.nbodies, c.iterations, mark, who, &p->m);
     return p->cf.drag ? query_velocity_prepare(o, frame, MW_QUERY_WORLD, mark, c.nbodies, c.iterations, mark, who, &p->m)
                       : query_prepare(o, frame, MW_QUERY_WORLD, mark, c.nbodies, c.iterations, mark, who, &p->m);
 }
@@ -280,16 +289,27 @@ static mw_status hull_reserve(mw_ocean* o, int64_t nv, int64_t nblk, int64_t nb,
     return MW_OK;
 }
 // the three launches on the handle's stream (nbodies > 0), the rows into c.out
-// velocity = false: the velocity field of this frame is already in o->vel.vert (mw_ocean_step_bodies computes it once per call)
+// velocity = false: the velocity field of this frame is already in o->vel.vert, and with draught on the layers are built
+// (mw_ocean_step_bodies does either once per call)
+// Draught on: the layers of the frame (column_build, whether or not drag is on: it makes layer 0's velocity current too), then the three
+// draught kernels of water_column.hip with the layer table.
 static mw_status hull_launch(mw_ocean* o, const HullPlan& p, const HullCall& c, bool velocity = true) {
     HullWork w;
     mw_status s = hull_reserve(o, (int64_t)c.nbodies * c.nverts, (int64_t)c.nbodies * hull_chunks(c), c.nbodies, &w);
     if (s != MW_OK) return s;
-    if (velocity && p.cf.drag && (s = velocity_to_handle(o)) != MW_OK) return s;
+    if (o->draught) {
+        if (velocity && (s = column_build(o)) != MW_OK) return s;
+    } else if (velocity && p.cf.drag && (s = velocity_to_handle(o)) != MW_OK) {
+        return s;
+    }
     HullArgs a = hull_args(o, p, c);
     a.vslab = w.vslab;
     a.part = w.part;
     a.out = static_cast<float4*>(c.out);
+    if (o->draught) {
+        HIP_TRY(draught_forces_launch(o->stream, w.gv, w.gt, w.gr, a, column_table(o, p.m)));
+        return MW_OK;
+    }
     if (a.m.period != 0.f) {
         HIP_TRY(tiled_hull_forces(w.gv, w.gt, w.gr, o->stream, a));
         return MW_OK;
@@ -410,11 +430,16 @@ static mw_status mass_row_check(const void* mass, int32_t b, const char* who) {
 }
 
 // every substep of the call on the handle's stream (nbodies > 0): the velocity field once (drag on), then one k_bodies_step launch, or
-// per substep hull_launch and k_bodies_integrate
+// per substep hull_launch and k_bodies_integrate.  Draught on: the layers once (the surface is frozen for the call), then per substep
+// hull_launch's draught kernels and k_draught_integrate; there is no one-launch plan on the column and MW_BODIES_PLAN is not read.
 static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c) {
     const int nchunks = hull_chunks(c);
     mw_status s;
-    if (p.cf.drag && (s = velocity_to_handle(o)) != MW_OK) return s;
+    if (o->draught) {
+        if ((s = column_build(o)) != MW_OK) return s;
+    } else if (p.cf.drag && (s = velocity_to_handle(o)) != MW_OK) {
+        return s;
+    }
     BodiesArgs a{};
     a.h = hull_args(o, p, c);
     a.bodies = static_cast<float4*>(c.bodies);
@@ -423,7 +448,7 @@ static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c
     a.g = p.g;
     a.dt = c.dt / (float)c.substeps;
     a.substeps = c.substeps;
-    if (bodies_one_launch(c.nverts, nchunks)) {
+    if (!o->draught && bodies_one_launch(c.nverts, nchunks)) {
         const size_t lds = bodies_step_lds(c.nverts, nchunks);
         if (a.h.m.period != 0.f) {
             HIP_TRY(tiled_bodies_step(dim3((unsigned)c.nbodies), lds, MW_BODIES_LDS_MAX, o->stream, a));
@@ -443,7 +468,8 @@ static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c
         if ((s = hull_launch(o, p, rows, false)) != MW_OK) return s;
         a.last = k == c.substeps - 1;
         const dim3 gi((unsigned)(((int64_t)c.nbodies + 255) / 256));
-        if (a.h.m.period != 0.f) HIP_TRY(tiled_bodies_integrate(gi, o->stream, a));
+        if (o->draught) HIP_TRY(draught_integrate_launch(o->stream, gi, a));
+        else if (a.h.m.period != 0.f) HIP_TRY(tiled_bodies_integrate(gi, o->stream, a));
         else k_bodies_integrate<<<gi, dim3(256), 0, o->stream>>>(a);
         HIP_TRY(hipGetLastError());
     }
@@ -655,9 +681,17 @@ static mw_status fleet_launch(mw_ocean* o, const FleetPlan& p, const FleetCall& 
     return MW_OK;
 }
 
+// Fleets do not read the column yet: with draught on (mw_ocean_set_draught) every fleet entry point refuses, before any other work.
+static bool fleet_draught(const mw_ocean* o) { return o && o->draught; }
+static mw_status fleet_draught_refusal(const char* who) {
+    return fail(MW_ESTATE, who, "fleets do not read the water column yet: the handle has draught on (mw_ocean_set_draught(o, 0) first, or "
+                                "mw_ocean_hull_forces / mw_ocean_step_bodies per hull)");
+}
+
 // the host form of both entry points: validate, stage, launch, copy back
 static mw_status fleet_host(mw_ocean* o, int32_t frame, const FleetCall& c, const char* who) {
     if (o) HIP_TRY(hipSetDevice(o->device));
+    if (fleet_draught(o)) return fleet_draught_refusal(who);
     FleetPlan p{};
     mw_status s = fleet_prepare(o, frame, c, who, &p);
     if (s != MW_OK || c.total_bodies == 0) return s;
@@ -681,6 +715,7 @@ static mw_status fleet_host(mw_ocean* o, int32_t frame, const FleetCall& c, cons
 // the device form: alignment, validate, launch on the caller's arrays; never waits for the stream
 static mw_status fleet_device(mw_ocean* o, int32_t frame, const FleetCall& c, const char* who) {
     if (o) HIP_TRY(hipSetDevice(o->device));
+    if (fleet_draught(o)) return fleet_draught_refusal(who);
     if (c.total_bodies > 0 && (misaligned(c.hull, 4) || misaligned(c.tris, 4) || misaligned(c.bodies, 16) || misaligned(c.mass, 16) ||
                                misaligned(c.wrench, 16) || misaligned(c.out, 16)))
         return fail(MW_EINVAL, who, "d_hull_xyz and d_triangles must be 4-byte, d_bodies, d_mass, d_wrench and d_out 16-byte aligned");
@@ -869,6 +904,23 @@ mw_status mw_ocean_get_column(mw_ocean* o, float* depths, int32_t* nlayers) {
     if (s != MW_OK) return s;
     if (nlayers) *nlayers = o->col.L;
     if (depths) for (int l = 0; l < o->col.L; l++) depths[l] = o->col.depth[l];
+    return MW_OK;
+}
+
+// Draught: a switch on the handle, read per call by the hull family (hull_prepare, hull_launch, bodies_launch) and refused by the fleets.
+// Only a handle that can have a column takes it; no column has to be set yet.
+mw_status mw_ocean_set_draught(mw_ocean* o, int32_t on) {
+    const char* who = "mw_ocean_set_draught";
+    if (!o) return fail(MW_EINVAL, who, "NULL handle");
+    if (on != 0 && on != 1) return fail(MW_EINVAL, who, "on must be 0 or 1");
+    mw_status s = column_handle_check(o, who);
+    if (s != MW_OK) return s;
+    o->draught = on != 0;
+    return MW_OK;
+}
+mw_status mw_ocean_get_draught(mw_ocean* o, int32_t* on) {
+    if (!o) return fail(MW_EINVAL, "mw_ocean_get_draught", "NULL handle");
+    if (on) *on = o->draught ? 1 : 0;
     return MW_OK;
 }
 

@@ -189,6 +189,9 @@ public:
                                     iterations, out.empty() ? nullptr : &out[0].velocity.x));
         for (auto& s : out) { s.velocity.x /= tDivision; s.velocity.y /= tDivision; s.velocity.z /= tDivision; }
     }
+    // Not in the reference: HullForces and StepBodies read the column (SetColumn) under every hull vertex instead of the surface above it:
+    // the pressure at the vertex's rest depth, the water's velocity down there (include/mistral_water.h, draught)
+    void SetDraught(bool on = true) { check(mw_ocean_set_draught(ocean_, on ? 1 : 0)); }
     // Not in the reference: the first hit of rays on the surface of the latest EvaluateWaves() (mouse picking, projectile segments, ...)
     void Raycast(const std::vector<Ray>& rays, std::vector<RayHit>& out, std::vector<RayHitId>* ids = nullptr) {
         raycast(ocean_, -1, rays, out, ids);

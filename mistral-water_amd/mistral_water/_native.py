@@ -238,6 +238,8 @@ def lib():
         "mw_ocean_column_layers": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(vp), C.POINTER(vp)]),
         "mw_ocean_query_column": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, C.c_int32, f32p]),
         "mw_ocean_query_column_device": (C.c_int, [vp, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int32, vp]),
+        "mw_ocean_set_draught": (C.c_int, [vp, C.c_int32]),
+        "mw_ocean_get_draught": (C.c_int, [vp, vp]),
         "mw_ocean_profile_kernels": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
         "mw_ocean_profile_kernels_stats": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
         "mw_gerstner_displace": (C.c_int, [f32p, C.c_int64, f32p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
@@ -291,6 +293,7 @@ ABI_SYMBOLS = [
     "mw_ocean_fleet_forces", "mw_ocean_fleet_forces_device", "mw_ocean_step_fleet", "mw_ocean_step_fleet_device",
     "mw_ocean_raycast", "mw_ocean_raycast_device", "mw_ocean_raycast_tiled", "mw_ocean_raycast_tiled_device",
     "mw_ocean_set_column", "mw_ocean_get_column", "mw_ocean_column_layers", "mw_ocean_query_column", "mw_ocean_query_column_device",
+    "mw_ocean_set_draught", "mw_ocean_get_draught",
     "mw_gerstner_displace",
     "mw_gerstner_displace_device", "mw_gerstner_displace_steps_device", "mw_gerstner_max_steps", "mw_pond_displace", "mw_pond_displace_device",
 ]

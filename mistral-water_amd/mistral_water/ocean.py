@@ -398,6 +398,20 @@ class Ocean:
         nat.check(nat.lib().mw_ocean_query_column_device(self._h, int(frame), self._QUERY_MODES[mode], C.c_void_p(d_xyz), int(n),
                                                           int(iterations), C.c_void_p(d_out)))
 
+    # -- draught (mw_ocean_set_draught) -----------------------------------------------------------
+    def set_draught(self, on: bool = True):
+        """Switch the hull family to the water column: hull_forces, step_bodies and their device forms give every instance vertex the
+        column's rest depth (pressure over rho g) and, with drag on, the column's water velocity instead of the surface's
+        (mw_ocean_set_draught).  Read per call; needs a column (set_column) by the time of the call, MW_ESTATE otherwise.  FFTMesh handles
+        only; the fleet calls refuse a handle with draught on."""
+        nat.check(nat.lib().mw_ocean_set_draught(self._h, 1 if on else 0))
+
+    @property
+    def draught(self) -> bool:
+        on = C.c_int32(0)
+        nat.check(nat.lib().mw_ocean_get_draught(self._h, C.byref(on)))
+        return bool(on.value)
+
     # -- hull forces (mw_ocean_hull_forces) ----------------------------------------------------
     def _hull_coeffs(self, density, gravity, linear_drag, quadratic_drag, velocity_scale):
         if velocity_scale is None:  # per second of delta_time: FFTMesh velocities are per unit of t = delta_time / t_division
@@ -409,7 +423,8 @@ class Ocean:
         """Buoyancy and drag on nbodies instances of one hull -> [nbodies, 8] float32 rows (Fx, Fy, Fz, wetted_area, tx, ty, tz,
         residual), torque about each body's reference point.  hull_xyz [nverts, 3] and triangles [ntris, 3] in body space,
         (b - a) x (c - a) pointing out; bodies [nbodies, 16] (pack_bodies).  velocity_scale None: 1 / t_division (FFTMesh, per
-        second of delta_time) or 1 (OceanRenderer).  With both drag coefficients 0 no velocity is computed."""
+        second of delta_time) or 1 (OceanRenderer).  With both drag coefficients 0 no velocity is computed.  With draught on
+        (set_draught) every vertex reads the water column: its rest depth for the pressure, its velocity for the drag."""
         hull = np.ascontiguousarray(hull_xyz, np.float32).reshape(-1, 3)
         tris = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
         bodies = np.ascontiguousarray(bodies, np.float32).reshape(-1, 16)
@@ -488,7 +503,8 @@ class Ocean:
         the frozen surface of `frame` -> bodies [nbodies, 16] float32 (p _ q v _ w _), and with return_forces the hull-forces rows
         [nbodies, 8] of the last substep (at the state at its start).  bodies is updated in place when it is a C-contiguous float32
         array (the same array is returned); mass [nbodies, 8] (pack_mass) about each body's centre of mass p, the hull about p too.
-        The other arguments mean what they mean in hull_forces; gravity also pulls the bodies along -y."""
+        The other arguments mean what they mean in hull_forces; gravity also pulls the bodies along -y.  With draught on (set_draught)
+        every substep reads the water column, whose layers are built once per call."""
         hull = np.ascontiguousarray(hull_xyz, np.float32).reshape(-1, 3)
         tris = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
         b = np.ascontiguousarray(bodies, np.float32).reshape(-1, 16)
