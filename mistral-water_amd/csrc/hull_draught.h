@@ -7,15 +7,16 @@
 // wave pressure under a hull of draught T falls off as e^{-kT} and the drag acts against the water down there.  In the air the column
 // returns eta - y and no velocity, so a dry corner carries what it carries without draught and hull_cut meets d = 0 between a wet and a
 // dry corner; below the deepest layer the rest depth continues hydrostatically.  Everything after the slab -- the clip, the integrals,
-// the ordered sum, the integration -- is hull_forces.h's and rigid_bodies.h's, called and not copied.
+// the ordered sum, the integration -- is hull_forces.h's and rigid_bodies.h's, called and not copied: the functions and the kernels.
 //
-// The kernels (k_draught_vertices, k_draught_triangles, k_draught_reduce, k_draught_integrate) stand in water_column.hip, built without
-// floating-point contraction and under names of their own: the SqMesh instantiations of k_hull_* are built with contraction and are
-// bit-pinned as they are, and a second instantiation of the same template in another translation unit would be a second weak definition
-// of one symbol.  Without contraction every draught row is what the g++ build of these functions computes (tests/draught_shim.cpp), bit
-// for bit, on the one footprint and on the tiling alike.
+// Draught adds one kernel, k_draught_vertices (water_column.hip, built without floating-point contraction).  The slab it writes goes to
+// the strict build of k_hull_triangles, k_hull_reduce and k_bodies_integrate that surface_tiled.hip already holds for the periodic
+// handle (strict_hull_rows, strict_bodies_integrate): those kernels read no mesh, so the instantiation named SqTiled serves the one
+// footprint as well (hull_forces.h).  The SqMesh instantiations, built with contraction and bit-pinned, are not touched, and no
+// template is instantiated in two translation units.  Without contraction every draught row is what the g++ build of these functions
+// computes (tests/draught_shim.cpp), bit for bit, on the one footprint and on the tiling alike.
 #pragma once
-#include "rigid_bodies.h"
+#include "hull_forces.h"
 #include "water_column.h"
 
 namespace mw {
@@ -53,12 +54,9 @@ struct DraughtArgsT {
     float4* vslab;         // [nbodies * nverts][2]
 };
 
-// how the host code (surface_services.inc) launches the draught kernels of water_column.hip; each enqueues on s and returns
-// hipGetLastError().  a.m.period != 0 selects the SqTiled instantiation of the vertex kernel; the other three do not read the mesh.
-// draught_forces_launch: the three launches of hull_launch (grids gv, gt, gr of hull_reserve), the rows into a.out
-MW_INTERNAL hipError_t draught_forces_launch(hipStream_t s, dim3 gv, dim3 gt, dim3 gr, const HullArgs& a, const ColTable& tb);
-// k_draught_integrate over a.h.nbodies bodies, after draught_forces_launch wrote a.rows
-MW_INTERNAL hipError_t draught_integrate_launch(hipStream_t s, dim3 gi, const BodiesArgs& a);
+// how the host code (surface_services.inc) launches the vertex phase with draught on: k_draught_vertices on the grid gv of
+// hull_reserve, a.m.period != 0 selecting its SqTiled instantiation; enqueues on s and returns hipGetLastError()
+MW_INTERNAL hipError_t draught_vertices_launch(hipStream_t s, dim3 gv, const HullArgs& a, const ColTable& tb);
 #endif
 
 }  // namespace mw

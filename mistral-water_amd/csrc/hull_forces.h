@@ -245,7 +245,8 @@ struct HullArgsT {
     float4* out;    // [nbodies][2]
 };
 using HullArgs = HullArgsT<SqMesh>;
-// the same call with its mesh read as the tiling (a periodic handle: the kernels' SqTiled instantiations, surface_tiled.hip)
+// the same call as the SqTiled instantiations of the kernels take it (surface_tiled.hip): the mesh read as the tiling by k_hull_vertices
+// on a periodic handle, and read by no kernel after the slab (the note below)
 inline HullArgsT<SqTiled> hull_args_tiled(const HullArgs& a) {
     return HullArgsT<SqTiled>{SqTiled{a.m}, a.vel, a.vscale, a.iters, a.cf, a.hull, a.tris, a.bodies, a.nverts, a.ntris, a.nchunks, a.nbodies,
                               a.vslab, a.part, a.out};
@@ -330,6 +331,12 @@ __global__ __launch_bounds__(256) void k_hull_vertices(HullArgsT<Mesh> a) {
     hull_vertex(a.m, a.vel, a.vscale, a.iters, body, h, s);
     hull_store_row(a.vslab + 2 * k, s);
 }
+
+// The kernels after the slab -- k_hull_triangles and k_hull_reduce below ("the rows") and k_bodies_integrate (rigid_bodies.h) -- read
+// nothing of a.m: their Mesh parameter only names the translation unit, and with it the rounding, an instantiation is built in.  SqMesh
+// is mistral_water.hip's, built with contraction and bit-pinned; SqTiled is surface_tiled.hip's, built without, and serves every call
+// whose rows are the strict float32 of the g++ build whatever wrote the slab: a periodic handle (k_hull_vertices<SqTiled>) and draught
+// on either handle (k_draught_vertices, water_column.hip).  One set of after-slab kernels per rounding mode; only the vertex phase varies.
 
 // One 256-lane workgroup per (body, chunk): lane l takes triangle c*256 + l and the residual of vertex c*256 + l (every vertex is
 // counted once, referenced or not); hull_chunk_partial reduces the 8 values.  Workgroups stride over the chunks (a 1-D grid of at most

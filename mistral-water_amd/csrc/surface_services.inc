@@ -288,36 +288,37 @@ static mw_status hull_reserve(mw_ocean* o, int64_t nv, int64_t nblk, int64_t nb,
     w->gr = dim3((unsigned)std::min<int64_t>((nb + 3) / 4, (int64_t)1 << 20));
     return MW_OK;
 }
-// the three launches on the handle's stream (nbodies > 0), the rows into c.out
-// velocity = false: the velocity field of this frame is already in o->vel.vert, and with draught on the layers are built
-// (mw_ocean_step_bodies does either once per call)
-// Draught on: the layers of the frame (column_build, whether or not drag is on: it makes layer 0's velocity current too), then the three
-// draught kernels of water_column.hip with the layer table.
+// The water a hull call reads, made current once per frame: with draught on the layers (column_build, whether or not drag is on: it
+// makes layer 0's velocity current too), otherwise with drag on the velocity field in o->vel.vert.
+static mw_status hull_water(mw_ocean* o, const HullPlan& p) {
+    if (o->draught) return column_build(o);
+    return p.cf.drag ? velocity_to_handle(o) : MW_OK;
+}
+// The kernels after the vertex slab exist once per rounding mode (hull_forces.h): the strict build (surface_tiled.hip) serves draught
+// and the periodic handle, mistral_water.hip's contracted one the one footprint without draught.
+static bool hull_strict(const mw_ocean* o, const SqMesh& m) { return o->draught || m.period != 0.f; }
+// the three launches on the handle's stream (nbodies > 0), the rows into c.out: the vertex phase, chosen by (draught, period), then
+// the rows (k_hull_triangles, k_hull_reduce), chosen by hull_strict
+// velocity = false: the water is current already (mw_ocean_step_bodies sees to it once per call)
 static mw_status hull_launch(mw_ocean* o, const HullPlan& p, const HullCall& c, bool velocity = true) {
     HullWork w;
     mw_status s = hull_reserve(o, (int64_t)c.nbodies * c.nverts, (int64_t)c.nbodies * hull_chunks(c), c.nbodies, &w);
     if (s != MW_OK) return s;
-    if (o->draught) {
-        if (velocity && (s = column_build(o)) != MW_OK) return s;
-    } else if (velocity && p.cf.drag && (s = velocity_to_handle(o)) != MW_OK) {
-        return s;
-    }
+    if (velocity && (s = hull_water(o, p)) != MW_OK) return s;
     HullArgs a = hull_args(o, p, c);
     a.vslab = w.vslab;
     a.part = w.part;
     a.out = static_cast<float4*>(c.out);
-    if (o->draught) {
-        HIP_TRY(draught_forces_launch(o->stream, w.gv, w.gt, w.gr, a, column_table(o, p.m)));
-        return MW_OK;
+    if (o->draught) HIP_TRY(draught_vertices_launch(o->stream, w.gv, a, column_table(o, p.m)));
+    else if (a.m.period != 0.f) HIP_TRY(tiled_hull_vertices(w.gv, o->stream, a));
+    else k_hull_vertices<<<w.gv, dim3(256), 0, o->stream>>>(a);
+    if (hull_strict(o, a.m)) {
+        HIP_TRY(strict_hull_rows(w.gt, w.gr, o->stream, a));
+    } else {
+        k_hull_triangles<<<w.gt, dim3(MW_HULL_CHUNK), 0, o->stream>>>(a);
+        k_hull_reduce<<<w.gr, dim3(256), 0, o->stream>>>(a);
+        HIP_TRY(hipGetLastError());
     }
-    if (a.m.period != 0.f) {
-        HIP_TRY(tiled_hull_forces(w.gv, w.gt, w.gr, o->stream, a));
-        return MW_OK;
-    }
-    k_hull_vertices<<<w.gv, dim3(256), 0, o->stream>>>(a);
-    k_hull_triangles<<<w.gt, dim3(MW_HULL_CHUNK), 0, o->stream>>>(a);
-    k_hull_reduce<<<w.gr, dim3(256), 0, o->stream>>>(a);
-    HIP_TRY(hipGetLastError());
     return MW_OK;
 }
 
@@ -429,17 +430,13 @@ static mw_status mass_row_check(const void* mass, int32_t b, const char* who) {
                                     " is invalid (m <= 0 or not finite, or I_b not positive definite)");
 }
 
-// every substep of the call on the handle's stream (nbodies > 0): the velocity field once (drag on), then one k_bodies_step launch, or
-// per substep hull_launch and k_bodies_integrate.  Draught on: the layers once (the surface is frozen for the call), then per substep
-// hull_launch's draught kernels and k_draught_integrate; there is no one-launch plan on the column and MW_BODIES_PLAN is not read.
+// every substep of the call on the handle's stream (nbodies > 0): the water once (hull_water: the surface is frozen for the call), then
+// one k_bodies_step launch, or per substep hull_launch and k_bodies_integrate, the strict build where hull_launch's rows are
+// (hull_strict).  Draught on: there is no one-launch plan on the column and MW_BODIES_PLAN is not read.
 static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c) {
     const int nchunks = hull_chunks(c);
-    mw_status s;
-    if (o->draught) {
-        if ((s = column_build(o)) != MW_OK) return s;
-    } else if (p.cf.drag && (s = velocity_to_handle(o)) != MW_OK) {
-        return s;
-    }
+    mw_status s = hull_water(o, p);
+    if (s != MW_OK) return s;
     BodiesArgs a{};
     a.h = hull_args(o, p, c);
     a.bodies = static_cast<float4*>(c.bodies);
@@ -468,8 +465,7 @@ static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c
         if ((s = hull_launch(o, p, rows, false)) != MW_OK) return s;
         a.last = k == c.substeps - 1;
         const dim3 gi((unsigned)(((int64_t)c.nbodies + 255) / 256));
-        if (o->draught) HIP_TRY(draught_integrate_launch(o->stream, gi, a));
-        else if (a.h.m.period != 0.f) HIP_TRY(tiled_bodies_integrate(gi, o->stream, a));
+        if (hull_strict(o, a.h.m)) HIP_TRY(strict_bodies_integrate(gi, o->stream, a));
         else k_bodies_integrate<<<gi, dim3(256), 0, o->stream>>>(a);
         HIP_TRY(hipGetLastError());
     }

@@ -5,6 +5,9 @@
 // instantiations stay in mistral_water.hip, compiled as they always were, so a handle with the switch off keeps its bits.
 // The tiled raycast (raycast_tiled.h, mw_ocean_raycast_tiled) has its kernels here for the same reason: sq_shift, sq_reduce and the
 // column planes of its walk must round as the g++ build rounds them (tests/raycast_tiled_shim.cpp).
+// The kernels after the vertex slab (k_hull_triangles, k_hull_reduce, k_bodies_integrate) do not read the mesh (hull_forces.h), so their
+// instantiations here are the library's strict build of them: strict_hull_rows and strict_bodies_integrate serve a periodic handle and,
+// on either handle, draught (hull_draught.h), whose own vertex kernel stands in water_column.hip.
 //
 // Each function enqueues on `s` with the grids the caller worked out (surface_services.inc: the same as for SqMesh) and returns
 // hipGetLastError().  Internal to the library: hidden from its exported symbols.
@@ -18,9 +21,12 @@ namespace mw {
 MW_INTERNAL hipError_t tiled_query_surface(dim3 grid, hipStream_t s, const SqMesh& m, int mode, int iters, const float2* xz, int64_t n, float4* out);
 MW_INTERNAL hipError_t tiled_query_velocity(dim3 grid, hipStream_t s, const SqMesh& m, const float* vel, int mode, int iters, const float2* xz,
                                             int64_t n, float4* out);
-// k_hull_vertices, k_hull_triangles, k_hull_reduce on their three grids
-MW_INTERNAL hipError_t tiled_hull_forces(dim3 vertices, dim3 triangles, dim3 reduce, hipStream_t s, const HullArgs& a);
-MW_INTERNAL hipError_t tiled_bodies_integrate(dim3 grid, hipStream_t s, const BodiesArgs& a);
+// k_hull_vertices on the tiling: the vertex phase of a periodic handle without draught
+MW_INTERNAL hipError_t tiled_hull_vertices(dim3 grid, hipStream_t s, const HullArgs& a);
+// the strict build of the kernels after the slab, whichever vertex kernel wrote it: k_hull_triangles then k_hull_reduce on their two
+// grids (the rows into a.out), and k_bodies_integrate
+MW_INTERNAL hipError_t strict_hull_rows(dim3 triangles, dim3 reduce, hipStream_t s, const HullArgs& a);
+MW_INTERNAL hipError_t strict_bodies_integrate(dim3 grid, hipStream_t s, const BodiesArgs& a);
 // k_bodies_step with `lds` bytes of dynamic LDS, at most lds_max (set as the kernel's attribute once per device)
 MW_INTERNAL hipError_t tiled_bodies_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const BodiesArgs& a);
 // the fleet kernels (fleet.h): k_fleet_vertices, k_fleet_triangles, k_fleet_reduce on their three grids; k_fleet_integrate; k_fleet_step

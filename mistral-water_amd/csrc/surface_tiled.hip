@@ -23,15 +23,19 @@ hipError_t tiled_query_velocity(dim3 grid, hipStream_t s, const SqMesh& m, const
     return hipGetLastError();
 }
 
-hipError_t tiled_hull_forces(dim3 vertices, dim3 triangles, dim3 reduce, hipStream_t s, const HullArgs& a) {
+hipError_t tiled_hull_vertices(dim3 grid, hipStream_t s, const HullArgs& a) {
+    k_hull_vertices<<<grid, dim3(256), 0, s>>>(hull_args_tiled(a));
+    return hipGetLastError();
+}
+
+hipError_t strict_hull_rows(dim3 triangles, dim3 reduce, hipStream_t s, const HullArgs& a) {
     const HullArgsT<SqTiled> t = hull_args_tiled(a);
-    k_hull_vertices<<<vertices, dim3(256), 0, s>>>(t);
     k_hull_triangles<<<triangles, dim3(MW_HULL_CHUNK), 0, s>>>(t);
     k_hull_reduce<<<reduce, dim3(256), 0, s>>>(t);
     return hipGetLastError();
 }
 
-hipError_t tiled_bodies_integrate(dim3 grid, hipStream_t s, const BodiesArgs& a) {
+hipError_t strict_bodies_integrate(dim3 grid, hipStream_t s, const BodiesArgs& a) {
     k_bodies_integrate<<<grid, dim3(256), 0, s>>>(bodies_args_tiled(a));
     return hipGetLastError();
 }

@@ -9,10 +9,10 @@ csrc/water_column.h (tests/column_shim.cpp), and two float64 references --
     device's early exit is checked against it, not assumed."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import shim_build
 import surface_ref as S
 import velocity_ref as V
 from conftest import REPO
@@ -30,8 +30,7 @@ def _p(a):
 
 
 def build_shim(path):
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", path, SHIM], check=True)
-    L = C.CDLL(path)
+    L = shim_build.strict_f32(SHIM, path)
     vp, i, f = C.c_void_p, C.c_int, C.c_float
     L.cs_query.argtypes = [i, f, f, i, vp, vp, vp, i, vp, C.c_int64, i, vp]
     L.cs_weight.restype = None

@@ -1,16 +1,16 @@
 """Helpers of the draught tests (tests/test_draught_cpu.py, tests/test_draught_gpu.py): the g++ build of the hull family on the water
-column (tests/draught_shim.cpp: hull_vertex_draught and the rows in the kernels' summation order, restated there by hand), and the
+column (tests/draught_shim.cpp: hull_vertex_draught and the rows in the kernels' summation order, restated by hand in tests/hull_order.h), and the
 float64 reference -- the composition of two references that exist: column_ref.query_f64 (which locates every layer, then brackets) at
 hull_ref.transform's instance vertices gives each vertex its rest depth, water velocity and residual, and hull_ref.forces / forces_terms
 clip and integrate them."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 import column_ref as CR
 import hull_ref as H
+import shim_build
 import surface_ref as S
 from conftest import REPO
 
@@ -24,8 +24,7 @@ def _p(a):
 
 
 def build_shim(path):
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", path, SHIM], check=True)
-    L = C.CDLL(path)
+    L = shim_build.strict_f32(SHIM, path)
     vp, i, f = C.c_void_p, C.c_int, C.c_float
     L.ds_hull_forces.argtypes = [i, f, f, i, vp, vp, vp, i, vp, i, vp, i, vp, i, vp, vp, vp]
     L.ds_step_bodies.argtypes = [i, f, f, i, vp, vp, vp, i, vp, i, vp, i, vp, vp, i, vp, f, i, vp]

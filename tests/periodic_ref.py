@@ -3,10 +3,10 @@ tiled mesh (tests/periodic_shim.cpp), synthetic meshes that really repeat, the e
 float64 brute force of tests/surface_ref.py, and query points over tiles, seam strips and tile corners."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import shim_build
 import surface_ref as S
 from conftest import REPO
 
@@ -19,8 +19,7 @@ def _p(a):
 
 
 def build_shim(path):
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", path, SHIM], check=True)
-    L = C.CDLL(path)
+    L = shim_build.strict_f32(SHIM, path)
     vp, i, f = C.c_void_p, C.c_int, C.c_float
     L.ps_period.restype = f
     L.ps_period.argtypes = [i, f]

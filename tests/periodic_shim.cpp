@@ -2,15 +2,15 @@
 //
 // The MW_HD functions of the surface services (mistral-water_amd/csrc/surface_query.h, hull_forces.h, rigid_bodies.h) compiled with g++
 // over a mesh read as its infinite tiling (SqTiled, period != 0) or as the one footprint (SqMesh, period == 0): the surface and velocity
-// queries, the hull vertex step, the rows summed in the kernels' own order, and the substep chain of the bodies in both plans' order.
+// queries, the hull vertex step, the rows summed in the kernels' own order, and the substep chain of the bodies in both plans' order
+// (the order is tests/hull_order.h's hand restatement, shared with draught_shim.cpp; the vertex step is this file's).
 // The tiled kernels are built without floating-point contraction (csrc/surface_tiled.hip), so what this file computes for period != 0 is
 // what the device computes, bit for bit (tests/test_periodic_gpu.py).  Never part of libmistral_water.so and not a fallback.
 //
-// build: g++ -O2 -std=c++17 -ffp-contract=off -fPIC -shared (tests/test_periodic_cpu.py)
+// build: g++ -O2 -std=c++17 -ffp-contract=off -fPIC -shared (tests/periodic_ref.py::build_shim)
 #include <cstdint>
-#include <vector>
 
-#include "../mistral-water_amd/csrc/rigid_bodies.h"
+#include "hull_order.h"
 
 using namespace mw;
 
@@ -23,103 +23,29 @@ SqMesh mesh_of(int R, float uw, float period, const float* vert, const float* no
 bool bad(int R, float uw, int iters) { return R < 2 || !(uw > 0.f) || iters < 0 || iters > MW_SQ_MAX_ITERS; }
 int its(int iters) { return iters == 0 ? MW_SQ_DEFAULT_ITERS : iters; }
 
-// lane 0 of the kernels' shuffle tree over 64 lanes: v[l] (+)= v[l + off], off = 32 ... 1 (only the lanes that reach lane 0 are kept)
-void tree(float acc[64][7], float res[64]) {
-    for (int off = 32; off > 0; off >>= 1)
-        for (int l = 0; l < off; l++) {
-            for (int k = 0; k < 7; k++) acc[l][k] += acc[l + off][k];
-            res[l] = hull_max(res[l], res[l + off]);
-        }
-}
-
-// the row of one body from its vertex slab vs [nverts][8], summed as k_hull_triangles and k_hull_reduce (and k_bodies_step) sum it:
-// 256-triangle chunks, a tree per wave, the four waves in order, the chunks of a lane in order, the lane tree
-void body_row(const int* tris, int ntris, int nverts, const float* vs, const float body[16], const HullCoeffs& cf, float row[8]) {
-    const int nchunks = ((ntris > nverts ? ntris : nverts) + MW_HULL_CHUNK - 1) / MW_HULL_CHUNK;
-    std::vector<float> part((size_t)nchunks * 8);
-    for (int c = 0; c < nchunks; c++) {
-        float o[8];
-        for (int w = 0; w < MW_HULL_CHUNK / 64; w++) {
-            float acc[64][7], res[64];
-            for (int lane = 0; lane < 64; lane++) {
-                for (int k = 0; k < 7; k++) acc[lane][k] = 0.f;
-                res[lane] = 0.f;
-                const int t = c * MW_HULL_CHUNK + w * 64 + lane;
-                if (t < ntris && !hull_triangle(tris + 3 * (size_t)t, nverts, vs, body, cf, acc[lane])) res[lane] = NAN;
-                if (t < nverts) res[lane] = hull_max(res[lane], vs[8 * (size_t)t + 7]);
-            }
-            tree(acc, res);
-            if (w == 0) {
-                for (int k = 0; k < 7; k++) o[k] = acc[0][k];
-                o[7] = res[0];
-            } else {
-                for (int k = 0; k < 7; k++) o[k] += acc[0][k];
-                o[7] = hull_max(o[7], res[0]);
-            }
-        }
-        for (int k = 0; k < 8; k++) part[8 * (size_t)c + k] = o[k];
-    }
-    float acc[64][7], res[64];
-    for (int l = 0; l < 64; l++) {
-        for (int k = 0; k < 7; k++) acc[l][k] = 0.f;
-        res[l] = 0.f;
-        for (int c = l; c < nchunks; c += 64) {
-            for (int k = 0; k < 7; k++) acc[l][k] += part[8 * (size_t)c + k];
-            res[l] = hull_max(res[l], part[8 * (size_t)c + 7]);
-        }
-    }
-    tree(acc, res);
-    hull_row(acc[0], res[0], row);
-}
-
+// the vertex step of one body over the mesh, as hull_order takes it
 template <typename Mesh>
-void vertices(const Mesh& m, const float* vel, float vscale, int iters, const float* hull, int nverts, const float body[16], float* slab) {
-    for (int v = 0; v < nverts; v++) hull_vertex(m, vel, vscale, iters, body, hull + 3 * v, slab + 8 * (size_t)v);
+auto vertices_of(const Mesh& m, const float* vel, float vscale, int iters, const float* hull, int nverts) {
+    return [=](const float body[16], float* slab) {
+        for (int v = 0; v < nverts; v++) hull_vertex(m, vel, vscale, iters, body, hull + 3 * v, slab + 8 * (size_t)v);
+    };
 }
 
-struct Call {
-    const float *vel, *hull; const int* tris; int nverts, ntris; float vscale; int iters; HullCoeffs cf; float g, h; int substeps;
-};
-
-// mw_ocean_step_bodies in the order of each plan (csrc/rigid_bodies.h): 0 per substep (every body's row, then every body's integration),
-// 1 one launch (a body runs all its substeps, stopping at a NaN row)
-template <typename Mesh>
-void step_bodies(const Mesh& m, const Call& c, int plan, float* bodies, const float* mass, int nbodies, float* out) {
-    std::vector<float> slab((size_t)c.nverts * 8), rows((size_t)nbodies * 8);
-    if (plan == 0) {
-        for (int s = 0; s < c.substeps; s++) {
-            for (int b = 0; b < nbodies; b++) {
-                vertices(m, c.vel, c.vscale, c.iters, c.hull, c.nverts, bodies + 16 * b, slab.data());
-                body_row(c.tris, c.ntris, c.nverts, slab.data(), bodies + 16 * b, c.cf, rows.data() + 8 * b);
-            }
-            for (int b = 0; b < nbodies; b++) {
-                float* row = rows.data() + 8 * b;
-                if (!body_mass_valid(mass + 8 * b)) {
-                    for (int k = 0; k < 8; k++) row[k] = NAN;
-                } else {
-                    body_integrate(bodies + 16 * b, row, mass + 8 * b, c.g, c.h);
-                }
-                if (s == c.substeps - 1 && out)
-                    for (int k = 0; k < 8; k++) out[8 * b + k] = row[k];
-            }
-        }
-        return;
-    }
-    for (int b = 0; b < nbodies; b++) {
-        float row[8];
-        if (!body_mass_valid(mass + 8 * b)) {
-            if (out)
-                for (int k = 0; k < 8; k++) out[8 * b + k] = NAN;
-            continue;
-        }
-        for (int s = 0; s < c.substeps; s++) {
-            vertices(m, c.vel, c.vscale, c.iters, c.hull, c.nverts, bodies + 16 * b, slab.data());
-            body_row(c.tris, c.ntris, c.nverts, slab.data(), bodies + 16 * b, c.cf, row);
-            if (!body_integrate(bodies + 16 * b, row, mass + 8 * b, c.g, c.h)) break;
-        }
-        if (out)
-            for (int k = 0; k < 8; k++) out[8 * b + k] = row[k];
-    }
+// A hull export's arguments as hull_order takes them: run(call, vertices) gets the vertex step on the mesh type the period selects.
+// 1: bad arguments
+template <typename Run>
+int hull_call(int R, float uw, float period, const float* vert, const float* vel, int iters, const float* hull, int nverts, const int* tris,
+              int ntris, const float* coeffs, float dt, int substeps, Run run) {
+    if (bad(R, uw, iters) || substeps < 1) return 1;
+    const SqMesh m = mesh_of(R, uw, period, vert, vert, vert, 3);  // normals / whitecap are not read
+    HullCoeffs cf;
+    float g, vscale;
+    hull_coeffs(coeffs, &cf, &g, &vscale);
+    const float* u = cf.drag ? vel : nullptr;
+    const hull_order::Call c{tris, nverts, ntris, cf, g, dt / (float)substeps, substeps};
+    if (period != 0.f) run(c, vertices_of(SqTiled{m}, u, vscale, its(iters), hull, nverts));
+    else run(c, vertices_of(m, u, vscale, its(iters), hull, nverts));
+    return 0;
 }
 }  // namespace
 
@@ -160,32 +86,15 @@ extern "C" int ps_velocity(int R, float unit_width, float period, const float* v
 // slab [nbodies][nverts][8] (hull_vertex) and rows [nbodies][8] in the kernels' summation order; vel may be NULL (drag off)
 extern "C" int ps_hull_forces(int R, float unit_width, float period, const float* vert, const float* vel, int iters, const float* hull, int nverts,
                               const int* tris, int ntris, const float* bodies, int nbodies, const float* coeffs, float* slab, float* rows) {
-    if (bad(R, unit_width, iters)) return 1;
-    const SqMesh m = mesh_of(R, unit_width, period, vert, vert, vert, 3);
-    HullCoeffs cf;
-    float g, vscale;
-    hull_coeffs(coeffs, &cf, &g, &vscale);
-    const float* u = cf.drag ? vel : nullptr;
-    for (int b = 0; b < nbodies; b++) {
-        float* s = slab + 8 * (size_t)b * nverts;
-        if (period != 0.f) vertices(SqTiled{m}, u, vscale, its(iters), hull, nverts, bodies + 16 * b, s);
-        else vertices(m, u, vscale, its(iters), hull, nverts, bodies + 16 * b, s);
-        body_row(tris, ntris, nverts, s, bodies + 16 * b, cf, rows + 8 * b);
-    }
-    return 0;
+    return hull_call(R, unit_width, period, vert, vel, iters, hull, nverts, tris, ntris, coeffs, 0.f, 1, [&](const hull_order::Call& c, auto vertices) {
+        for (int b = 0; b < nbodies; b++) hull_order::forces(c, vertices, bodies + 16 * b, slab + 8 * (size_t)b * nverts, rows + 8 * b);
+    });
 }
 
 // mw_ocean_step_bodies: bodies [nbodies][16] in place, out [nbodies][8] or NULL; plan 0 per substep, 1 one launch
 extern "C" int ps_step_bodies(int R, float unit_width, float period, const float* vert, const float* vel, int iters, const float* hull, int nverts,
                               const int* tris, int ntris, float* bodies, const float* mass, int nbodies, const float* coeffs, float dt,
                               int substeps, int plan, float* out) {
-    if (bad(R, unit_width, iters) || substeps < 1) return 1;
-    const SqMesh m = mesh_of(R, unit_width, period, vert, vert, vert, 3);
-    HullCoeffs cf;
-    float g, vscale;
-    hull_coeffs(coeffs, &cf, &g, &vscale);
-    const Call c{cf.drag ? vel : nullptr, hull, tris, nverts, ntris, vscale, its(iters), cf, g, dt / (float)substeps, substeps};
-    if (period != 0.f) step_bodies(SqTiled{m}, c, plan, bodies, mass, nbodies, out);
-    else step_bodies(m, c, plan, bodies, mass, nbodies, out);
-    return 0;
+    return hull_call(R, unit_width, period, vert, vel, iters, hull, nverts, tris, ntris, coeffs, dt, substeps,
+                     [&](const hull_order::Call& c, auto vertices) { hull_order::step_bodies(c, vertices, plan, bodies, mass, nbodies, out); });
 }

@@ -2,17 +2,17 @@
 order, the ray families both tiers cast, triangle_t_f64 -- a float64 Möller–Trumbore over every triangle (numpy) -- and facing_f64."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+import shim_build
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(REPO, "tests", "raycast_shim.cpp")
 
 
 def build_shim(path):
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", path, SHIM], check=True)
-    L = C.CDLL(path)
+    L = shim_build.strict_f32(SHIM, path)
     vp, i64, ci = C.c_void_p, C.c_int64, C.c_int
     L.rc_shim_default_block.restype = ci
     L.rc_shim_default_block.argtypes = []

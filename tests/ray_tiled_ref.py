@@ -3,10 +3,10 @@ synthetic N x N frames (any displacement of the rest grid tiles by construction)
 with the brute force and the float64 view of a window's triangle instances."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import shim_build
 from ray_ref import _p, pack
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,8 +15,7 @@ OUT_OF_REACH = -2
 
 
 def build_shim(path):
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", path, SHIM], check=True)
-    L = C.CDLL(path)
+    L = shim_build.strict_f32(SHIM, path)
     vp, i64, ci, cf = C.c_void_p, C.c_int64, C.c_int, C.c_float
     L.rct_shim_max_reach.restype = ci
     L.rct_shim_nodes.restype = i64

@@ -9,13 +9,13 @@
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import body_ref as B
 import hull_ref as H
+import shim_build
 from conftest import REPO
 
 SHIM = os.path.join(REPO, "tests", "bodies_shim.cpp")
@@ -29,8 +29,7 @@ def _p(a):
 @pytest.fixture(scope="module")
 def bs(tmp_path_factory):
     path = str(tmp_path_factory.mktemp("bodies") / "libbodies_shim.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", path, SHIM], check=True)
-    L = C.CDLL(path)
+    L = shim_build.strict_f32(SHIM, path)
     L.bs_integrate.restype = None
     L.bs_integrate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p]
     L.bs_mass_valid.restype = None

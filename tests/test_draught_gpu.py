@@ -1,7 +1,8 @@
 """GPU tier of draught (mw_ocean_set_draught, include/mistral_water.h) through the C ABI.
 
-* the draught kernels are compiled without floating-point contraction (csrc/water_column.hip), so the reference of every row and every
-  stepped state is the g++ build of the same MW_HD functions with the summation order restated by hand (tests/draught_shim.cpp) run on
+* with draught on every kernel of the hull family is one compiled without floating-point contraction (the vertex kernel of
+  csrc/water_column.hip, then the strict rows and integration of csrc/surface_tiled.hip), so the reference of every row and every stepped
+  state is the g++ build of the same MW_HD functions with the summation order restated by hand (tests/draught_shim.cpp, hull_order.h) run on
   the device's own layer arrays: bit for bit, on the one footprint and on the tiling, host and device forms, drag off and on;
 * the Smith effect through the whole stack: a one-bin spectrum, 16 spars a sixteenth of a wavelength apart;
 * the state rules, and that the switch moves nothing else and leaves nothing behind when it is switched off again."""
@@ -13,6 +14,7 @@ import pytest
 import draught_ref as DR
 import hull_ref as H
 import periodic_ref as PR
+import test_hull_sizes_gpu as THS
 import workloads
 
 pytestmark = pytest.mark.gpu
@@ -164,6 +166,34 @@ def test_device_equals_the_shim_bit_for_bit(mw, shim, L, periodic):
                     if drag and (~nan & ~air).any():
                         assert (slab[~nan & ~air][:, :, 4:7] != 0).any()
         assert min(seen.values()) >= 2 * len(HULLS), seen
+
+
+@pytest.mark.parametrize("periodic", [False, True], ids=["footprint", "periodic"])
+def test_t16385_the_second_lap_of_the_reduce_equals_the_shim(mw, shim, periodic):
+    """The hulls above stop at 257 triangles, 2 chunks.  t16385 (test_hull_sizes_gpu.hull_of) has 65: the smallest hull at which a lane of
+    the reduce adds two partials (hull_body_sum's second lap), which draught reaches through the strict kernels it shares with the
+    periodic handle.  Two bodies with the bottom sheet and so every sentinel wet (hull_ref.afloat_poses), on the periodic handle the
+    second in another tile; L = 2, drag on, one forces call per handle."""
+    p = workloads.fftmesh_params(64, choppiness=1.0)
+    depths = _depths(2)
+    hull, tris = THS.hull_of("t16385")
+    rng = np.random.default_rng(65 + periodic)
+    with _ocean(mw, p) as o:
+        o.set_column(depths)
+        o.evaluate(1.7)
+        if periodic:
+            o.set_periodic(True)
+        o.set_draught(True)
+        pos, vel = _layers(o, 2)
+        P = o.period if periodic else 0.0
+        eta = lambda xz: o.query_surface(np.ascontiguousarray(xz, f32))[:, 1].astype(np.float64)  # noqa: E731
+        pq = H.afloat_poses(2, rng, 20.0, eta, tile_shift=(P, -2 * P) if periodic else None)
+        bodies = DR.pack(*pq, rng.standard_normal((2, 3)) * 0.8, rng.standard_normal((2, 3)) * 0.3)
+        slab, want = DR.forces(shim, 64, 1.0, P, depths, pos, vel, hull, tris, bodies, _coeffs(True))
+        got = _forces_device(o, hull, tris, bodies, True)
+    assert np.isfinite(want).all() and (slab[:, :, 4:7] != 0).any()
+    assert len(H.sentinel_slots(len(tris))) == 5 and (want[:, 3] > 5 * 18.0 * 0.99).all()   # wet area: every sentinel, 18 each
+    assert np.array_equal(bits(got), bits(want)), (got, want)
 
 
 # ---- 2. stepping ----------------------------------------------------------------------------------------------------------------------

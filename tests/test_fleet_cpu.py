@@ -8,13 +8,13 @@
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import body_ref as B
 import hull_ref as H
+import shim_build
 from conftest import REPO
 
 SHIM = os.path.join(REPO, "tests", "fleet_shim.cpp")
@@ -30,8 +30,7 @@ def _p(a):
 @pytest.fixture(scope="module")
 def fs(tmp_path_factory):
     path = str(tmp_path_factory.mktemp("fleet") / "libfleet_shim.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", path, SHIM], check=True)
-    L = C.CDLL(path)
+    L = shim_build.strict_f32(SHIM, path)
     L.fs_totals.restype = None
     L.fs_totals.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
     L.fs_map_all.restype = None

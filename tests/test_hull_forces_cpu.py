@@ -10,12 +10,12 @@ against tests/hull_ref.py (numpy float64):
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import hull_ref as H
+import shim_build
 import surface_ref as S
 from conftest import REPO, has_gpu
 from test_surface_query_cpu import build_shim as build_sq_shim, query as sq_query
@@ -34,8 +34,7 @@ def _p(a):
 @pytest.fixture(scope="module")
 def hs(tmp_path_factory):
     path = str(tmp_path_factory.mktemp("hull") / "libhull_shim.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", path, SHIM], check=True)
-    L = C.CDLL(path)
+    L = shim_build.strict_f32(SHIM, path)
     L.hs_vertices.restype = C.c_int
     L.hs_vertices.argtypes = [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                               C.c_void_p]
@@ -56,8 +55,7 @@ def sqshim(tmp_path_factory):
 @pytest.fixture(scope="module")
 def vshim(tmp_path_factory):
     path = str(tmp_path_factory.mktemp("vqh") / "libvq_shim.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", path, VSHIM], check=True)
-    L = C.CDLL(path)
+    L = shim_build.strict_f32(VSHIM, path)
     L.vq_shim_query.restype = C.c_int
     L.vq_shim_query.argtypes = [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     return L

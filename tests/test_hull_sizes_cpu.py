@@ -1,6 +1,6 @@
 """CPU tier of the hull summation scheme at its size edges (csrc/hull_forces.h, rigid_bodies.h, fleet.h): 256-triangle chunks, a 64-lane
 tree per wave, the four waves in order, one partial row per chunk, and a reduce in which lane l adds chunks l, l + 64, ... before a lane
-tree.  The kernels that run it are device-only; tests/periodic_shim.cpp::body_row restates its order by hand and is what the GPU tier
+tree.  The kernels that run it are device-only; tests/hull_order.h::body_row (built into tests/periodic_shim.cpp) restates its order by hand and is what the GPU tier
 (tests/test_hull_sizes_gpu.py) compares bits with.  Here that restatement is itself checked, on the edge hulls of tests/hull_ref.py
 (edge_hull: 255 / 256 / 257 triangles, 40 triangles on 600 vertices, 16 384 / 16 385 and 32 769 triangles, i.e. 1, 1, 2, 3, 64, 65 and
 129 chunks), over the synthetic periodic mesh periodic_synth(64, 1.0, 0.5):
@@ -12,13 +12,13 @@ tree.  The kernels that run it are device-only; tests/periodic_shim.cpp::body_ro
 * the launch arithmetic: hull_chunks / fleet_chunks at the chunk edges, bodies_step_lds at the one-launch plan's LDS limit."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import hull_ref as H
 import periodic_ref as PR
+import shim_build
 from conftest import REPO
 
 RHO, G = 1000.0, 9.81
@@ -172,9 +172,7 @@ def test_deleting_a_sentinel_moves_the_reference_by_100_bounds(shim, mesh, name)
 @pytest.fixture(scope="module")
 def fleet_shim(tmp_path_factory):
     path = str(tmp_path_factory.mktemp("hs_fleet") / "libfleet_shim.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", path, os.path.join(REPO, "tests", "fleet_shim.cpp")],
-                   check=True)
-    L = C.CDLL(path)
+    L = shim_build.strict_f32(os.path.join(REPO, "tests", "fleet_shim.cpp"), path)
     L.fs_chunks.argtypes = [C.c_int, C.c_int]
     return L
 

@@ -6,11 +6,11 @@
   synthetic choppy meshes below and beyond the fold limit."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import shim_build
 import surface_ref as S
 from conftest import REPO, has_gpu
 
@@ -19,9 +19,7 @@ HDR = os.path.join(REPO, "mistral-water_amd", "csrc", "surface_query.h")
 
 
 def build_shim(path, defs=()):
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"] + ["-D" + d for d in defs] + ["-o", path, SHIM],
-                   check=True)
-    L = C.CDLL(path)
+    L = shim_build.strict_f32(SHIM, path, defs)
     L.sq_shim_query.restype = C.c_int
     L.sq_shim_query.argtypes = [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64,
                                 C.c_int, C.c_void_p]

@@ -8,11 +8,11 @@
 * the four entry points are exported and refuse bad arguments with a status, without a GPU."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import shim_build
 import surface_ref as S
 import velocity_ref as V
 import workloads
@@ -30,8 +30,7 @@ def _p(a):
 @pytest.fixture(scope="module")
 def vshim(tmp_path_factory):
     path = str(tmp_path_factory.mktemp("vq") / "libvq_shim.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", path, SHIM], check=True)
-    L = C.CDLL(path)
+    L = shim_build.strict_f32(SHIM, path)
     L.vq_shim_query.restype = C.c_int
     L.vq_shim_query.argtypes = [C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     L.vq_shim_omega.restype = None
