@@ -27,6 +27,7 @@ public static class MistralWaterNative
     public const int BodyNMass = 8;
     public const int RcDefaultReach = 16, RcMaxReach = 1024;
     public const int FleetMaxHulls = 32, FleetNHull = 5;
+    public const int MooringMaxLines = 8, MooringNLine = 12;
     public const int ColumnMaxLayers = 16;
 
     [StructLayout(LayoutKind.Sequential)]   // mw_params: 56 bytes
@@ -136,6 +137,10 @@ public static class MistralWaterNative
     [DllImport(Lib)] public static extern Status mw_hull_mass_properties(float[] hullXyz, int nverts, int[] triangles, int ntris, float density, [Out] float[] massProperties);
     [DllImport(Lib)] public static extern Status mw_ocean_step_bodies(IntPtr ocean, int frame, float[] hullXyz, int nverts, int[] triangles, int ntris, [In] [Out] float[] bodies, float[] mass, int nbodies, float[] coeffs, float dt, int substeps, int iterations, [Out] float[] result);
     [DllImport(Lib)] public static extern Status mw_ocean_step_bodies_device(IntPtr ocean, int frame, IntPtr dHullXyz, int nverts, IntPtr dTriangles, int ntris, IntPtr dBodies, IntPtr dMass, int nbodies, float[] coeffs, float dt, int substeps, int iterations, IntPtr dResult);
+    // moorings: step_bodies with lines [nbodies][linesPerBody][MooringNLine] = (hx, hy, hz, L0 | ax, ay, az, k | c, _, _, _) from a point of the body
+    // (body space, about p) to a fixed anchor (world); linesPerBody in [1, MooringMaxLines]; tension [nbodies][linesPerBody] or null
+    [DllImport(Lib)] public static extern Status mw_ocean_step_moored(IntPtr ocean, int frame, float[] hullXyz, int nverts, int[] triangles, int ntris, [In] [Out] float[] bodies, float[] mass, float[] lines, int linesPerBody, int nbodies, float[] coeffs, float dt, int substeps, int iterations, [Out] float[] result, [Out] float[] tension);
+    [DllImport(Lib)] public static extern Status mw_ocean_step_moored_device(IntPtr ocean, int frame, IntPtr dHullXyz, int nverts, IntPtr dTriangles, int ntris, IntPtr dBodies, IntPtr dMass, IntPtr dLines, int linesPerBody, int nbodies, float[] coeffs, float dt, int substeps, int iterations, IntPtr dResult, IntPtr dTension);
     // mixed fleets: every hull's geometry concatenated (triangle indices local to their hull), hulls [nhulls][FleetNHull] = (vertFirst, nverts,
     // triFirst, ntris, nbodies), coeffs [nhulls][HullNCoeffs]; bodies, mass, wrench [totalBodies][8] = (Fx, Fy, Fz, _, tx, ty, tz, _) or null
     // and result hull after hull in table order; a body's row and state have the bits of the single-hull call on its hull alone

@@ -443,6 +443,51 @@ mw_status mw_ocean_step_bodies_device(mw_ocean* o, int32_t frame, const void* d_
                                       int32_t ntris, void* d_bodies, const void* d_mass, int32_t nbodies, const float* coeffs,
                                       float dt, int32_t substeps, int32_t iterations, void* d_out);
 
+/* ---- moorings: step floating bodies tethered to anchors by lines ---------------------------------------------------
+ * mw_ocean_step_moored is mw_ocean_step_bodies with up to MW_MOORING_MAX_LINES lines per body, each from a point of the body to a fixed
+ *   anchor.  A line's force depends on the pose and velocity of the body at every substep, so it is computed inside the substep loop, on
+ *   the device: the state still crosses the API once per call.
+ * lines [nbodies][lines_per_body][MW_MOORING_NLINE], lines_per_body = K in [1, MW_MOORING_MAX_LINES].  One slot is three float4:
+ *     hx hy hz L0 | ax ay az k | c _ _ _
+ *   h: the attachment point in body space, about p, like the hull.  L0 >= 0: the unstretched length.  a: the anchor in the object space
+ *   of the bodies (world).  k >= 0: the stiffness.  c >= 0: the damping along the line.  The last three floats are padding and are not
+ *   read.  A slot with k == 0 and c == 0 is empty and is skipped.
+ * Per substep, at the state at its start (the state the water row is evaluated at), for every non-empty slot in slot order:
+ *   1. x = p + R(q) h, R the rotation the hull vertices use;   2. va = v + w x (x - p);   3. r = a - x, l = |r|;
+ *   4. l <= L0: the line is slack and contributes nothing (l == 0 included);
+ *   5. e = r / l, T = max(0, k (l - L0) - c (va . e)): a line pulls and never pushes;   6. F = T e, tau = (x - p) x F.
+ *   (x - p is evaluated as R(q) h, before p is added.)  The body's mooring wrench M is the sum of the taut slots' (F, tau) in slot order,
+ *   starting from the first taut slot's own value.  With at least one slot taut, steps 2 and 3 of the integrator see F[k] + M[k] and
+ *   tau[k] + M[4+k], one float32 add each, exactly as mw_ocean_step_fleet adds a wrench.  With no slot taut the water row is used as
+ *   it is, no addition: a call whose lines all stay slack or empty leaves the bits of the unmoored call on a periodic handle and with
+ *   draught on (on the one footprint without draught mw_ocean_step_bodies integrates with contraction and this call strictly: equal to
+ *   rounding there).  out still reports the water row alone.  All of it is strict float32.
+ * tension [nbodies][lines_per_body] is optional (NULL allowed): each slot's T at the start of the last substep, 0 for a slack or
+ *   empty slot.
+ * Stability: the integrator is the semi-implicit Euler of mw_ocean_step_bodies.  It needs h sqrt(k_total / m) < 2, h = dt / substeps,
+ *   for the stiffest direction (k_total the summed stiffness of the lines along it).  The library does not check this.
+ * Invalid slots: a slot is invalid when one of its nine used floats is not finite or L0, k or c is negative.  It is treated like an
+ *   invalid mass row: the host form returns MW_EINVAL naming body and slot, the device form gives that body a NaN out row and NaN
+ *   tensions and leaves its state unchanged.  The NaN-row rule of mw_ocean_step_bodies is unchanged.
+ * Everything else -- frame, state, argument, alignment and size rules, "changes nothing of the handle's state", the periodic switch and
+ *   the draught switch -- is mw_ocean_step_bodies'.  In addition MW_EINVAL for lines_per_body outside [1, MW_MOORING_MAX_LINES] or a
+ *   NULL lines with nbodies > 0; device form: d_lines 16-byte, d_tension 4-byte aligned.
+ * Plans: on a periodic handle without draught the call follows mw_ocean_step_bodies' plan rule (one launch for hulls of fewer than 4
+ *   chunks, per substep above); on a non-periodic handle and with draught on it always steps per substep.  The bits are the same.
+ * Not yet: mw_ocean_step_fleet has no lines, and there are no body-to-body lines (tow lines): a body's substep reads no other body.    */
+#define MW_MOORING_MAX_LINES 8
+#define MW_MOORING_NLINE 12   /* slot: hx hy hz L0 | ax ay az k | c _ _ _ */
+/* host arrays, synchronous */
+mw_status mw_ocean_step_moored(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles,
+                               int32_t ntris, float* bodies, const float* mass, const float* lines, int32_t lines_per_body,
+                               int32_t nbodies, const float* coeffs, float dt, int32_t substeps, int32_t iterations, float* out,
+                               float* tension);
+/* device arrays, asynchronous on the handle's stream; coeffs host */
+mw_status mw_ocean_step_moored_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
+                                      int32_t ntris, void* d_bodies, const void* d_mass, const void* d_lines, int32_t lines_per_body,
+                                      int32_t nbodies, const float* coeffs, float dt, int32_t substeps, int32_t iterations,
+                                      void* d_out, void* d_tension);
+
 /* ---- mixed fleets: forces and stepping for many hull shapes in one call ---------------------------------------------
  * mw_ocean_fleet_forces and mw_ocean_step_fleet are mw_ocean_hull_forces and mw_ocean_step_bodies for a whole scene: up to
  *   MW_FLEET_MAX_HULLS hull shapes, each with its own coefficients and its own bodies, in one call.  The velocity field (drag on) is
@@ -480,7 +525,8 @@ mw_status mw_ocean_step_bodies_device(mw_ocean* o, int32_t frame, const void* d_
  * MW_EINVAL for a broken hull-table rule; total_bodies, sum nbodies_h * nverts_h or sum nbodies_h * ntris_h above 2^31 - 256; a NULL
  *   array with total_bodies > 0 (hulls and coeffs always); a negative or non-finite coefficient; a batched handle; and the substeps,
  *   dt, frame, iterations and alignment rules of the single-hull calls (d_wrench 16-byte aligned).  total_bodies == 0 does nothing.
- *   Caller arrays are untouched on failure; nothing of the handle's state changes.  The calls share the single-hull calls' buffers. */
+ *   Caller arrays are untouched on failure; nothing of the handle's state changes.  The calls share the single-hull calls' buffers.
+ * mw_ocean_step_fleet has no mooring lines yet (mw_ocean_step_moored steps one hull's bodies on theirs).                            */
 #define MW_FLEET_MAX_HULLS 32
 #define MW_FLEET_NHULL 5   /* hull row: vert_first, nverts, tri_first, ntris, nbodies */
 /* host arrays, synchronous */

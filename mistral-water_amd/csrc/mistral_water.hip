@@ -131,7 +131,7 @@ static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 namespace {  // internal linkage: at file scope Stage::begin / finish would join the library's exported symbols
 struct Stage {
     struct Region { void** dev; const void* in; void* out; size_t bytes, off; };
-    static constexpr int MAX = 6;
+    static constexpr int MAX = 7;  // mw_ocean_step_moored declares the most: hull, triangles, bodies, mass, lines, out, tension
     mw_ocean* o;
     Region r[MAX];
     int n = 0;
@@ -140,7 +140,7 @@ struct Stage {
     void add(void** dev, const void* in, void* out, size_t bytes) {
         *dev = nullptr;
         if (!in && !out) return;
-        if (n == MAX) std::abort();  // a seventh region is a mistake in this file, never a caller's: stop before writing past r[]
+        if (n == MAX) std::abort();  // an eighth region is a mistake in this file, never a caller's: stop before writing past r[]
         const size_t off = align256(total);
         r[n++] = Region{dev, in, out, bytes, off};
         total = off + bytes;

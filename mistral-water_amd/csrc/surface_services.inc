@@ -513,6 +513,118 @@ mw_status mw_ocean_step_bodies(mw_ocean* o, int32_t frame, const float* hull_xyz
     return st.finish();
 }
 
+// ---- moorings (csrc/moorings.h) -----------------------------------------------------------------------------------
+static_assert(MW_MOORING_MAX_LINES == MW_MOORING_LINES && MW_MOORING_NLINE == MW_MOORING_SLOT, "moorings.h and the ABI size a slot alike");
+// what a moored call carries beyond a step-bodies call (HullCall); as there, the caller's pointers or their staged copies
+struct MooredLines { const void* lines; int32_t K; void* tension; };
+
+// Validates a step-moored call: its own arguments, then the step-bodies rules (bodies_prepare).
+static mw_status moored_prepare(mw_ocean* o, int32_t frame, const HullCall& c, const MooredLines& ml, const char* who, HullPlan* p) {
+    if (ml.K < 1 || ml.K > MW_MOORING_MAX_LINES) return fail(MW_EINVAL, who, "lines_per_body must be in [1, MW_MOORING_MAX_LINES]");
+    if (c.nbodies > 0 && !ml.lines) return fail(MW_EINVAL, who, "NULL lines");
+    return bodies_prepare(o, frame, c, who, p);
+}
+// the one-launch plan takes the hull when step bodies would (bodies_one_launch) and k_moored_step's static LDS fits beside it
+static bool moored_one_launch(int nverts, int nchunks) {
+    return bodies_one_launch(nverts, nchunks) && bodies_step_lds(nverts, nchunks) + MW_MOORED_LDS_STATIC <= MW_BODIES_LDS_MAX;
+}
+// every substep of the call on the handle's stream (nbodies > 0), as bodies_launch: the water once, then one k_moored_step launch (a
+// periodic handle without draught whose hull qualifies; MW_BODIES_PLAN is honoured) or per substep hull_launch and k_moored_integrate.
+// A non-periodic handle and draught always step per substep, as the fleets and draught do.
+static mw_status moored_launch(mw_ocean* o, const HullPlan& p, const HullCall& c, const MooredLines& ml) {
+    const int nchunks = hull_chunks(c);
+    mw_status s = hull_water(o, p);
+    if (s != MW_OK) return s;
+    const float h = c.dt / (float)c.substeps;
+    if (!o->draught && p.m.period != 0.f && moored_one_launch(c.nverts, nchunks)) {
+        BodiesArgs a{};
+        a.h = hull_args(o, p, c);
+        a.bodies = static_cast<float4*>(c.bodies);
+        a.mass = static_cast<const float4*>(c.mass);
+        a.out = static_cast<float4*>(c.out);
+        a.g = p.g;
+        a.dt = h;
+        a.substeps = c.substeps;
+        HIP_TRY(tiled_moored_step(dim3((unsigned)c.nbodies), bodies_step_lds(c.nverts, nchunks), MW_BODIES_LDS_MAX, o->stream, a,
+                                  static_cast<const float4*>(ml.lines), ml.K, static_cast<float*>(ml.tension)));
+        return MW_OK;
+    }
+    if ((s = grow_reserve(o, o->bodies, (size_t)c.nbodies * 8 * sizeof(float), "the step-bodies row buffer")) != MW_OK) return s;
+    MooredArgs a{};
+    a.bodies = static_cast<float4*>(c.bodies);
+    a.mass = static_cast<const float4*>(c.mass);
+    a.rows = static_cast<const float4*>(o->bodies.p);
+    a.lines = static_cast<const float4*>(ml.lines);
+    a.out = static_cast<float4*>(c.out);
+    a.tension = static_cast<float*>(ml.tension);
+    a.g = p.g;
+    a.dt = h;
+    a.nbodies = c.nbodies;
+    a.K = ml.K;
+    HullCall rows = c;  // the hull forces of a substep: the same call, its rows into the handle's buffer
+    rows.out = o->bodies.p;
+    const dim3 gi((unsigned)(((int64_t)c.nbodies + 255) / 256));
+    for (int k = 0; k < c.substeps; k++) {
+        if ((s = hull_launch(o, p, rows, false)) != MW_OK) return s;
+        a.last = k == c.substeps - 1;
+        HIP_TRY(strict_moored_integrate(gi, o->stream, a));
+    }
+    return MW_OK;
+}
+
+mw_status mw_ocean_step_moored_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
+                                      int32_t ntris, void* d_bodies, const void* d_mass, const void* d_lines, int32_t lines_per_body,
+                                      int32_t nbodies, const float* coeffs, float dt, int32_t substeps, int32_t iterations, void* d_out,
+                                      void* d_tension) {
+    const char* who = "mw_ocean_step_moored_device";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (nbodies > 0 && (misaligned(d_hull_xyz, 4) || misaligned(d_triangles, 4) || misaligned(d_bodies, 16) || misaligned(d_mass, 16) ||
+                        misaligned(d_lines, 16) || misaligned(d_out, 16) || misaligned(d_tension, 4)))
+        return fail(MW_EINVAL, who, "d_hull_xyz, d_triangles and d_tension must be 4-byte, d_bodies, d_mass, d_lines and d_out 16-byte aligned");
+    const HullCall c{d_hull_xyz, d_triangles, d_bodies, d_mass, d_out, nverts, ntris, nbodies, iterations, coeffs, dt, substeps};
+    const MooredLines ml{d_lines, lines_per_body, d_tension};
+    HullPlan p{};
+    mw_status s = moored_prepare(o, frame, c, ml, who, &p);
+    if (s != MW_OK || nbodies == 0) return s;
+    return moored_launch(o, p, c, ml);
+}
+
+mw_status mw_ocean_step_moored(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles, int32_t ntris,
+                               float* bodies, const float* mass, const float* lines, int32_t lines_per_body, int32_t nbodies,
+                               const float* coeffs, float dt, int32_t substeps, int32_t iterations, float* out, float* tension) {
+    const char* who = "mw_ocean_step_moored";
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    const HullCall c{hull_xyz, triangles, bodies, mass, out, nverts, ntris, nbodies, iterations, coeffs, dt, substeps};
+    MooredLines ml{lines, lines_per_body, tension};
+    HullPlan p{};
+    mw_status s = moored_prepare(o, frame, c, ml, who, &p);
+    if (s != MW_OK || nbodies == 0) return s;
+    if (!triangles_in_range(triangles, ntris, nverts)) return fail(MW_EINVAL, who, "triangle index outside [0, nverts)");
+    const size_t K = (size_t)lines_per_body;
+    for (int32_t b = 0; b < nbodies; b++) {
+        if ((s = mass_row_check(mass, b, who)) != MW_OK) return s;
+        for (size_t k = 0; k < K; k++)
+            if (!mooring_slot_valid(lines + MW_MOORING_NLINE * ((size_t)b * K + k)))
+                return fail(MW_EINVAL, who, "slot " + std::to_string(k) + " of body " + std::to_string(b) +
+                                                " is invalid (a non-finite float, or L0, k or c negative)");
+    }
+    void *d_hull, *d_tris, *d_bodies, *d_mass, *d_lines, *d_out, *d_tension;
+    Stage st(o);
+    st.in(&d_hull, hull_xyz, (size_t)nverts * 3 * sizeof(float));
+    st.in(&d_tris, triangles, (size_t)ntris * 3 * sizeof(int32_t));
+    st.inout(&d_bodies, bodies, (size_t)nbodies * 16 * sizeof(float));
+    st.in(&d_mass, mass, (size_t)nbodies * 8 * sizeof(float));
+    st.in(&d_lines, lines, (size_t)nbodies * K * MW_MOORING_NLINE * sizeof(float));
+    st.out(&d_out, out, (size_t)nbodies * 8 * sizeof(float));      // optional
+    st.out(&d_tension, tension, (size_t)nbodies * K * sizeof(float));  // optional
+    if ((s = st.begin()) != MW_OK) return s;
+    HullCall d = c;
+    d.hull = d_hull; d.tris = d_tris; d.bodies = d_bodies; d.mass = d_mass; d.out = d_out;
+    ml.lines = d_lines; ml.tension = d_tension;
+    if ((s = moored_launch(o, p, d, ml)) != MW_OK) return s;
+    return st.finish();
+}
+
 // ---- mixed fleets (csrc/fleet.h) ----------------------------------------------------------------------------------
 static_assert(MW_FLEET_MAX_HULLS == MW_FLEET_HULLS && MW_FLEET_NHULL == 5, "fleet.h and the ABI size the hull table alike");
 // The arguments of a fleet-forces or step-fleet call; as HullCall, the host and the device form differ only in whose pointers it holds.

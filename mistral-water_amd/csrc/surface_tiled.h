@@ -14,6 +14,7 @@
 #pragma once
 #include "rigid_bodies.h"
 #include "fleet.h"
+#include "moorings.h"
 #include "raycast.h"  // RcTree
 
 namespace mw {
@@ -34,6 +35,11 @@ MW_INTERNAL hipError_t tiled_bodies_step(dim3 grid, size_t lds, int lds_max, hip
 MW_INTERNAL hipError_t tiled_fleet_forces(dim3 vertices, dim3 triangles, dim3 reduce, hipStream_t s, const FleetArgs& a);
 MW_INTERNAL hipError_t tiled_fleet_integrate(dim3 grid, hipStream_t s, const FleetArgs& a);
 MW_INTERNAL hipError_t tiled_fleet_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const FleetArgs& a);
+// moorings (moorings.h): k_moored_integrate, which reads no mesh and serves every handle, and k_moored_step on the tiling with `lds`
+// bytes of dynamic LDS, as tiled_bodies_step
+MW_INTERNAL hipError_t strict_moored_integrate(dim3 grid, hipStream_t s, const MooredArgs& a);
+MW_INTERNAL hipError_t tiled_moored_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const BodiesArgs& a, const float4* lines, int K,
+                                         float* tension);
 // k_rct_build_leaves: the leaf boxes of one tile and the levels above them up to D - 4 (k_rc_build_top, launched by the caller, does the
 // rest); k_raycast_tiled: one lane per ray.  m.period is the tiling's P.
 MW_INTERNAL hipError_t tiled_raycast_build_leaves(dim3 grid, hipStream_t s, const SqMesh& m, const RcTree& tr);

@@ -124,6 +124,28 @@ inline void step_bodies(mw_ocean* o, int32_t frame, const std::vector<Vector3>& 
                                forces && !forces->empty() ? &(*forces)[0].force.x : nullptr));
 }
 
+// mw_ocean_step_moored: one slot of a body's lines -- from `attach` (body space, about the centre of mass) to the fixed `anchor` (world)
+struct MooringLine {
+    Vector3 attach; float restLength = 0.f;
+    Vector3 anchor; float stiffness = 0.f;  // stiffness == 0 and damping == 0: an empty slot
+    float damping = 0.f; float pad[3] = {0.f, 0.f, 0.f};
+};
+static_assert(sizeof(MooringLine) == MW_MOORING_NLINE * sizeof(float), "[nbodies][K][MW_MOORING_NLINE] floats of mw_ocean_step_moored");
+// step_bodies with lines [nbodies * linesPerBody], body after body; tension (optional) gets each slot's pull at the start of the last substep
+inline void step_moored(mw_ocean* o, int32_t frame, const std::vector<Vector3>& hull, const std::vector<int32_t>& triangles,
+                        std::vector<HullBody>& bodies, const std::vector<BodyMass>& mass, const std::vector<MooringLine>& lines,
+                        int32_t linesPerBody, float dt, int32_t substeps, float density, float gravity, float linearDrag, float quadraticDrag,
+                        float velocityScale, std::vector<HullForce>* forces, std::vector<float>* tension) {
+    if (forces) forces->resize(bodies.size());
+    if (tension) tension->resize(lines.size());
+    const float coeffs[MW_HULL_NCOEFFS] = {density, gravity, linearDrag, quadraticDrag, velocityScale};
+    check(mw_ocean_step_moored(o, frame, hull.empty() ? nullptr : &hull[0].x, (int32_t)hull.size(), triangles.empty() ? nullptr : &triangles[0],
+                               (int32_t)(triangles.size() / 3), bodies.empty() ? nullptr : &bodies[0].position.x,
+                               mass.empty() ? nullptr : &mass[0].mass, lines.empty() ? nullptr : &lines[0].attach.x, linesPerBody,
+                               (int32_t)bodies.size(), coeffs, dt, substeps, 0, forces && !forces->empty() ? &(*forces)[0].force.x : nullptr,
+                               tension && !tension->empty() ? tension->data() : nullptr));
+}
+
 class FFTMesh {
 public:
     // ---- public Inspector fields, S/FFTMesh.cs:9-23 -------------------------------------------------
@@ -210,6 +232,14 @@ public:
                     float linearDrag = 0.f, float quadraticDrag = 0.f, std::vector<HullForce>* forces = nullptr) {
         step_bodies(ocean_, -1, hull, triangles, bodies, mass, deltaTime, substeps, density, gravity, linearDrag, quadraticDrag,
                     1.f / tDivision, forces);
+    }
+    // Not in the reference: StepBodies with mooring lines, linesPerBody slots per body (lines [bodies.size() * linesPerBody])
+    void StepMoored(const std::vector<Vector3>& hull, const std::vector<int32_t>& triangles, std::vector<HullBody>& bodies,
+                    const std::vector<BodyMass>& mass, const std::vector<MooringLine>& lines, int32_t linesPerBody, float deltaTime,
+                    int32_t substeps = 1, float density = 1000.f, float gravity = 9.81f, float linearDrag = 0.f, float quadraticDrag = 0.f,
+                    std::vector<HullForce>* forces = nullptr, std::vector<float>* tension = nullptr) {
+        step_moored(ocean_, -1, hull, triangles, bodies, mass, lines, linesPerBody, deltaTime, substeps, density, gravity, linearDrag,
+                    quadraticDrag, 1.f / tDivision, forces, tension);
     }
     float timer() const { return timer_; }
     mw_ocean* handle() { return ocean_; }
@@ -325,6 +355,14 @@ public:
                     float linearDrag = 0.f, float quadraticDrag = 0.f, std::vector<HullForce>* forces = nullptr, int32_t frame = -1) {
         step_bodies(ocean_, frame, hull, triangles, bodies, mass, deltaTime, substeps, density, gravity, linearDrag, quadraticDrag, 1.f,
                     forces);
+    }
+    // Not in the reference: StepBodies with mooring lines, linesPerBody slots per body (lines [bodies.size() * linesPerBody])
+    void StepMoored(const std::vector<Vector3>& hull, const std::vector<int32_t>& triangles, std::vector<HullBody>& bodies,
+                    const std::vector<BodyMass>& mass, const std::vector<MooringLine>& lines, int32_t linesPerBody, float deltaTime,
+                    int32_t substeps = 1, float density = 1000.f, float gravity = 9.81f, float linearDrag = 0.f, float quadraticDrag = 0.f,
+                    std::vector<HullForce>* forces = nullptr, std::vector<float>* tension = nullptr, int32_t frame = -1) {
+        step_moored(ocean_, frame, hull, triangles, bodies, mass, lines, linesPerBody, deltaTime, substeps, density, gravity, linearDrag,
+                    quadraticDrag, 1.f, forces, tension);
     }
 
 private:

@@ -528,6 +528,46 @@ class Ocean:
                                                          int(ntris), C.c_void_p(d_bodies), C.c_void_p(d_mass), int(nbodies), _p(cf),
                                                          float(dt), int(substeps), int(iterations), C.c_void_p(d_out or None)))
 
+    # -- moorings (mw_ocean_step_moored) -----------------------------------------------------------
+    def step_moored(self, hull_xyz, triangles, bodies, mass, lines, dt, substeps: int = 1, density=1000.0, gravity=9.81, linear_drag=0.0,
+                    quadratic_drag=0.0, velocity_scale=None, frame: int = -1, iterations: int = 0, return_forces: bool = False,
+                    return_tension: bool = False):
+        """step_bodies with mooring lines -> bodies [nbodies, 16] (updated in place when it is a C-contiguous float32 array), then with
+        return_forces the water rows [nbodies, 8] of the last substep and with return_tension the tensions [nbodies, K] at its start.
+        lines [nbodies, K, 12] (pack_lines), K in [1, 8]: per slot the attachment point h (body space, about p), the unstretched length
+        L0, the anchor a (world), the stiffness k and the damping c along the line; a slot with k == 0 and c == 0 is empty.  Every
+        substep adds the taut lines' pull and torque to the water row before integrating (the returned rows stay the water's alone).
+        Everything else as step_bodies; the integrator needs (dt / substeps) sqrt(k_total / m) < 2."""
+        hull = np.ascontiguousarray(hull_xyz, np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+        b = np.ascontiguousarray(bodies, np.float32).reshape(-1, 16)
+        m = np.ascontiguousarray(mass, np.float32).reshape(-1, nat.MW_BODY_NMASS)
+        ln = np.ascontiguousarray(lines, np.float32)
+        if ln.ndim != 3 or ln.shape[2] != nat.MW_MOORING_NLINE:
+            raise ValueError(f"step_moored: lines must be [nbodies, K, {nat.MW_MOORING_NLINE}], got {ln.shape}")
+        if m.shape[0] != b.shape[0] or ln.shape[0] != b.shape[0]:
+            raise ValueError(f"step_moored: {b.shape[0]} bodies but {m.shape[0]} mass rows and {ln.shape[0]} rows of lines")
+        cf = self._hull_coeffs(density, gravity, linear_drag, quadratic_drag, velocity_scale)
+        out = np.empty((b.shape[0], 8), np.float32) if return_forces else None
+        ten = np.empty((b.shape[0], ln.shape[1]), np.float32) if return_tension else None
+        nat.check(nat.lib().mw_ocean_step_moored(self._h, int(frame), _p(hull), hull.shape[0], _p(tris), tris.shape[0], _p(b), _p(m),
+                                                  _p(ln), ln.shape[1], b.shape[0], _p(cf), float(dt), int(substeps), int(iterations),
+                                                  _p(out), _p(ten)))
+        res = (b,) + ((out,) if return_forces else ()) + ((ten,) if return_tension else ())
+        return res if len(res) > 1 else b
+
+    def step_moored_device(self, d_hull_xyz: int, nverts: int, d_triangles: int, ntris: int, d_bodies: int, d_mass: int, d_lines: int,
+                           lines_per_body: int, nbodies: int, dt, substeps: int = 1, d_out: int = 0, d_tension: int = 0, density=1000.0,
+                           gravity=9.81, linear_drag=0.0, quadratic_drag=0.0, velocity_scale=None, frame: int = -1, iterations: int = 0):
+        """Device-pointer form: d_bodies [nbodies][16] updated in place, d_mass [nbodies][8], d_lines [nbodies][lines_per_body][12],
+        d_out [nbodies][8] or 0 (16-byte aligned), d_tension [nbodies][lines_per_body] or 0; asynchronous on the handle's stream.  An
+        invalid mass row or slot gives that body a NaN row and NaN tensions and leaves it unchanged."""
+        cf = self._hull_coeffs(density, gravity, linear_drag, quadratic_drag, velocity_scale)
+        nat.check(nat.lib().mw_ocean_step_moored_device(self._h, int(frame), C.c_void_p(d_hull_xyz), int(nverts), C.c_void_p(d_triangles),
+                                                         int(ntris), C.c_void_p(d_bodies), C.c_void_p(d_mass), C.c_void_p(d_lines),
+                                                         int(lines_per_body), int(nbodies), _p(cf), float(dt), int(substeps),
+                                                         int(iterations), C.c_void_p(d_out or None), C.c_void_p(d_tension or None)))
+
     # -- mixed fleets (mw_ocean_fleet_forces, mw_ocean_step_fleet) --------------------------------
     def _fleet_coeffs(self, nhulls, coeffs):
         """[nhulls, 5] float32 rows (density, gravity, linear_drag, quadratic_drag, velocity_scale): None = water at rest drag (1000,
@@ -649,6 +689,24 @@ def pack_mass(mass, inertia):
     out[:, 0] = m
     out[:, 1], out[:, 2], out[:, 3] = I[:, 0, 0], I[:, 1, 1], I[:, 2, 2]
     out[:, 4], out[:, 5], out[:, 6] = I[:, 0, 1], I[:, 0, 2], I[:, 1, 2]
+    return out
+
+
+def pack_lines(nbodies, lines_per_body, attach=None, anchor=None, rest_length=0.0, stiffness=0.0, damping=0.0):
+    """lines [nbodies, lines_per_body, 12] float32 for Ocean.step_moored: per slot (hx, hy, hz, L0, ax, ay, az, k, c, 0, 0, 0).  Called
+    with the two counts alone it gives empty slots to fill in (out[b, s, 0:3] = h, [3] = L0, [4:7] = a, [7] = k, [8] = c); attach and
+    anchor [nbodies, lines_per_body, 3] and rest_length, stiffness, damping [nbodies, lines_per_body] (or scalars) are broadcast."""
+    n, K = int(nbodies), int(lines_per_body)
+    if not 1 <= K <= nat.MW_MOORING_MAX_LINES:
+        raise ValueError(f"pack_lines: lines_per_body must be in [1, {nat.MW_MOORING_MAX_LINES}]")
+    out = np.zeros((n, K, nat.MW_MOORING_NLINE), np.float32)
+    if attach is not None:
+        out[:, :, 0:3] = np.broadcast_to(np.asarray(attach, np.float32), (n, K, 3))
+    if anchor is not None:
+        out[:, :, 4:7] = np.broadcast_to(np.asarray(anchor, np.float32), (n, K, 3))
+    out[:, :, 3] = np.broadcast_to(np.asarray(rest_length, np.float32), (n, K))
+    out[:, :, 7] = np.broadcast_to(np.asarray(stiffness, np.float32), (n, K))
+    out[:, :, 8] = np.broadcast_to(np.asarray(damping, np.float32), (n, K))
     return out
 
 
