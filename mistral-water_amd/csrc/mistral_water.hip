@@ -7,6 +7,7 @@
 #include <dlfcn.h>  // tiles.inc binds RCCL at run time (dlopen / dlsym)
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -128,19 +129,31 @@ static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 // copied to the device before the launches, back after them, or both); each region starts on a 256-byte boundary.  begin() reserves
 // the sum, sets every declared device pointer and issues the copies in; finish() issues the copies out and waits for the stream.  All
 // copies run on the handle's stream in declaration order.  An array the caller left out (NULL) gets no region and a NULL device pointer.
+// A stage holds as many regions as its declaration has arrays: Stage<N> st(o) followed by at most N in / out / inout, or, for a call
+// record that lists its arrays (Arr; the surface services), Stage st(o, record.arrays()), whose N is the list's own length.
 namespace {  // internal linkage: at file scope Stage::begin / finish would join the library's exported symbols
+// One array of a call record, declared once: the record's pointer to it (the caller's going in, the staged copy's after begin()), its
+// size, which way the host form copies it, and the alignment the device form asks of it (a power of two).
+enum Dir { IN, OUT, INOUT };
+struct Arr { void** slot; size_t bytes; Dir dir; uintptr_t align; };
+template <size_t N>
 struct Stage {
     struct Region { void** dev; const void* in; void* out; size_t bytes, off; };
-    static constexpr int MAX = 7;  // mw_ocean_step_moored declares the most: hull, triangles, bodies, mass, lines, out, tension
     mw_ocean* o;
-    Region r[MAX];
-    int n = 0;
+    Region r[N];
+    size_t n = 0;
     size_t total = 0;
     explicit Stage(mw_ocean* o_) : o(o_) {}
+    Stage(mw_ocean* o_, const std::array<Arr, N>& arrays) : o(o_) {
+        for (const Arr& a : arrays) {
+            void* host = *a.slot;
+            add(a.slot, a.dir != OUT ? host : nullptr, a.dir != IN ? host : nullptr, a.bytes);
+        }
+    }
     void add(void** dev, const void* in, void* out, size_t bytes) {
         *dev = nullptr;
         if (!in && !out) return;
-        if (n == MAX) std::abort();  // an eighth region is a mistake in this file, never a caller's: stop before writing past r[]
+        if (n == N) std::abort();  // only a Stage<N> st(o) given more than its N arrays gets here: stop before writing past r[]
         const size_t off = align256(total);
         r[n++] = Region{dev, in, out, bytes, off};
         total = off + bytes;
@@ -151,13 +164,13 @@ struct Stage {
     mw_status begin() {
         mw_status s = scratch_reserve(o, total);
         if (s != MW_OK) return s;
-        for (int k = 0; k < n; k++) *r[k].dev = static_cast<char*>(o->scratch.p) + r[k].off;
-        for (int k = 0; k < n; k++)
+        for (size_t k = 0; k < n; k++) *r[k].dev = static_cast<char*>(o->scratch.p) + r[k].off;
+        for (size_t k = 0; k < n; k++)
             if (r[k].in) HIP_TRY(hipMemcpyAsync(*r[k].dev, r[k].in, r[k].bytes, hipMemcpyHostToDevice, o->stream));
         return MW_OK;
     }
     mw_status finish() {
-        for (int k = 0; k < n; k++)
+        for (size_t k = 0; k < n; k++)
             if (r[k].out) HIP_TRY(hipMemcpyAsync(r[k].out, *r[k].dev, r[k].bytes, hipMemcpyDeviceToHost, o->stream));
         HIP_TRY(hipStreamSynchronize(o->stream));
         return MW_OK;
@@ -461,7 +474,7 @@ mw_status mw_ocean_set_spectrum(mw_ocean* o, const float* h0_xy, const float* h0
     const size_t bytes = sizeof(cf) * (size_t)o->N * o->N * tiles;
     if (o->sem == MW_SEM_OCEANRENDERER) {  // initialTexture.rg / .ba, texel (px,py) at py*M + px, tile-major
         void *a, *b;
-        Stage st(o);
+        Stage<2> st(o);
         st.in(&a, h0_xy, bytes);
         st.in(&b, h0conj_xy, bytes);
         mw_status s = st.begin();
@@ -487,7 +500,7 @@ mw_status mw_ocean_get_spectrum(mw_ocean* o, float* h0_xy, float* h0conj_xy) {
     const size_t bytes = sizeof(cf) * (size_t)o->N * o->N * tiles;
     if (o->sem == MW_SEM_OCEANRENDERER) {
         void *a, *b;
-        Stage st(o);
+        Stage<2> st(o);
         st.out(&a, h0_xy, bytes);
         st.out(&b, h0conj_xy, bytes);
         mw_status s = st.begin();
@@ -589,7 +602,7 @@ mw_status mw_ocean_rest_mesh(mw_ocean* o, float* vertices_xyz, float* normals_xy
     const int N = o->p.resolution;  // mesh resolution (not the 8x texture size in OceanRenderer mode)
     const size_t NN = (size_t)N * N, nidx = (size_t)(N - 1) * (N - 1) * 6;
     void *dv, *dn, *du, *di;
-    Stage st(o);
+    Stage<4> st(o);
     st.out(&dv, vertices_xyz, NN * 3 * sizeof(float));
     st.out(&dn, normals_xyz, NN * 3 * sizeof(float));
     st.out(&du, uvs_xy, NN * 2 * sizeof(float));
@@ -677,7 +690,7 @@ static mw_status frames_to_host(mw_ocean* o, const float* delta_time, int n, boo
     HIP_TRY(hipSetDevice(o->device));
     const size_t texels = (size_t)o->N * o->N * (size_t)(steps ? n : o->orr.tiles);
     void* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    Stage st(o);
+    Stage<4> st(o);
     if (rgba) {
         for (int k = 0; k < 4; k++) st.out(&dev[k], host[k], texels * 4 * sizeof(float));
         mw_status s = st.begin();
@@ -767,7 +780,7 @@ mw_status mw_ocean_displace_mesh(mw_ocean* o, float* vertices_xyz, float* normal
     HIP_TRY(hipSetDevice(o->device));
     const size_t nv = (size_t)o->p.resolution * o->p.resolution * o->orr.tiles;
     void *dv, *dn, *dc;
-    Stage st(o);
+    Stage<3> st(o);
     st.out(&dv, vertices_xyz, nv * 3 * sizeof(float));
     st.out(&dn, normals_xyz, nv * 3 * sizeof(float));
     st.out(&dc, colors, nv * sizeof(float));

@@ -357,7 +357,7 @@ MW_HD void sq_velocity_point(const Mesh& m, const float* vel, int mode, float qx
 #if defined(__HIPCC__)
 // One lane per query: a coalesced 8-byte load of the point, the walk's dependent 3-vertex gathers (L2 / Infinity Cache: the
 // vertex array of a 1024^2 mesh is 12 MB), one final gather of positions, normals and whitecap, two 16-byte stores.
-// Mesh: SqMesh, or SqTiled on a periodic handle (query_launch).
+// Mesh: SqMesh, or SqTiled on a periodic handle (QuerySurface::launch).
 template <typename Mesh>
 __global__ __launch_bounds__(256) void k_query_surface(Mesh m, int mode, int iters, const float2* __restrict__ xz, int64_t n,
                                                        float4* __restrict__ out) {

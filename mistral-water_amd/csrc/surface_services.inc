@@ -1,17 +1,80 @@
 // surface_services.inc -- the host code of the services that read the displaced surface: surface queries, surface velocity, hull
-// forces, floating bodies, mixed fleets, raycasts, the water column.  Included by mistral_water.hip inside its extern "C" block (one translation unit: the handle, fail,
-// HIP_TRY, dmalloc, grow_reserve, Stage and the frame record are file-static there).  Every service is a pair of entry points over a
-// shared prepare (validate, name the mesh of the queried frame) and launch (the kernels, on the handle's stream): the device form
-// checks alignment and launches on the caller's arrays, the host form stages its arrays in the handle's scratch buffer (Stage).
+// forces, floating bodies, moorings, mixed fleets, raycasts, the water column.  Included by mistral_water.hip inside its extern "C" block
+// (one translation unit: the handle, fail, HIP_TRY, dmalloc, grow_reserve, Stage / Arr and the frame record are file-static there).
+//
+// Every service with a host and a device form is a call record and two functions that run it, service_host and service_device below.
+// The exported entry points only construct the record.  A record supplies
+//   Plan                      what prepare derives from the call and the handle (the mesh of the queried frame, coefficients, ...);
+//   prepare(o, frame, who, &plan)   every check either form makes, argument rules first and the handle's state rules last;
+//   count()                   the points or bodies of the call: 0 is an empty call, which returns after prepare;
+//   check_host(who)           the checks only a host form can make (it reads the caller's arrays);
+//   arrays()                  its arrays, declared once (Arr): from this list the device form makes its alignment test and the host form
+//                             its Stage, which swaps the staged copies into the record;
+//   launch(o, plan)           the kernels, on the handle's stream, on the record's pointers.
+// The point services (queries, raycasts, the column query) are PointCall and a struct each; the hull family (hull forces, step bodies,
+// step moored) is one HullCall whose optional parts say which call it is; the fleets are one FleetCall.  The per-substep plan of all
+// stepping is run_substeps, the raycasts' hierarchy raycast_tree.  mw_ocean_velocity / _device have no arrays to stage and stand alone.
 
 static int sq_iters(int32_t iterations) { return iterations == 0 ? MW_SQ_DEFAULT_ITERS : iterations; }
 // device entry points: p is not a multiple of `bytes` (a power of two)
 static bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
-static bool triangles_in_range(const int32_t* triangles, int32_t ntris, int32_t nverts) {
+static bool triangles_in_range(const void* triangles, int32_t ntris, int32_t nverts) {
+    const int32_t* t = static_cast<const int32_t*>(triangles);
     for (int64_t k = 0; k < (int64_t)ntris * 3; k++)
-        if (triangles[k] < 0 || triangles[k] >= nverts) return false;
+        if (t[k] < 0 || t[k] >= nverts) return false;
     return true;
 }
+static void* vp(const void* p) { return const_cast<void*>(p); }  // a call record keeps every array pointer as void* (Arr::slot)
+// the handle has one surface to read: not NULL, not a batch of tiles
+static mw_status single_surface_check(const mw_ocean* o, const char* who) {
+    if (!o) return fail(MW_EINVAL, who, "NULL handle");
+    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
+        return fail(MW_EINVAL, who, "a batched handle (mw_ocean_create_batch) has no single surface");
+    return MW_OK;
+}
+
+extern "C++" {  // templates stand outside C linkage
+// The host form of a service: validate, return on an empty call, the host-only checks, stage the arrays, launch on the copies, copy back
+// and wait for the stream.
+template <class Call>
+static mw_status service_host(mw_ocean* o, int32_t frame, const Call& c, const char* who) {
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    typename Call::Plan p{};
+    mw_status s = c.prepare(o, frame, who, &p);
+    if (s != MW_OK || c.count() == 0) return s;
+    if ((s = c.check_host(who)) != MW_OK) return s;
+    Call d = c;  // the same call on the staged copies
+    Stage st(o, d.arrays());
+    if ((s = st.begin()) != MW_OK || (s = d.launch(o, p)) != MW_OK) return s;
+    return st.finish();
+}
+// The device form: the alignment of the caller's arrays (before the handle is looked at; `aligned` is the entry point's own message),
+// validate, return on an empty call, launch.  Never waits for the stream.
+template <class Call>
+static mw_status service_device(mw_ocean* o, int32_t frame, Call c, const char* who, const char* aligned) {
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    if (c.count() > 0)
+        for (const Arr& a : c.arrays())
+            if (misaligned(*a.slot, a.align)) return fail(MW_EINVAL, who, aligned);
+    typename Call::Plan p{};
+    mw_status s = c.prepare(o, frame, who, &p);
+    if (s != MW_OK || c.count() == 0) return s;
+    return c.launch(o, p);
+}
+}  // extern "C++"
+
+// The arguments of a point service: n points (or rays) in, n rows out, and for the raycasts the optional hit record per ray.  The host and
+// the device form differ only in whose pointers it holds; each service below adds its prepare, arrays and launch.
+namespace {
+struct PointCall {
+    using Plan = SqMesh;
+    void *pts, *out, *hit;
+    int64_t n; int32_t mode, iterations, reach;
+    int64_t count() const { return n; }
+    mw_status check_host(const char*) const { return MW_OK; }
+    size_t floats(int per) const { return (size_t)n * per * sizeof(float); }  // bytes of n rows of `per` 4-byte words
+};
+}  // namespace
 
 // ---- surface queries (csrc/surface_query.h) -------------------------------------------------------------------
 // Validates the call and names the vertex arrays of the queried frame.  OceanRenderer: the material's vertex stage of that frame
@@ -57,38 +120,30 @@ static mw_status query_prepare(mw_ocean* o, int32_t frame, int32_t mode, const v
     m->vert = qv; m->norm = qn; m->white = qw; m->R = res; m->wstride = 1;
     return MW_OK;
 }
-static mw_status query_launch(mw_ocean* o, const SqMesh& m, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    const float2* xz = static_cast<const float2*>(d_xz);
-    if (m.period != 0.f) HIP_TRY(tiled_query_surface(grid, o->stream, m, mode, sq_iters(iterations), xz, n, static_cast<float4*>(d_out)));
-    else k_query_surface<<<grid, block, 0, o->stream>>>(m, mode, sq_iters(iterations), xz, n, static_cast<float4*>(d_out));
-    HIP_TRY(hipGetLastError());
-    return MW_OK;
-}
+namespace {
+struct QuerySurface : PointCall {
+    mw_status prepare(mw_ocean* o, int32_t frame, const char* who, SqMesh* m) const {
+        return query_prepare(o, frame, mode, pts, n, iterations, out, who, m);
+    }
+    std::array<Arr, 2> arrays() { return {{{&pts, floats(2), IN, 8}, {&out, floats(8), OUT, 16}}}; }
+    mw_status launch(mw_ocean* o, const SqMesh& m) const {
+        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+        const float2* xz = static_cast<const float2*>(pts);
+        if (m.period != 0.f) HIP_TRY(tiled_query_surface(grid, o->stream, m, mode, sq_iters(iterations), xz, n, static_cast<float4*>(out)));
+        else k_query_surface<<<grid, block, 0, o->stream>>>(m, mode, sq_iters(iterations), xz, n, static_cast<float4*>(out));
+        HIP_TRY(hipGetLastError());
+        return MW_OK;
+    }
+};
+}  // namespace
 
 mw_status mw_ocean_query_surface_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xz, int64_t n, int32_t iterations,
                                         void* d_out) {
-    const char* who = "mw_ocean_query_surface_device";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (n > 0 && (misaligned(d_xz, 8) || misaligned(d_out, 16))) return fail(MW_EINVAL, who, "d_xz must be 8-byte and d_out 16-byte aligned");
-    SqMesh m{};
-    mw_status s = query_prepare(o, frame, mode, d_xz, n, iterations, d_out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    return query_launch(o, m, mode, d_xz, n, iterations, d_out);
+    return service_device(o, frame, QuerySurface{{vp(d_xz), d_out, nullptr, n, mode, iterations, 0}}, "mw_ocean_query_surface_device",
+                          "d_xz must be 8-byte and d_out 16-byte aligned");
 }
-
 mw_status mw_ocean_query_surface(mw_ocean* o, int32_t frame, int32_t mode, const float* xz, int64_t n, int32_t iterations, float* out) {
-    const char* who = "mw_ocean_query_surface";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    SqMesh m{};
-    mw_status s = query_prepare(o, frame, mode, xz, n, iterations, out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    void *d_xz, *d_out;
-    Stage st(o);
-    st.in(&d_xz, xz, (size_t)n * 2 * sizeof(float));
-    st.out(&d_out, out, (size_t)n * 8 * sizeof(float));
-    if ((s = st.begin()) != MW_OK || (s = query_launch(o, m, mode, d_xz, n, iterations, d_out)) != MW_OK) return s;
-    return st.finish();
+    return service_host(o, frame, QuerySurface{{vp(xz), out, nullptr, n, mode, iterations, 0}}, "mw_ocean_query_surface");
 }
 
 // ---- surface velocity (csrc/velocity_kernels.h) --------------------------------------------------------------------
@@ -96,9 +151,8 @@ mw_status mw_ocean_query_surface(mw_ocean* o, int32_t frame, int32_t mode, const
 // frame's (-1) or the last frame of the latest steps call while no other call has moved the phase since.  Argument errors first, as
 // query_prepare orders them.
 static mw_status velocity_check(mw_ocean* o, int32_t frame, const char* who) {
-    if (!o) return fail(MW_EINVAL, who, "NULL handle");
-    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
-        return fail(MW_EINVAL, who, "a batched handle (mw_ocean_create_batch) has no single surface");
+    mw_status s = single_surface_check(o, who);
+    if (s != MW_OK) return s;
     if (o->sem == MW_SEM_FFTMESH && frame != -1) return fail(MW_EINVAL, who, "FFTMesh handles keep one frame (frame = -1)");
     if (o->sem == MW_SEM_OCEANRENDERER && frame != -1 && !(frame >= 0 && frame == o->or_steps_tail))
         return fail(MW_EINVAL, who, "the handle keeps only the latest phase: frame must be -1 or the last frame of the latest "
@@ -186,47 +240,43 @@ static mw_status query_velocity_prepare(mw_ocean* o, int32_t frame, int32_t mode
                                     "belong to different instants (make a frame first)");
     return s;
 }
-static mw_status query_velocity_launch(mw_ocean* o, const SqMesh& m, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
-    mw_status s = velocity_to_handle(o);
-    if (s != MW_OK) return s;
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    const float2* xz = static_cast<const float2*>(d_xz);
-    if (m.period != 0.f) HIP_TRY(tiled_query_velocity(grid, o->stream, m, o->vel.vert, mode, sq_iters(iterations), xz, n, static_cast<float4*>(d_out)));
-    else k_query_velocity<<<grid, block, 0, o->stream>>>(m, o->vel.vert, mode, sq_iters(iterations), xz, n, static_cast<float4*>(d_out));
-    HIP_TRY(hipGetLastError());
-    return MW_OK;
-}
+namespace {
+struct QueryVelocity : PointCall {
+    mw_status prepare(mw_ocean* o, int32_t frame, const char* who, SqMesh* m) const {
+        return query_velocity_prepare(o, frame, mode, pts, n, iterations, out, who, m);
+    }
+    std::array<Arr, 2> arrays() { return {{{&pts, floats(2), IN, 8}, {&out, floats(4), OUT, 16}}}; }
+    mw_status launch(mw_ocean* o, const SqMesh& m) const {
+        mw_status s = velocity_to_handle(o);
+        if (s != MW_OK) return s;
+        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+        const float2* xz = static_cast<const float2*>(pts);
+        if (m.period != 0.f) HIP_TRY(tiled_query_velocity(grid, o->stream, m, o->vel.vert, mode, sq_iters(iterations), xz, n, static_cast<float4*>(out)));
+        else k_query_velocity<<<grid, block, 0, o->stream>>>(m, o->vel.vert, mode, sq_iters(iterations), xz, n, static_cast<float4*>(out));
+        HIP_TRY(hipGetLastError());
+        return MW_OK;
+    }
+};
+}  // namespace
 
 mw_status mw_ocean_query_velocity_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xz, int64_t n, int32_t iterations, void* d_out) {
-    const char* who = "mw_ocean_query_velocity_device";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (n > 0 && (misaligned(d_xz, 8) || misaligned(d_out, 16))) return fail(MW_EINVAL, who, "d_xz must be 8-byte and d_out 16-byte aligned");
-    SqMesh m{};
-    mw_status s = query_velocity_prepare(o, frame, mode, d_xz, n, iterations, d_out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    return query_velocity_launch(o, m, mode, d_xz, n, iterations, d_out);
+    return service_device(o, frame, QueryVelocity{{vp(d_xz), d_out, nullptr, n, mode, iterations, 0}}, "mw_ocean_query_velocity_device",
+                          "d_xz must be 8-byte and d_out 16-byte aligned");
 }
-
 mw_status mw_ocean_query_velocity(mw_ocean* o, int32_t frame, int32_t mode, const float* xz, int64_t n, int32_t iterations, float* out) {
-    const char* who = "mw_ocean_query_velocity";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    SqMesh m{};
-    mw_status s = query_velocity_prepare(o, frame, mode, xz, n, iterations, out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    void *d_xz, *d_out;
-    Stage st(o);
-    st.in(&d_xz, xz, (size_t)n * 2 * sizeof(float));
-    st.out(&d_out, out, (size_t)n * 4 * sizeof(float));
-    if ((s = st.begin()) != MW_OK || (s = query_velocity_launch(o, m, mode, d_xz, n, iterations, d_out)) != MW_OK) return s;
-    return st.finish();
+    return service_host(o, frame, QueryVelocity{{vp(xz), out, nullptr, n, mode, iterations, 0}}, "mw_ocean_query_velocity");
 }
 
 // ---- hull forces (csrc/hull_forces.h) -----------------------------------------------------------------------------
-// The arguments of a hull-forces or step-bodies call.  The host and the device form of an entry point differ only in which pointers
-// it holds: the caller's own (prepare reads none of them but the host-side coeffs), or their staged copies (launch).
+// The arguments of a hull-family call.  The host and the device form of an entry point differ only in which pointers it holds: the
+// caller's own (prepare reads none of them but the host-side coeffs), or their staged copies (launch).  Its optional parts say which
+// call it is.  step (mw_ocean_step_bodies): mass is required, bodies are updated in place, out is optional, dt and substeps are read.
+// moored (mw_ocean_step_moored, a stepping call): lines, K = lines_per_body and the optional tension.
 struct HullCall {
-    const void *hull, *tris; void* bodies; const void* mass; void* out;  // bodies: updated in place by step bodies
-    int32_t nverts, ntris, nbodies, iterations; const float* coeffs; float dt; int32_t substeps;
+    void *hull, *tris, *bodies, *out;
+    int32_t nverts, ntris, nbodies, iterations; const float* coeffs;
+    bool step; void* mass; float dt; int32_t substeps;
+    bool moored; void* lines; int32_t K; void* tension;
 };
 // what prepare derives from the call and the handle: the mesh of the queried frame and the coefficients as the kernels take them
 struct HullPlan { SqMesh m; HullCoeffs cf; float vscale, g; };  // vscale = coeffs[4]; g = coeffs[1], gravity (step bodies)
@@ -242,9 +292,8 @@ static ColTable column_table(const mw_ocean* o, const SqMesh& m);
 // With draught on, drag on or off, the column's (column_prepare: the same mesh, MW_ESTATE without a column or once the spectrum or phase
 // moved on) after the call's own argument checks.
 static mw_status hull_prepare(mw_ocean* o, int32_t frame, const HullCall& c, const char* who, HullPlan* p) {
-    if (!o) return fail(MW_EINVAL, who, "NULL handle");
-    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
-        return fail(MW_EINVAL, who, "a batched handle (mw_ocean_create_batch) has no single surface");
+    mw_status s = single_surface_check(o, who);
+    if (s != MW_OK) return s;
     if (c.nbodies < 0) return fail(MW_EINVAL, who, "nbodies < 0");
     if (c.nverts < 3 || c.ntris < 1) return fail(MW_EINVAL, who, "a hull needs nverts >= 3 and ntris >= 1");
     if (!c.coeffs) return fail(MW_EINVAL, who, "NULL coeffs");
@@ -322,42 +371,6 @@ static mw_status hull_launch(mw_ocean* o, const HullPlan& p, const HullCall& c, 
     return MW_OK;
 }
 
-mw_status mw_ocean_hull_forces_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
-                                      int32_t ntris, const void* d_bodies, int32_t nbodies, const float* coeffs, int32_t iterations,
-                                      void* d_out) {
-    const char* who = "mw_ocean_hull_forces_device";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (nbodies > 0 && (misaligned(d_hull_xyz, 4) || misaligned(d_triangles, 4) || misaligned(d_bodies, 16) || misaligned(d_out, 16)))
-        return fail(MW_EINVAL, who, "d_hull_xyz and d_triangles must be 4-byte, d_bodies and d_out 16-byte aligned");
-    const HullCall c{d_hull_xyz, d_triangles, const_cast<void*>(d_bodies), nullptr, d_out, nverts, ntris, nbodies, iterations, coeffs, 0.f, 1};
-    HullPlan p{};
-    mw_status s = hull_prepare(o, frame, c, who, &p);
-    if (s != MW_OK || nbodies == 0) return s;
-    return hull_launch(o, p, c);
-}
-
-mw_status mw_ocean_hull_forces(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles, int32_t ntris,
-                               const float* bodies, int32_t nbodies, const float* coeffs, int32_t iterations, float* out) {
-    const char* who = "mw_ocean_hull_forces";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    const HullCall c{hull_xyz, triangles, const_cast<float*>(bodies), nullptr, out, nverts, ntris, nbodies, iterations, coeffs, 0.f, 1};
-    HullPlan p{};
-    mw_status s = hull_prepare(o, frame, c, who, &p);
-    if (s != MW_OK || nbodies == 0) return s;
-    if (!triangles_in_range(triangles, ntris, nverts)) return fail(MW_EINVAL, who, "triangle index outside [0, nverts)");
-    void *d_hull, *d_tris, *d_bodies, *d_out;
-    Stage st(o);
-    st.in(&d_hull, hull_xyz, (size_t)nverts * 3 * sizeof(float));
-    st.in(&d_tris, triangles, (size_t)ntris * 3 * sizeof(int32_t));
-    st.in(&d_bodies, bodies, (size_t)nbodies * 16 * sizeof(float));
-    st.out(&d_out, out, (size_t)nbodies * 8 * sizeof(float));
-    if ((s = st.begin()) != MW_OK) return s;
-    HullCall d = c;
-    d.hull = d_hull; d.tris = d_tris; d.bodies = d_bodies; d.out = d_out;
-    if ((s = hull_launch(o, p, d)) != MW_OK) return s;
-    return st.finish();
-}
-
 // ---- floating bodies (csrc/rigid_bodies.h) ------------------------------------------------------------------------
 static_assert(MW_BODY_NMASS == 8, "rigid_bodies.h reads 8 floats per mass row");
 
@@ -430,13 +443,8 @@ static mw_status mass_row_check(const void* mass, int32_t b, const char* who) {
                                     " is invalid (m <= 0 or not finite, or I_b not positive definite)");
 }
 
-// every substep of the call on the handle's stream (nbodies > 0): the water once (hull_water: the surface is frozen for the call), then
-// one k_bodies_step launch, or per substep hull_launch and k_bodies_integrate, the strict build where hull_launch's rows are
-// (hull_strict).  Draught on: there is no one-launch plan on the column and MW_BODIES_PLAN is not read.
-static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c) {
-    const int nchunks = hull_chunks(c);
-    mw_status s = hull_water(o, p);
-    if (s != MW_OK) return s;
+// the kernels' view of a stepping call on device pointers; rows and last are the per-substep plan's own (run_substeps)
+static BodiesArgs bodies_args(const mw_ocean* o, const HullPlan& p, const HullCall& c) {
     BodiesArgs a{};
     a.h = hull_args(o, p, c);
     a.bodies = static_cast<float4*>(c.bodies);
@@ -445,6 +453,31 @@ static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c
     a.g = p.g;
     a.dt = c.dt / (float)c.substeps;
     a.substeps = c.substeps;
+    return a;
+}
+extern "C++" {
+// The per-substep plan of every stepping call, on the handle's stream: the handle's row buffer holds nrows rows; per substep rows(buf)
+// launches the hull forces of the bodies' current state into it and integrate(buf, last) steps the bodies by them, last on the final
+// substep (the one whose rows go to the caller's out).
+template <class Rows, class Integrate>
+static mw_status run_substeps(mw_ocean* o, int64_t nrows, int substeps, Rows rows, Integrate integrate) {
+    mw_status s = grow_reserve(o, o->bodies, (size_t)nrows * 8 * sizeof(float), "the step-bodies row buffer");
+    if (s != MW_OK) return s;
+    float4* buf = static_cast<float4*>(o->bodies.p);
+    for (int k = 0; k < substeps; k++)
+        if ((s = rows(buf)) != MW_OK || (s = integrate(buf, k == substeps - 1)) != MW_OK) return s;
+    return MW_OK;
+}
+}  // extern "C++"
+
+// every substep of the call on the handle's stream (nbodies > 0): the water once (hull_water: the surface is frozen for the call), then
+// one k_bodies_step launch, or per substep hull_launch and k_bodies_integrate, the strict build where hull_launch's rows are
+// (hull_strict).  Draught on: there is no one-launch plan on the column and MW_BODIES_PLAN is not read.
+static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c) {
+    const int nchunks = hull_chunks(c);
+    mw_status s = hull_water(o, p);
+    if (s != MW_OK) return s;
+    BodiesArgs a = bodies_args(o, p, c);
     if (!o->draught && bodies_one_launch(c.nverts, nchunks)) {
         const size_t lds = bodies_step_lds(c.nverts, nchunks);
         if (a.h.m.period != 0.f) {
@@ -457,71 +490,27 @@ static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c
         HIP_TRY(hipGetLastError());
         return MW_OK;
     }
-    if ((s = grow_reserve(o, o->bodies, (size_t)c.nbodies * 8 * sizeof(float), "the step-bodies row buffer")) != MW_OK) return s;
-    a.rows = static_cast<const float4*>(o->bodies.p);
     HullCall rows = c;  // the hull forces of a substep: the same call, its rows into the handle's buffer
-    rows.out = o->bodies.p;
-    for (int k = 0; k < c.substeps; k++) {
-        if ((s = hull_launch(o, p, rows, false)) != MW_OK) return s;
-        a.last = k == c.substeps - 1;
-        const dim3 gi((unsigned)(((int64_t)c.nbodies + 255) / 256));
-        if (hull_strict(o, a.h.m)) HIP_TRY(strict_bodies_integrate(gi, o->stream, a));
-        else k_bodies_integrate<<<gi, dim3(256), 0, o->stream>>>(a);
-        HIP_TRY(hipGetLastError());
-    }
-    return MW_OK;
-}
-
-mw_status mw_ocean_step_bodies_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
-                                      int32_t ntris, void* d_bodies, const void* d_mass, int32_t nbodies, const float* coeffs,
-                                      float dt, int32_t substeps, int32_t iterations, void* d_out) {
-    const char* who = "mw_ocean_step_bodies_device";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (nbodies > 0 && (misaligned(d_hull_xyz, 4) || misaligned(d_triangles, 4) || misaligned(d_bodies, 16) || misaligned(d_mass, 16) ||
-                        misaligned(d_out, 16)))
-        return fail(MW_EINVAL, who, "d_hull_xyz and d_triangles must be 4-byte, d_bodies, d_mass and d_out 16-byte aligned");
-    const HullCall c{d_hull_xyz, d_triangles, d_bodies, d_mass, d_out, nverts, ntris, nbodies, iterations, coeffs, dt, substeps};
-    HullPlan p{};
-    mw_status s = bodies_prepare(o, frame, c, who, &p);
-    if (s != MW_OK || nbodies == 0) return s;
-    return bodies_launch(o, p, c);
-}
-
-mw_status mw_ocean_step_bodies(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles,
-                               int32_t ntris, float* bodies, const float* mass, int32_t nbodies, const float* coeffs, float dt,
-                               int32_t substeps, int32_t iterations, float* out) {
-    const char* who = "mw_ocean_step_bodies";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    const HullCall c{hull_xyz, triangles, bodies, mass, out, nverts, ntris, nbodies, iterations, coeffs, dt, substeps};
-    HullPlan p{};
-    mw_status s = bodies_prepare(o, frame, c, who, &p);
-    if (s != MW_OK || nbodies == 0) return s;
-    if (!triangles_in_range(triangles, ntris, nverts)) return fail(MW_EINVAL, who, "triangle index outside [0, nverts)");
-    for (int32_t b = 0; b < nbodies; b++)
-        if ((s = mass_row_check(mass, b, who)) != MW_OK) return s;
-    void *d_hull, *d_tris, *d_bodies, *d_mass, *d_out;
-    Stage st(o);
-    st.in(&d_hull, hull_xyz, (size_t)nverts * 3 * sizeof(float));
-    st.in(&d_tris, triangles, (size_t)ntris * 3 * sizeof(int32_t));
-    st.inout(&d_bodies, bodies, (size_t)nbodies * 16 * sizeof(float));
-    st.in(&d_mass, mass, (size_t)nbodies * 8 * sizeof(float));
-    st.out(&d_out, out, (size_t)nbodies * 8 * sizeof(float));  // optional
-    if ((s = st.begin()) != MW_OK) return s;
-    HullCall d = c;
-    d.hull = d_hull; d.tris = d_tris; d.bodies = d_bodies; d.mass = d_mass; d.out = d_out;
-    if ((s = bodies_launch(o, p, d)) != MW_OK) return s;
-    return st.finish();
+    const dim3 gi((unsigned)(((int64_t)c.nbodies + 255) / 256));
+    return run_substeps(
+        o, c.nbodies, c.substeps, [&](float4* buf) { rows.out = buf; return hull_launch(o, p, rows, false); },
+        [&](const float4* buf, bool last) -> mw_status {
+            a.rows = buf;
+            a.last = last;
+            if (hull_strict(o, a.h.m)) HIP_TRY(strict_bodies_integrate(gi, o->stream, a));
+            else k_bodies_integrate<<<gi, dim3(256), 0, o->stream>>>(a);
+            HIP_TRY(hipGetLastError());
+            return MW_OK;
+        });
 }
 
 // ---- moorings (csrc/moorings.h) -----------------------------------------------------------------------------------
 static_assert(MW_MOORING_MAX_LINES == MW_MOORING_LINES && MW_MOORING_NLINE == MW_MOORING_SLOT, "moorings.h and the ABI size a slot alike");
-// what a moored call carries beyond a step-bodies call (HullCall); as there, the caller's pointers or their staged copies
-struct MooredLines { const void* lines; int32_t K; void* tension; };
 
 // Validates a step-moored call: its own arguments, then the step-bodies rules (bodies_prepare).
-static mw_status moored_prepare(mw_ocean* o, int32_t frame, const HullCall& c, const MooredLines& ml, const char* who, HullPlan* p) {
-    if (ml.K < 1 || ml.K > MW_MOORING_MAX_LINES) return fail(MW_EINVAL, who, "lines_per_body must be in [1, MW_MOORING_MAX_LINES]");
-    if (c.nbodies > 0 && !ml.lines) return fail(MW_EINVAL, who, "NULL lines");
+static mw_status moored_prepare(mw_ocean* o, int32_t frame, const HullCall& c, const char* who, HullPlan* p) {
+    if (c.K < 1 || c.K > MW_MOORING_MAX_LINES) return fail(MW_EINVAL, who, "lines_per_body must be in [1, MW_MOORING_MAX_LINES]");
+    if (c.nbodies > 0 && !c.lines) return fail(MW_EINVAL, who, "NULL lines");
     return bodies_prepare(o, frame, c, who, p);
 }
 // the one-launch plan takes the hull when step bodies would (bodies_one_launch) and k_moored_step's static LDS fits beside it
@@ -531,98 +520,121 @@ static bool moored_one_launch(int nverts, int nchunks) {
 // every substep of the call on the handle's stream (nbodies > 0), as bodies_launch: the water once, then one k_moored_step launch (a
 // periodic handle without draught whose hull qualifies; MW_BODIES_PLAN is honoured) or per substep hull_launch and k_moored_integrate.
 // A non-periodic handle and draught always step per substep, as the fleets and draught do.
-static mw_status moored_launch(mw_ocean* o, const HullPlan& p, const HullCall& c, const MooredLines& ml) {
+static mw_status moored_launch(mw_ocean* o, const HullPlan& p, const HullCall& c) {
     const int nchunks = hull_chunks(c);
     mw_status s = hull_water(o, p);
     if (s != MW_OK) return s;
-    const float h = c.dt / (float)c.substeps;
     if (!o->draught && p.m.period != 0.f && moored_one_launch(c.nverts, nchunks)) {
-        BodiesArgs a{};
-        a.h = hull_args(o, p, c);
-        a.bodies = static_cast<float4*>(c.bodies);
-        a.mass = static_cast<const float4*>(c.mass);
-        a.out = static_cast<float4*>(c.out);
-        a.g = p.g;
-        a.dt = h;
-        a.substeps = c.substeps;
-        HIP_TRY(tiled_moored_step(dim3((unsigned)c.nbodies), bodies_step_lds(c.nverts, nchunks), MW_BODIES_LDS_MAX, o->stream, a,
-                                  static_cast<const float4*>(ml.lines), ml.K, static_cast<float*>(ml.tension)));
+        HIP_TRY(tiled_moored_step(dim3((unsigned)c.nbodies), bodies_step_lds(c.nverts, nchunks), MW_BODIES_LDS_MAX, o->stream, bodies_args(o, p, c),
+                                  static_cast<const float4*>(c.lines), c.K, static_cast<float*>(c.tension)));
         return MW_OK;
     }
-    if ((s = grow_reserve(o, o->bodies, (size_t)c.nbodies * 8 * sizeof(float), "the step-bodies row buffer")) != MW_OK) return s;
     MooredArgs a{};
     a.bodies = static_cast<float4*>(c.bodies);
     a.mass = static_cast<const float4*>(c.mass);
-    a.rows = static_cast<const float4*>(o->bodies.p);
-    a.lines = static_cast<const float4*>(ml.lines);
+    a.lines = static_cast<const float4*>(c.lines);
     a.out = static_cast<float4*>(c.out);
-    a.tension = static_cast<float*>(ml.tension);
+    a.tension = static_cast<float*>(c.tension);
     a.g = p.g;
-    a.dt = h;
+    a.dt = c.dt / (float)c.substeps;
     a.nbodies = c.nbodies;
-    a.K = ml.K;
+    a.K = c.K;
     HullCall rows = c;  // the hull forces of a substep: the same call, its rows into the handle's buffer
-    rows.out = o->bodies.p;
     const dim3 gi((unsigned)(((int64_t)c.nbodies + 255) / 256));
-    for (int k = 0; k < c.substeps; k++) {
-        if ((s = hull_launch(o, p, rows, false)) != MW_OK) return s;
-        a.last = k == c.substeps - 1;
-        HIP_TRY(strict_moored_integrate(gi, o->stream, a));
-    }
-    return MW_OK;
+    return run_substeps(
+        o, c.nbodies, c.substeps, [&](float4* buf) { rows.out = buf; return hull_launch(o, p, rows, false); },
+        [&](const float4* buf, bool last) -> mw_status {
+            a.rows = buf;
+            a.last = last;
+            HIP_TRY(strict_moored_integrate(gi, o->stream, a));
+            return MW_OK;
+        });
 }
 
+// ---- the hull family's entry points ---------------------------------------------------------------------------------------
+// One record for hull forces, step bodies and step moored.  Each layer of prepare does its own checks and calls the one below
+// (moored_prepare, bodies_prepare, hull_prepare); the host-only checks run triangles first, then body by body the mass row and the slots.
+namespace {  // internal linkage, like Stage
+struct HullService : HullCall {
+    using Plan = HullPlan;
+    int64_t count() const { return nbodies; }
+    mw_status prepare(mw_ocean* o, int32_t frame, const char* who, HullPlan* p) const {
+        return moored ? moored_prepare(o, frame, *this, who, p) : step ? bodies_prepare(o, frame, *this, who, p) : hull_prepare(o, frame, *this, who, p);
+    }
+    mw_status check_host(const char* who) const {
+        if (!triangles_in_range(tris, ntris, nverts)) return fail(MW_EINVAL, who, "triangle index outside [0, nverts)");
+        if (!step) return MW_OK;
+        for (int32_t b = 0; b < nbodies; b++) {
+            const mw_status s = mass_row_check(mass, b, who);
+            if (s != MW_OK) return s;
+            for (int32_t k = 0; moored && k < K; k++)
+                if (!mooring_slot_valid(static_cast<const float*>(lines) + MW_MOORING_NLINE * ((size_t)b * K + k)))
+                    return fail(MW_EINVAL, who, "slot " + std::to_string(k) + " of body " + std::to_string(b) +
+                                                    " is invalid (a non-finite float, or L0, k or c negative)");
+        }
+        return MW_OK;
+    }
+    // mass, lines, out (when stepping) and tension are optional or absent: a NULL array has no region and any alignment
+    std::array<Arr, 7> arrays() {
+        const size_t nb = (size_t)nbodies, slots = moored ? nb * (size_t)K : 0;
+        return {{{&hull, (size_t)nverts * 3 * sizeof(float), IN, 4},
+                 {&tris, (size_t)ntris * 3 * sizeof(int32_t), IN, 4},
+                 {&bodies, nb * 16 * sizeof(float), step ? INOUT : IN, 16},
+                 {&mass, nb * 8 * sizeof(float), IN, 16},
+                 {&lines, slots * MW_MOORING_NLINE * sizeof(float), IN, 16},
+                 {&out, nb * 8 * sizeof(float), OUT, 16},
+                 {&tension, slots * sizeof(float), OUT, 4}}};
+    }
+    mw_status launch(mw_ocean* o, const HullPlan& p) const {
+        return moored ? moored_launch(o, p, *this) : step ? bodies_launch(o, p, *this) : hull_launch(o, p, *this);
+    }
+};
+}  // namespace
+
+mw_status mw_ocean_hull_forces_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
+                                      int32_t ntris, const void* d_bodies, int32_t nbodies, const float* coeffs, int32_t iterations,
+                                      void* d_out) {
+    const HullService c{{vp(d_hull_xyz), vp(d_triangles), vp(d_bodies), d_out, nverts, ntris, nbodies, iterations, coeffs, false, nullptr, 0.f, 1,
+                         false, nullptr, 0, nullptr}};
+    return service_device(o, frame, c, "mw_ocean_hull_forces_device",
+                          "d_hull_xyz and d_triangles must be 4-byte, d_bodies and d_out 16-byte aligned");
+}
+mw_status mw_ocean_hull_forces(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles, int32_t ntris,
+                               const float* bodies, int32_t nbodies, const float* coeffs, int32_t iterations, float* out) {
+    const HullService c{{vp(hull_xyz), vp(triangles), vp(bodies), out, nverts, ntris, nbodies, iterations, coeffs, false, nullptr, 0.f, 1, false,
+                         nullptr, 0, nullptr}};
+    return service_host(o, frame, c, "mw_ocean_hull_forces");
+}
+mw_status mw_ocean_step_bodies_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
+                                      int32_t ntris, void* d_bodies, const void* d_mass, int32_t nbodies, const float* coeffs,
+                                      float dt, int32_t substeps, int32_t iterations, void* d_out) {
+    const HullService c{{vp(d_hull_xyz), vp(d_triangles), d_bodies, d_out, nverts, ntris, nbodies, iterations, coeffs, true, vp(d_mass), dt,
+                         substeps, false, nullptr, 0, nullptr}};
+    return service_device(o, frame, c, "mw_ocean_step_bodies_device",
+                          "d_hull_xyz and d_triangles must be 4-byte, d_bodies, d_mass and d_out 16-byte aligned");
+}
+mw_status mw_ocean_step_bodies(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles,
+                               int32_t ntris, float* bodies, const float* mass, int32_t nbodies, const float* coeffs, float dt,
+                               int32_t substeps, int32_t iterations, float* out) {
+    const HullService c{{vp(hull_xyz), vp(triangles), bodies, out, nverts, ntris, nbodies, iterations, coeffs, true, vp(mass), dt, substeps, false,
+                         nullptr, 0, nullptr}};
+    return service_host(o, frame, c, "mw_ocean_step_bodies");
+}
 mw_status mw_ocean_step_moored_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t nverts, const void* d_triangles,
                                       int32_t ntris, void* d_bodies, const void* d_mass, const void* d_lines, int32_t lines_per_body,
                                       int32_t nbodies, const float* coeffs, float dt, int32_t substeps, int32_t iterations, void* d_out,
                                       void* d_tension) {
-    const char* who = "mw_ocean_step_moored_device";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (nbodies > 0 && (misaligned(d_hull_xyz, 4) || misaligned(d_triangles, 4) || misaligned(d_bodies, 16) || misaligned(d_mass, 16) ||
-                        misaligned(d_lines, 16) || misaligned(d_out, 16) || misaligned(d_tension, 4)))
-        return fail(MW_EINVAL, who, "d_hull_xyz, d_triangles and d_tension must be 4-byte, d_bodies, d_mass, d_lines and d_out 16-byte aligned");
-    const HullCall c{d_hull_xyz, d_triangles, d_bodies, d_mass, d_out, nverts, ntris, nbodies, iterations, coeffs, dt, substeps};
-    const MooredLines ml{d_lines, lines_per_body, d_tension};
-    HullPlan p{};
-    mw_status s = moored_prepare(o, frame, c, ml, who, &p);
-    if (s != MW_OK || nbodies == 0) return s;
-    return moored_launch(o, p, c, ml);
+    const HullService c{{vp(d_hull_xyz), vp(d_triangles), d_bodies, d_out, nverts, ntris, nbodies, iterations, coeffs, true, vp(d_mass), dt,
+                         substeps, true, vp(d_lines), lines_per_body, d_tension}};
+    return service_device(o, frame, c, "mw_ocean_step_moored_device",
+                          "d_hull_xyz, d_triangles and d_tension must be 4-byte, d_bodies, d_mass, d_lines and d_out 16-byte aligned");
 }
-
 mw_status mw_ocean_step_moored(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t nverts, const int32_t* triangles, int32_t ntris,
                                float* bodies, const float* mass, const float* lines, int32_t lines_per_body, int32_t nbodies,
                                const float* coeffs, float dt, int32_t substeps, int32_t iterations, float* out, float* tension) {
-    const char* who = "mw_ocean_step_moored";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    const HullCall c{hull_xyz, triangles, bodies, mass, out, nverts, ntris, nbodies, iterations, coeffs, dt, substeps};
-    MooredLines ml{lines, lines_per_body, tension};
-    HullPlan p{};
-    mw_status s = moored_prepare(o, frame, c, ml, who, &p);
-    if (s != MW_OK || nbodies == 0) return s;
-    if (!triangles_in_range(triangles, ntris, nverts)) return fail(MW_EINVAL, who, "triangle index outside [0, nverts)");
-    const size_t K = (size_t)lines_per_body;
-    for (int32_t b = 0; b < nbodies; b++) {
-        if ((s = mass_row_check(mass, b, who)) != MW_OK) return s;
-        for (size_t k = 0; k < K; k++)
-            if (!mooring_slot_valid(lines + MW_MOORING_NLINE * ((size_t)b * K + k)))
-                return fail(MW_EINVAL, who, "slot " + std::to_string(k) + " of body " + std::to_string(b) +
-                                                " is invalid (a non-finite float, or L0, k or c negative)");
-    }
-    void *d_hull, *d_tris, *d_bodies, *d_mass, *d_lines, *d_out, *d_tension;
-    Stage st(o);
-    st.in(&d_hull, hull_xyz, (size_t)nverts * 3 * sizeof(float));
-    st.in(&d_tris, triangles, (size_t)ntris * 3 * sizeof(int32_t));
-    st.inout(&d_bodies, bodies, (size_t)nbodies * 16 * sizeof(float));
-    st.in(&d_mass, mass, (size_t)nbodies * 8 * sizeof(float));
-    st.in(&d_lines, lines, (size_t)nbodies * K * MW_MOORING_NLINE * sizeof(float));
-    st.out(&d_out, out, (size_t)nbodies * 8 * sizeof(float));      // optional
-    st.out(&d_tension, tension, (size_t)nbodies * K * sizeof(float));  // optional
-    if ((s = st.begin()) != MW_OK) return s;
-    HullCall d = c;
-    d.hull = d_hull; d.tris = d_tris; d.bodies = d_bodies; d.mass = d_mass; d.out = d_out;
-    ml.lines = d_lines; ml.tension = d_tension;
-    if ((s = moored_launch(o, p, d, ml)) != MW_OK) return s;
-    return st.finish();
+    const HullService c{{vp(hull_xyz), vp(triangles), bodies, out, nverts, ntris, nbodies, iterations, coeffs, true, vp(mass), dt, substeps, true,
+                         vp(lines), lines_per_body, tension}};
+    return service_host(o, frame, c, "mw_ocean_step_moored");
 }
 
 // ---- mixed fleets (csrc/fleet.h) ----------------------------------------------------------------------------------
@@ -630,7 +642,7 @@ static_assert(MW_FLEET_MAX_HULLS == MW_FLEET_HULLS && MW_FLEET_NHULL == 5, "flee
 // The arguments of a fleet-forces or step-fleet call; as HullCall, the host and the device form differ only in whose pointers it holds.
 // hulls and coeffs are host arrays in both.
 struct FleetCall {
-    const void *hull, *tris; void* bodies; const void *mass, *wrench; void* out;
+    void *hull, *tris, *bodies, *mass, *wrench, *out;
     const int32_t* hulls; const float* coeffs;
     int32_t total_verts, total_tris, nhulls, total_bodies, iterations; float dt; int32_t substeps;
     bool step;  // mw_ocean_step_fleet: mass is required, out is optional, dt and substeps are read
@@ -641,9 +653,8 @@ struct FleetPlan { SqMesh m; FleetTable all; bool drag; };
 // Validates a fleet call (the hull table, the sums, the arrays, every hull's coefficients, the stepping arguments) and names the surface
 // as hull_prepare does: the velocity query's rules when any hull's row has drag, the surface query's otherwise.
 static mw_status fleet_prepare(mw_ocean* o, int32_t frame, const FleetCall& c, const char* who, FleetPlan* p) {
-    if (!o) return fail(MW_EINVAL, who, "NULL handle");
-    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
-        return fail(MW_EINVAL, who, "a batched handle (mw_ocean_create_batch) has no single surface");
+    mw_status s = single_surface_check(o, who);
+    if (s != MW_OK) return s;
     if (c.step && !(c.substeps >= 1 && c.substeps <= 64)) return fail(MW_EINVAL, who, "substeps must be in [1, 64]");
     if (c.step && !(c.dt >= 0.f && c.dt <= 3.4e38f)) return fail(MW_EINVAL, who, "dt must be finite and >= 0");
     if (c.nhulls < 1 || c.nhulls > MW_FLEET_MAX_HULLS) return fail(MW_EINVAL, who, "nhulls must be in [1, MW_FLEET_MAX_HULLS]");
@@ -757,110 +768,95 @@ static mw_status fleet_launch(mw_ocean* o, const FleetPlan& p, const FleetCall& 
         HIP_TRY(tiled_fleet_step(dim3((unsigned)a.t.total[MW_FLEET_BODIES]), lds, MW_BODIES_LDS_MAX, o->stream, a));
     a.t = fleet_group(p, c, ~one);
     if (a.t.total[MW_FLEET_BODIES] == 0) return MW_OK;
-    if ((s = grow_reserve(o, o->bodies, (size_t)c.total_bodies * 8 * sizeof(float), "the step-bodies row buffer")) != MW_OK) return s;
-    a.rows = static_cast<float4*>(o->bodies.p);
-    for (int k = 0; k < c.substeps; k++) {
-        if ((s = fleet_rows(o, a)) != MW_OK) return s;
-        a.last = k == c.substeps - 1;
-        const dim3 gi((unsigned)(((int64_t)a.t.total[MW_FLEET_BODIES] + 255) / 256));
-        if (a.m.period != 0.f) {
-            HIP_TRY(tiled_fleet_integrate(gi, o->stream, a));
-        } else if (a.wrench) {
-            k_fleet_integrate<SqMesh, true><<<gi, dim3(256), 0, o->stream>>>(a);
-        } else {
-            // the one footprint, no wrench: k_bodies_integrate itself over each hull's bodies -- mw_ocean_step_bodies' bits by
-            // construction, where no k_fleet_integrate reproduced them (fleet.h, "operand order")
-            for (int h = 0; h < a.t.nhulls; h++) {
-                const FleetHull& f = a.t.hull[h];
-                const int64_t nb = (h + 1 < a.t.nhulls ? a.t.hull[h + 1].first[MW_FLEET_BODIES] : a.t.total[MW_FLEET_BODIES]) - f.first[MW_FLEET_BODIES];
-                if (nb == 0) continue;
-                BodiesArgs ba{};
-                ba.h.nbodies = nb;
-                ba.bodies = a.bodies + 4 * (size_t)f.body_first;
-                ba.mass = a.mass + 2 * (size_t)f.body_first;
-                ba.rows = a.rows + 2 * (size_t)f.body_first;
-                ba.out = a.out ? a.out + 2 * (size_t)f.body_first : nullptr;
-                ba.g = f.g; ba.dt = a.dt; ba.substeps = a.substeps; ba.last = a.last;
-                k_bodies_integrate<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, o->stream>>>(ba);
+    const dim3 gi((unsigned)(((int64_t)a.t.total[MW_FLEET_BODIES] + 255) / 256));
+    return run_substeps(
+        o, c.total_bodies, c.substeps, [&](float4* buf) { a.rows = buf; return fleet_rows(o, a); },
+        [&](const float4*, bool last) -> mw_status {
+            a.last = last;
+            if (a.m.period != 0.f) {
+                HIP_TRY(tiled_fleet_integrate(gi, o->stream, a));
+            } else if (a.wrench) {
+                k_fleet_integrate<SqMesh, true><<<gi, dim3(256), 0, o->stream>>>(a);
+            } else {
+                // the one footprint, no wrench: k_bodies_integrate itself over each hull's bodies -- mw_ocean_step_bodies' bits by
+                // construction, where no k_fleet_integrate reproduced them (fleet.h, "operand order")
+                for (int h = 0; h < a.t.nhulls; h++) {
+                    const FleetHull& f = a.t.hull[h];
+                    const int64_t nb = (h + 1 < a.t.nhulls ? a.t.hull[h + 1].first[MW_FLEET_BODIES] : a.t.total[MW_FLEET_BODIES]) - f.first[MW_FLEET_BODIES];
+                    if (nb == 0) continue;
+                    BodiesArgs ba{};
+                    ba.h.nbodies = nb;
+                    ba.bodies = a.bodies + 4 * (size_t)f.body_first;
+                    ba.mass = a.mass + 2 * (size_t)f.body_first;
+                    ba.rows = a.rows + 2 * (size_t)f.body_first;
+                    ba.out = a.out ? a.out + 2 * (size_t)f.body_first : nullptr;
+                    ba.g = f.g; ba.dt = a.dt; ba.substeps = a.substeps; ba.last = a.last;
+                    k_bodies_integrate<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, o->stream>>>(ba);
+                }
             }
-        }
-        HIP_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
+            return MW_OK;
+        });
+}
+
+namespace {  // internal linkage, like Stage
+struct FleetService : FleetCall {
+    using Plan = FleetPlan;
+    int64_t count() const { return total_bodies; }
+    mw_status prepare(mw_ocean* o, int32_t frame, const char* who, FleetPlan* p) const { return fleet_prepare(o, frame, *this, who, p); }
+    mw_status check_host(const char* who) const { return fleet_check_host(*this, who); }
+    // mass (forces), wrench and, when stepping, out are optional or absent
+    std::array<Arr, 6> arrays() {
+        const size_t nb = (size_t)total_bodies;
+        return {{{&hull, (size_t)total_verts * 3 * sizeof(float), IN, 4},
+                 {&tris, (size_t)total_tris * 3 * sizeof(int32_t), IN, 4},
+                 {&bodies, nb * 16 * sizeof(float), step ? INOUT : IN, 16},
+                 {&mass, nb * 8 * sizeof(float), IN, 16},
+                 {&wrench, nb * 8 * sizeof(float), IN, 16},
+                 {&out, nb * 8 * sizeof(float), OUT, 16}}};
     }
-    return MW_OK;
-}
-
-// Fleets do not read the column yet: with draught on (mw_ocean_set_draught) every fleet entry point refuses, before any other work.
-static bool fleet_draught(const mw_ocean* o) { return o && o->draught; }
-static mw_status fleet_draught_refusal(const char* who) {
-    return fail(MW_ESTATE, who, "fleets do not read the water column yet: the handle has draught on (mw_ocean_set_draught(o, 0) first, or "
-                                "mw_ocean_hull_forces / mw_ocean_step_bodies per hull)");
-}
-
-// the host form of both entry points: validate, stage, launch, copy back
-static mw_status fleet_host(mw_ocean* o, int32_t frame, const FleetCall& c, const char* who) {
+    mw_status launch(mw_ocean* o, const FleetPlan& p) const { return fleet_launch(o, p, *this); }
+};
+}  // namespace
+// Fleets do not read the column yet: with draught on (mw_ocean_set_draught) every fleet entry point refuses, before any other work --
+// its alignment test included -- and after nothing but the NULL handle, which the service reports.
+static mw_status fleet_entry(mw_ocean* o, int32_t frame, const FleetService& c, const char* who, bool device) {
     if (o) HIP_TRY(hipSetDevice(o->device));
-    if (fleet_draught(o)) return fleet_draught_refusal(who);
-    FleetPlan p{};
-    mw_status s = fleet_prepare(o, frame, c, who, &p);
-    if (s != MW_OK || c.total_bodies == 0) return s;
-    if ((s = fleet_check_host(c, who)) != MW_OK) return s;
-    const size_t nb = (size_t)c.total_bodies;
-    void *d_hull, *d_tris, *d_bodies, *d_mass, *d_wrench, *d_out;
-    Stage st(o);
-    st.in(&d_hull, c.hull, (size_t)c.total_verts * 3 * sizeof(float));
-    st.in(&d_tris, c.tris, (size_t)c.total_tris * 3 * sizeof(int32_t));
-    if (c.step) st.inout(&d_bodies, c.bodies, nb * 16 * sizeof(float));
-    else st.in(&d_bodies, c.bodies, nb * 16 * sizeof(float));
-    st.in(&d_mass, c.mass, nb * 8 * sizeof(float));
-    st.in(&d_wrench, c.wrench, nb * 8 * sizeof(float));  // optional
-    st.out(&d_out, c.out, nb * 8 * sizeof(float));       // optional when stepping
-    if ((s = st.begin()) != MW_OK) return s;
-    FleetCall d = c;
-    d.hull = d_hull; d.tris = d_tris; d.bodies = d_bodies; d.mass = d_mass; d.wrench = d_wrench; d.out = d_out;
-    if ((s = fleet_launch(o, p, d)) != MW_OK) return s;
-    return st.finish();
-}
-// the device form: alignment, validate, launch on the caller's arrays; never waits for the stream
-static mw_status fleet_device(mw_ocean* o, int32_t frame, const FleetCall& c, const char* who) {
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (fleet_draught(o)) return fleet_draught_refusal(who);
-    if (c.total_bodies > 0 && (misaligned(c.hull, 4) || misaligned(c.tris, 4) || misaligned(c.bodies, 16) || misaligned(c.mass, 16) ||
-                               misaligned(c.wrench, 16) || misaligned(c.out, 16)))
-        return fail(MW_EINVAL, who, "d_hull_xyz and d_triangles must be 4-byte, d_bodies, d_mass, d_wrench and d_out 16-byte aligned");
-    FleetPlan p{};
-    mw_status s = fleet_prepare(o, frame, c, who, &p);
-    if (s != MW_OK || c.total_bodies == 0) return s;
-    return fleet_launch(o, p, c);
+    if (o && o->draught)
+        return fail(MW_ESTATE, who, "fleets do not read the water column yet: the handle has draught on (mw_ocean_set_draught(o, 0) first, or "
+                                    "mw_ocean_hull_forces / mw_ocean_step_bodies per hull)");
+    if (!device) return service_host(o, frame, c, who);
+    return service_device(o, frame, c, who, "d_hull_xyz and d_triangles must be 4-byte, d_bodies, d_mass, d_wrench and d_out 16-byte aligned");
 }
 
 mw_status mw_ocean_fleet_forces(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t total_verts, const int32_t* triangles,
                                 int32_t total_tris, const int32_t* hulls, int32_t nhulls, const float* bodies, int32_t total_bodies,
                                 const float* coeffs, int32_t iterations, float* out) {
-    const FleetCall c{hull_xyz, triangles, const_cast<float*>(bodies), nullptr, nullptr, out, hulls, coeffs, total_verts, total_tris, nhulls,
-                      total_bodies, iterations, 0.f, 1, false};
-    return fleet_host(o, frame, c, "mw_ocean_fleet_forces");
+    const FleetService c{{vp(hull_xyz), vp(triangles), vp(bodies), nullptr, nullptr, out, hulls, coeffs, total_verts, total_tris, nhulls,
+                          total_bodies, iterations, 0.f, 1, false}};
+    return fleet_entry(o, frame, c, "mw_ocean_fleet_forces", false);
 }
 mw_status mw_ocean_fleet_forces_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t total_verts, const void* d_triangles,
                                        int32_t total_tris, const int32_t* hulls, int32_t nhulls, const void* d_bodies,
                                        int32_t total_bodies, const float* coeffs, int32_t iterations, void* d_out) {
-    const FleetCall c{d_hull_xyz, d_triangles, const_cast<void*>(d_bodies), nullptr, nullptr, d_out, hulls, coeffs, total_verts, total_tris,
-                      nhulls, total_bodies, iterations, 0.f, 1, false};
-    return fleet_device(o, frame, c, "mw_ocean_fleet_forces_device");
+    const FleetService c{{vp(d_hull_xyz), vp(d_triangles), vp(d_bodies), nullptr, nullptr, d_out, hulls, coeffs, total_verts, total_tris, nhulls,
+                          total_bodies, iterations, 0.f, 1, false}};
+    return fleet_entry(o, frame, c, "mw_ocean_fleet_forces_device", true);
 }
 mw_status mw_ocean_step_fleet(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t total_verts, const int32_t* triangles,
                               int32_t total_tris, const int32_t* hulls, int32_t nhulls, float* bodies, const float* mass, const float* wrench,
                               int32_t total_bodies, const float* coeffs, float dt, int32_t substeps, int32_t iterations, float* out) {
-    const FleetCall c{hull_xyz, triangles, bodies, mass, wrench, out, hulls, coeffs, total_verts, total_tris, nhulls, total_bodies, iterations,
-                      dt, substeps, true};
-    return fleet_host(o, frame, c, "mw_ocean_step_fleet");
+    const FleetService c{{vp(hull_xyz), vp(triangles), bodies, vp(mass), vp(wrench), out, hulls, coeffs, total_verts, total_tris, nhulls,
+                          total_bodies, iterations, dt, substeps, true}};
+    return fleet_entry(o, frame, c, "mw_ocean_step_fleet", false);
 }
 mw_status mw_ocean_step_fleet_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t total_verts, const void* d_triangles,
                                      int32_t total_tris, const int32_t* hulls, int32_t nhulls, void* d_bodies, const void* d_mass,
                                      const void* d_wrench, int32_t total_bodies, const float* coeffs, float dt, int32_t substeps,
                                      int32_t iterations, void* d_out) {
-    const FleetCall c{d_hull_xyz, d_triangles, d_bodies, d_mass, d_wrench, d_out, hulls, coeffs, total_verts, total_tris, nhulls, total_bodies,
-                      iterations, dt, substeps, true};
-    return fleet_device(o, frame, c, "mw_ocean_step_fleet_device");
+    const FleetService c{{vp(d_hull_xyz), vp(d_triangles), d_bodies, vp(d_mass), vp(d_wrench), d_out, hulls, coeffs, total_verts, total_tris,
+                          nhulls, total_bodies, iterations, dt, substeps, true}};
+    return fleet_entry(o, frame, c, "mw_ocean_step_fleet_device", true);
 }
 
 // ---- raycasts (csrc/raycast.h) -------------------------------------------------------------------------------------
@@ -874,47 +870,50 @@ static mw_status raycast_prepare(mw_ocean* o, int32_t frame, const void* rays, i
                                     "for the tiled surface)");
     return s;
 }
-static mw_status raycast_launch(mw_ocean* o, const SqMesh& m, const void* d_rays, int64_t n, void* d_out, void* d_hit) {
+extern "C++" {
+// The hierarchy of a surface of side x side grid lines into the handle's tree buffer, on the handle's stream: leaves(grid, tree) launches
+// the leaf builder of the surface, k_rc_build_top the levels above for trees deeper than 4.  *tr names the tree, its boxes included.
+template <class Leaves>
+static mw_status raycast_tree(mw_ocean* o, int side, Leaves leaves, RcTree* tr) {
     int B = sw(SW_RC_BLOCK);
     if (B <= 0) B = MW_RC_DEFAULT_BLOCK;
-    const int minB = (m.R - 2) / (1 << MW_RC_MAX_LEVEL) + 1;  // at most 2^MW_RC_MAX_LEVEL leaves per side
-    RcTree tr = rc_tree(nullptr, m.R, B < minB ? minB : B);
-    mw_status s = grow_reserve(o, o->rc_tree, (size_t)rc_nodes(tr.D) * 8 * sizeof(float), "the raycast hierarchy");
+    const int minB = (side - 2) / (1 << MW_RC_MAX_LEVEL) + 1;  // at most 2^MW_RC_MAX_LEVEL leaves per side
+    *tr = rc_tree(nullptr, side, B < minB ? minB : B);
+    mw_status s = grow_reserve(o, o->rc_tree, (size_t)rc_nodes(tr->D) * 8 * sizeof(float), "the raycast hierarchy");
     if (s != MW_OK) return s;
-    tr.box = static_cast<float*>(o->rc_tree.p);
-    const int T = tr.D >= 4 ? 16 : (1 << tr.D), tiles = (1 << tr.D) / T;
-    k_rc_build_leaves<<<dim3((unsigned)(tiles * tiles)), dim3(256), 0, o->stream>>>(m, tr);
-    if (tr.D > 4) k_rc_build_top<<<dim3(1), dim3(256), 0, o->stream>>>(tr);
-    k_raycast<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, tr, static_cast<const float4*>(d_rays), n,
-                                                                              static_cast<float4*>(d_out), static_cast<int2*>(d_hit));
+    tr->box = static_cast<float*>(o->rc_tree.p);
+    const int T = tr->D >= 4 ? 16 : (1 << tr->D), tiles = (1 << tr->D) / T;
+    HIP_TRY(leaves(dim3((unsigned)(tiles * tiles)), *tr));
+    if (tr->D > 4) k_rc_build_top<<<dim3(1), dim3(256), 0, o->stream>>>(*tr);
     HIP_TRY(hipGetLastError());
     return MW_OK;
 }
+}  // extern "C++"
+namespace {
+struct Raycast : PointCall {
+    mw_status prepare(mw_ocean* o, int32_t frame, const char* who, SqMesh* m) const { return raycast_prepare(o, frame, pts, n, out, who, m); }
+    std::array<Arr, 3> arrays() { return {{{&pts, floats(8), IN, 16}, {&out, floats(8), OUT, 16}, {&hit, floats(2), OUT, 8}}}; }  // hit: optional
+    mw_status launch(mw_ocean* o, const SqMesh& m) const {
+        RcTree tr;
+        mw_status s = raycast_tree(o, m.R, [&](dim3 grid, const RcTree& t) {
+            k_rc_build_leaves<<<grid, dim3(256), 0, o->stream>>>(m, t);
+            return hipSuccess;
+        }, &tr);
+        if (s != MW_OK) return s;
+        k_raycast<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, tr, static_cast<const float4*>(pts), n, static_cast<float4*>(out),
+                                                                                  static_cast<int2*>(hit));
+        HIP_TRY(hipGetLastError());
+        return MW_OK;
+    }
+};
+}  // namespace
 
 mw_status mw_ocean_raycast_device(mw_ocean* o, int32_t frame, const void* d_rays, int64_t n, void* d_out, void* d_hit) {
-    const char* who = "mw_ocean_raycast_device";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (n > 0 && (misaligned(d_rays, 16) || misaligned(d_out, 16) || misaligned(d_hit, 8)))
-        return fail(MW_EINVAL, who, "d_rays and d_out must be 16-byte and d_hit 8-byte aligned");
-    SqMesh m{};
-    mw_status s = raycast_prepare(o, frame, d_rays, n, d_out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    return raycast_launch(o, m, d_rays, n, d_out, d_hit);
+    return service_device(o, frame, Raycast{{vp(d_rays), d_out, d_hit, n, MW_QUERY_WORLD, 0, 0}}, "mw_ocean_raycast_device",
+                          "d_rays and d_out must be 16-byte and d_hit 8-byte aligned");
 }
-
 mw_status mw_ocean_raycast(mw_ocean* o, int32_t frame, const float* rays, int64_t n, float* out, int32_t* hit) {
-    const char* who = "mw_ocean_raycast";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    SqMesh m{};
-    mw_status s = raycast_prepare(o, frame, rays, n, out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    void *d_rays, *d_out, *d_hit;
-    Stage st(o);
-    st.in(&d_rays, rays, (size_t)n * 8 * sizeof(float));
-    st.out(&d_out, out, (size_t)n * 8 * sizeof(float));
-    st.out(&d_hit, hit, (size_t)n * 2 * sizeof(int32_t));  // optional
-    if ((s = st.begin()) != MW_OK || (s = raycast_launch(o, m, d_rays, n, d_out, d_hit)) != MW_OK) return s;
-    return st.finish();
+    return service_host(o, frame, Raycast{{vp(rays), out, hit, n, MW_QUERY_WORLD, 0, 0}}, "mw_ocean_raycast");
 }
 
 // ---- tiled raycasts (csrc/raycast_tiled.h) ------------------------------------------------------------------------------
@@ -924,59 +923,40 @@ mw_status mw_ocean_raycast(mw_ocean* o, int32_t frame, const float* rays, int64_
 // k_rc_build_top for trees deeper than 4 levels), then one lane per ray (k_raycast_tiled), all on the handle's stream.
 static mw_status raycast_tiled_prepare(mw_ocean* o, int32_t frame, const void* rays, int64_t n, int32_t reach, const void* out, const char* who,
                                        SqMesh* m) {
-    if (!o) return fail(MW_EINVAL, who, "NULL handle");
-    if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
-        return fail(MW_EINVAL, who, "a batched handle (mw_ocean_create_batch) has no single surface");
+    mw_status s = single_surface_check(o, who);
+    if (s != MW_OK) return s;
     if (o->sem != MW_SEM_FFTMESH) return fail(MW_ESTATE, who, "an OceanRenderer mesh does not tile (mw_ocean_set_periodic)");
     if (reach < 0 || reach > MW_RC_MAX_REACH) return fail(MW_EINVAL, who, "reach must be in [0, MW_RC_MAX_REACH]");
     const float P = grid_period(o);
     if (P == 0.f)
         return fail(MW_ENOTCOMMENSURATE, who, "the frame repeats only where unit_width * resolution == length and the resolution is even");
-    mw_status s = query_prepare(o, frame, MW_QUERY_WORLD, rays, n, 0, out, who, m);
+    s = query_prepare(o, frame, MW_QUERY_WORLD, rays, n, 0, out, who, m);
     m->period = P;
     return s;
 }
-static mw_status raycast_tiled_launch(mw_ocean* o, const SqMesh& m, const void* d_rays, int64_t n, int32_t reach, void* d_out, void* d_hit) {
-    int B = sw(SW_RC_BLOCK);
-    if (B <= 0) B = MW_RC_DEFAULT_BLOCK;
-    const int minB = (m.R - 1) / (1 << MW_RC_MAX_LEVEL) + 1;  // at most 2^MW_RC_MAX_LEVEL leaves per side
-    RcTree tr = rc_tree(nullptr, m.R + 1, B < minB ? minB : B);  // rct_tree: the N x N cells of one tile, grid line N the wrapped line 0
-    mw_status s = grow_reserve(o, o->rc_tree, (size_t)rc_nodes(tr.D) * 8 * sizeof(float), "the raycast hierarchy");
-    if (s != MW_OK) return s;
-    tr.box = static_cast<float*>(o->rc_tree.p);
-    const int T = tr.D >= 4 ? 16 : (1 << tr.D), tiles = (1 << tr.D) / T;
-    HIP_TRY(tiled_raycast_build_leaves(dim3((unsigned)(tiles * tiles)), o->stream, m, tr));
-    if (tr.D > 4) k_rc_build_top<<<dim3(1), dim3(256), 0, o->stream>>>(tr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(tiled_raycast(dim3((unsigned)((n + 255) / 256)), o->stream, m, tr, static_cast<const float4*>(d_rays), n, reach,
-                          static_cast<float4*>(d_out), static_cast<int4*>(d_hit)));
-    return MW_OK;
-}
+namespace {
+struct RaycastTiled : PointCall {
+    mw_status prepare(mw_ocean* o, int32_t frame, const char* who, SqMesh* m) const {
+        return raycast_tiled_prepare(o, frame, pts, n, reach, out, who, m);
+    }
+    std::array<Arr, 3> arrays() { return {{{&pts, floats(8), IN, 16}, {&out, floats(8), OUT, 16}, {&hit, floats(4), OUT, 16}}}; }  // hit: optional
+    mw_status launch(mw_ocean* o, const SqMesh& m) const {
+        RcTree tr;  // rct_tree: the N x N cells of one tile, grid line N the wrapped line 0
+        mw_status s = raycast_tree(o, m.R + 1, [&](dim3 grid, const RcTree& t) { return tiled_raycast_build_leaves(grid, o->stream, m, t); }, &tr);
+        if (s != MW_OK) return s;
+        HIP_TRY(tiled_raycast(dim3((unsigned)((n + 255) / 256)), o->stream, m, tr, static_cast<const float4*>(pts), n, reach,
+                              static_cast<float4*>(out), static_cast<int4*>(hit)));
+        return MW_OK;
+    }
+};
+}  // namespace
 
 mw_status mw_ocean_raycast_tiled_device(mw_ocean* o, int32_t frame, const void* d_rays, int64_t n, int32_t reach, void* d_out, void* d_hit) {
-    const char* who = "mw_ocean_raycast_tiled_device";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (n > 0 && (misaligned(d_rays, 16) || misaligned(d_out, 16) || misaligned(d_hit, 16)))
-        return fail(MW_EINVAL, who, "d_rays, d_out and d_hit must be 16-byte aligned");
-    SqMesh m{};
-    mw_status s = raycast_tiled_prepare(o, frame, d_rays, n, reach, d_out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    return raycast_tiled_launch(o, m, d_rays, n, reach, d_out, d_hit);
+    return service_device(o, frame, RaycastTiled{{vp(d_rays), d_out, d_hit, n, MW_QUERY_WORLD, 0, reach}}, "mw_ocean_raycast_tiled_device",
+                          "d_rays, d_out and d_hit must be 16-byte aligned");
 }
-
 mw_status mw_ocean_raycast_tiled(mw_ocean* o, int32_t frame, const float* rays, int64_t n, int32_t reach, float* out, int32_t* hit) {
-    const char* who = "mw_ocean_raycast_tiled";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    SqMesh m{};
-    mw_status s = raycast_tiled_prepare(o, frame, rays, n, reach, out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    void *d_rays, *d_out, *d_hit;
-    Stage st(o);
-    st.in(&d_rays, rays, (size_t)n * 8 * sizeof(float));
-    st.out(&d_out, out, (size_t)n * 8 * sizeof(float));
-    st.out(&d_hit, hit, (size_t)n * 4 * sizeof(int32_t));  // optional
-    if ((s = st.begin()) != MW_OK || (s = raycast_tiled_launch(o, m, d_rays, n, reach, d_out, d_hit)) != MW_OK) return s;
-    return st.finish();
+    return service_host(o, frame, RaycastTiled{{vp(rays), out, hit, n, MW_QUERY_WORLD, 0, reach}}, "mw_ocean_raycast_tiled");
 }
 
 // ---- the water column (csrc/water_column.h) -----------------------------------------------------------------------------
@@ -1108,13 +1088,21 @@ static ColTable column_table(const mw_ocean* o, const SqMesh& m) {
     }
     return tb;
 }
-static mw_status column_launch(mw_ocean* o, const SqMesh& m, int32_t mode, const void* d_xyz, int64_t n, int32_t iterations, void* d_out) {
-    mw_status s = column_build(o);
-    if (s != MW_OK) return s;
-    HIP_TRY(column_query_launch(o->stream, m, column_table(o, m), mode, sq_iters(iterations), static_cast<const float4*>(d_xyz), n,
-                                static_cast<float4*>(d_out)));
-    return MW_OK;
-}
+namespace {
+struct QueryColumn : PointCall {
+    mw_status prepare(mw_ocean* o, int32_t frame, const char* who, SqMesh* m) const {
+        return column_prepare(o, frame, mode, pts, n, iterations, out, who, m);
+    }
+    std::array<Arr, 2> arrays() { return {{{&pts, floats(4), IN, 16}, {&out, floats(MW_COL_NOUT), OUT, 16}}}; }
+    mw_status launch(mw_ocean* o, const SqMesh& m) const {
+        mw_status s = column_build(o);
+        if (s != MW_OK) return s;
+        HIP_TRY(column_query_launch(o->stream, m, column_table(o, m), mode, sq_iters(iterations), static_cast<const float4*>(pts), n,
+                                    static_cast<float4*>(out)));
+        return MW_OK;
+    }
+};
+}  // namespace
 
 mw_status mw_ocean_column_layers(mw_ocean* o, int32_t frame, int32_t layer, void** d_positions, void** d_velocities) {
     const char* who = "mw_ocean_column_layers";
@@ -1131,25 +1119,9 @@ mw_status mw_ocean_column_layers(mw_ocean* o, int32_t frame, int32_t layer, void
 }
 
 mw_status mw_ocean_query_column_device(mw_ocean* o, int32_t frame, int32_t mode, const void* d_xyz_, int64_t n, int32_t iterations, void* d_out) {
-    const char* who = "mw_ocean_query_column_device";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    if (n > 0 && (misaligned(d_xyz_, 16) || misaligned(d_out, 16))) return fail(MW_EINVAL, who, "d_xyz_ and d_out must be 16-byte aligned");
-    SqMesh m{};
-    mw_status s = column_prepare(o, frame, mode, d_xyz_, n, iterations, d_out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    return column_launch(o, m, mode, d_xyz_, n, iterations, d_out);
+    return service_device(o, frame, QueryColumn{{vp(d_xyz_), d_out, nullptr, n, mode, iterations, 0}}, "mw_ocean_query_column_device",
+                          "d_xyz_ and d_out must be 16-byte aligned");
 }
-
 mw_status mw_ocean_query_column(mw_ocean* o, int32_t frame, int32_t mode, const float* xyz_, int64_t n, int32_t iterations, float* out) {
-    const char* who = "mw_ocean_query_column";
-    if (o) HIP_TRY(hipSetDevice(o->device));
-    SqMesh m{};
-    mw_status s = column_prepare(o, frame, mode, xyz_, n, iterations, out, who, &m);
-    if (s != MW_OK || n == 0) return s;
-    void *d_xyz, *d_out;
-    Stage st(o);
-    st.in(&d_xyz, xyz_, (size_t)n * 4 * sizeof(float));
-    st.out(&d_out, out, (size_t)n * MW_COL_NOUT * sizeof(float));
-    if ((s = st.begin()) != MW_OK || (s = column_launch(o, m, mode, d_xyz, n, iterations, d_out)) != MW_OK) return s;
-    return st.finish();
+    return service_host(o, frame, QueryColumn{{vp(xyz_), out, nullptr, n, mode, iterations, 0}}, "mw_ocean_query_column");
 }
