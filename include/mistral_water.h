@@ -468,7 +468,8 @@ mw_status mw_ocean_step_bodies_device(mw_ocean* o, int32_t frame, const void* d_
  *   for the stiffest direction (k_total the summed stiffness of the lines along it).  The library does not check this.
  * Invalid slots: a slot is invalid when one of its nine used floats is not finite or L0, k or c is negative.  It is treated like an
  *   invalid mass row: the host form returns MW_EINVAL naming body and slot, the device form gives that body a NaN out row and NaN
- *   tensions and leaves its state unchanged.  The NaN-row rule of mw_ocean_step_bodies is unchanged.
+ *   tensions and leaves its state unchanged.  The NaN-row rule of mw_ocean_step_bodies is unchanged, and a body whose last substep had
+ *   a NaN row reports NaN tensions beside its NaN out row: a pose that is not known says nothing about its lines.
  * Everything else -- frame, state, argument, alignment and size rules, "changes nothing of the handle's state", the periodic switch and
  *   the draught switch -- is mw_ocean_step_bodies'.  In addition MW_EINVAL for lines_per_body outside [1, MW_MOORING_MAX_LINES] or a
  *   NULL lines with nbodies > 0; device form: d_lines 16-byte, d_tension 4-byte aligned.

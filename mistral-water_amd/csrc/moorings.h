@@ -131,12 +131,16 @@ MW_HD int mooring_wrench(const float body[16], const float* lines, int K, float 
 }
 
 // One substep of a moored body under its water row: the mooring wrench of the current state, the pushed row, body_integrate.  The slots
-// must be valid (mooring_slot_valid).  Returns what body_integrate returns.
+// must be valid (mooring_slot_valid).  Returns what body_integrate returns; a substep that leaves the body as it was (a NaN row) reports
+// NaN tensions beside its NaN row, as an invalid slot does: a pose that is not known says nothing about its lines.
 MW_HD bool moored_integrate(float body[16], const float row[8], const float mass[8], const float* lines, int K, float g, float h,
                             float* tension) {
     float M[8];
     const int taut = mooring_wrench(body, lines, K, M, tension);
-    return fleet_integrate(body, row, mass, taut > 0 ? M : nullptr, g, h);
+    const bool ok = fleet_integrate(body, row, mass, taut > 0 ? M : nullptr, g, h);
+    if (!ok && tension)
+        for (int s = 0; s < K; s++) tension[s] = NAN;
+    return ok;
 }
 
 // LDS k_moored_step takes beyond k_bodies_step's: the staged slots and their tensions
@@ -182,6 +186,8 @@ __global__ __launch_bounds__(256) void k_moored_integrate(MooredArgs a) {
             for (int s = 0; s < a.K; s++) a.tension[(size_t)b * a.K + s] = NAN;
     } else if (fleet_integrate(body, row, mass, m.any ? m.M : nullptr, a.g, a.dt)) {
         for (int k = 0; k < 4; k++) a.bodies[4 * b + k] = make_float4(body[4 * k], body[4 * k + 1], body[4 * k + 2], body[4 * k + 3]);
+    } else if (tell) {  // a NaN row: the body stays and its tensions are NaN (moored_integrate)
+        for (int s = 0; s < a.K; s++) a.tension[(size_t)b * a.K + s] = NAN;
     }
     if (a.last && a.out) hull_store_row(a.out + 2 * b, row);
 }

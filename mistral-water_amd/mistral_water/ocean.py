@@ -561,7 +561,7 @@ class Ocean:
                            gravity=9.81, linear_drag=0.0, quadratic_drag=0.0, velocity_scale=None, frame: int = -1, iterations: int = 0):
         """Device-pointer form: d_bodies [nbodies][16] updated in place, d_mass [nbodies][8], d_lines [nbodies][lines_per_body][12],
         d_out [nbodies][8] or 0 (16-byte aligned), d_tension [nbodies][lines_per_body] or 0; asynchronous on the handle's stream.  An
-        invalid mass row or slot gives that body a NaN row and NaN tensions and leaves it unchanged."""
+        invalid mass row or slot gives that body a NaN row and NaN tensions and leaves it unchanged; so does a NaN water row."""
         cf = self._hull_coeffs(density, gravity, linear_drag, quadratic_drag, velocity_scale)
         nat.check(nat.lib().mw_ocean_step_moored_device(self._h, int(frame), C.c_void_p(d_hull_xyz), int(nverts), C.c_void_p(d_triangles),
                                                          int(ntris), C.c_void_p(d_bodies), C.c_void_p(d_mass), C.c_void_p(d_lines),

@@ -48,6 +48,8 @@ def ms(tmp_path_factory):
     L.ms_body_integrate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p]
     L.ms_slot_valid.restype = None
     L.ms_slot_valid.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.ms_moored_lds_static.restype = C.c_int64
+    L.ms_moored_lds_static.argtypes = []
     return L
 
 

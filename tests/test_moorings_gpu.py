@@ -10,6 +10,7 @@ OceanRenderer resolution 8; the hulls are hull_ref.box (12 triangles) and icosph
 * a moored box on flat water surges with the period of its lines; invalid slots and NaN rows stay local; the argument, frame and state
   rules; the handle's state is untouched;
 * the one footprint without draught, whose rows come from kernels built with contraction, against the float64 composition.
+Hulls of more than one chunk, the one-launch plan's LDS edge, K = 2 .. 7 and taut lines under draught: tests/test_mooring_sizes_gpu.py.
 
 Measured on an MI355X (this file's seeds): the footprint check's worst error is 2.41e-5 of the displacement over the call for p (an ulp of
 |p| ~ 20 against 0.04 moved), 3.18e-6 of the change over the call for v, 3.33e-6 for w and 2.62e-6 for q; the asserted bounds are 8x those
