@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import workloads
+from pond_ref import bound
 
 pytestmark = pytest.mark.gpu
 
@@ -701,14 +702,6 @@ def test_gerstner_edge_parameters(mw, oracle):
     assert (out == pos).all()
     out = mw.gerstner_displace(pos, W, P["amplitude"], P["frequency"], 0.0, 1.25)
     assert (out[:, 0] == pos[:, 0]).all() and (out[:, 2] == pos[:, 2]).all() and np.abs(out[:, 1] - pos[:, 1]).max() > 0
-    def bound(wv, t):
-        # the shader's phase theta = frequency * dot(dir, x) + t * speed is FLOAT32 (W/MistralWaterLib.cginc:80-84, `half` = f32 on desktop),
-        # the oracle's f64: each of theta's roundings (the product t * speed, the sum) moves it by up to half an ulp of |theta|, and an
-        # offset moves by at most its amplitude times that, per wave
-        wv = np.asarray(wv, np.float64).reshape(-1, 3)
-        th = np.abs(P["frequency"] * (wv[:, 0] * 50.0 * 1.0 + np.abs(wv[:, 1]) * 50.0)) + abs(t) * np.abs(wv[:, 2])
-        ulp = float(np.spacing(np.float32(th.max())))
-        return 2e-5 + 8e-6 + len(wv) * max(P["amplitude"], P["amplitude"] * P["steepness"]) * 1.5 * ulp
     for t in (-7.5, 3600.0, -3600.0):
         for wv in (W, W[:1]):
             got = mw.gerstner_displace(pos, wv, P["amplitude"], P["frequency"], P["steepness"], t)
