@@ -31,7 +31,15 @@
 // widened by MW_RC_TSLACK of its ends' magnitudes (>= 2 gamma_3, Ize 2013), meets [tmin, min(tmax, best t)]: a box whose entry
 // distance equals the best t is still entered, so a tie with a smaller id is found.
 //
-// Everything but the __global__ wrappers is MW_HD: tests/raycast_shim.cpp compiles the same functions with g++ -ffp-contract=off.
+// One footprint or one tile: the leaf box, the builds, the cell test, the sibling step and the hit row are templates on the mesh type, as
+// the other surface services are.  SqMesh is the R x R footprint above; SqTiled is one tile of the tiling raycast_tiled.h casts on, its
+// N x N cells the tree of an (N+1) x (N+1) mesh whose last grid line is line 0 a period on.  The two differ in rc_side (cells per side,
+// which is also the stride of the ids), in rc_corner (how a grid vertex is fetched) and in the order rc_keep keeps (the tiling puts the
+// tile between t and id); everything else is one body, so both fetch and shear a vertex the same way.
+//
+// Everything but the __global__ wrappers is MW_HD: tests/raycast_shim.cpp compiles the same functions with g++ -ffp-contract=off.  Every
+// function here that does float arithmetic carries MW_RC_STRICT, but SqTiled's rc_corner calls sq_shift, which has no strict scope: the
+// SqTiled instantiations belong to a translation unit compiled without contraction (surface_tiled.hip) and to the g++ shims.
 #pragma once
 #include "mw_math.h"
 #include "surface_query.h"
@@ -73,17 +81,66 @@ MW_HD RcTree rc_tree(float* box, int R, int B) {
 MW_HD float rc_sel3(float a, float b, float c, int k) { return k == 0 ? a : (k == 1 ? b : c); }
 MW_HD bool rc_finite(float x) { return fabsf(x) <= 3.40282347e38f; }
 
-// the box of leaf (bx, bz): the AABB of its block's vertices, inflated; empty for padding leaves
-MW_HD void rc_leaf_box(const SqMesh& m, const RcTree& t, int bx, int bz, float lo[3], float hi[3]) {
+// ---- what the mesh type decides ------------------------------------------------------------------------------------------
+// cells per side, and so the stride of the triangle ids 2*(i*side + j) + upper
+template <typename Mesh>
+MW_HD int rc_side(const Mesh& m) { return Mesh::tiled ? m.R : m.R - 1; }
+// vertex on grid lines (i, j), 0 <= i, j <= rc_side: its position into p, its index in the frame returned.  The footprint reads it where
+// it lies and has no tiles; the tiling wraps line N to line 0 of the next tile and places relative tile (kx, kz) with sq_shift -- a vertex
+// on grid line g = k N + a is always sq_shift(v[a], k, P), whichever cell or tile asks.
+template <typename Mesh>
+MW_HD int rc_corner(const Mesh& m, int i, int j, int kx, int kz, float p[3]) {
+    if constexpr (Mesh::tiled) {
+        const int N = m.R, wi = i == N ? 1 : 0, wj = j == N ? 1 : 0;
+        const int v = (wi ? 0 : i) * N + (wj ? 0 : j);
+        const float* q = m.vert + 3 * (size_t)v;
+        p[0] = sq_shift(q[0], kx + wi, m.period);
+        p[1] = q[1];
+        p[2] = sq_shift(q[2], kz + wj, m.period);
+        return v;
+    } else {
+        const int v = i * m.R + j;
+        const float* q = m.vert + 3 * (size_t)v;
+        p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
+        return v;
+    }
+}
+// the best hit so far: t, the relative tile of the triangle's cell (the footprint leaves it alone), the id.  Nothing yet:
+// (+inf, INT32_MIN, INT32_MIN, -1), which no candidate with t = +inf betters.
+struct RcBest {
+    float t;
+    int kx, kz, id;
+};
+MW_HD RcBest rc_none() {
+    RcBest b;
+    b.t = INFINITY;
+    b.kx = b.kz = INT32_MIN;
+    b.id = -1;
+    return b;
+}
+// keeps the candidate when it comes first: by (t, id) on the footprint, by (t, tile x, tile z, id) on the tiling
+template <typename Mesh>
+MW_HD void rc_keep(float t, int kx, int kz, int id, RcBest* b) {
+    bool better;
+    if constexpr (Mesh::tiled) better = t != b->t ? t < b->t : (kx != b->kx ? kx < b->kx : (kz != b->kz ? kz < b->kz : id < b->id));
+    else better = t < b->t || (t == b->t && id < b->id);
+    if (better) { b->t = t; b->kx = kx; b->kz = kz; b->id = id; }
+}
+
+// ---- the hierarchy ---------------------------------------------------------------------------------------------------
+// the box of leaf (bx, bz): the AABB of its block's vertices (of tile 0), inflated; empty for padding leaves
+template <typename Mesh>
+MW_HD void rc_leaf_box(const Mesh& m, const RcTree& t, int bx, int bz, float lo[3], float hi[3]) {
     MW_RC_STRICT
     for (int c = 0; c < 3; c++) { lo[c] = INFINITY; hi[c] = -INFINITY; }
     if (bx >= t.nb || bz >= t.nb) return;
-    const int R = m.R;
-    const int i0 = bx * t.B, i1 = i0 + t.B < R - 1 ? i0 + t.B : R - 1;
-    const int j0 = bz * t.B, j1 = j0 + t.B < R - 1 ? j0 + t.B : R - 1;
+    const int S = rc_side(m);
+    const int i0 = bx * t.B, i1 = i0 + t.B < S ? i0 + t.B : S;
+    const int j0 = bz * t.B, j1 = j0 + t.B < S ? j0 + t.B : S;
     for (int i = i0; i <= i1; i++)
         for (int j = j0; j <= j1; j++) {
-            const float* v = m.vert + 3 * ((size_t)i * R + j);
+            float v[3];
+            rc_corner(m, i, j, 0, 0, v);
             for (int c = 0; c < 3; c++) { lo[c] = fminf(lo[c], v[c]); hi[c] = fmaxf(hi[c], v[c]); }
         }
     for (int c = 0; c < 3; c++) {
@@ -114,7 +171,8 @@ MW_HD void rc_merge(float lo[3], float hi[3], const float cl[3], const float ch[
 }
 
 // the whole tree, serially (the CPU shim; the device builds the same boxes with k_rc_build_leaves and k_rc_build_top)
-MW_HD void rc_build_serial(const SqMesh& m, const RcTree& t) {
+template <typename Mesh>
+MW_HD void rc_build_serial(const Mesh& m, const RcTree& t) {
     const int S = 1 << t.D;
     for (int x = 0; x < S; x++)
         for (int z = 0; z < S; z++) {
@@ -210,26 +268,28 @@ MW_HD bool rc_triangle(const RcV& A, const RcV& B, const RcV& C, float tmin, flo
     return true;
 }
 
-// cells [i0, i1) x [j0, j1), both triangles of each, in id order: keeps the (t, id) minimum in (*bt, *bid).  Along j a cell's corners
-// (i,j+1) (i+1,j+1) are the next cell's (i,j) (i+1,j): sheared once (a vertex's sheared coordinates do not depend on the cell).
-MW_HD void rc_cells(const SqMesh& m, const RcRay& r, int i0, int i1, int j0, int j1, float* bt, int* bid) {
-    const int R = m.R;
+// the sheared vertex on grid lines (i, j) of relative tile (kx, kz)
+template <typename Mesh>
+MW_HD RcV rc_vertex(const Mesh& m, const RcRay& r, int i, int j, int kx, int kz) {
+    float p[3];
+    rc_corner(m, i, j, kx, kz, p);
+    return rc_shear(r, p);
+}
+// cells [i0, i1) x [j0, j1) of relative tile (kx, kz), both triangles of each, in id order: keeps the first hit in *best.  Along j a
+// cell's corners (i,j+1) (i+1,j+1) are the next cell's (i,j) (i+1,j): sheared once (a vertex's sheared coordinates do not depend on the
+// cell).
+template <typename Mesh>
+MW_HD void rc_cells(const Mesh& m, const RcRay& r, int i0, int i1, int j0, int j1, int kx, int kz, RcBest* best) {
+    const int S = rc_side(m);
     for (int i = i0; i < i1; i++) {
-        const float* p = m.vert + 3 * ((size_t)i * R + j0);
-        RcV a = rc_shear(r, p), b = rc_shear(r, p + 3 * R);
-        for (int j = j0; j < j1; j++, p += 3) {
-            const RcV c = rc_shear(r, p + 3), d = rc_shear(r, p + 3 * R + 3);
-            const int id = 2 * (i * (R - 1) + j);
+        RcV a = rc_vertex(m, r, i, j0, kx, kz), b = rc_vertex(m, r, i + 1, j0, kx, kz);
+        for (int j = j0; j < j1; j++) {
+            const RcV c = rc_vertex(m, r, i, j + 1, kx, kz), d = rc_vertex(m, r, i + 1, j + 1, kx, kz);
+            const int id = 2 * (i * S + j);
             float t, U, V, W, det;
             // lower (i,j) (i+1,j) (i,j+1), then upper (i+1,j+1) (i+1,j) (i,j+1)
-            if (rc_triangle(a, b, c, r.tmin, r.tmax, &t, &U, &V, &W, &det) && (t < *bt || (t == *bt && id < *bid))) {
-                *bt = t;
-                *bid = id;
-            }
-            if (rc_triangle(d, b, c, r.tmin, r.tmax, &t, &U, &V, &W, &det) && (t < *bt || (t == *bt && id + 1 < *bid))) {
-                *bt = t;
-                *bid = id + 1;
-            }
+            if (rc_triangle(a, b, c, r.tmin, r.tmax, &t, &U, &V, &W, &det)) rc_keep<Mesh>(t, kx, kz, id, best);
+            if (rc_triangle(d, b, c, r.tmin, r.tmax, &t, &U, &V, &W, &det)) rc_keep<Mesh>(t, kx, kz, id + 1, best);
             a = c;
             b = d;
         }
@@ -251,27 +311,18 @@ MW_HD bool rc_slab(const RcRay& r, const float lo[3], const float hi[3], float t
     return t0 <= t1 && t0 <= tlimit && t1 >= r.tmin;
 }
 
-// first hit through the hierarchy: (*bt, *bid) stays (+inf, -1) when nothing is hit
-MW_HD void rc_trace(const SqMesh& m, const RcTree& tr, const RcRay& r, float* bt, int* bid) {
-    const int fx = r.dx < 0.f, fz = r.dz < 0.f;     // child bit 1 is the near half along an axis the ray runs down
-    const bool xminor = fabsf(r.dx) >= fabsf(r.dz);  // the axis of the larger |d| varies fastest
-    int L = 0, x = 0, z = 0;
-    for (;;) {
-        float lo[3], hi[3];
-        rc_load_box(tr.box, rc_level_offset(L) + ((int64_t)x << L) + z, lo, hi);
-        if (rc_slab(r, lo, hi, fminf(*bt, r.tmax))) {
-            if (L < tr.D) {  // the first child in the ray's order
-                L++;
-                x = 2 * x + fx;
-                z = 2 * z + fz;
-                continue;
-            }
-            const int i0 = x * tr.B, j0 = z * tr.B;  // a padding leaf's box is empty: i0, j0 < R - 1 here
-            rc_cells(m, r, i0, i0 + tr.B < m.R - 1 ? i0 + tr.B : m.R - 1, j0, j0 + tr.B < m.R - 1 ? j0 + tr.B : m.R - 1, bt, bid);
-        }
-        // the next sibling in the ray's order, else the parent's next sibling
+// The place of a stackless walk in the implicit tree: node (x, z) of level L, off = rc_level_offset(L).  The children of a node are
+// visited in the ray's order: fx, fz = 1 where the ray runs down the axis (child bit 1 is then the near half), xminor when x varies
+// fastest.
+struct RcCursor {
+    int L, x, z, off;
+    MW_HD int node() const { return off + (x << L) + z; }
+    // to the first child in the ray's order
+    MW_HD void descend(int fx, int fz) { L++; off = 4 * off + 1; x = 2 * x + fx; z = 2 * z + fz; }
+    // to the next sibling in the ray's order, else the parent's next sibling; false, at the root, when there is none
+    MW_HD bool next(int fx, int fz, bool xminor) {
         for (;;) {
-            if (L == 0) return;
+            if (L == 0) return false;
             const int ax = (x & 1) ^ fx, az = (z & 1) ^ fz;
             const int c = xminor ? (az << 1 | ax) : (ax << 1 | az);
             if (c < 3) {
@@ -279,39 +330,55 @@ MW_HD void rc_trace(const SqMesh& m, const RcTree& tr, const RcRay& r, float* bt
                 const int nx = xminor ? (n & 1) : (n >> 1), nz = xminor ? (n >> 1) : (n & 1);
                 x = (x & ~1) | (nx ^ fx);
                 z = (z & ~1) | (nz ^ fz);
-                break;
+                return true;
             }
-            L--;
-            x >>= 1;
-            z >>= 1;
+            L--; off = (off - 1) >> 2; x >>= 1; z >>= 1;
         }
+    }
+};
+// the cells of leaf (x, z): a padding leaf's box is empty, so x B, z B < rc_side here
+template <typename Mesh>
+MW_HD void rc_leaf_cells(const Mesh& m, const RcTree& tr, const RcRay& r, int x, int z, int kx, int kz, RcBest* best) {
+    const int S = rc_side(m), i0 = x * tr.B, j0 = z * tr.B;
+    rc_cells(m, r, i0, i0 + tr.B < S ? i0 + tr.B : S, j0, j0 + tr.B < S ? j0 + tr.B : S, kx, kz, best);
+}
+
+// first hit through the hierarchy: *best stays rc_none() when nothing is hit
+MW_HD void rc_trace(const SqMesh& m, const RcTree& tr, const RcRay& r, RcBest* best) {
+    const int fx = r.dx < 0.f, fz = r.dz < 0.f;
+    const bool xminor = fabsf(r.dx) >= fabsf(r.dz);  // the axis of the larger |d| varies fastest
+    RcCursor cur = {0, 0, 0, 0};
+    for (;;) {
+        float lo[3], hi[3];
+        rc_load_box(tr.box, cur.node(), lo, hi);
+        if (rc_slab(r, lo, hi, fminf(best->t, r.tmax))) {
+            if (cur.L < tr.D) {
+                cur.descend(fx, fz);
+                continue;
+            }
+            rc_leaf_cells(m, tr, r, cur.x, cur.z, 0, 0, best);
+        }
+        if (!cur.next(fx, fz, xminor)) return;
     }
 }
 
-// the row of a ray: out = t px py pz nx ny nz white, hit = (id, facing); misses and invalid rays as include/mistral_water.h says
-MW_HD void rc_finish(const SqMesh& m, const RcRay& r, bool valid, float bt, int bid, float out[8], int hit[2]) {
+// The row of a hit but for where the surface stands: out[0] = t and out[4..7] = normal and whitecap, hit = (id, facing); the caller
+// places out[1..3].  The corners of triangle best.id of relative tile (best.kx, best.kz) in sq_triangle order -- lower (i,j) (i+1,j)
+// (i,j+1), upper (i+1,j+1) (i+1,j) (i,j+1) -- go through rc_triangle once more for the search's own bits.
+template <typename Mesh>
+MW_HD void rc_hit_row(const Mesh& m, const RcRay& r, const RcBest& best, float out[8], int hit[2]) {
     MW_RC_STRICT
-    for (int k = 0; k < 8; k++) out[k] = NAN;
-    hit[0] = -1;
-    hit[1] = 0;
-    if (!valid) return;
-    if (bid < 0) {
-        out[0] = INFINITY;
-        return;
-    }
-    const int R = m.R, cell = bid >> 1, i = cell / (R - 1), j = cell - i * (R - 1);
-    const bool upper = (bid & 1) != 0;
+    const int S = rc_side(m), cell = best.id >> 1, i = cell / S, j = cell - i * S;
+    const bool upper = (best.id & 1) != 0;
+    float pa[3], pb[3], pc[3];
     int v[3];
-    float wr[3];
-    sq_triangle(R, i, j, upper, 0.f, 0.f, v, wr);
-    const float *pa = m.vert + 3 * (size_t)v[0], *pb = m.vert + 3 * (size_t)v[1], *pc = m.vert + 3 * (size_t)v[2];
-    float t = bt, U = 0.f, V = 0.f, W = 0.f, det = 1.f;
-    rc_triangle(rc_shear(r, pa), rc_shear(r, pb), rc_shear(r, pc), r.tmin, r.tmax, &t, &U, &V, &W, &det);  // the search's own bits
+    v[0] = rc_corner(m, upper ? i + 1 : i, upper ? j + 1 : j, best.kx, best.kz, pa);
+    v[1] = rc_corner(m, i + 1, j, best.kx, best.kz, pb);
+    v[2] = rc_corner(m, i, j + 1, best.kx, best.kz, pc);
+    float t = best.t, U = 0.f, V = 0.f, W = 0.f, det = 1.f;
+    rc_triangle(rc_shear(r, pa), rc_shear(r, pb), rc_shear(r, pc), r.tmin, r.tmax, &t, &U, &V, &W, &det);
     const float wa = U / det, wb = V / det, wc = W / det;
     out[0] = t;
-    out[1] = r.ox + t * r.dx;
-    out[2] = r.oy + t * r.dy;
-    out[3] = r.oz + t * r.dz;
     float n[3];
     for (int c = 0; c < 3; c++) n[c] = (wa * m.norm[3 * v[0] + c] + wb * m.norm[3 * v[1] + c]) + wc * m.norm[3 * v[2] + c];
     const float inv = 1.f / sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
@@ -319,35 +386,50 @@ MW_HD void rc_finish(const SqMesh& m, const RcRay& r, bool valid, float bt, int 
     out[5] = n[1] * inv;
     out[6] = n[2] * inv;
     out[7] = (wa * m.white[(size_t)m.wstride * v[0]] + wb * m.white[(size_t)m.wstride * v[1]]) + wc * m.white[(size_t)m.wstride * v[2]];
-    // facing: the sign of d . n_g in float64, n_g = e1 x e2 the displaced triangle's normal oriented as the rest triangle's +y
-    // (corners in sq_triangle order; lower: e1 = C - A, e2 = B - A; upper: e1 = B - A, e2 = C - A)
+    // facing: the sign of d . n_g in float64, n_g = e1 x e2 the displaced triangle's normal oriented as the rest triangle's +y, on the
+    // float32 corners (lower: e1 = C - A, e2 = B - A; upper: e1 = B - A, e2 = C - A)
     const float* q1 = upper ? pb : pc;
     const float* q2 = upper ? pc : pb;
     const double e1x = (double)q1[0] - (double)pa[0], e1y = (double)q1[1] - (double)pa[1], e1z = (double)q1[2] - (double)pa[2];
     const double e2x = (double)q2[0] - (double)pa[0], e2y = (double)q2[1] - (double)pa[1], e2z = (double)q2[2] - (double)pa[2];
     const double gx = e1y * e2z - e1z * e2y, gy = e1z * e2x - e1x * e2z, gz = e1x * e2y - e1y * e2x;
     const double dn = ((double)r.dx * gx + (double)r.dy * gy) + (double)r.dz * gz;
-    hit[0] = bid;
+    hit[0] = best.id;
     hit[1] = dn < 0.0 ? 1 : -1;
+}
+
+// the row of a ray: out = t px py pz nx ny nz white, hit = (id, facing); misses and invalid rays as include/mistral_water.h says
+MW_HD void rc_finish(const SqMesh& m, const RcRay& r, bool valid, const RcBest& best, float out[8], int hit[2]) {
+    MW_RC_STRICT
+    for (int k = 0; k < 8; k++) out[k] = NAN;
+    hit[0] = -1;
+    hit[1] = 0;
+    if (!valid) return;
+    if (best.id < 0) {
+        out[0] = INFINITY;
+        return;
+    }
+    rc_hit_row(m, r, best, out, hit);
+    out[1] = r.ox + out[0] * r.dx;
+    out[2] = r.oy + out[0] * r.dy;
+    out[3] = r.oz + out[0] * r.dz;
 }
 
 // one ray through the hierarchy
 MW_HD void rc_cast(const SqMesh& m, const RcTree& tr, const float ray[8], float out[8], int hit[2]) {
     RcRay r;
     const bool valid = rc_setup(ray, &r);
-    float bt = INFINITY;
-    int bid = -1;
-    if (valid) rc_trace(m, tr, r, &bt, &bid);
-    rc_finish(m, r, valid, bt, bid, out, hit);
+    RcBest best = rc_none();
+    if (valid) rc_trace(m, tr, r, &best);
+    rc_finish(m, r, valid, best, out, hit);
 }
 // one ray against every triangle in id order: the same intersection without a hierarchy (the tests' brute force)
 MW_HD void rc_cast_brute(const SqMesh& m, const float ray[8], float out[8], int hit[2]) {
     RcRay r;
     const bool valid = rc_setup(ray, &r);
-    float bt = INFINITY;
-    int bid = -1;
-    if (valid) rc_cells(m, r, 0, m.R - 1, 0, m.R - 1, &bt, &bid);
-    rc_finish(m, r, valid, bt, bid, out, hit);
+    RcBest best = rc_none();
+    if (valid) rc_cells(m, r, 0, m.R - 1, 0, m.R - 1, 0, 0, &best);
+    rc_finish(m, r, valid, best, out, hit);
 }
 
 #if defined(__HIPCC__)
@@ -363,10 +445,10 @@ __device__ __forceinline__ void rc_reduce_lds(const float4* s_lo, const float4* 
             hi->x = fmaxf(hi->x, ch.x); hi->y = fmaxf(hi->y, ch.y); hi->z = fmaxf(hi->z, ch.z);
         }
 }
-#if !defined(MW_RC_NO_KERNELS)  // a second translation unit takes the functions above without defining the kernels again
 // Leaves and the levels above them up to level D - 4: one workgroup per T x T tile of leaves (T = min(16, 2^D)), one lane per leaf
 // gathering its (B+1)^2 vertices, then the tile reduced 2 x 2 in LDS up to its own root; every level is written out.
-__global__ __launch_bounds__(256) void k_rc_build_leaves(SqMesh m, RcTree tr) {
+template <typename Mesh>
+__global__ __launch_bounds__(256) void k_rc_build_leaves(Mesh m, RcTree tr) {
     __shared__ float4 s_lo[256], s_hi[256];
     const int T = tr.D >= 4 ? 16 : (1 << tr.D);
     const int tiles = (1 << tr.D) / T;
@@ -397,6 +479,17 @@ __global__ __launch_bounds__(256) void k_rc_build_leaves(SqMesh m, RcTree tr) {
         }
     }
 }
+// a ray's two 16-byte loads and its row's two 16-byte stores
+__device__ __forceinline__ void rc_load_ray(const float4* __restrict__ rays, int64_t k, float ray[8]) {
+    const float4 a = rays[2 * k], b = rays[2 * k + 1];
+    ray[0] = a.x; ray[1] = a.y; ray[2] = a.z; ray[3] = a.w;
+    ray[4] = b.x; ray[5] = b.y; ray[6] = b.z; ray[7] = b.w;
+}
+__device__ __forceinline__ void rc_store_row(float4* __restrict__ out, int64_t k, const float o[8]) {
+    out[2 * k] = make_float4(o[0], o[1], o[2], o[3]);
+    out[2 * k + 1] = make_float4(o[4], o[5], o[6], o[7]);
+}
+#if !defined(MW_RC_NO_KERNELS)  // the two kernels that are no templates are defined in one translation unit, mistral_water.hip
 // The top levels of a tree deeper than 4: one workgroup reads level D - 4 (at most 32 x 32 nodes) into LDS and reduces it to the root.
 __global__ __launch_bounds__(256) void k_rc_build_top(RcTree tr) {
     __shared__ float4 s_lo[1024], s_hi[1024];
@@ -421,19 +514,17 @@ __global__ __launch_bounds__(256) void k_rc_build_top(RcTree tr) {
         }
     }
 }
-// One lane per ray: two 16-byte loads of the ray, the stackless traversal (32 B per node, from L2), the leaves' vertex gathers, two
-// 16-byte stores and an 8-byte one.
+// One lane per ray: the ray's loads, the stackless traversal (32 B per node, from L2), the leaves' vertex gathers, the row's stores and
+// an 8-byte one of the hit.
 __global__ __launch_bounds__(256) void k_raycast(SqMesh m, RcTree tr, const float4* __restrict__ rays, int64_t n, float4* __restrict__ out,
                                                  int2* __restrict__ hit) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
-    const float4 a = rays[2 * k], b = rays[2 * k + 1];
-    const float ray[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    float o[8];
+    float ray[8], o[8];
     int h[2];
+    rc_load_ray(rays, k, ray);
     rc_cast(m, tr, ray, o, h);
-    out[2 * k] = make_float4(o[0], o[1], o[2], o[3]);
-    out[2 * k + 1] = make_float4(o[4], o[5], o[6], o[7]);
+    rc_store_row(out, k, o);
     if (hit) hit[k] = make_int2(h[0], h[1]);
 }
 #endif  // MW_RC_NO_KERNELS

@@ -896,7 +896,7 @@ struct Raycast : PointCall {
     mw_status launch(mw_ocean* o, const SqMesh& m) const {
         RcTree tr;
         mw_status s = raycast_tree(o, m.R, [&](dim3 grid, const RcTree& t) {
-            k_rc_build_leaves<<<grid, dim3(256), 0, o->stream>>>(m, t);
+            k_rc_build_leaves<SqMesh><<<grid, dim3(256), 0, o->stream>>>(m, t);
             return hipSuccess;
         }, &tr);
         if (s != MW_OK) return s;
@@ -919,7 +919,7 @@ mw_status mw_ocean_raycast(mw_ocean* o, int32_t frame, const float* rays, int64_
 // ---- tiled raycasts (csrc/raycast_tiled.h) ------------------------------------------------------------------------------
 // The entry point names its surface: the handle's periodic switch is neither read nor changed.  Handle rules first (batched, OceanRenderer,
 // a grid that does not repeat), then the arguments and the frame (query_prepare), and the mesh carries the grid's period whatever the switch
-// says.  The hierarchy of one tile goes into the same tree buffer as mw_ocean_raycast's (k_rct_build_leaves in surface_tiled.hip, then
+// says.  The hierarchy of one tile goes into the same tree buffer as mw_ocean_raycast's (k_rc_build_leaves<SqTiled> in surface_tiled.hip, then
 // k_rc_build_top for trees deeper than 4 levels), then one lane per ray (k_raycast_tiled), all on the handle's stream.
 static mw_status raycast_tiled_prepare(mw_ocean* o, int32_t frame, const void* rays, int64_t n, int32_t reach, const void* out, const char* who,
                                        SqMesh* m) {

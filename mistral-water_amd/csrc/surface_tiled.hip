@@ -6,12 +6,14 @@
 #include "mw_host.h"  // AttrOnce
 #include "mw_math.h"
 #pragma clang fp contract(off)
-#define MW_RC_NO_KERNELS  // k_raycast and the two build kernels are mistral_water.hip's
+#define MW_RC_NO_KERNELS  // k_raycast and k_rc_build_top are mistral_water.hip's
 #define MW_MOORING_KERNELS  // k_moored_integrate and k_moored_step stand here alone
 #include "surface_tiled.h"
 #include "raycast_tiled.h"
 
 namespace mw {
+
+static_assert(MW_RCT_MAX_REACH == MW_RC_MAX_REACH, "raycast_tiled.h and the ABI bound the reach alike");
 
 hipError_t tiled_query_surface(dim3 grid, hipStream_t s, const SqMesh& m, int mode, int iters, const float2* xz, int64_t n, float4* out) {
     k_query_surface<<<grid, dim3(256), 0, s>>>(SqTiled{m}, mode, iters, xz, n, out);
@@ -86,7 +88,7 @@ hipError_t tiled_moored_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, 
 }
 
 hipError_t tiled_raycast_build_leaves(dim3 grid, hipStream_t s, const SqMesh& m, const RcTree& tr) {
-    k_rct_build_leaves<<<grid, dim3(256), 0, s>>>(m, tr);
+    k_rc_build_leaves<<<grid, dim3(256), 0, s>>>(SqTiled{m}, tr);
     return hipGetLastError();
 }
 
