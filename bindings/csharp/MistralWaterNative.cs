@@ -28,6 +28,7 @@ public static class MistralWaterNative
     public const int RcDefaultReach = 16, RcMaxReach = 1024;
     public const int FleetMaxHulls = 32, FleetNHull = 5;
     public const int MooringMaxLines = 8, MooringNLine = 12;
+    public const int RigAnchor = -1;
     public const int ColumnMaxLayers = 16;
 
     [StructLayout(LayoutKind.Sequential)]   // mw_params: 56 bytes
@@ -148,6 +149,10 @@ public static class MistralWaterNative
     [DllImport(Lib)] public static extern Status mw_ocean_fleet_forces_device(IntPtr ocean, int frame, IntPtr dHullXyz, int totalVerts, IntPtr dTriangles, int totalTris, int[] hulls, int nhulls, IntPtr dBodies, int totalBodies, float[] coeffs, int iterations, IntPtr dResult);
     [DllImport(Lib)] public static extern Status mw_ocean_step_fleet(IntPtr ocean, int frame, float[] hullXyz, int totalVerts, int[] triangles, int totalTris, int[] hulls, int nhulls, [In] [Out] float[] bodies, float[] mass, float[] wrench, int totalBodies, float[] coeffs, float dt, int substeps, int iterations, [Out] float[] result);
     [DllImport(Lib)] public static extern Status mw_ocean_step_fleet_device(IntPtr ocean, int frame, IntPtr dHullXyz, int totalVerts, IntPtr dTriangles, int totalTris, int[] hulls, int nhulls, IntPtr dBodies, IntPtr dMass, IntPtr dWrench, int totalBodies, float[] coeffs, float dt, int substeps, int iterations, IntPtr dResult);
+    // rigged fleets: step_fleet with step_moored's lines [totalBodies][linesPerBody][MooringNLine] and targets [totalBodies][linesPerBody] or null
+    // (RigAnchor: a is a fixed world point; j >= 0: a is a point in the body space of body j, a tow line); tension [totalBodies][linesPerBody] or null
+    [DllImport(Lib)] public static extern Status mw_ocean_step_rigged(IntPtr ocean, int frame, float[] hullXyz, int totalVerts, int[] triangles, int totalTris, int[] hulls, int nhulls, [In] [Out] float[] bodies, float[] mass, float[] wrench, float[] lines, int[] targets, int linesPerBody, int totalBodies, float[] coeffs, float dt, int substeps, int iterations, [Out] float[] result, [Out] float[] tension);
+    [DllImport(Lib)] public static extern Status mw_ocean_step_rigged_device(IntPtr ocean, int frame, IntPtr dHullXyz, int totalVerts, IntPtr dTriangles, int totalTris, int[] hulls, int nhulls, IntPtr dBodies, IntPtr dMass, IntPtr dWrench, IntPtr dLines, IntPtr dTargets, int linesPerBody, int totalBodies, float[] coeffs, float dt, int substeps, int iterations, IntPtr dResult, IntPtr dTension);
     // raycasts: rays [n][8] = (ox, oy, oz, tmin, dx, dy, dz, tmax) -> result [n][8] = (t, px, py, pz, nx, ny, nz, white), hit [n][2] =
     // (triangle, facing) or null; a miss: t = +infinity, an invalid ray: NaN
     [DllImport(Lib)] public static extern Status mw_ocean_raycast(IntPtr ocean, int frame, float[] rays, long n, [Out] float[] result, [Out] int[] hit);

@@ -475,7 +475,7 @@ mw_status mw_ocean_step_bodies_device(mw_ocean* o, int32_t frame, const void* d_
  *   NULL lines with nbodies > 0; device form: d_lines 16-byte, d_tension 4-byte aligned.
  * Plans: on a periodic handle without draught the call follows mw_ocean_step_bodies' plan rule (one launch for hulls of fewer than 4
  *   chunks, per substep above); on a non-periodic handle and with draught on it always steps per substep.  The bits are the same.
- * Not yet: mw_ocean_step_fleet has no lines, and there are no body-to-body lines (tow lines): a body's substep reads no other body.    */
+ * Lines on a mixed fleet, and body-to-body lines (tow lines): mw_ocean_step_rigged, below the fleets.                               */
 #define MW_MOORING_MAX_LINES 8
 #define MW_MOORING_NLINE 12   /* slot: hx hy hz L0 | ax ay az k | c _ _ _ */
 /* host arrays, synchronous */
@@ -527,7 +527,7 @@ mw_status mw_ocean_step_moored_device(mw_ocean* o, int32_t frame, const void* d_
  *   array with total_bodies > 0 (hulls and coeffs always); a negative or non-finite coefficient; a batched handle; and the substeps,
  *   dt, frame, iterations and alignment rules of the single-hull calls (d_wrench 16-byte aligned).  total_bodies == 0 does nothing.
  *   Caller arrays are untouched on failure; nothing of the handle's state changes.  The calls share the single-hull calls' buffers.
- * mw_ocean_step_fleet has no mooring lines yet (mw_ocean_step_moored steps one hull's bodies on theirs).                            */
+ * Mooring and tow lines on a fleet: mw_ocean_step_rigged, below.                                                                     */
 #define MW_FLEET_MAX_HULLS 32
 #define MW_FLEET_NHULL 5   /* hull row: vert_first, nverts, tri_first, ntris, nbodies */
 /* host arrays, synchronous */
@@ -548,6 +548,57 @@ mw_status mw_ocean_step_fleet_device(mw_ocean* o, int32_t frame, const void* d_h
                                      int32_t total_tris, const int32_t* hulls, int32_t nhulls, void* d_bodies, const void* d_mass,
                                      const void* d_wrench, int32_t total_bodies, const float* coeffs, float dt, int32_t substeps,
                                      int32_t iterations, void* d_out);
+
+/* ---- rigged fleets: mooring lines and tow lines on a mixed fleet in one call --------------------------------------------
+ * mw_ocean_step_rigged is mw_ocean_step_fleet plus lines, targets, lines_per_body and tension: every body of a mixed fleet carries up
+ *   to MW_MOORING_MAX_LINES lines, each to a fixed anchor (mw_ocean_step_moored's line) or to a point of another body of the call (a tow
+ *   line).  Everything not stated here is mw_ocean_step_fleet's rule.
+ * lines [total_bodies][lines_per_body][MW_MOORING_NLINE], lines_per_body = K in [1, MW_MOORING_MAX_LINES]: mw_ocean_step_moored's slot,
+ *   hx hy hz L0 | ax ay az k | c _ _ _, with its validity rule; a slot with k == 0 and c == 0 is empty and is skipped.
+ * targets [total_bodies][lines_per_body], int32, optional (NULL: every slot is anchored).  MW_RIG_ANCHOR: a is a fixed point of the
+ *   bodies' object space, exactly as in mw_ocean_step_moored.  j >= 0: a is an attachment point in the body space of body j, an index
+ *   into the call's bodies array.  The target of an empty slot is not read.
+ * tension [total_bodies][lines_per_body] is optional, with mw_ocean_step_moored's meaning.  wrench and out are optional as in
+ *   mw_ocean_step_fleet; out still reports the water row alone.
+ * Per substep every slot is evaluated at the state ALL bodies had at the start of that substep (a snapshot: no body sees another
+ *   body's already-advanced state, so the result does not depend on the order of the bodies).  A tow slot of body i with target j:
+ *   d_j = R(q_j) a, x_j = p_j + d_j, vb = v_j + w_j x d_j, the same expressions as the owner's d = R(q_i) h, x, va; then steps 3 to 6 of
+ *   mw_ocean_step_moored with the anchor replaced by x_j (r = x_j - x) and the closing speed (va - vb) . e.  With MW_RIG_ANCHOR the slot
+ *   is mw_ocean_step_moored's, bit for bit (vb is absent, not zero).
+ * A line joining bodies i and j is written in both tables: body i holds (h_i; a = h_j; target j) and body j holds (h_j; a = h_i;
+ *   target i), with the same L0, k and c.  Such mirrored slots give F_i == -F_j and T_i == T_j bitwise at every substep: r, va - vb and e
+ *   of the two ends are exact negations, l and T equal bits.  The library does NOT check mirroring: a one-sided slot pulls only its
+ *   owner, which suits a scripted tug whose own motion is prescribed.  Lines are Euclidean in the bodies' object space; on a periodic
+ *   handle nothing wraps.
+ * The body's line wrench M is the slot-order sum of its taut slots, as in mw_ocean_step_moored.  The integrator sees (F + W) + M: first
+ *   the wrench add of mw_ocean_step_fleet, when wrench != NULL, then the M add, when a slot is taut; no add happens for an absent part.
+ *   With targets NULL or all MW_RIG_ANCHOR and wrench NULL every body has mw_ocean_step_moored's bits on its hull alone; with no slot
+ *   taut the call has mw_ocean_step_fleet's bits on a periodic handle (equal to rounding on the one footprint, where this call
+ *   integrates strictly).  All of it is strict float32.
+ * Failures stay local.  A body is invalid for the call when a non-empty slot's target lies outside [-1, total_bodies) or is the body's
+ *   own index, or a slot is invalid.  It is treated like an invalid mass row: the host form returns MW_EINVAL naming body and slot, the
+ *   device form gives that body a NaN out row and NaN tensions and leaves its state unchanged, and reads nothing out of range.  A
+ *   non-empty tow slot whose target's state holds a non-finite float among p, q, v, w at the start of a substep makes that substep a
+ *   NaN-row substep of the owner: the owner keeps its bits for the rest of the call, with a NaN out row and NaN tensions.  A neighbour
+ *   that is held or invalid is simply read at its unchanged state: failures do not spread beyond the bodies tied to a non-finite one.
+ * Plans: the call always steps per substep, on every surface and whatever the library's plan switch says: a tow slot reads another
+ *   body's state at the start of the substep, which one workgroup per body cannot see without a grid-wide barrier.  The substeps read
+ *   the state from one array and write it to another, the caller's bodies and a buffer of the handle in turn.
+ * MW_EINVAL in addition to mw_ocean_step_fleet's: lines_per_body outside [1, MW_MOORING_MAX_LINES]; a NULL lines with total_bodies > 0;
+ *   device form: d_lines 16-byte, d_targets and d_tension 4-byte aligned.  Draught on: MW_ESTATE, as every fleet entry point.          */
+#define MW_RIG_ANCHOR (-1)
+/* host arrays, synchronous */
+mw_status mw_ocean_step_rigged(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t total_verts, const int32_t* triangles,
+                               int32_t total_tris, const int32_t* hulls, int32_t nhulls, float* bodies, const float* mass,
+                               const float* wrench, const float* lines, const int32_t* targets, int32_t lines_per_body,
+                               int32_t total_bodies, const float* coeffs, float dt, int32_t substeps, int32_t iterations, float* out,
+                               float* tension);
+/* device arrays, asynchronous on the handle's stream; hulls and coeffs host */
+mw_status mw_ocean_step_rigged_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t total_verts, const void* d_triangles,
+                                      int32_t total_tris, const int32_t* hulls, int32_t nhulls, void* d_bodies, const void* d_mass,
+                                      const void* d_wrench, const void* d_lines, const void* d_targets, int32_t lines_per_body,
+                                      int32_t total_bodies, const float* coeffs, float dt, int32_t substeps, int32_t iterations,
+                                      void* d_out, void* d_tension);
 
 /* ---- raycasts: where does this ray hit the water? -----------------------------------------------------------------
  * The first hit of each of n rays on the surface mw_ocean_query_surface reads, under its frame rules: FFTMesh frame -1 (the latest

@@ -96,9 +96,10 @@ struct mw_ocean {
     bool draught = false;       // mw_ocean_set_draught: hull forces and bodies read the water column (hull_draught.h; not part of the frame record)
     VelState vel;            // mw_ocean_velocity: the weighted spectrum and the velocity buffers (velocity_kernels.h)
     ColState col;            // mw_ocean_set_column: the layers below the surface (water_column.h)
-    // four separate buffers: the host forms keep their staged inputs in scratch while hull, bodies and rc_tree are in use
+    // five separate buffers: the host forms keep their staged inputs in scratch while hull, bodies and rc_tree are in use
     GrowBuf hull;     // mw_ocean_hull_forces: vertex slab + chunk partials (hull_forces.h)
     GrowBuf bodies;   // mw_ocean_step_bodies, per-substep plan: the rows of a substep [nbodies][8]
+    GrowBuf rig;      // mw_ocean_step_rigged: the second state array of the substeps' pair [total_bodies][16] (rigging.h)
     GrowBuf rc_tree;  // mw_ocean_raycast: the bounds hierarchy of the queried surface (raycast.h), rebuilt every call
     GrowBuf scratch;  // device staging of the host-pointer entry points (Stage)
     float* q_mesh = nullptr;  // OceanRenderer surface queries: the vertex stage of the queried frame, [res^2][3 + 3 + 1], allocated on first use
@@ -320,7 +321,7 @@ void mw_ocean_destroy(mw_ocean* o) {
     hipSetDevice(o->device);
     if (hipStreamSynchronize(o->stream) != hipSuccess) (void)hipGetLastError();  // a dead caller stream has nothing pending
     hipFree(o->q_mesh);
-    for (GrowBuf* b : {&o->scratch, &o->hull, &o->bodies, &o->rc_tree}) hipFree(b->p);
+    for (GrowBuf* b : {&o->scratch, &o->hull, &o->bodies, &o->rig, &o->rc_tree}) hipFree(b->p);
     vel_free(o->vel);
     col_release(o->col);
     direct_free(o->direct);

@@ -94,18 +94,22 @@ MW_HD void mooring_begin(MooringSum* m) {
     m->any = false;
     m->valid = true;
 }
-// adds one slot; returns its tension (an invalid slot's arithmetic passes through: the caller drops the sum when !valid)
-MW_HD float mooring_add(MooringSum* m, const float body[16], const float R[9], const float s[MW_MOORING_SLOT]) {
+// takes one evaluated slot into the sum: a taut slot's (F, tau) is added (the first one is copied), any other leaves the sum as it is
+MW_HD void mooring_take(MooringSum* m, bool taut, const float F[3], const float tau[3]) {
     MW_MOORING_STRICT
-    float F[3], tau[3], T;
-    m->valid = m->valid && mooring_slot_valid(s);
-    const bool taut = mooring_slot(body, R, s, F, tau, &T);
     for (int c = 0; c < 3; c++) {
         const float f = m->any ? m->M[c] + F[c] : F[c], q = m->any ? m->M[4 + c] + tau[c] : tau[c];
         m->M[c] = taut ? f : m->M[c];
         m->M[4 + c] = taut ? q : m->M[4 + c];
     }
     m->any = m->any || taut;
+}
+// adds one slot; returns its tension (an invalid slot's arithmetic passes through: the caller drops the sum when !valid)
+MW_HD float mooring_add(MooringSum* m, const float body[16], const float R[9], const float s[MW_MOORING_SLOT]) {
+    float F[3], tau[3], T;
+    m->valid = m->valid && mooring_slot_valid(s);
+    const bool taut = mooring_slot(body, R, s, F, tau, &T);
+    mooring_take(m, taut, F, tau);
     return T;
 }
 

@@ -1,5 +1,5 @@
 // surface_services.inc -- the host code of the services that read the displaced surface: surface queries, surface velocity, hull
-// forces, floating bodies, moorings, mixed fleets, raycasts, the water column.  Included by mistral_water.hip inside its extern "C" block
+// forces, floating bodies, moorings, mixed fleets, rigged fleets, raycasts, the water column.  Included by mistral_water.hip inside its extern "C" block
 // (one translation unit: the handle, fail, HIP_TRY, dmalloc, grow_reserve, Stage / Arr and the frame record are file-static there).
 //
 // Every service with a host and a device form is a call record and two functions that run it, service_host and service_device below.
@@ -12,7 +12,7 @@
 //                             its Stage, which swaps the staged copies into the record;
 //   launch(o, plan)           the kernels, on the handle's stream, on the record's pointers.
 // The point services (queries, raycasts, the column query) are PointCall and a struct each; the hull family (hull forces, step bodies,
-// step moored) is one HullCall whose optional parts say which call it is; the fleets are one FleetCall.  The per-substep plan of all
+// step moored) is one HullCall whose optional parts say which call it is; the fleets (step rigged included) are one FleetCall.  The per-substep plan of all
 // stepping is run_substeps, the raycasts' hierarchy raycast_tree.  mw_ocean_velocity / _device have no arrays to stage and stand alone.
 
 static int sq_iters(int32_t iterations) { return iterations == 0 ? MW_SQ_DEFAULT_ITERS : iterations; }
@@ -639,13 +639,15 @@ mw_status mw_ocean_step_moored(mw_ocean* o, int32_t frame, const float* hull_xyz
 
 // ---- mixed fleets (csrc/fleet.h) ----------------------------------------------------------------------------------
 static_assert(MW_FLEET_MAX_HULLS == MW_FLEET_HULLS && MW_FLEET_NHULL == 5, "fleet.h and the ABI size the hull table alike");
-// The arguments of a fleet-forces or step-fleet call; as HullCall, the host and the device form differ only in whose pointers it holds.
+// The arguments of a fleet-forces, step-fleet or step-rigged call; as HullCall, the host and the device form differ only in whose pointers it holds.
 // hulls and coeffs are host arrays in both.
 struct FleetCall {
     void *hull, *tris, *bodies, *mass, *wrench, *out;
     const int32_t* hulls; const float* coeffs;
     int32_t total_verts, total_tris, nhulls, total_bodies, iterations; float dt; int32_t substeps;
     bool step;  // mw_ocean_step_fleet: mass is required, out is optional, dt and substeps are read
+    // rigged (mw_ocean_step_rigged, a stepping call; csrc/rigging.h): lines, the optional targets, K = lines_per_body, the optional tension
+    bool rigged; void *lines, *targets; int32_t K; void* tension;
 };
 // what prepare derives: the mesh of the queried frame, the table of every hull with its coefficients, whether any hull has drag
 struct FleetPlan { SqMesh m; FleetTable all; bool drag; };
@@ -690,7 +692,14 @@ static mw_status fleet_prepare(mw_ocean* o, int32_t frame, const FleetCall& c, c
     return p->drag ? query_velocity_prepare(o, frame, MW_QUERY_WORLD, mark, c.total_bodies, c.iterations, mark, who, &p->m)
                    : query_prepare(o, frame, MW_QUERY_WORLD, mark, c.total_bodies, c.iterations, mark, who, &p->m);
 }
-// the checks only a host form can make: every hull's triangle indices, and for stepping every mass and wrench row
+// Validates a step-rigged call: its own arguments, then the fleet's rules (fleet_prepare).
+static mw_status rig_prepare(mw_ocean* o, int32_t frame, const FleetCall& c, const char* who, FleetPlan* p) {
+    if (c.K < 1 || c.K > MW_MOORING_MAX_LINES) return fail(MW_EINVAL, who, "lines_per_body must be in [1, MW_MOORING_MAX_LINES]");
+    if (c.total_bodies > 0 && !c.lines) return fail(MW_EINVAL, who, "NULL lines");
+    return fleet_prepare(o, frame, c, who, p);
+}
+// the checks only a host form can make: every hull's triangle indices, for stepping every mass and wrench row, and for a rigged call
+// every slot and every non-empty slot's target
 static mw_status fleet_check_host(const FleetCall& c, const char* who) {
     for (int h = 0; h < c.nhulls; h++) {
         const int32_t* r = c.hulls + MW_FLEET_NHULL * h;
@@ -703,6 +712,16 @@ static mw_status fleet_check_host(const FleetCall& c, const char* who) {
         if (s != MW_OK) return s;
         if (c.wrench && !fleet_wrench_valid(static_cast<const float*>(c.wrench) + 8 * (size_t)b))
             return fail(MW_EINVAL, who, "the wrench row of body " + std::to_string(b) + " is not finite");
+        for (int32_t k = 0; c.rigged && k < c.K; k++) {
+            const size_t slot = (size_t)b * c.K + k;
+            const float* ln = static_cast<const float*>(c.lines) + MW_MOORING_NLINE * slot;
+            const std::string where = "slot " + std::to_string(k) + " of body " + std::to_string(b);
+            if (!mooring_slot_valid(ln)) return fail(MW_EINVAL, who, where + " is invalid (a non-finite float, or L0, k or c negative)");
+            const int32_t t = c.targets ? static_cast<const int32_t*>(c.targets)[slot] : MW_RIG_ANCHOR;
+            if (rig_slot_kind(ln, t, b, c.total_bodies) == MW_RIG_SLOT_BAD)
+                return fail(MW_EINVAL, who, where + ": its target " + std::to_string(t) +
+                                                " must be MW_RIG_ANCHOR or another body of the call, in [0, total_bodies)");
+        }
     }
     return MW_OK;
 }
@@ -799,23 +818,67 @@ static mw_status fleet_launch(mw_ocean* o, const FleetPlan& p, const FleetCall& 
         });
 }
 
+// ---- rigged fleets (csrc/rigging.h) -------------------------------------------------------------------------------
+static_assert(MW_RIG_ANCHOR == MW_RIG_TARGET_ANCHOR, "rigging.h and the ABI name the anchor target alike");
+// Every substep of a step-rigged call on the handle's stream (total_bodies > 0).  Always the per-substep plan, over every hull of the
+// fleet at once: a tow slot reads another body's state at the start of the substep, and a workgroup per body cannot see that without a
+// grid-wide barrier.  Per substep fleet_rows on the current state, then k_rigged_integrate, which reads the state from one array and
+// writes every body's next state to the other of a pair: the caller's array and the handle's rig buffer.  The first substep reads the
+// one that lets the last write land in the caller's array (an odd count starts from a copy in the buffer).
+static mw_status rig_launch(mw_ocean* o, const FleetPlan& p, const FleetCall& c) {
+    mw_status s;
+    if (p.drag && (s = velocity_to_handle(o)) != MW_OK) return s;
+    const size_t bytes = (size_t)c.total_bodies * 16 * sizeof(float);
+    if ((s = grow_reserve(o, o->rig, bytes, "the step-rigged state buffer")) != MW_OK) return s;
+    float4* pair[2] = {static_cast<float4*>(c.bodies), static_cast<float4*>(o->rig.p)};
+    int from = c.substeps & 1;
+    if (from) HIP_TRY(hipMemcpyAsync(pair[1], pair[0], bytes, hipMemcpyDeviceToDevice, o->stream));
+    FleetArgs a{};
+    a.m = p.m;
+    a.vel = p.drag ? o->vel.vert : nullptr;
+    a.iters = sq_iters(c.iterations);
+    a.hull = static_cast<const float*>(c.hull); a.tris = static_cast<const int32_t*>(c.tris);
+    a.t = p.all;
+    RigArgs r{};
+    r.mass = static_cast<const float4*>(c.mass); r.wrench = static_cast<const float4*>(c.wrench);
+    r.lines = static_cast<const float4*>(c.lines); r.targets = static_cast<const int32_t*>(c.targets);
+    r.out = static_cast<float4*>(c.out); r.tension = static_cast<float*>(c.tension);
+    r.dt = c.dt / (float)c.substeps;
+    r.K = c.K;
+    r.t = p.all;
+    const dim3 gi((unsigned)(((int64_t)c.total_bodies + 255) / 256));
+    return run_substeps(
+        o, c.total_bodies, c.substeps, [&](float4* buf) { a.bodies = pair[from]; a.rows = buf; return fleet_rows(o, a); },
+        [&](const float4* buf, bool last) -> mw_status {
+            r.snap = pair[from]; r.next = pair[from ^ 1]; r.rows = buf; r.last = last;
+            from ^= 1;
+            HIP_TRY(strict_rigged_integrate(gi, o->stream, r));
+            return MW_OK;
+        });
+}
+
 namespace {  // internal linkage, like Stage
 struct FleetService : FleetCall {
     using Plan = FleetPlan;
     int64_t count() const { return total_bodies; }
-    mw_status prepare(mw_ocean* o, int32_t frame, const char* who, FleetPlan* p) const { return fleet_prepare(o, frame, *this, who, p); }
+    mw_status prepare(mw_ocean* o, int32_t frame, const char* who, FleetPlan* p) const {
+        return rigged ? rig_prepare(o, frame, *this, who, p) : fleet_prepare(o, frame, *this, who, p);
+    }
     mw_status check_host(const char* who) const { return fleet_check_host(*this, who); }
-    // mass (forces), wrench and, when stepping, out are optional or absent
-    std::array<Arr, 6> arrays() {
-        const size_t nb = (size_t)total_bodies;
+    // mass (forces), wrench, when stepping out, and a rigged call's targets and tension are optional or absent
+    std::array<Arr, 9> arrays() {
+        const size_t nb = (size_t)total_bodies, slots = rigged ? nb * (size_t)K : 0;
         return {{{&hull, (size_t)total_verts * 3 * sizeof(float), IN, 4},
                  {&tris, (size_t)total_tris * 3 * sizeof(int32_t), IN, 4},
                  {&bodies, nb * 16 * sizeof(float), step ? INOUT : IN, 16},
                  {&mass, nb * 8 * sizeof(float), IN, 16},
                  {&wrench, nb * 8 * sizeof(float), IN, 16},
-                 {&out, nb * 8 * sizeof(float), OUT, 16}}};
+                 {&lines, slots * MW_MOORING_NLINE * sizeof(float), IN, 16},
+                 {&targets, slots * sizeof(int32_t), IN, 4},
+                 {&out, nb * 8 * sizeof(float), OUT, 16},
+                 {&tension, slots * sizeof(float), OUT, 4}}};
     }
-    mw_status launch(mw_ocean* o, const FleetPlan& p) const { return fleet_launch(o, p, *this); }
+    mw_status launch(mw_ocean* o, const FleetPlan& p) const { return rigged ? rig_launch(o, p, *this) : fleet_launch(o, p, *this); }
 };
 }  // namespace
 // Fleets do not read the column yet: with draught on (mw_ocean_set_draught) every fleet entry point refuses, before any other work --
@@ -826,28 +889,31 @@ static mw_status fleet_entry(mw_ocean* o, int32_t frame, const FleetService& c, 
         return fail(MW_ESTATE, who, "fleets do not read the water column yet: the handle has draught on (mw_ocean_set_draught(o, 0) first, or "
                                     "mw_ocean_hull_forces / mw_ocean_step_bodies per hull)");
     if (!device) return service_host(o, frame, c, who);
-    return service_device(o, frame, c, who, "d_hull_xyz and d_triangles must be 4-byte, d_bodies, d_mass, d_wrench and d_out 16-byte aligned");
+    return service_device(o, frame, c, who,
+                          c.rigged ? "d_hull_xyz, d_triangles, d_targets and d_tension must be 4-byte, d_bodies, d_mass, d_wrench, d_lines and "
+                                     "d_out 16-byte aligned"
+                                   : "d_hull_xyz and d_triangles must be 4-byte, d_bodies, d_mass, d_wrench and d_out 16-byte aligned");
 }
 
 mw_status mw_ocean_fleet_forces(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t total_verts, const int32_t* triangles,
                                 int32_t total_tris, const int32_t* hulls, int32_t nhulls, const float* bodies, int32_t total_bodies,
                                 const float* coeffs, int32_t iterations, float* out) {
     const FleetService c{{vp(hull_xyz), vp(triangles), vp(bodies), nullptr, nullptr, out, hulls, coeffs, total_verts, total_tris, nhulls,
-                          total_bodies, iterations, 0.f, 1, false}};
+                          total_bodies, iterations, 0.f, 1, false, false, nullptr, nullptr, 0, nullptr}};
     return fleet_entry(o, frame, c, "mw_ocean_fleet_forces", false);
 }
 mw_status mw_ocean_fleet_forces_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t total_verts, const void* d_triangles,
                                        int32_t total_tris, const int32_t* hulls, int32_t nhulls, const void* d_bodies,
                                        int32_t total_bodies, const float* coeffs, int32_t iterations, void* d_out) {
     const FleetService c{{vp(d_hull_xyz), vp(d_triangles), vp(d_bodies), nullptr, nullptr, d_out, hulls, coeffs, total_verts, total_tris, nhulls,
-                          total_bodies, iterations, 0.f, 1, false}};
+                          total_bodies, iterations, 0.f, 1, false, false, nullptr, nullptr, 0, nullptr}};
     return fleet_entry(o, frame, c, "mw_ocean_fleet_forces_device", true);
 }
 mw_status mw_ocean_step_fleet(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t total_verts, const int32_t* triangles,
                               int32_t total_tris, const int32_t* hulls, int32_t nhulls, float* bodies, const float* mass, const float* wrench,
                               int32_t total_bodies, const float* coeffs, float dt, int32_t substeps, int32_t iterations, float* out) {
     const FleetService c{{vp(hull_xyz), vp(triangles), bodies, vp(mass), vp(wrench), out, hulls, coeffs, total_verts, total_tris, nhulls,
-                          total_bodies, iterations, dt, substeps, true}};
+                          total_bodies, iterations, dt, substeps, true, false, nullptr, nullptr, 0, nullptr}};
     return fleet_entry(o, frame, c, "mw_ocean_step_fleet", false);
 }
 mw_status mw_ocean_step_fleet_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t total_verts, const void* d_triangles,
@@ -855,8 +921,26 @@ mw_status mw_ocean_step_fleet_device(mw_ocean* o, int32_t frame, const void* d_h
                                      const void* d_wrench, int32_t total_bodies, const float* coeffs, float dt, int32_t substeps,
                                      int32_t iterations, void* d_out) {
     const FleetService c{{vp(d_hull_xyz), vp(d_triangles), d_bodies, vp(d_mass), vp(d_wrench), d_out, hulls, coeffs, total_verts, total_tris,
-                          nhulls, total_bodies, iterations, dt, substeps, true}};
+                          nhulls, total_bodies, iterations, dt, substeps, true, false, nullptr, nullptr, 0, nullptr}};
     return fleet_entry(o, frame, c, "mw_ocean_step_fleet_device", true);
+}
+
+mw_status mw_ocean_step_rigged(mw_ocean* o, int32_t frame, const float* hull_xyz, int32_t total_verts, const int32_t* triangles,
+                               int32_t total_tris, const int32_t* hulls, int32_t nhulls, float* bodies, const float* mass, const float* wrench,
+                               const float* lines, const int32_t* targets, int32_t lines_per_body, int32_t total_bodies,
+                               const float* coeffs, float dt, int32_t substeps, int32_t iterations, float* out, float* tension) {
+    const FleetService c{{vp(hull_xyz), vp(triangles), bodies, vp(mass), vp(wrench), out, hulls, coeffs, total_verts, total_tris, nhulls,
+                          total_bodies, iterations, dt, substeps, true, true, vp(lines), vp(targets), lines_per_body, tension}};
+    return fleet_entry(o, frame, c, "mw_ocean_step_rigged", false);
+}
+mw_status mw_ocean_step_rigged_device(mw_ocean* o, int32_t frame, const void* d_hull_xyz, int32_t total_verts, const void* d_triangles,
+                                      int32_t total_tris, const int32_t* hulls, int32_t nhulls, void* d_bodies, const void* d_mass,
+                                      const void* d_wrench, const void* d_lines, const void* d_targets, int32_t lines_per_body,
+                                      int32_t total_bodies, const float* coeffs, float dt, int32_t substeps, int32_t iterations,
+                                      void* d_out, void* d_tension) {
+    const FleetService c{{vp(d_hull_xyz), vp(d_triangles), d_bodies, vp(d_mass), vp(d_wrench), d_out, hulls, coeffs, total_verts, total_tris,
+                          nhulls, total_bodies, iterations, dt, substeps, true, true, vp(d_lines), vp(d_targets), lines_per_body, d_tension}};
+    return fleet_entry(o, frame, c, "mw_ocean_step_rigged_device", true);
 }
 
 // ---- raycasts (csrc/raycast.h) -------------------------------------------------------------------------------------

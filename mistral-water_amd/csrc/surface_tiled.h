@@ -6,7 +6,7 @@
 // The tiled raycast (raycast_tiled.h, mw_ocean_raycast_tiled) has its kernels here for the same reason -- k_raycast_tiled and the SqTiled
 // instantiation of raycast.h's k_rc_build_leaves: sq_shift, sq_reduce and the column planes of its walk must round as the g++ build
 // rounds them (tests/raycast_tiled_shim.cpp).
-// The kernels after the vertex slab (k_hull_triangles, k_hull_reduce, k_bodies_integrate) do not read the mesh (hull_forces.h), so their
+// The kernels after the vertex slab (k_hull_triangles, k_hull_reduce, k_bodies_integrate, k_moored_integrate, k_rigged_integrate) do not read the mesh (hull_forces.h), so their
 // instantiations here are the library's strict build of them: strict_hull_rows and strict_bodies_integrate serve a periodic handle and,
 // on either handle, draught (hull_draught.h), whose own vertex kernel stands in water_column.hip.
 //
@@ -16,6 +16,7 @@
 #include "rigid_bodies.h"
 #include "fleet.h"
 #include "moorings.h"
+#include "rigging.h"
 #include "raycast.h"  // RcTree, k_rc_build_leaves
 
 namespace mw {
@@ -41,6 +42,8 @@ MW_INTERNAL hipError_t tiled_fleet_step(dim3 grid, size_t lds, int lds_max, hipS
 MW_INTERNAL hipError_t strict_moored_integrate(dim3 grid, hipStream_t s, const MooredArgs& a);
 MW_INTERNAL hipError_t tiled_moored_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const BodiesArgs& a, const float4* lines, int K,
                                          float* tension);
+// rigged fleets (rigging.h): k_rigged_integrate, which reads no mesh and serves every handle, after the fleet's rows of the substep
+MW_INTERNAL hipError_t strict_rigged_integrate(dim3 grid, hipStream_t s, const RigArgs& a);
 // k_rc_build_leaves<SqTiled>: the leaf boxes of one tile and the levels above them up to D - 4 (k_rc_build_top, launched by the caller, does the
 // rest); k_raycast_tiled: one lane per ray.  m.period is the tiling's P.
 MW_INTERNAL hipError_t tiled_raycast_build_leaves(dim3 grid, hipStream_t s, const SqMesh& m, const RcTree& tr);

@@ -7,7 +7,7 @@
 #include "mw_math.h"
 #pragma clang fp contract(off)
 #define MW_RC_NO_KERNELS  // k_raycast and k_rc_build_top are mistral_water.hip's
-#define MW_MOORING_KERNELS  // k_moored_integrate and k_moored_step stand here alone
+#define MW_MOORING_KERNELS  // k_moored_integrate, k_moored_step and k_rigged_integrate stand here alone
 #include "surface_tiled.h"
 #include "raycast_tiled.h"
 
@@ -84,6 +84,11 @@ hipError_t tiled_moored_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, 
     const hipError_t e = attr.set(reinterpret_cast<const void*>(k_moored_step<SqTiled>), lds_max);
     if (e != hipSuccess) return e;
     k_moored_step<<<grid, dim3(MW_HULL_CHUNK), lds, s>>>(MooredStepArgsT<SqTiled>{bodies_args_tiled(a), lines, tension, K});
+    return hipGetLastError();
+}
+
+hipError_t strict_rigged_integrate(dim3 grid, hipStream_t s, const RigArgs& a) {
+    k_rigged_integrate<<<grid, dim3(256), 0, s>>>(a);
     return hipGetLastError();
 }
 

@@ -26,6 +26,7 @@ MW_BODY_NMASS = 8
 MW_RC_DEFAULT_REACH, MW_RC_MAX_REACH = 16, 1024
 MW_FLEET_MAX_HULLS, MW_FLEET_NHULL = 32, 5
 MW_MOORING_MAX_LINES, MW_MOORING_NLINE = 8, 12
+MW_RIG_ANCHOR = -1
 MW_COLUMN_MAX_LAYERS = 16
 STATUS_NAMES = {0: "MW_OK", 1: "MW_EINVAL", 2: "MW_ENOTPOW2", 3: "MW_ENOTCOMMENSURATE", 4: "MW_ENOMEM",
                 5: "MW_EDEVICE", 6: "MW_ESTATE"}
@@ -234,6 +235,10 @@ def lib():
                                           f32p, C.c_float, C.c_int32, C.c_int32, f32p]),
         "mw_ocean_step_fleet_device": (C.c_int, [vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, i32p, C.c_int32, vp, vp, vp, C.c_int32, f32p,
                                                  C.c_float, C.c_int32, C.c_int32, vp]),
+        "mw_ocean_step_rigged": (C.c_int, [vp, C.c_int32, f32p, C.c_int32, i32p, C.c_int32, i32p, C.c_int32, f32p, f32p, f32p, f32p, i32p,
+                                           C.c_int32, C.c_int32, f32p, C.c_float, C.c_int32, C.c_int32, f32p, f32p]),
+        "mw_ocean_step_rigged_device": (C.c_int, [vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, i32p, C.c_int32, vp, vp, vp, vp, vp, C.c_int32,
+                                                  C.c_int32, f32p, C.c_float, C.c_int32, C.c_int32, vp, vp]),
         "mw_ocean_raycast": (C.c_int, [vp, C.c_int32, f32p, C.c_int64, f32p, i32p]),
         "mw_ocean_raycast_device": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, vp]),
         "mw_ocean_raycast_tiled": (C.c_int, [vp, C.c_int32, f32p, C.c_int64, C.c_int32, f32p, i32p]),
@@ -297,6 +302,7 @@ ABI_SYMBOLS = [
     "mw_ocean_hull_forces", "mw_ocean_hull_forces_device", "mw_hull_mass_properties", "mw_ocean_step_bodies", "mw_ocean_step_bodies_device",
     "mw_ocean_step_moored", "mw_ocean_step_moored_device",
     "mw_ocean_fleet_forces", "mw_ocean_fleet_forces_device", "mw_ocean_step_fleet", "mw_ocean_step_fleet_device",
+    "mw_ocean_step_rigged", "mw_ocean_step_rigged_device",
     "mw_ocean_raycast", "mw_ocean_raycast_device", "mw_ocean_raycast_tiled", "mw_ocean_raycast_tiled_device",
     "mw_ocean_set_column", "mw_ocean_get_column", "mw_ocean_column_layers", "mw_ocean_query_column", "mw_ocean_query_column_device",
     "mw_ocean_set_draught", "mw_ocean_get_draught",

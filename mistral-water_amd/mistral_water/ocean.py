@@ -648,6 +648,55 @@ class Ocean:
                                                         int(total_bodies), _p(cf), float(dt), int(substeps), int(iterations),
                                                         C.c_void_p(d_out or None)))
 
+    # -- rigged fleets (mw_ocean_step_rigged) ------------------------------------------------------
+    def step_rigged(self, hull_xyz, triangles, hulls, bodies, mass, lines, dt, substeps: int = 1, targets=None, wrench=None, coeffs=None,
+                    frame: int = -1, iterations: int = 0, return_forces: bool = False, return_tension: bool = False):
+        """step_fleet with lines on every body -> bodies [total_bodies, 16] (updated in place when it is a C-contiguous float32 array),
+        then with return_forces the water rows [total_bodies, 8] of the last substep and with return_tension the tensions
+        [total_bodies, K] at its start.  lines [total_bodies, K, 12] as step_moored's (pack_lines); targets [total_bodies, K] int32 or
+        None (every slot anchored): MW_RIG_ANCHOR (-1) makes a slot's a a fixed world point, j >= 0 an attachment point in the body space
+        of body j (a tow line).  Every slot is evaluated at the state all bodies had at the start of the substep.  A line between two
+        bodies is written in both tables (h and a exchanged, the same L0, k, c): its two ends then pull with opposite bits; a one-sided
+        slot pulls its owner alone.  Everything else as step_fleet and step_moored."""
+        hull, tris, table = self._fleet_arrays(hull_xyz, triangles, hulls)
+        b = np.ascontiguousarray(bodies, np.float32).reshape(-1, 16)
+        m = np.ascontiguousarray(mass, np.float32).reshape(-1, nat.MW_BODY_NMASS)
+        w = None if wrench is None else np.ascontiguousarray(wrench, np.float32).reshape(-1, 8)
+        ln = np.ascontiguousarray(lines, np.float32)
+        if ln.ndim != 3 or ln.shape[2] != nat.MW_MOORING_NLINE:
+            raise ValueError(f"step_rigged: lines must be [total_bodies, K, {nat.MW_MOORING_NLINE}], got {ln.shape}")
+        tg = None if targets is None else np.ascontiguousarray(targets, np.int32)
+        if m.shape[0] != b.shape[0] or ln.shape[0] != b.shape[0] or (w is not None and w.shape[0] != b.shape[0]):
+            raise ValueError(f"step_rigged: {b.shape[0]} bodies but {m.shape[0]} mass rows and {ln.shape[0]} rows of lines"
+                             + ("" if w is None else f" and {w.shape[0]} wrench rows"))
+        if tg is not None and tg.shape != ln.shape[:2]:
+            raise ValueError(f"step_rigged: targets must be {ln.shape[:2]}, got {tg.shape}")
+        cf = self._fleet_coeffs(table.shape[0], coeffs)
+        out = np.empty((b.shape[0], 8), np.float32) if return_forces else None
+        ten = np.empty((b.shape[0], ln.shape[1]), np.float32) if return_tension else None
+        nat.check(nat.lib().mw_ocean_step_rigged(self._h, int(frame), _p(hull), hull.shape[0], _p(tris), tris.shape[0], _p(table),
+                                                  table.shape[0], _p(b), _p(m), _p(w), _p(ln), _p(tg), ln.shape[1], b.shape[0], _p(cf),
+                                                  float(dt), int(substeps), int(iterations), _p(out), _p(ten)))
+        res = (b,) + ((out,) if return_forces else ()) + ((ten,) if return_tension else ())
+        return res if len(res) > 1 else b
+
+    def step_rigged_device(self, d_hull_xyz: int, total_verts: int, d_triangles: int, total_tris: int, hulls, d_bodies: int, d_mass: int,
+                           d_lines: int, lines_per_body: int, total_bodies: int, dt, substeps: int = 1, d_targets: int = 0,
+                           d_wrench: int = 0, d_out: int = 0, d_tension: int = 0, coeffs=None, frame: int = -1, iterations: int = 0):
+        """Device-pointer form: d_bodies [total_bodies][16] updated in place, d_mass, d_wrench (0 = none) and d_out (0 = none)
+        [total_bodies][8], d_lines [total_bodies][lines_per_body][12], all 16-byte aligned; d_targets (0 = all anchored, int32) and
+        d_tension (0 = none) [total_bodies][lines_per_body]; hulls and coeffs host arrays; asynchronous on the handle's stream.  An
+        invalid mass, wrench or slot, a target out of range or the body itself gives that body a NaN row and NaN tensions and leaves it
+        unchanged; so does a tow line to a body whose state is not finite."""
+        table = np.ascontiguousarray(hulls, np.int32).reshape(-1, nat.MW_FLEET_NHULL)
+        cf = self._fleet_coeffs(table.shape[0], coeffs)
+        nat.check(nat.lib().mw_ocean_step_rigged_device(self._h, int(frame), C.c_void_p(d_hull_xyz), int(total_verts),
+                                                         C.c_void_p(d_triangles), int(total_tris), _p(table), table.shape[0],
+                                                         C.c_void_p(d_bodies), C.c_void_p(d_mass), C.c_void_p(d_wrench or None),
+                                                         C.c_void_p(d_lines or None), C.c_void_p(d_targets or None), int(lines_per_body),
+                                                         int(total_bodies), _p(cf), float(dt), int(substeps), int(iterations),
+                                                         C.c_void_p(d_out or None), C.c_void_p(d_tension or None)))
+
 
 def pack_fleet(hulls):
     """(hull_xyz [total_verts, 3] float32, triangles [total_tris, 3] int32, table [nhulls, 5] int32) of Ocean.fleet_forces / step_fleet
