@@ -4,6 +4,7 @@
  * NOT part of the drop-in boundary (include/mistral_water.h): a host integration never calls these and the C# import table
  * (bindings/csharp/MistralWaterNative.cs) does not carry them.  bench.py uses the measurement hook, tests/ use the rest
  * to compare intermediate quantities of the kernels (omega*t, hds, the device sincos) with the oracle bit for bit.
+ * mw_debug_raycast_tree returns the raycasts' device-built hierarchy, which tests/ compare box for box with the serial build.
  */
 #ifndef MISTRAL_WATER_HOOKS_H
 #define MISTRAL_WATER_HOOKS_H
@@ -53,6 +54,13 @@ mw_status mw_debug_set_switch(const char* name, int32_t value);
 int32_t mw_debug_get_switch(const char* name);
 /* streams `bytes` of device memory through `width`-byte per-lane loads (4, 8 or 16): FETCH_SIZE calibration */
 mw_status mw_debug_stream_read(int64_t bytes, int32_t width, int32_t iters);
+/* The hierarchy a raycast of `frame` would traverse, built by the cast's own launches after the cast's own checks (tiled = 0:
+ * mw_ocean_raycast, the footprint; tiled = 1: mw_ocean_raycast_tiled, one tile) with the same statuses.  geom = (B leaf block side in
+ * cells, nb leaf blocks per side, D leaf level), filled even when box_host is NULL; the tree has (4^(D+1) - 1) / 3 nodes, level L a
+ * 2^L x 2^L grid from node (4^L - 1) / 3, row-major.  box_host [nodes][8] = lo.x lo.y lo.z 0 hi.x hi.y hi.z 0; MW_EINVAL (and nothing
+ * written to box_host) when capacity_nodes is below the node count.  The tree buffer is set to 0xFF bytes before the build: a node no
+ * kernel wrote comes back NaN.  Waits for the handle's stream.                                                                      */
+mw_status mw_debug_raycast_tree(mw_ocean* o, int32_t frame, int32_t tiled, float* box_host, int64_t capacity_nodes, int32_t geom[3]);
 
 #ifdef __cplusplus
 }

@@ -291,6 +291,34 @@ mw_status mw_debug_get_omega(mw_ocean* o, float* out_host) {  // [j][i] layout
     return MW_OK;
 }
 
+// test hook: the hierarchy a raycast of this frame would traverse (raycast.h), every node of every level.  The cast's own checks
+// (raycast_prepare / raycast_tiled_prepare, on one ray's worth of arrays that are only tested against NULL: an OceanRenderer mesh is
+// displaced only for a call that has rays) and the cast's own build (raycast_build / raycast_tiled_build).  The first build sizes the
+// handle's tree buffer and names the geometry; its rc_nodes(D) boxes are then set to 0xFF bytes and built again, so that a node no
+// kernel writes comes back NaN.
+mw_status mw_debug_raycast_tree(mw_ocean* o, int32_t frame, int32_t tiled, float* box_host, int64_t capacity_nodes, int32_t geom[3]) {
+    const char* who = "mw_debug_raycast_tree";
+    if (!geom) return fail(MW_EINVAL, who, "NULL geom");
+    if (o) HIP_TRY(hipSetDevice(o->device));
+    SqMesh m{};
+    mw_status s = tiled ? raycast_tiled_prepare(o, frame, geom, 1, 0, geom, who, &m) : raycast_prepare(o, frame, geom, 1, geom, who, &m);
+    if (s != MW_OK) return s;
+    RcTree tr;
+    auto build = [&] { return tiled ? raycast_tiled_build(o, m, &tr) : raycast_build(o, m, &tr); };
+    if ((s = build()) != MW_OK) return s;
+    const size_t bytes = (size_t)rc_nodes(tr.D) * 8 * sizeof(float);
+    HIP_TRY(hipMemsetAsync(tr.box, 0xFF, bytes, o->stream));
+    if ((s = build()) != MW_OK) return s;
+    geom[0] = tr.B; geom[1] = tr.nb; geom[2] = tr.D;
+    if (box_host && capacity_nodes < rc_nodes(tr.D)) {
+        HIP_TRY(hipStreamSynchronize(o->stream));
+        return fail(MW_EINVAL, who, "capacity_nodes is below the tree's node count (geom[2] = D; (4^(D+1) - 1) / 3 nodes)");
+    }
+    if (box_host) HIP_TRY(hipMemcpyAsync(box_host, tr.box, bytes, hipMemcpyDeviceToHost, o->stream));
+    HIP_TRY(hipStreamSynchronize(o->stream));
+    return MW_OK;
+}
+
 #ifdef MW_TIMING
 mw_status mw_debug_get_stamps(long long* out_host) {
     HIP_TRY(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_stamps), sizeof(long long) * 2 * 64 * 16 * 32));

@@ -973,16 +973,20 @@ static mw_status raycast_tree(mw_ocean* o, int side, Leaves leaves, RcTree* tr) 
     return MW_OK;
 }
 }  // extern "C++"
+// the footprint's tree: what mw_ocean_raycast casts through and mw_debug_raycast_tree returns
+static mw_status raycast_build(mw_ocean* o, const SqMesh& m, RcTree* tr) {
+    return raycast_tree(o, m.R, [&](dim3 grid, const RcTree& t) {
+        k_rc_build_leaves<SqMesh><<<grid, dim3(256), 0, o->stream>>>(m, t);
+        return hipSuccess;
+    }, tr);
+}
 namespace {
 struct Raycast : PointCall {
     mw_status prepare(mw_ocean* o, int32_t frame, const char* who, SqMesh* m) const { return raycast_prepare(o, frame, pts, n, out, who, m); }
     std::array<Arr, 3> arrays() { return {{{&pts, floats(8), IN, 16}, {&out, floats(8), OUT, 16}, {&hit, floats(2), OUT, 8}}}; }  // hit: optional
     mw_status launch(mw_ocean* o, const SqMesh& m) const {
         RcTree tr;
-        mw_status s = raycast_tree(o, m.R, [&](dim3 grid, const RcTree& t) {
-            k_rc_build_leaves<SqMesh><<<grid, dim3(256), 0, o->stream>>>(m, t);
-            return hipSuccess;
-        }, &tr);
+        mw_status s = raycast_build(o, m, &tr);
         if (s != MW_OK) return s;
         k_raycast<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, o->stream>>>(m, tr, static_cast<const float4*>(pts), n, static_cast<float4*>(out),
                                                                                   static_cast<int2*>(hit));
@@ -1018,6 +1022,11 @@ static mw_status raycast_tiled_prepare(mw_ocean* o, int32_t frame, const void* r
     m->period = P;
     return s;
 }
+// the tree of one tile (rct_tree: its N x N cells, grid line N the wrapped line 0): what mw_ocean_raycast_tiled casts through and
+// mw_debug_raycast_tree returns
+static mw_status raycast_tiled_build(mw_ocean* o, const SqMesh& m, RcTree* tr) {
+    return raycast_tree(o, m.R + 1, [&](dim3 grid, const RcTree& t) { return tiled_raycast_build_leaves(grid, o->stream, m, t); }, tr);
+}
 namespace {
 struct RaycastTiled : PointCall {
     mw_status prepare(mw_ocean* o, int32_t frame, const char* who, SqMesh* m) const {
@@ -1025,8 +1034,8 @@ struct RaycastTiled : PointCall {
     }
     std::array<Arr, 3> arrays() { return {{{&pts, floats(8), IN, 16}, {&out, floats(8), OUT, 16}, {&hit, floats(4), OUT, 16}}}; }  // hit: optional
     mw_status launch(mw_ocean* o, const SqMesh& m) const {
-        RcTree tr;  // rct_tree: the N x N cells of one tile, grid line N the wrapped line 0
-        mw_status s = raycast_tree(o, m.R + 1, [&](dim3 grid, const RcTree& t) { return tiled_raycast_build_leaves(grid, o->stream, m, t); }, &tr);
+        RcTree tr;
+        mw_status s = raycast_tiled_build(o, m, &tr);
         if (s != MW_OK) return s;
         HIP_TRY(tiled_raycast(dim3((unsigned)((n + 255) / 256)), o->stream, m, tr, static_cast<const float4*>(pts), n, reach,
                               static_cast<float4*>(out), static_cast<int4*>(hit)));

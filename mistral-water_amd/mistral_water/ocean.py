@@ -496,6 +496,18 @@ class Ocean:
         nat.check(nat.lib().mw_ocean_raycast_tiled_device(self._h, int(frame), C.c_void_p(d_rays), int(n), int(reach), C.c_void_p(d_out),
                                                            C.c_void_p(d_hit) if d_hit else None))
 
+    def raycast_tree(self, frame: int = -1, tiled: bool = False):
+        """Test hook (mw_debug_raycast_tree): the hierarchy raycast() (tiled: raycast_tiled()) of this frame would traverse, built by
+        the cast's own launches -> (box [nodes, 8] float32 rows (lo.x, lo.y, lo.z, 0, hi.x, hi.y, hi.z, 0), B, nb, D): leaf blocks of
+        B cells, nb a side, at level D; level L is a 2^L x 2^L grid from node (4^L - 1) / 3, row-major.  A node no kernel wrote is
+        NaN."""
+        geom = np.zeros(3, np.int32)
+        cap = (4 ** 10 - 1) // 3   # the deepest tree: leaf level MW_RC_MAX_LEVEL = 9 (csrc/raycast.h)
+        box = np.empty((cap, 8), np.float32)
+        nat.check(nat.lib().mw_debug_raycast_tree(self._h, int(frame), int(bool(tiled)), _p(box), cap, _p(geom)))
+        nodes = (4 ** (int(geom[2]) + 1) - 1) // 3
+        return box[:nodes].copy(), int(geom[0]), int(geom[1]), int(geom[2])
+
     # -- floating bodies (mw_ocean_step_bodies) --------------------------------------------------
     def step_bodies(self, hull_xyz, triangles, bodies, mass, dt, substeps: int = 1, density=1000.0, gravity=9.81, linear_drag=0.0,
                     quadratic_drag=0.0, velocity_scale=None, frame: int = -1, iterations: int = 0, return_forces: bool = False):

@@ -1,11 +1,13 @@
 """Helpers of the raycast tests (mw_ocean_raycast, csrc/raycast.h): the g++ build of tests/raycast_shim.cpp, the grid's triangles in id
-order, the ray families both tiers cast, triangle_t_f64 -- a float64 Möller–Trumbore over every triangle (numpy) -- and facing_f64."""
+order, synthetic meshes, tree_ref -- the hierarchy written in numpy from the comment of raycast.h --, the ray families both tiers cast,
+triangle_t_f64 -- a float64 Möller–Trumbore over every triangle (numpy) -- and facing_f64."""
 import ctypes as C
 import os
 
 import numpy as np
 
 import shim_build
+import surface_ref as S
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(REPO, "tests", "raycast_shim.cpp")
@@ -39,6 +41,83 @@ class Mesh:
         self.norm = np.ascontiguousarray(norm, np.float32).reshape(-1, 3)
         self.white = np.ascontiguousarray(white, np.float32).reshape(-1)
         assert len(self.vert) == self.R * self.R and len(self.white) == self.R * self.R * self.wstride
+
+
+def synthetic(R, kind, seed):
+    """flat (y = 0 exactly, horizontally displaced), rough (below the fold limit), choppy (folded: overhangs, several hits per ray) or
+    far (rough, translated to x = 1e4: the magnitude of a coordinate dwarfs a leaf's extent)"""
+    jit, fold = {"flat": (0.2, 0.6), "rough": (0.2, 0.6), "choppy": (1.2, 1.8), "far": (0.2, 0.6)}[kind]
+    if R <= 3:  # too small for synth_mesh's waves: random corners around the rest grid
+        rng = np.random.default_rng(seed)
+        rest = S.rest_plane(R, 1.0).astype(np.float64)
+        vert = np.c_[rest[:, 0], rng.uniform(-0.5, 0.5, R * R), rest[:, 1]] + np.c_[rng.uniform(-jit, jit, (R * R, 1)), np.zeros(R * R),
+                                                                                   rng.uniform(-jit, jit, (R * R, 1))]
+        norm = rng.normal(size=(R * R, 3)) + [0.0, 3.0, 0.0]
+        norm /= np.linalg.norm(norm, axis=1, keepdims=True)
+        white = rng.uniform(0, 1, R * R)
+    else:
+        vert, norm, white = S.synth_mesh(R, 1.0, fold, seed=seed)
+        vert = vert.astype(np.float64)
+    if kind == "flat":
+        vert[:, 1] = 0.0
+    if kind == "far":
+        vert[:, 0] += 1.0e4
+    return Mesh(R, vert, norm, white)
+
+
+PAD = np.float32(2.0 ** -14)   # MW_RC_PAD
+
+
+def tree_ref(grid, B):
+    """(box [nodes, 8] float32, nb, D): the hierarchy of csrc/raycast.h written from its comment, in float32.  grid [S+1, S+1, 3] holds
+    the vertices on the grid lines of the S x S cells.  nb = ceil(S / B) leaf blocks a side at level D, 2^D >= nb; leaf (bx, bz) holds
+    the exact min and max of the vertices on lines [bx B, min(bx B + B, S)] x [bz B, min(bz B + B, S)], grown per axis by
+    p = PAD ((hi - lo) + max(|lo|, |hi|)), every operation rounded to float32; padding leaves are (+inf, -inf); a parent is the min and
+    max of its 2 x 2 children; level L is a 2^L x 2^L grid from node (4^L - 1) / 3, row-major; slots 3 and 7 are 0."""
+    g = np.ascontiguousarray(grid, np.float32)
+    S_ = g.shape[0] - 1
+    assert g.shape == (S_ + 1, S_ + 1, 3) and S_ >= 1 and B >= 1
+    nb = -(-S_ // B)
+    D = (nb - 1).bit_length()
+    first = np.arange(nb) * B
+    lines = [np.minimum(first + k, S_) for k in range(B + 1)]     # line k of every block, the last block cut at line S
+    lo = np.minimum.reduce([g[l] for l in lines])                 # [nb, S+1, 3]: over the block's lines along x ...
+    hi = np.maximum.reduce([g[l] for l in lines])
+    lo = np.minimum.reduce([lo[:, l] for l in lines])             # ... then along z: [nb, nb, 3]
+    hi = np.maximum.reduce([hi[:, l] for l in lines])
+    p = PAD * ((hi - lo) + np.maximum(np.abs(lo), np.abs(hi)))
+    assert p.dtype == np.float32
+    s = 1 << D
+    lvl = np.zeros((s, s, 8), np.float32)
+    lvl[:, :, 0:3], lvl[:, :, 4:7] = np.inf, -np.inf
+    lvl[:nb, :nb, 0:3], lvl[:nb, :nb, 4:7] = lo - p, hi + p
+    levels = [lvl]
+    while s > 1:
+        s >>= 1
+        c = levels[0].reshape(s, 2, s, 2, 8)
+        lvl = np.zeros((s, s, 8), np.float32)
+        lvl[:, :, 0:3], lvl[:, :, 4:7] = c[..., 0:3].min((1, 3)), c[..., 4:7].max((1, 3))
+        levels.insert(0, lvl)
+    box = np.concatenate([l.reshape(-1, 8) for l in levels])
+    assert box.dtype == np.float32 and len(box) == (4 ** (D + 1) - 1) // 3
+    return box, nb, D
+
+
+def shim_tree(L, m, B):
+    """the serial build of the shim (rc_build_serial): box [nodes, 8]"""
+    box = np.full((L.rc_shim_nodes(m.R, B), 8), np.nan, np.float32)
+    assert L.rc_shim_build(m.R, _p(m.vert), B, _p(box)) == 0
+    return box
+
+
+def same_tree(a, b):
+    """every node equal as float32 values (no NaN; only the sign of a zero may differ in bits); else the first nodes that differ"""
+    if a.shape == b.shape and np.array_equal(a, b):
+        return True, None
+    if a.shape != b.shape:
+        return False, (a.shape, b.shape)
+    bad = np.flatnonzero(~(a == b).all(1))
+    return False, (len(bad), bad[:6], a[bad[:3]], b[bad[:3]])
 
 
 def cast(L, m, rays, B=None, brute=False):

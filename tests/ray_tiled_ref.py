@@ -1,5 +1,5 @@
 """Helpers of the tiled raycast tests (mw_ocean_raycast_tiled, csrc/raycast_tiled.h): the g++ build of tests/raycast_tiled_shim.cpp,
-synthetic N x N frames (any displacement of the rest grid tiles by construction), the ray families both tiers cast, the comparison
+synthetic N x N frames (any displacement of the rest grid tiles by construction), a tile's grid lines for ray_ref.tree_ref, the ray families both tiers cast, the comparison
 with the brute force and the float64 view of a window's triangle instances."""
 import ctypes as C
 import os
@@ -22,6 +22,7 @@ def build_shim(path):
     L.rct_shim_nodes.argtypes = [ci, ci]
     L.rct_shim_build.argtypes = [ci, cf, cf, vp, ci, vp]
     L.rct_shim_root.argtypes = [ci, cf, cf, vp, ci, vp, vp, vp]
+    L.rct_shim_overhang.argtypes = [ci, cf, cf, vp]
     L.rct_shim_cast.argtypes = [ci, cf, cf, vp, vp, vp, ci, ci, ci, vp, i64, vp, vp]
     L.rct_shim_brute.argtypes = [ci, cf, cf, vp, vp, vp, ci, ci, vp, i64, vp, vp]
     return L
@@ -49,13 +50,18 @@ class TMesh:
 
 def synthetic(N, kind, seed, uw=1.0):
     """flat: the rest grid at y = 0.25; rough: heights and a horizontal displacement below half a cell; folded: horizontal displacement
-    of up to 1.5 cells (triangles fold over); big: some vertices displaced horizontally by more than a period (h = 2)"""
+    of up to 1.5 cells (triangles fold over); big: some vertices displaced horizontally by more than a period (h = 2); level: rough
+    with y = 0 exactly; far: rough, translated to x = 1e4 (the magnitude of a coordinate dwarfs a leaf's extent)"""
     rng = np.random.default_rng(seed)
     r = rest(N, uw).astype(np.float64)
     X, Z = np.meshgrid(r, r, indexing="ij")
-    amp = {"flat": 0.0, "rough": 0.45, "folded": 1.5, "big": 0.45}[kind] * uw
+    amp = {"flat": 0.0, "rough": 0.45, "folded": 1.5, "big": 0.45, "level": 0.45, "far": 0.45}[kind] * uw
     dx, dz = rng.uniform(-amp, amp, (2, N, N))
     y = np.full((N, N), 0.25) if kind == "flat" else rng.uniform(-1.0, 1.0, (N, N)) * max(uw, 0.5)
+    if kind == "level":
+        y = np.zeros((N, N))
+    if kind == "far":
+        dx += 1.0e4
     if kind == "big":
         P = N * uw
         k = rng.integers(0, N * N, max(1, N * N // 8))
@@ -71,6 +77,32 @@ def root(L, m, B=2):
     r6, x0, h = np.empty(6, np.float32), C.c_float(0), C.c_int32(0)
     assert L.rct_shim_root(m.N, m.uw, m.P, _p(m.vert), B, _p(r6), C.byref(x0), C.byref(h)) == 0
     return r6[:3].copy(), r6[3:].copy(), int(h.value)
+
+
+def overhang_tiles(L, m, lo, hi):
+    """rct_overhang_tiles of a root box (lo [3], hi [3]) of frame m"""
+    r6 = np.ascontiguousarray(np.r_[lo, hi], np.float32)
+    return int(L.rct_shim_overhang(m.N, m.uw, m.P, _p(r6)))
+
+
+def tile_grid(m):
+    """[N+1, N+1, 3] float32: the vertices on the grid lines of one tile's N x N cells, line N = line 0 with x + 1*P (or z), the
+    expression of sq_shift"""
+    N, P = m.N, np.float32(m.P)
+    g = np.empty((N + 1, N + 1, 3), np.float32)
+    g[:N, :N] = m.vert.reshape(N, N, 3)
+    g[N, :N] = g[0, :N]
+    g[N, :N, 0] = g[0, :N, 0] + np.float32(1) * P
+    g[:, N] = g[:, 0]
+    g[:, N, 2] = g[:, 0, 2] + np.float32(1) * P
+    return g
+
+
+def shim_tree(L, m, B):
+    """the serial build of the shim (rct_build_serial): box [nodes, 8]"""
+    box = np.full((L.rct_shim_nodes(m.N, B), 8), np.nan, np.float32)
+    assert L.rct_shim_build(m.N, m.uw, m.P, _p(m.vert), B, _p(box)) == 0
+    return box
 
 
 def cast(L, m, rays, reach, B=2, brute=False):
@@ -142,9 +174,13 @@ def families(m, rng, n=60, far=1000):
         c = x0 + P / 2
         return rng.uniform([c - tiles * P, ylo - hgt, c - tiles * P], [c + tiles * P, yhi + hgt, c + tiles * P], (k, 3)).astype(np.float32)
 
+    tt = []   # tile_triangles(m), made once
+
     def seam_points(k, frac):
         """points of the edges of seam cells (ai or aj = N-1) of the tiles around tile 0: corner e of a triangle towards the next corner"""
-        tv, wi, wj = tile_triangles(m)
+        if not tt:
+            tt.extend(tile_triangles(m))
+        tv, wi, wj = tt
         cell = np.arange(2 * N * N) // 2
         t = rng.choice(np.flatnonzero((cell // N == N - 1) | (cell % N == N - 1)), k)
         kx, kz, e = rng.integers(-1, 2, k), rng.integers(-1, 2, k), rng.integers(0, 3, k)

@@ -41,6 +41,11 @@ extern "C" int rct_shim_root(int N, float uw, float P, const float* vert, int B,
     return 0;
 }
 
+// h of a root box (lo.x lo.y lo.z hi.x hi.y hi.z) somebody else built
+extern "C" int rct_shim_overhang(int N, float uw, float P, const float* root6) {
+    return rct_overhang_tiles(root6, root6 + 3, rest_coord(N, uw, 0), P);
+}
+
 // build, then the column walk -> out [n][8], hit [n][4]
 extern "C" int rct_shim_cast(int N, float uw, float P, const float* vert, const float* norm, const float* white, int wstride, int B,
                              int reach, const float* rays, int64_t n, float* out, int32_t* hit) {

@@ -23,23 +23,7 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
-def _mesh(R, kind, seed):
-    """flat (y = 0, horizontally displaced), rough (below the fold limit) or choppy (folded: overhangs, several hits per ray)"""
-    if R <= 3:  # too small for synth_mesh's waves: random corners around the rest grid
-        rng = np.random.default_rng(seed)
-        rest = S.rest_plane(R, 1.0).astype(np.float64)
-        jit = {"flat": 0.2, "rough": 0.2, "choppy": 1.2}[kind]
-        vert = np.c_[rest[:, 0], rng.uniform(-0.5, 0.5, R * R), rest[:, 1]] + np.c_[rng.uniform(-jit, jit, (R * R, 1)), np.zeros(R * R),
-                                                                                   rng.uniform(-jit, jit, (R * R, 1))]
-        norm = rng.normal(size=(R * R, 3)) + [0.0, 3.0, 0.0]
-        norm /= np.linalg.norm(norm, axis=1, keepdims=True)
-        white = rng.uniform(0, 1, R * R)
-    else:
-        vert, norm, white = S.synth_mesh(R, 1.0, {"flat": 0.6, "rough": 0.6, "choppy": 1.8}[kind], seed=seed)
-        vert = vert.astype(np.float64)
-    if kind == "flat":
-        vert[:, 1] = 0.0
-    return RR.Mesh(R, vert, norm, white)
+_mesh = RR.synthetic   # flat (y = 0, horizontally displaced), rough (below the fold limit) or choppy (folded)
 
 
 def _rays(m, seed, n):
