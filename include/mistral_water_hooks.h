@@ -5,6 +5,7 @@
  * (bindings/csharp/MistralWaterNative.cs) does not carry them.  bench.py uses the measurement hook, tests/ use the rest
  * to compare intermediate quantities of the kernels (omega*t, hds, the device sincos) with the oracle bit for bit.
  * mw_debug_raycast_tree returns the raycasts' device-built hierarchy, which tests/ compare box for box with the serial build.
+ * mw_debug_query_mesh runs the footprint surface and velocity query kernels on a caller's mesh.
  */
 #ifndef MISTRAL_WATER_HOOKS_H
 #define MISTRAL_WATER_HOOKS_H
@@ -61,6 +62,14 @@ mw_status mw_debug_stream_read(int64_t bytes, int32_t width, int32_t iters);
  * written to box_host) when capacity_nodes is below the node count.  The tree buffer is set to 0xFF bytes before the build: a node no
  * kernel wrote comes back NaN.  Waits for the handle's stream.                                                                      */
 mw_status mw_debug_raycast_tree(mw_ocean* o, int32_t frame, int32_t tiled, float* box_host, int64_t capacity_nodes, int32_t geom[3]);
+/* The footprint queries (mw_ocean_query_surface, mw_ocean_query_velocity) on a caller's mesh, without a handle: host arrays vert and norm
+ * [R*R][3], white [R*R][wstride] (wstride 1 or 4, the whitecap in channel 0), vel [R*R][3] or NULL; xz [n][2] -> out [n][8] as
+ * mw_ocean_query_surface writes it and, when vel is given, vout [n][4] as mw_ocean_query_velocity writes it.  The arrays are copied to
+ * the device, the services' own launches run on them (the same kernels, grid rule and iterations mapping), the rows are copied back.
+ * The queries' argument rules with their statuses, and R >= 2, unit_width > 0: MW_EINVAL, before the device is touched.  n == 0
+ * returns MW_OK and reads no array.                                                                                              */
+mw_status mw_debug_query_mesh(int32_t R, float unit_width, const float* vert, const float* norm, const float* white, int32_t wstride,
+                              const float* vel, int32_t mode, int32_t iterations, const float* xz, int64_t n, float* out, float* vout);
 
 #ifdef __cplusplus
 }

@@ -319,6 +319,45 @@ mw_status mw_debug_raycast_tree(mw_ocean* o, int32_t frame, int32_t tiled, float
     return MW_OK;
 }
 
+// test hook: the footprint queries on a caller's mesh.  No handle: the arrays go to the device, the services' own launches
+// (query_surface_launch / query_velocity_launch, surface_services.inc: k_query_surface<SqMesh>, k_query_velocity<SqMesh>) run on the null
+// stream, the rows come back.  The services' argument rules (query_args_check) and the mesh rules a handle guarantees (R >= 2,
+// unit_width > 0, a whitecap stride of 1 or 4), before any device call.
+mw_status mw_debug_query_mesh(int32_t R, float unit_width, const float* vert, const float* norm, const float* white, int32_t wstride,
+                              const float* vel, int32_t mode, int32_t iterations, const float* xz, int64_t n, float* out, float* vout) {
+    const char* who = "mw_debug_query_mesh";
+    if (R < 2 || R > 16384) return fail(MW_EINVAL, who, "R must be in [2, 16384]");  // 3 R^2 stays an int
+    if (!(unit_width > 0.f)) return fail(MW_EINVAL, who, "the mesh needs unit_width > 0");
+    if (wstride != 1 && wstride != 4) return fail(MW_EINVAL, who, "wstride must be 1 or 4");
+    mw_status s = query_args_check(mode, xz, n, iterations, out, who);
+    if (s != MW_OK) return s;
+    if (n == 0) return MW_OK;
+    if (!vert || !norm || !white) return fail(MW_EINVAL, who, "NULL mesh array");
+    if (vel && !vout) return fail(MW_EINVAL, who, "vel without vout");
+    const size_t nv = (size_t)R * R, nn = (size_t)n;
+    DevTmp<float> dvo, dout, dxz, dvel, dwhite, dnorm, dvert;
+    HIP_TRY(dvert.alloc(3 * nv));
+    HIP_TRY(dnorm.alloc(3 * nv));
+    HIP_TRY(dwhite.alloc((size_t)wstride * nv));
+    HIP_TRY(dxz.alloc(2 * nn));
+    HIP_TRY(dout.alloc(8 * nn));
+    HIP_TRY(hipMemcpy(dvert.p, vert, sizeof(float) * 3 * nv, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dnorm.p, norm, sizeof(float) * 3 * nv, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dwhite.p, white, sizeof(float) * wstride * nv, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dxz.p, xz, sizeof(float) * 2 * nn, hipMemcpyHostToDevice));
+    const SqMesh m{dvert.p, dnorm.p, dwhite.p, R, wstride, unit_width, 0.f};
+    if ((s = query_surface_launch(nullptr, m, mode, iterations, dxz.p, n, dout.p)) != MW_OK) return s;
+    if (vel) {
+        HIP_TRY(dvel.alloc(3 * nv));
+        HIP_TRY(dvo.alloc(4 * nn));
+        HIP_TRY(hipMemcpy(dvel.p, vel, sizeof(float) * 3 * nv, hipMemcpyHostToDevice));
+        if ((s = query_velocity_launch(nullptr, m, dvel.p, mode, iterations, dxz.p, n, dvo.p)) != MW_OK) return s;
+        HIP_TRY(hipMemcpy(vout, dvo.p, sizeof(float) * 4 * nn, hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(hipMemcpy(out, dout.p, sizeof(float) * 8 * nn, hipMemcpyDeviceToHost));  // waits for the null stream
+    return MW_OK;
+}
+
 #ifdef MW_TIMING
 mw_status mw_debug_get_stamps(long long* out_host) {
     HIP_TRY(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_stamps), sizeof(long long) * 2 * 64 * 16 * 32));

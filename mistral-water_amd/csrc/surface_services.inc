@@ -81,15 +81,40 @@ struct PointCall {
 // (k_or_displace_mesh, so the vertices are those of mw_ocean_displace_mesh bit for bit) runs into the handle's q_mesh first.
 // This is the one place an SqMesh is filled: a periodic handle (mw_ocean_set_periodic) gets its period here, every other mesh 0, and the
 // launches below pick the kernels' SqTiled instantiations (surface_tiled.h) from m.period != 0.
-static mw_status query_prepare(mw_ocean* o, int32_t frame, int32_t mode, const void* xz, int64_t n, int32_t iterations, const void* out,
-                               const char* who, SqMesh* m) {
-    if (!o) return fail(MW_EINVAL, who, "NULL handle");
+// the argument rules of a point query that need no handle (mw_debug_query_mesh, debug_hooks.inc, applies them to a caller's mesh)
+static mw_status query_args_check(int32_t mode, const void* xz, int64_t n, int32_t iterations, const void* out, const char* who) {
     if (n < 0) return fail(MW_EINVAL, who, "n < 0");
     if (n > 0 && (!xz || !out)) return fail(MW_EINVAL, who, "NULL array");
     if (mode != MW_QUERY_REST && mode != MW_QUERY_WORLD) return fail(MW_EINVAL, who, "mode must be MW_QUERY_REST or MW_QUERY_WORLD");
     if (iterations < 0 || iterations > MW_SQ_MAX_ITERS) return fail(MW_EINVAL, who, "iterations must be in [0,64]");
     // one launch: gridDim.x * blockDim.x must fit in 32 bits
     if (n > (int64_t)UINT32_MAX - 255) return fail(MW_EINVAL, who, "n > 2^32 - 256 (one launch)");
+    return MW_OK;
+}
+// The launches of the two point queries, one lane per point in blocks of 256: the services below and mw_debug_query_mesh both launch here,
+// so the hook runs the services' grid rule, iterations mapping and kernel instantiations.
+static mw_status query_surface_launch(hipStream_t st, const SqMesh& m, int32_t mode, int32_t iterations, const void* pts, int64_t n, void* out) {
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    const float2* xz = static_cast<const float2*>(pts);
+    if (m.period != 0.f) HIP_TRY(tiled_query_surface(grid, st, m, mode, sq_iters(iterations), xz, n, static_cast<float4*>(out)));
+    else k_query_surface<<<grid, block, 0, st>>>(m, mode, sq_iters(iterations), xz, n, static_cast<float4*>(out));
+    HIP_TRY(hipGetLastError());
+    return MW_OK;
+}
+static mw_status query_velocity_launch(hipStream_t st, const SqMesh& m, const float* vel, int32_t mode, int32_t iterations, const void* pts,
+                                       int64_t n, void* out) {
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    const float2* xz = static_cast<const float2*>(pts);
+    if (m.period != 0.f) HIP_TRY(tiled_query_velocity(grid, st, m, vel, mode, sq_iters(iterations), xz, n, static_cast<float4*>(out)));
+    else k_query_velocity<<<grid, block, 0, st>>>(m, vel, mode, sq_iters(iterations), xz, n, static_cast<float4*>(out));
+    HIP_TRY(hipGetLastError());
+    return MW_OK;
+}
+static mw_status query_prepare(mw_ocean* o, int32_t frame, int32_t mode, const void* xz, int64_t n, int32_t iterations, const void* out,
+                               const char* who, SqMesh* m) {
+    if (!o) return fail(MW_EINVAL, who, "NULL handle");
+    const mw_status args = query_args_check(mode, xz, n, iterations, out, who);
+    if (args != MW_OK) return args;
     if (o->sem == MW_SEM_OCEANRENDERER && o->orr.tiles != 1)
         return fail(MW_EINVAL, who, "a batched handle (mw_ocean_create_batch) has no single surface");
     if (o->sem == MW_SEM_FFTMESH && frame != -1) return fail(MW_EINVAL, who, "FFTMesh handles keep one frame (frame = -1)");
@@ -126,14 +151,7 @@ struct QuerySurface : PointCall {
         return query_prepare(o, frame, mode, pts, n, iterations, out, who, m);
     }
     std::array<Arr, 2> arrays() { return {{{&pts, floats(2), IN, 8}, {&out, floats(8), OUT, 16}}}; }
-    mw_status launch(mw_ocean* o, const SqMesh& m) const {
-        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-        const float2* xz = static_cast<const float2*>(pts);
-        if (m.period != 0.f) HIP_TRY(tiled_query_surface(grid, o->stream, m, mode, sq_iters(iterations), xz, n, static_cast<float4*>(out)));
-        else k_query_surface<<<grid, block, 0, o->stream>>>(m, mode, sq_iters(iterations), xz, n, static_cast<float4*>(out));
-        HIP_TRY(hipGetLastError());
-        return MW_OK;
-    }
+    mw_status launch(mw_ocean* o, const SqMesh& m) const { return query_surface_launch(o->stream, m, mode, iterations, pts, n, out); }
 };
 }  // namespace
 
@@ -248,13 +266,7 @@ struct QueryVelocity : PointCall {
     std::array<Arr, 2> arrays() { return {{{&pts, floats(2), IN, 8}, {&out, floats(4), OUT, 16}}}; }
     mw_status launch(mw_ocean* o, const SqMesh& m) const {
         mw_status s = velocity_to_handle(o);
-        if (s != MW_OK) return s;
-        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-        const float2* xz = static_cast<const float2*>(pts);
-        if (m.period != 0.f) HIP_TRY(tiled_query_velocity(grid, o->stream, m, o->vel.vert, mode, sq_iters(iterations), xz, n, static_cast<float4*>(out)));
-        else k_query_velocity<<<grid, block, 0, o->stream>>>(m, o->vel.vert, mode, sq_iters(iterations), xz, n, static_cast<float4*>(out));
-        HIP_TRY(hipGetLastError());
-        return MW_OK;
+        return s != MW_OK ? s : query_velocity_launch(o->stream, m, o->vel.vert, mode, iterations, pts, n, out);
     }
 };
 }  // namespace

@@ -272,6 +272,8 @@ def lib():
         "mw_debug_set_switch": (C.c_int, [C.c_char_p, C.c_int32]),
         "mw_debug_get_switch": (C.c_int32, [C.c_char_p]),
         "mw_debug_raycast_tree": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, i32p]),
+        "mw_debug_query_mesh": (C.c_int, [C.c_int32, C.c_float, f32p, f32p, f32p, C.c_int32, f32p, C.c_int32, C.c_int32, f32p, C.c_int64,
+                                          f32p, f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here = ABI symbol missing: fail loudly
@@ -313,7 +315,7 @@ ABI_SYMBOLS = [
 #: measurement and test hooks (include/mistral_water_hooks.h): exported, but not part of the drop-in boundary
 HOOK_SYMBOLS = ["mw_ocean_profile_kernels", "mw_ocean_profile_kernels_stats", "mw_debug_pass1_time_group", "mw_debug_omega_t", "mw_debug_evaluate_hds", "mw_debug_get_omega", "mw_debug_sincos",
                 "mw_debug_sincos_fast", "mw_debug_stream_read", "mw_debug_wave_transpose4", "mw_debug_set_switch", "mw_debug_get_switch",
-                "mw_debug_raycast_tree"]
+                "mw_debug_raycast_tree", "mw_debug_query_mesh"]
 
 
 def build_id() -> str:

@@ -508,6 +508,21 @@ class Ocean:
         nodes = (4 ** (int(geom[2]) + 1) - 1) // 3
         return box[:nodes].copy(), int(geom[0]), int(geom[1]), int(geom[2])
 
+    @staticmethod
+    def query_mesh(R: int, unit_width: float, vert, norm, white, xz, mode: str = "world", iterations: int = 0, vel=None, wstride: int = 1):
+        """Test hook (mw_debug_query_mesh), no handle: query_surface's kernel on a caller's mesh -- vert and norm [R*R, 3], white [R*R]
+        (stored with `wstride` floats per vertex, the whitecap in channel 0) -> out [n, 8]; with vel [R*R, 3] also query_velocity's
+        kernel -> (out, vout [n, 4])."""
+        f = lambda a, shape: np.ascontiguousarray(np.asarray(a, np.float32).reshape(shape))
+        vert, norm, xz = f(vert, (-1, 3)), f(norm, (-1, 3)), f(xz, (-1, 2))
+        wh = np.ascontiguousarray(np.repeat(f(white, (-1, 1)), int(wstride), 1))
+        vel = None if vel is None else f(vel, (-1, 3))
+        out = np.empty((xz.shape[0], 8), np.float32)
+        vout = None if vel is None else np.empty((xz.shape[0], 4), np.float32)
+        nat.check(nat.lib().mw_debug_query_mesh(int(R), float(unit_width), _p(vert), _p(norm), _p(wh), int(wstride), _p(vel),
+                                                 Ocean._QUERY_MODES[mode], int(iterations), _p(xz), xz.shape[0], _p(out), _p(vout)))
+        return out if vel is None else (out, vout)
+
     # -- floating bodies (mw_ocean_step_bodies) --------------------------------------------------
     def step_bodies(self, hull_xyz, triangles, bodies, mass, dt, substeps: int = 1, density=1000.0, gravity=9.81, linear_drag=0.0,
                     quadratic_drag=0.0, velocity_scale=None, frame: int = -1, iterations: int = 0, return_forces: bool = False):
