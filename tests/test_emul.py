@@ -5,6 +5,7 @@ involved.  (The emulation is test infrastructure; the product has no CPU path.)"
 import numpy as np
 import pytest
 
+import p1_groups
 import workloads
 
 
@@ -275,6 +276,46 @@ def test_pass1_time_group_block_map_is_a_bijection(emul, gx, nsteps, tgroup):
         if slot % tgroup:
             prev = blocks[(slot - 1) * 8 + xcd]
             assert prev == (v[0], v[1] - 1)
+
+
+def test_pass1_time_group_rule():
+    """tests/p1_groups.py against the sizes written out by hand: the default cap of 8, and the switch's caps on 24 steps."""
+    assert p1_groups.plain_grid_sizes() == [1, 11, 13, 17, 19, 23, 29, 31]
+    assert [p1_groups.time_group(ns) for ns in (2, 3, 5, 7, 6, 9, 12, 20, 21, 22, 24, 25, 26, 27, 32)] == [2, 3, 5, 7, 6, 3, 6, 5, 7, 2, 8, 5, 2, 3, 8]
+    assert [p1_groups.time_group(24, cap) for cap in (0, 1, 2, 3, 4, 5, 6, 7, 8)] == [0, 0, 2, 3, 4, 4, 6, 6, 8]
+    assert [p1_groups.time_group(21, cap) for cap in (0, 2, 3, 6, 7, 8)] == [0, 0, 3, 3, 7, 7]
+    assert p1_groups.group_sizes(24) == [2, 3, 4, 6, 8] and p1_groups.group_sizes(12) == [2, 3, 4, 6] and p1_groups.group_sizes(31) == []
+    assert all(p1_groups.time_group(ns, cap) == 0 for ns in range(1, 33) for cap in (-1, 0, 1))
+
+
+@pytest.mark.parametrize("gx", [17, 33, 65, 129, 257, 513, 1025])
+def test_pass1_block_map_every_batch_size_and_group(emul, gx):
+    """The 1-D grid of pass 1 at every FFT size (gx = N / 4 + 1 column jobs, 64^2 .. 4096^2), every batch size 2 .. 32 and every group size
+    the rule returns for it under the caps 2 .. 8: the grid is p1_grid_blocks long, its live blocks are a bijection onto (column job,
+    step), fewer than 8 * tgroup blocks are padding, and the steps of a group sit in consecutive slots of one XCD."""
+    ncases = 0
+    for nsteps in range(2, p1_groups.MAX_BATCH + 1):
+        for tgroup in p1_groups.group_sizes(nsteps):
+            assert 2 <= tgroup <= 8 and nsteps % tgroup == 0
+            blocks = emul.p1_block_map(gx, nsteps, tgroup)
+            nb = len(blocks)
+            assert nb == emul.L.emul_p1_grid_blocks(gx, nsteps, tgroup) == -(-gx * (nsteps // tgroup) // 8) * 8 * tgroup, (nsteps, tgroup)
+            live = np.array([b is not None for b in blocks])
+            jb = np.array([b[0] if b is not None else -1 for b in blocks])
+            st = np.array([b[1] if b is not None else -1 for b in blocks])
+            assert int(live.sum()) == gx * nsteps and nb - gx * nsteps < 8 * tgroup, (nsteps, tgroup)
+            assert ((jb[live] >= 0) & (jb[live] < gx) & (st[live] >= 0) & (st[live] < nsteps)).all(), (nsteps, tgroup)
+            assert np.unique(jb[live] * nsteps + st[live]).size == gx * nsteps, (nsteps, tgroup)      # onto, hence one to one
+            # block b runs on XCD b % 8 in slot b // 8: a slot that does not open a group continues the column job of the slot before
+            # it on the same XCD with the next step (a padding block continues a padding block)
+            b = np.arange(nb)
+            cont = (b // 8) % tgroup != 0
+            prev = b[cont] - 8
+            assert (live[b[cont]] == live[prev]).all(), (nsteps, tgroup)
+            both = live[b[cont]]
+            assert (jb[b[cont]][both] == jb[prev][both]).all() and (st[b[cont]][both] == st[prev][both] + 1).all(), (nsteps, tgroup)
+            ncases += 1
+    assert ncases == 53      # sum over nsteps = 2 .. 32 of its divisors in [2, 8]
 
 
 def _pond_cases(oracle):

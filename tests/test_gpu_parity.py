@@ -370,7 +370,8 @@ def test_batched_device_steps_equal_single_steps(mw, oracle):
             v, n, c = o.evaluate(t)
             assert (dv[k].cpu().numpy() == v).all() and (dn[k].cpu().numpy() == n).all()
             assert (dw[k].cpu().numpy() == c[:, 0]).all()
-        # every pass-1 time-group size (p1_block_map): 24 -> groups of 8, 12 -> 4, 6 -> 2, 7 -> plain 2-D grid
+        # pass-1 time groups (p1_block_map; the largest divisor of the batch size up to 8): 24 -> groups of 8, 12 -> 6, 6 -> 6, 7 -> 7.  (The plain
+        # 2-D grid runs for 1, 11, 13, 17, 19, 23, 29 and 31 steps only: tests/test_fftmesh_batch_gpu.py.)
         dv = torch.empty((24, NN, 3), dtype=torch.float32, device="cuda")
         dn = torch.empty((24, NN, 3), dtype=torch.float32, device="cuda")
         dw = torch.empty((24, NN), dtype=torch.float32, device="cuda")
@@ -390,7 +391,8 @@ def test_batched_device_steps_equal_single_steps(mw, oracle):
 
 @pytest.mark.parametrize("N", [1024, 2048])
 def test_every_kind_of_batch_size_equals_single_steps(mw, oracle, N):
-    """Enqueues of 2, 3, 5, 16, 31 and 32 steps (prime sizes take the plain 2-D grid of pass 1, the others time groups of 2 .. 8) at the
+    """Enqueues of 2, 3, 5, 16, 31 and 32 steps (31 takes the plain 2-D grid of pass 1, as every size without a divisor in 2 .. 8 does: 1, 11,
+    13, 17, 19, 23, 29, 31; the others run time groups -- 2, 3 and 5 are their own group size, 16 and 32 group by 8) at the
     headline's grid -- where a single step runs the frame plan's kernels and a batch the sequential-halo kernel with the in-wave exchange --
     and at 2048^2: first and last step of every batch == the same time evaluated alone, bit for bit."""
     import torch
