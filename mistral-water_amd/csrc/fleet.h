@@ -8,6 +8,11 @@
 // single-hull counterpart calls: hull_vertex, hull_triangle, hull_chunk_partial, hull_body_sum, hull_row, body_integrate.  The order
 // of a row's sum is hull_forces.h's alone; k_fleet_step repeats only k_bodies_step's phases around those calls.
 //
+// k_fleet_step is also the one-launch kernel of every strict single-hull call: mw_ocean_step_bodies on a periodic handle and
+// mw_ocean_step_moored's one-launch plan run it on a one-hull table (surface_services.inc: hull_step_launch), the second with the
+// body's mooring lines (moorings.h).  The substep loop therefore stands in two places, here and in k_bodies_step, which is the one
+// kernel that cannot share it (rigid_bodies.h).
+//
 // The table travels by value in the kernel arguments (FleetTable, under 2 KiB): nothing to upload, so a second call enqueued before
 // the first has run reads its own table.  A work index (instance vertex, (body, chunk) or body) maps to (hull, body, item) through
 // the per-hull starts of that space: fleet_map, a loop over the hulls with a uniform index and compare-and-select, so that a lane-varying
@@ -17,7 +22,8 @@
 //   k_fleet_triangles  one 256-lane workgroup per (body, chunk) over all hulls   (k_hull_triangles)
 //   k_fleet_reduce     one wave per body                                         (k_hull_reduce)
 //   k_fleet_integrate  one lane per body, with the wrench                        (k_bodies_integrate)
-//   k_fleet_step       one 256-lane workgroup per body runs every substep        (k_bodies_step; SqTiled only, see below)
+//   k_fleet_step       one 256-lane workgroup per body runs every substep        (k_bodies_step; SqTiled only, see below), with
+//                      the external wrench and the mooring lines, each optional
 //
 // Operand order.  The SqTiled instantiations are compiled without contraction (surface_tiled.hip), where equal operations give equal
 // bits.  The SqMesh instantiations are compiled with contraction, and there the compiler fuses the FIRST product of a sum of two
@@ -34,7 +40,7 @@
 //
 // Everything but the __global__ wrappers is MW_HD: tests/fleet_shim.cpp compiles the same functions with g++.
 #pragma once
-#include "rigid_bodies.h"
+#include "moorings.h"  // the lines of k_fleet_step; rigid_bodies.h: the pushed row
 
 namespace mw {
 
@@ -117,30 +123,6 @@ MW_HD FleetItem fleet_map(const FleetTable& t, int space, int w) {
     it.body = (int)(local / per);
     it.item = (int)(local - (unsigned)it.body * per);
     return it;
-}
-
-// a usable wrench row (Fx Fy Fz _ tx ty tz _): the six entries finite
-MW_HD bool fleet_wrench_valid(const float wrench[8]) {
-    for (int k = 0; k < 3; k++)
-        if (!(fabsf(wrench[k]) <= 3.4e38f && fabsf(wrench[4 + k]) <= 3.4e38f)) return false;
-    return true;
-}
-
-// The row steps 2 and 3 of the integrator see: the water row, and when wrench != nullptr the external force and torque added to it,
-// F[k] + wrench[k] and tau[k] + wrench[4 + k], one float32 add each.  wrench == nullptr: the water row itself, no addition.
-MW_HD void fleet_pushed_row(const float row[8], const float* wrench, float r[8]) {
-    for (int k = 0; k < 8; k++) r[k] = row[k];
-    if (!wrench) return;
-    for (int k = 0; k < 3; k++) {
-        r[k] = row[k] + wrench[k];
-        r[4 + k] = row[4 + k] + wrench[4 + k];
-    }
-}
-// One substep of a body under its water row and its wrench (nullptr: none, and then this is body_integrate on the row).
-MW_HD bool fleet_integrate(float body[16], const float row[8], const float mass[8], const float* wrench, float g, float h) {
-    float r[8];
-    fleet_pushed_row(row, wrench, r);
-    return body_integrate(body, r, mass, g, h);
 }
 
 #if defined(__HIPCC__)
@@ -255,13 +237,20 @@ __global__ __launch_bounds__(256) void k_fleet_integrate(FleetArgsT<Mesh> a) {
     if (a.last && a.out) hull_store_row(a.out + 2 * b, row);
 }
 
-// One-launch plan: one 256-lane workgroup per body of the table runs every substep (k_bodies_step per workgroup, with the wrench).
+// One-launch plan: one 256-lane workgroup per body of the table runs every substep (k_bodies_step per workgroup), with the call's
+// optional parts: the external wrench (a.wrench) and K mooring slots per body (lines [total_bodies][K][3], K == 0: none; tension
+// [total_bodies][K] or nullptr).  The slots are staged once in LDS, and the tensions of the latest substep wait there for the end of the
+// call.  Lane 0 ends a substep in one expression for every combination: the line wrench M of the state the row was evaluated at
+// (mooring_wrench), then (F + W) + M, each add only when its part exists (fleet_pushed_row, fleet_integrate) -- moored_integrate on the
+// row pushed by W.  No entry point passes a wrench and lines together.
 // Dynamic LDS: the largest bodies_step_lds of the table's hulls; each workgroup lays out its own hull's slab and partials in it.
 template <typename Mesh>
-__global__ __launch_bounds__(MW_HULL_CHUNK) void k_fleet_step(FleetArgsT<Mesh> a) {
+__global__ __launch_bounds__(MW_HULL_CHUNK) void k_fleet_step(FleetArgsT<Mesh> a, const float4* lines, float* tension, int K) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ float pose[16];
     __shared__ int stop;
+    __shared__ __attribute__((aligned(16))) float slots[MW_MOORING_LINES * MW_MOORING_SLOT];
+    __shared__ float tens[MW_MOORING_LINES];
     const FleetItem it = fleet_map(a.t, MW_FLEET_BODIES, (int)blockIdx.x);
     const int nverts = it.row.nverts, ntris = it.row.ntris, nchunks = it.row.nchunks;
     const float* hull = a.hull + 3 * (size_t)it.row.vert_first;
@@ -275,14 +264,20 @@ __global__ __launch_bounds__(MW_HULL_CHUNK) void k_fleet_step(FleetArgsT<Mesh> a
     float body[16], mass[8], row[8], wr[8];
     hull_load_body(a.bodies + 4 * b, body);
     hull_load_row(a.mass + 2 * b, mass);
+    if (K > 0) {  // uniform over the launch
+        if (l < 3 * K) reinterpret_cast<float4*>(slots)[l] = lines[3 * b * K + l];
+        __syncthreads();
+    }
     bool valid = body_mass_valid(mass);
     if (a.wrench) {
         hull_load_row(a.wrench + 2 * b, wr);
         valid = valid && fleet_wrench_valid(wr);
     }
+    for (int s = 0; s < K; s++) valid = valid && mooring_slot_valid(slots + MW_MOORING_SLOT * s);
     if (!valid) {  // uniform over the workgroup
         for (int k = 0; k < 8; k++) row[k] = NAN;
         if (l == 0 && a.out) hull_store_row(a.out + 2 * b, row);
+        if (l < K && tension) tension[b * K + l] = NAN;
         return;
     }
     for (int s = 0; s < a.substeps; s++) {
@@ -306,13 +301,15 @@ __global__ __launch_bounds__(MW_HULL_CHUNK) void k_fleet_step(FleetArgsT<Mesh> a
             if (t < nverts) res = hull_max(res, vs[8 * (size_t)t + 7]);
             hull_chunk_partial(acc, res, part + 2 * c);
         }
-        // the row (k_hull_reduce) and the integration, in wave 0
+        // the row (k_hull_reduce), the line wrench and the integration, in wave 0
         if (l < 64) {
             float acc[7], res;
             hull_body_sum(part, 0, nchunks, l, acc, res);
             if (l == 0) {
+                float pushed[8];
                 hull_row(acc, res, row);
-                const bool ok = a.wrench ? fleet_integrate(body, row, mass, wr, it.row.g, a.dt) : body_integrate(body, row, mass, it.row.g, a.dt);
+                fleet_pushed_row(row, a.wrench ? wr : nullptr, pushed);
+                const bool ok = moored_integrate(body, pushed, mass, slots, K, it.row.g, a.dt, tens);
                 for (int k = 0; k < 16; k++) pose[k] = body[k];
                 stop = ok ? 0 : 1;
             }
@@ -326,6 +323,7 @@ __global__ __launch_bounds__(MW_HULL_CHUNK) void k_fleet_step(FleetArgsT<Mesh> a
         for (int k = 0; k < 4; k++) a.bodies[4 * b + k] = make_float4(body[4 * k], body[4 * k + 1], body[4 * k + 2], body[4 * k + 3]);
         if (a.out) hull_store_row(a.out + 2 * b, row);
     }
+    if (l < K && tension) tension[b * K + l] = tens[l];  // lane 0 wrote tens before the loop's last barrier
 }
 #endif
 

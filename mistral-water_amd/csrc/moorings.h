@@ -15,7 +15,7 @@
 //   6. F = T e,  tau = d x F
 // The mooring wrench M = (F _ tau _) is the sum of the taut slots' (F, tau) in slot order, starting from the first taut slot's own
 // value, not from zero.  With at least one slot taut, steps 2 and 3 of the integrator (rigid_bodies.h) see F[k] + M[k] and
-// tau[k] + M[4 + k], one float32 add each -- fleet_pushed_row (fleet.h) with M as the wrench.  With no slot taut the water row is used as
+// tau[k] + M[4 + k], one float32 add each -- fleet_pushed_row (rigid_bodies.h) with M as the wrench.  With no slot taut the water row is used as
 // it is, no addition (adding a zero would turn a -0 into +0): the substep is body_integrate on the bare row.
 // A slot is invalid when one of its nine used floats is not finite or L0, k or c is negative; the three padding floats are not read.
 // One invalid slot makes the body's call invalid, like an invalid mass row.
@@ -24,19 +24,20 @@
 // (k_total the summed stiffness of the lines pulling along it).  Nothing here checks that.
 //
 // Strict float32: every function below sets its own `fp contract(off)`, so its multiplies and adds keep their own rounding in whichever
-// translation unit it is inlined into, and the bits are those of tests/moorings_shim.cpp (g++ -ffp-contract=off).  The kernels stand in
-// surface_tiled.hip, which compiles the functions they share with the hull family (hull_rotation, body_integrate) strictly as well.
+// translation unit it is inlined into, and the bits are those of tests/moorings_shim.cpp (g++ -ffp-contract=off).  The kernels that run them stand
+// in surface_tiled.hip, which compiles the functions they share with the hull family (hull_rotation, body_integrate) strictly as well.
 //
 // Two plans with the same bits (surface_services.inc: moored_launch):
 //   per substep   hull_launch's kernels, then k_moored_integrate (one lane per body: the slots as float4, the wrench, the pushed row,
-//                 body_integrate), once per substep
-//   one launch    k_moored_step: k_bodies_step's loop (one workgroup per body, slab and partials in LDS, only workgroup barriers) with
-//                 the body's slots staged once in LDS and lane 0 computing the wrench beside the integration.  A kernel of its own, as
-//                 k_fleet_step is: k_bodies_step built from a routine shared with another kernel lost its bits.
+//                 body_integrate), once per substep.  k_rigged_integrate (rigging.h) without targets computes the same bits and was
+//                 measured in its place: 3.5-6 % slower per call, the target's four 16-byte loads per slot
+//   one launch    k_fleet_step (fleet.h) on a one-hull table, with the body's slots staged once in LDS and lane 0 computing the
+//                 wrench beside the integration (moored_integrate).  Strict kernels can share the substep loop; the one kernel
+//                 that cannot is the contracted k_bodies_step<SqMesh> (rigid_bodies.h).
 //
-// Everything but the __global__ wrappers is MW_HD: tests/moorings_shim.cpp compiles the same functions with g++.
+// Everything but the __global__ wrapper is MW_HD: tests/moorings_shim.cpp compiles the same functions with g++.
 #pragma once
-#include "fleet.h"  // fleet_integrate: the pushed row
+#include "rigid_bodies.h"  // fleet_integrate: the pushed row
 
 namespace mw {
 
@@ -58,7 +59,7 @@ MW_HD bool mooring_slot_valid(const float s[MW_MOORING_SLOT]) {
 
 // Steps 1-6 of one slot for the body (p _ q v _ w _) with R = hull_rotation(q).  Returns true when the line is taut, with its pull in
 // F and its torque about p in tau; *T is the tension, 0 for an empty or slack slot (F and tau then hold nothing of use).  Written
-// without branches -- every step is computed and the answer selected -- so that lane 0 of k_moored_step carries no nest of saved
+// without branches -- every step is computed and the answer selected -- so that lane 0 of k_fleet_step carries no nest of saved
 // execution masks through its slot loop; a slack line's r / l may divide by zero, and its quotient is dropped unread.
 MW_HD bool mooring_slot(const float body[16], const float R[9], const float s[MW_MOORING_SLOT], float F[3], float tau[3], float* T) {
     MW_MOORING_STRICT
@@ -147,7 +148,8 @@ MW_HD bool moored_integrate(float body[16], const float row[8], const float mass
     return ok;
 }
 
-// LDS k_moored_step takes beyond k_bodies_step's: the staged slots and their tensions
+// LDS k_fleet_step holds for a call's lines beyond k_bodies_step's: the staged slots and their tensions.  moored_one_launch
+// (surface_services.inc) counts it as the plan rule of the moored call.
 #define MW_MOORED_LDS_STATIC ((MW_MOORING_LINES * MW_MOORING_SLOT + MW_MOORING_LINES) * sizeof(float))
 
 #if defined(__HIPCC__)
@@ -163,7 +165,7 @@ struct MooredArgs {
     int last;             // this is the call's last substep (write out and tension)
 };
 
-#if defined(MW_MOORING_KERNELS)  // one translation unit holds the kernels (surface_tiled.hip): k_moored_integrate is no template
+#if defined(MW_STRICT_LINE_KERNELS)  // one translation unit holds the line kernels (surface_tiled.hip): k_moored_integrate is no template
 // Per-substep plan, after hull_launch: one lane per body.  The slots come in as three 16-byte loads each and are summed as they come,
 // so no slot array is indexed at run time.
 __global__ __launch_bounds__(256) void k_moored_integrate(MooredArgs a) {
@@ -195,89 +197,7 @@ __global__ __launch_bounds__(256) void k_moored_integrate(MooredArgs a) {
     }
     if (a.last && a.out) hull_store_row(a.out + 2 * b, row);
 }
-
-template <typename Mesh>
-struct MooredStepArgsT {
-    BodiesArgsT<Mesh> b;  // the step-bodies arguments of the call
-    const float4* lines;  // [nbodies][K][3]
-    float* tension;       // [nbodies][K] or nullptr
-    int K;
-};
-
-// One-launch plan: k_bodies_step's loop with the body's slots staged once in LDS; lane 0 computes the wrench of the state the row was
-// evaluated at and integrates under the pushed row.  The tensions of the latest substep wait in LDS for the end of the call.
-template <typename Mesh>
-__global__ __launch_bounds__(MW_HULL_CHUNK) void k_moored_step(MooredStepArgsT<Mesh> ma) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ float pose[16];
-    __shared__ int stop;
-    __shared__ __attribute__((aligned(16))) float slots[MW_MOORING_LINES * MW_MOORING_SLOT];
-    __shared__ float tens[MW_MOORING_LINES];
-    const BodiesArgsT<Mesh>& a = ma.b;
-    const HullArgsT<Mesh>& ha = a.h;
-    float4* slab = reinterpret_cast<float4*>(smem);  // [nverts][2]
-    float4* part = slab + 2 * (size_t)ha.nverts;     // [nchunks][2]
-    const float* vs = reinterpret_cast<const float*>(slab);
-    const int l = threadIdx.x;
-    const int64_t b = blockIdx.x;
-    const int K = ma.K;
-    float body[16], mass[8], row[8];
-    hull_load_body(a.bodies + 4 * b, body);
-    hull_load_row(a.mass + 2 * b, mass);
-    if (l < 3 * K) reinterpret_cast<float4*>(slots)[l] = ma.lines[3 * (size_t)b * K + l];
-    __syncthreads();
-    bool valid = body_mass_valid(mass);
-    for (int s = 0; s < K; s++) valid = valid && mooring_slot_valid(slots + MW_MOORING_SLOT * s);
-    if (!valid) {  // uniform over the workgroup
-        for (int k = 0; k < 8; k++) row[k] = NAN;
-        if (l == 0 && a.out) hull_store_row(a.out + 2 * b, row);
-        if (l < K && ma.tension) ma.tension[(size_t)b * K + l] = NAN;
-        return;
-    }
-    for (int s = 0; s < a.substeps; s++) {
-        // vertices (k_hull_vertices)
-        for (int v = l; v < ha.nverts; v += MW_HULL_CHUNK) {
-            float h[3], sl[8];
-            for (int c = 0; c < 3; c++) h[c] = ha.hull[3 * (size_t)v + c];
-            hull_vertex(ha.m, ha.vel, ha.vscale, ha.iters, body, h, sl);
-            hull_store_row(slab + 2 * v, sl);
-        }
-        __syncthreads();
-        // triangles (k_hull_triangles), chunk by chunk
-        for (int c = 0; c < ha.nchunks; c++) {
-            float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            float res = 0.f;
-            const int t = c * MW_HULL_CHUNK + l;
-            if (t < ha.ntris) {
-                const int idx[3] = {ha.tris[3 * (size_t)t], ha.tris[3 * (size_t)t + 1], ha.tris[3 * (size_t)t + 2]};
-                if (!hull_triangle(idx, ha.nverts, vs, body, ha.cf, acc)) res = NAN;
-            }
-            if (t < ha.nverts) res = hull_max(res, vs[8 * (size_t)t + 7]);
-            hull_chunk_partial(acc, res, part + 2 * c);
-        }
-        // the row (k_hull_reduce), the mooring wrench and the integration, in wave 0
-        if (l < 64) {
-            float acc[7], res;
-            hull_body_sum(part, 0, ha.nchunks, l, acc, res);
-            if (l == 0) {
-                hull_row(acc, res, row);
-                const bool ok = moored_integrate(body, row, mass, slots, K, a.g, a.dt, tens);
-                for (int k = 0; k < 16; k++) pose[k] = body[k];
-                stop = ok ? 0 : 1;
-            }
-        }
-        __syncthreads();
-        for (int k = 0; k < 16; k++) body[k] = pose[k];
-        if (stop) break;  // a NaN row: the state stays, and so would every later row
-        __syncthreads();  // pose and stop are written again by the next substep
-    }
-    if (l == 0) {
-        for (int k = 0; k < 4; k++) a.bodies[4 * b + k] = make_float4(body[4 * k], body[4 * k + 1], body[4 * k + 2], body[4 * k + 3]);
-        if (a.out) hull_store_row(a.out + 2 * b, row);
-    }
-    if (l < K && ma.tension) ma.tension[(size_t)b * K + l] = tens[l];  // lane 0 wrote tens before the loop's last barrier
-}
-#endif  // MW_MOORING_KERNELS
+#endif  // MW_STRICT_LINE_KERNELS
 #endif
 
 }  // namespace mw

@@ -20,7 +20,7 @@ enum Switch {
     SW_DIRECT_CZT,        // 1: non-FFT grids by chirp-z (N <= 2048); 0: the MFMA GEMM form (read when a handle is CREATED)
     SW_TILES_FORCE_RCCL,  // 1: mw_tiles_gather sends every tile through ncclSend / ncclRecv, the root's own included
     SW_OR_PACKED,         // 1: OceanRenderer planar-texture calls with a symmetric phase run two transforms per frame; 0: always three
-    SW_BODIES_PLAN,       // mw_ocean_step_bodies: 1 one launch (k_bodies_step) where the hull fits in LDS; 0 per substep; -1 the built-in rule
+    SW_BODIES_PLAN,       // mw_ocean_step_bodies: 1 one launch (k_bodies_step; the strict k_fleet_step on a periodic handle) where the hull fits in LDS; 0 per substep; -1 the built-in rule
     SW_RC_BLOCK,          // mw_ocean_raycast: leaf block side of the hierarchy in cells; <= 0 the built-in MW_RC_DEFAULT_BLOCK
     SW_COUNT
 };

@@ -26,7 +26,7 @@
 // Strict float32 as moorings.h: every function sets its own `fp contract(off)`, the kernel stands in surface_tiled.hip, and the bits
 // are those of tests/rig_shim.cpp (g++ -ffp-contract=off).  Everything but the __global__ wrapper is MW_HD.
 #pragma once
-#include "moorings.h"
+#include "fleet.h"  // the hull table; moorings.h: the slots
 
 namespace mw {
 
@@ -183,7 +183,7 @@ struct RigArgs {
     FleetTable t;            // every hull of the call: total[MW_FLEET_BODIES] == total_bodies
 };
 
-#if defined(MW_MOORING_KERNELS)
+#if defined(MW_STRICT_LINE_KERNELS)
 // One lane per body of the whole fleet.  The slots come in as three 16-byte loads each, a tow slot's target as four, and are summed as
 // they come.  Reads bodies from snap only and writes them to next only.
 __global__ __launch_bounds__(256) void k_rigged_integrate(RigArgs a) {
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(256) void k_rigged_integrate(RigArgs a) {
         a.next[4 * (size_t)b + k] = moved ? make_float4(body[4 * k], body[4 * k + 1], body[4 * k + 2], body[4 * k + 3]) : keep[k];
     if (a.last && a.out) hull_store_row(a.out + 2 * (size_t)b, row);
 }
-#endif  // MW_MOORING_KERNELS
+#endif  // MW_STRICT_LINE_KERNELS
 #endif
 
 }  // namespace mw

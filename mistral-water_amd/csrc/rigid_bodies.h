@@ -18,9 +18,12 @@
 //   one launch    k_bodies_step: one workgroup per body runs every substep; the vertex slab (32 B per vertex), the per-chunk partial
 //                 rows and the pose stay in LDS.  Its phases call what k_hull_vertices, k_hull_triangles and k_hull_reduce call
 //                 (hull_vertex, hull_triangle, hull_chunk_partial, hull_body_sum, hull_row), so its rows are hull_launch's bit for
-//                 bit.  k_fleet_step (fleet.h) is the same loop with the hull read from a table and a wrench; the two stay apart
-//                 because k_bodies_step<SqMesh> built from a routine shared with it lost those bits.
-//                 Only workgroup barriers: no flags, no atomics, nothing between workgroups.
+//                 bit.  Only workgroup barriers: no flags, no atomics, nothing between workgroups.
+//                 k_bodies_step is instantiated for SqMesh alone, with contraction (mistral_water.hip).  It is the one kernel that
+//                 cannot share its loop: built from a routine shared with k_fleet_step it lost its bits, because the compiler
+//                 fused another operand.  Strict kernels can share it, and do: a periodic handle runs
+//                 k_fleet_step (fleet.h), the same loop with the hull read from a one-hull table, where equal operations give
+//                 equal bits.
 //
 // Everything but the __global__ wrappers is MW_HD: tests/bodies_shim.cpp compiles the same functions with g++.
 #pragma once
@@ -97,6 +100,31 @@ MW_HD bool body_integrate(float body[16], const float row[8], const float mass[8
     const float inv = 1.f / sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2] + n[3] * n[3]);
     for (int k = 0; k < 4; k++) q[k] = n[k] * inv;
     return true;
+}
+
+// The pushed row: a body under its water row and a wrench from outside the water -- the external wrench of a fleet call (fleet.h) or
+// the wrench of the body's lines (rigging.h).  It stands here, below the integrator, because every header built on this one pushes it.
+// a usable wrench row (Fx Fy Fz _ tx ty tz _): the six entries finite
+MW_HD bool fleet_wrench_valid(const float wrench[8]) {
+    for (int k = 0; k < 3; k++)
+        if (!(fabsf(wrench[k]) <= 3.4e38f && fabsf(wrench[4 + k]) <= 3.4e38f)) return false;
+    return true;
+}
+// The row steps 2 and 3 of the integrator see: the water row, and when wrench != nullptr the external force and torque added to it,
+// F[k] + wrench[k] and tau[k] + wrench[4 + k], one float32 add each.  wrench == nullptr: the water row itself, no addition.
+MW_HD void fleet_pushed_row(const float row[8], const float* wrench, float r[8]) {
+    for (int k = 0; k < 8; k++) r[k] = row[k];
+    if (!wrench) return;
+    for (int k = 0; k < 3; k++) {
+        r[k] = row[k] + wrench[k];
+        r[4 + k] = row[4 + k] + wrench[4 + k];
+    }
+}
+// One substep of a body under its water row and its wrench (nullptr: none, and then this is body_integrate on the row).
+MW_HD bool fleet_integrate(float body[16], const float row[8], const float mass[8], const float* wrench, float g, float h) {
+    float r[8];
+    fleet_pushed_row(row, wrench, r);
+    return body_integrate(body, r, mass, g, h);
 }
 
 // LDS of k_bodies_step beyond its static arrays: the vertex slab and the chunk partials, 32 B each

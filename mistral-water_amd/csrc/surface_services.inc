@@ -443,7 +443,7 @@ static mw_status bodies_prepare(mw_ocean* o, int32_t frame, const HullCall& c, c
 // The plan rule (MW_BODIES_PLAN = -1), DESIGN.md section 7e: one launch for hulls of at most 3 chunks (768 triangles and vertices),
 // per substep above.  Measured: 1024 icospheres (2 chunks) 0.49x the per-substep time; 64 barges (22 chunks) 1.8x.
 static bool bodies_one_launch_rule(int nchunks) { return nchunks < 4; }
-// a hull steps in one launch (k_bodies_step, k_fleet_step): its slab and partials fit in LDS, and the switch asks for it or the rule does
+// a hull steps in one launch (k_bodies_step on the one footprint, k_fleet_step on a periodic handle): its slab and partials fit in LDS, and the switch asks for it or the rule does
 static bool bodies_one_launch(int nverts, int nchunks) {
     const int plan = sw(SW_BODIES_PLAN);
     return bodies_step_lds(nverts, nchunks) <= MW_BODIES_LDS_MAX && (plan == 1 || (plan < 0 && bodies_one_launch_rule(nchunks)));
@@ -467,6 +467,30 @@ static BodiesArgs bodies_args(const mw_ocean* o, const HullPlan& p, const HullCa
     a.substeps = c.substeps;
     return a;
 }
+// The call as a one-hull fleet table with the plan's coefficients: what the strict one-launch kernel shared with the fleets reads (fleet.h)
+static FleetTable hull_table(const HullPlan& p, const HullCall& c) {
+    const int32_t one[MW_FLEET_NHULL] = {0, c.nverts, 0, c.ntris, c.nbodies};
+    FleetTable t{};
+    fleet_table(one, 1, 1u, &t);
+    t.hull[0].cf = p.cf; t.hull[0].g = p.g; t.hull[0].vscale = p.vscale;
+    return t;
+}
+// The one-launch plan of a single-hull stepping call on a periodic handle: k_fleet_step over the call's one-hull table, without a
+// wrench, with the call's lines when it is moored (K == 0 otherwise)
+static mw_status hull_step_launch(mw_ocean* o, const HullPlan& p, const HullCall& c) {
+    const HullArgs h = hull_args(o, p, c);  // the surface, the velocity rule and the geometry are the hull call's
+    FleetArgs a{};
+    a.m = h.m; a.vel = h.vel; a.iters = h.iters; a.hull = h.hull; a.tris = h.tris;
+    a.bodies = static_cast<float4*>(c.bodies);
+    a.mass = static_cast<const float4*>(c.mass);
+    a.out = static_cast<float4*>(c.out);
+    a.dt = c.dt / (float)c.substeps;
+    a.substeps = c.substeps;
+    a.t = hull_table(p, c);
+    HIP_TRY(tiled_fleet_step(dim3((unsigned)c.nbodies), bodies_step_lds(c.nverts, hull_chunks(c)), MW_BODIES_LDS_MAX, o->stream, a,
+                             static_cast<const float4*>(c.lines), c.K, static_cast<float*>(c.tension)));
+    return MW_OK;
+}
 extern "C++" {
 // The per-substep plan of every stepping call, on the handle's stream: the handle's row buffer holds nrows rows; per substep rows(buf)
 // launches the hull forces of the bodies' current state into it and integrate(buf, last) steps the bodies by them, last on the final
@@ -483,22 +507,19 @@ static mw_status run_substeps(mw_ocean* o, int64_t nrows, int substeps, Rows row
 }  // extern "C++"
 
 // every substep of the call on the handle's stream (nbodies > 0): the water once (hull_water: the surface is frozen for the call), then
-// one k_bodies_step launch, or per substep hull_launch and k_bodies_integrate, the strict build where hull_launch's rows are
-// (hull_strict).  Draught on: there is no one-launch plan on the column and MW_BODIES_PLAN is not read.
+// one launch (k_fleet_step on a periodic handle, hull_step_launch; the contracted k_bodies_step on the one footprint), or per substep
+// hull_launch and k_bodies_integrate, the strict build where hull_launch's rows are (hull_strict).  Draught on: there is no one-launch
+// plan on the column and MW_BODIES_PLAN is not read.
 static mw_status bodies_launch(mw_ocean* o, const HullPlan& p, const HullCall& c) {
     const int nchunks = hull_chunks(c);
     mw_status s = hull_water(o, p);
     if (s != MW_OK) return s;
     BodiesArgs a = bodies_args(o, p, c);
     if (!o->draught && bodies_one_launch(c.nverts, nchunks)) {
-        const size_t lds = bodies_step_lds(c.nverts, nchunks);
-        if (a.h.m.period != 0.f) {
-            HIP_TRY(tiled_bodies_step(dim3((unsigned)c.nbodies), lds, MW_BODIES_LDS_MAX, o->stream, a));
-            return MW_OK;
-        }
+        if (p.m.period != 0.f) return hull_step_launch(o, p, c);
         static AttrOnce attr;
         HIP_TRY(attr.set(reinterpret_cast<const void*>(k_bodies_step<SqMesh>), MW_BODIES_LDS_MAX));
-        k_bodies_step<<<dim3((unsigned)c.nbodies), dim3(MW_HULL_CHUNK), lds, o->stream>>>(a);
+        k_bodies_step<<<dim3((unsigned)c.nbodies), dim3(MW_HULL_CHUNK), bodies_step_lds(c.nverts, nchunks), o->stream>>>(a);
         HIP_TRY(hipGetLastError());
         return MW_OK;
     }
@@ -525,22 +546,19 @@ static mw_status moored_prepare(mw_ocean* o, int32_t frame, const HullCall& c, c
     if (c.nbodies > 0 && !c.lines) return fail(MW_EINVAL, who, "NULL lines");
     return bodies_prepare(o, frame, c, who, p);
 }
-// the one-launch plan takes the hull when step bodies would (bodies_one_launch) and k_moored_step's static LDS fits beside it
+// The one-launch plan takes the hull when step bodies would (bodies_one_launch) and the slots and tensions fit beside its slab in the
+// 1 KiB MW_BODIES_LDS_MAX leaves free.  A plan rule, not a fit rule: k_fleet_step holds that LDS for every call, so the launch would
+// fit up to step bodies' own edge; the rule keeps the plan of every hull size where it was (the edge at 5055 / 5056 vertices).
 static bool moored_one_launch(int nverts, int nchunks) {
     return bodies_one_launch(nverts, nchunks) && bodies_step_lds(nverts, nchunks) + MW_MOORED_LDS_STATIC <= MW_BODIES_LDS_MAX;
 }
-// every substep of the call on the handle's stream (nbodies > 0), as bodies_launch: the water once, then one k_moored_step launch (a
-// periodic handle without draught whose hull qualifies; MW_BODIES_PLAN is honoured) or per substep hull_launch and k_moored_integrate.
-// A non-periodic handle and draught always step per substep, as the fleets and draught do.
+// every substep of the call on the handle's stream (nbodies > 0), as bodies_launch: the water once, then one k_fleet_step launch with
+// the lines (hull_step_launch: a periodic handle without draught whose hull qualifies; MW_BODIES_PLAN is honoured) or per substep
+// hull_launch and k_moored_integrate.  A non-periodic handle and draught always step per substep, as the fleets and draught do.
 static mw_status moored_launch(mw_ocean* o, const HullPlan& p, const HullCall& c) {
-    const int nchunks = hull_chunks(c);
     mw_status s = hull_water(o, p);
     if (s != MW_OK) return s;
-    if (!o->draught && p.m.period != 0.f && moored_one_launch(c.nverts, nchunks)) {
-        HIP_TRY(tiled_moored_step(dim3((unsigned)c.nbodies), bodies_step_lds(c.nverts, nchunks), MW_BODIES_LDS_MAX, o->stream, bodies_args(o, p, c),
-                                  static_cast<const float4*>(c.lines), c.K, static_cast<float*>(c.tension)));
-        return MW_OK;
-    }
+    if (!o->draught && p.m.period != 0.f && moored_one_launch(c.nverts, hull_chunks(c))) return hull_step_launch(o, p, c);
     MooredArgs a{};
     a.bodies = static_cast<float4*>(c.bodies);
     a.mass = static_cast<const float4*>(c.mass);
@@ -796,7 +814,7 @@ static mw_status fleet_launch(mw_ocean* o, const FleetPlan& p, const FleetCall& 
     if (a.m.period == 0.f) one = 0;
     a.t = fleet_group(p, c, one);
     if (a.t.total[MW_FLEET_BODIES] > 0)
-        HIP_TRY(tiled_fleet_step(dim3((unsigned)a.t.total[MW_FLEET_BODIES]), lds, MW_BODIES_LDS_MAX, o->stream, a));
+        HIP_TRY(tiled_fleet_step(dim3((unsigned)a.t.total[MW_FLEET_BODIES]), lds, MW_BODIES_LDS_MAX, o->stream, a, nullptr, 0, nullptr));
     a.t = fleet_group(p, c, ~one);
     if (a.t.total[MW_FLEET_BODIES] == 0) return MW_OK;
     const dim3 gi((unsigned)(((int64_t)a.t.total[MW_FLEET_BODIES] + 255) / 256));

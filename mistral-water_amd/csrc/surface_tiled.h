@@ -6,7 +6,8 @@
 // The tiled raycast (raycast_tiled.h, mw_ocean_raycast_tiled) has its kernels here for the same reason -- k_raycast_tiled and the SqTiled
 // instantiation of raycast.h's k_rc_build_leaves: sq_shift, sq_reduce and the column planes of its walk must round as the g++ build
 // rounds them (tests/raycast_tiled_shim.cpp).
-// The kernels after the vertex slab (k_hull_triangles, k_hull_reduce, k_bodies_integrate, k_moored_integrate, k_rigged_integrate) do not read the mesh (hull_forces.h), so their
+// The kernels after the vertex slab (k_hull_triangles, k_hull_reduce, k_bodies_integrate, k_moored_integrate, k_rigged_integrate) do not read the mesh
+// (hull_forces.h), so their
 // instantiations here are the library's strict build of them: strict_hull_rows and strict_bodies_integrate serve a periodic handle and,
 // on either handle, draught (hull_draught.h), whose own vertex kernel stands in water_column.hip.
 //
@@ -30,19 +31,17 @@ MW_INTERNAL hipError_t tiled_hull_vertices(dim3 grid, hipStream_t s, const HullA
 // grids (the rows into a.out), and k_bodies_integrate
 MW_INTERNAL hipError_t strict_hull_rows(dim3 triangles, dim3 reduce, hipStream_t s, const HullArgs& a);
 MW_INTERNAL hipError_t strict_bodies_integrate(dim3 grid, hipStream_t s, const BodiesArgs& a);
-// k_bodies_step with `lds` bytes of dynamic LDS, at most lds_max (set as the kernel's attribute once per device)
-MW_INTERNAL hipError_t tiled_bodies_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const BodiesArgs& a);
-// the fleet kernels (fleet.h): k_fleet_vertices, k_fleet_triangles, k_fleet_reduce on their three grids; k_fleet_integrate; k_fleet_step
-// with `lds` bytes of dynamic LDS, as tiled_bodies_step
+// the fleet kernels (fleet.h): k_fleet_vertices, k_fleet_triangles, k_fleet_reduce on their three grids; k_fleet_integrate
 MW_INTERNAL hipError_t tiled_fleet_forces(dim3 vertices, dim3 triangles, dim3 reduce, hipStream_t s, const FleetArgs& a);
 MW_INTERNAL hipError_t tiled_fleet_integrate(dim3 grid, hipStream_t s, const FleetArgs& a);
-MW_INTERNAL hipError_t tiled_fleet_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const FleetArgs& a);
-// moorings (moorings.h): k_moored_integrate, which reads no mesh and serves every handle, and k_moored_step on the tiling with `lds`
-// bytes of dynamic LDS, as tiled_bodies_step
+// k_fleet_step, the one one-launch kernel of this translation unit (step fleet, and on a one-hull table step bodies and step moored;
+// k_bodies_step is instantiated for SqMesh alone, in mistral_water.hip): `lds` bytes of dynamic LDS, at most lds_max (set as the
+// kernel's attribute once per device); lines [total_bodies][K][3] and tension, K == 0: no lines
+MW_INTERNAL hipError_t tiled_fleet_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const FleetArgs& a, const float4* lines, int K,
+                                        float* tension);
+// the per-substep line integrators, which read no mesh and serve every handle, after the rows of the substep: k_moored_integrate
+// (moorings.h) and k_rigged_integrate (rigging.h)
 MW_INTERNAL hipError_t strict_moored_integrate(dim3 grid, hipStream_t s, const MooredArgs& a);
-MW_INTERNAL hipError_t tiled_moored_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const BodiesArgs& a, const float4* lines, int K,
-                                         float* tension);
-// rigged fleets (rigging.h): k_rigged_integrate, which reads no mesh and serves every handle, after the fleet's rows of the substep
 MW_INTERNAL hipError_t strict_rigged_integrate(dim3 grid, hipStream_t s, const RigArgs& a);
 // k_rc_build_leaves<SqTiled>: the leaf boxes of one tile and the levels above them up to D - 4 (k_rc_build_top, launched by the caller, does the
 // rest); k_raycast_tiled: one lane per ray.  m.period is the tiling's P.

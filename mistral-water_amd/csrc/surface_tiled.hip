@@ -7,7 +7,7 @@
 #include "mw_math.h"
 #pragma clang fp contract(off)
 #define MW_RC_NO_KERNELS  // k_raycast and k_rc_build_top are mistral_water.hip's
-#define MW_MOORING_KERNELS  // k_moored_integrate, k_moored_step and k_rigged_integrate stand here alone
+#define MW_STRICT_LINE_KERNELS  // k_moored_integrate and k_rigged_integrate stand here alone
 #include "surface_tiled.h"
 #include "raycast_tiled.h"
 
@@ -43,14 +43,6 @@ hipError_t strict_bodies_integrate(dim3 grid, hipStream_t s, const BodiesArgs& a
     return hipGetLastError();
 }
 
-hipError_t tiled_bodies_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const BodiesArgs& a) {
-    static AttrOnce attr;
-    const hipError_t e = attr.set(reinterpret_cast<const void*>(k_bodies_step<SqTiled>), lds_max);
-    if (e != hipSuccess) return e;
-    k_bodies_step<<<grid, dim3(MW_HULL_CHUNK), lds, s>>>(bodies_args_tiled(a));
-    return hipGetLastError();
-}
-
 hipError_t tiled_fleet_forces(dim3 vertices, dim3 triangles, dim3 reduce, hipStream_t s, const FleetArgs& a) {
     const FleetArgsT<SqTiled> t = fleet_args_tiled(a);
     k_fleet_vertices<<<vertices, dim3(256), 0, s>>>(t);
@@ -65,25 +57,17 @@ hipError_t tiled_fleet_integrate(dim3 grid, hipStream_t s, const FleetArgs& a) {
     return hipGetLastError();
 }
 
-hipError_t tiled_fleet_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const FleetArgs& a) {
+hipError_t tiled_fleet_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const FleetArgs& a, const float4* lines, int K,
+                            float* tension) {
     static AttrOnce attr;
     const hipError_t e = attr.set(reinterpret_cast<const void*>(k_fleet_step<SqTiled>), lds_max);
     if (e != hipSuccess) return e;
-    k_fleet_step<<<grid, dim3(MW_HULL_CHUNK), lds, s>>>(fleet_args_tiled(a));
+    k_fleet_step<<<grid, dim3(MW_HULL_CHUNK), lds, s>>>(fleet_args_tiled(a), lines, tension, K);
     return hipGetLastError();
 }
 
 hipError_t strict_moored_integrate(dim3 grid, hipStream_t s, const MooredArgs& a) {
     k_moored_integrate<<<grid, dim3(256), 0, s>>>(a);
-    return hipGetLastError();
-}
-
-hipError_t tiled_moored_step(dim3 grid, size_t lds, int lds_max, hipStream_t s, const BodiesArgs& a, const float4* lines, int K,
-                             float* tension) {
-    static AttrOnce attr;
-    const hipError_t e = attr.set(reinterpret_cast<const void*>(k_moored_step<SqTiled>), lds_max);
-    if (e != hipSuccess) return e;
-    k_moored_step<<<grid, dim3(MW_HULL_CHUNK), lds, s>>>(MooredStepArgsT<SqTiled>{bodies_args_tiled(a), lines, tension, K});
     return hipGetLastError();
 }
 

@@ -42,7 +42,7 @@ extern "C" void ms_body_integrate(float* bodies, const float* rows, const float*
     for (int b = 0; b < n; b++) ok[b] = body_integrate(bodies + 16 * b, rows + 8 * b, mass + 8 * b, g, h) ? 1 : 0;
 }
 
-// the LDS k_moored_step takes beside k_bodies_step's slab and partials: the launch rule of moored_one_launch (surface_services.inc)
+// the LDS k_fleet_step holds for a call's lines beside the slab and partials: the plan rule of moored_one_launch (surface_services.inc)
 extern "C" int64_t ms_moored_lds_static() { return (int64_t)MW_MOORED_LDS_STATIC; }
 
 // mooring_slot_valid of n slots [n][12] -> ok[n]

@@ -1,5 +1,5 @@
-"""CPU tier of the moorings at the hull chunk and LDS edges (csrc/moorings.h: k_moored_step's copy of k_bodies_step's loop, the launch
-rule of moored_one_launch).  The GPU tier (tests/test_mooring_sizes_gpu.py) compares the device bit for bit with a chain that holds no
+"""CPU tier of the moorings at the hull chunk and LDS edges (csrc/fleet.h: k_fleet_step, the strict one-launch loop a moored call runs with its lines; the
+plan rule of moored_one_launch).  The GPU tier (tests/test_mooring_sizes_gpu.py) compares the device bit for bit with a chain that holds no
 device value -- mooring_ref.chain: per substep the rows of an ordered g++ shim (tests/periodic_shim.cpp, tests/draught_shim.cpp), then
 one substep of tests/moorings_shim.cpp.  Here that chain is itself checked, over the synthetic periodic mesh periodic_synth(64, 1.0, 0.5)
 with the edge hulls t257 (2 chunks) and t40_v600 (3 chunks, two of them without a triangle), 4 substeps of h = 0.05, drag on:

@@ -8,8 +8,8 @@ holds it to float64 and shows that a lost sentinel or slot moves it by a hundred
 
 1. a periodic handle, the edge hulls of tests/test_hull_sizes_gpu.py (255 / 256 / 257 triangles, 40 triangles on 600 vertices, 16 385
    triangles: 1, 1, 2, 3 and 65 chunks), the plans MW_BODIES_PLAN = 1, 0 and -1, host and device forms, drag off and on;
-2. the moored one-launch plan's LDS edge: v5055 (bodies_step_lds + 416 B = MW_BODIES_LDS_MAX, the largest slab k_moored_step is
-   launched with), v5056 (32 B above: a forced plan 1 steps per substep) and v5068 (step bodies' own edge);
+2. the moored one-launch plan's LDS edge: v5055 (bodies_step_lds + 416 B = MW_BODIES_LDS_MAX, the largest slab k_fleet_step is
+   launched with for a moored call), v5056 (32 B above: a forced plan 1 steps per substep) and v5068 (step bodies' own edge);
 3. K = 1 .. 8: which lanes stage the slots and store the tensions, with a canary behind [nbodies][K];
 4. substeps = 1 and 64;
 5. taut lines under draught: periodic and non-periodic handle, 2 and 5 layers, the spar, the icosphere and t257, with the NaN pose, the
@@ -107,7 +107,7 @@ def test_periodic_edge_hulls_equal_the_chain_in_every_plan(mw, shim, ms, name, n
 # ---- 2. the moored LDS edge ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["v5055", "v5056", "v5068"])
 def test_the_moored_lds_edge(mw, shim, ms, name):  # noqa: F811
-    """v5055: 162 400 B of dynamic LDS beside k_moored_step's static arrays, the documented limit -- a refused launch would be an error
+    """v5055: 162 400 B of dynamic LDS beside k_fleet_step's static arrays, the documented limit -- a refused launch would be an error
     status, which the wrappers raise.  v5056 and v5068 (where step bodies still takes one launch) must step per substep under a forced
     plan 1.  Which plan ran is not visible through the ABI: the bits and the statuses are what is asserted."""
     s = Sea(mw, name, 2, 8, seed=len(name) + 60)
@@ -245,7 +245,7 @@ def test_footprint_equals_the_shims_step_on_the_devices_rows(mw, ms, name, n):  
 
 # ---- 7. failures stay local on a multi-chunk hull --------------------------------------------------------------------------------
 def test_a_nan_vertex_freezes_every_body_in_both_plans(mw, shim, ms):  # noqa: F811
-    """t40_v600 with its last vertex, which no triangle references, NaN: hull_row's rule makes every row NaN, so k_moored_step stops
+    """t40_v600 with its last vertex, which no triangle references, NaN: hull_row's rule makes every row NaN, so k_fleet_step stops
     after its first pass over the three chunks.  Rows and tensions are NaN and no state moves."""
     s = Sea(mw, "t40_v600", 4, 8, seed=100)
     bad = s.hull.copy()

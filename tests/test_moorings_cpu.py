@@ -394,15 +394,30 @@ def test_step_moored_bad_arguments_are_statuses(mw):
 
 def test_kernels_use_the_hd_functions():
     """both plans compute the wrench with mooring_add / mooring_wrench and integrate through fleet_integrate; the one-launch kernel is
-    k_bodies_step's loop (the shared ordered sums), a kernel of its own; nothing between workgroups"""
+    the strict k_fleet_step (k_bodies_step's loop, the shared ordered sums); the rigged fleets' own-slot branch is mooring_add; nothing
+    between workgroups"""
     csrc = os.path.join(REPO, "mistral-water_amd", "csrc")
     src = open(os.path.join(csrc, "moorings.h")).read()
-    integ = src[src.index("void k_moored_integrate"):src.index("struct MooredStepArgsT")]
+    integ = src[src.index("void k_moored_integrate"):]
     assert "mooring_add(&m, body, R, slot)" in integ and "fleet_integrate(body, row, mass, m.any ? m.M : nullptr, a.g, a.dt)" in integ
-    stepk = src[src.index("void k_moored_step"):]
-    assert "moored_integrate(body, row, mass, slots, K, a.g, a.dt, tens)" in stepk
-    assert "hull_vertex(ha.m, ha.vel, ha.vscale, ha.iters, body, h, sl)" in stepk and "hull_row(acc, res, row)" in stepk
+    fleet = open(os.path.join(csrc, "fleet.h")).read()
+    stepk = fleet[fleet.index("void k_fleet_step"):]
+    assert "moored_integrate(body, pushed, mass, slots, K, it.row.g, a.dt, tens)" in stepk
+    assert "fleet_pushed_row(row, a.wrench ? wr : nullptr, pushed)" in stepk
+    moored = src[src.index("MW_HD bool moored_integrate("):src.index("#define MW_MOORED_LDS_STATIC")]
+    assert "mooring_wrench(body, lines, K, M, tension)" in moored
+    assert "fleet_integrate(body, row, mass, taut > 0 ? M : nullptr, g, h)" in moored
+    assert "hull_vertex(a.m, vel, it.row.vscale, a.iters, body, h, sl)" in stepk and "hull_row(acc, res, row)" in stepk
+    assert "hull_triangle(idx, nverts, vs, body, it.row.cf, acc)" in stepk
     assert "hull_chunk_partial(acc, res, part + 2 * c)" in stepk and "hull_body_sum(part, 0, " in stepk
+    services = open(os.path.join(csrc, "surface_services.inc")).read()
+    launch = services[services.index("static mw_status moored_launch("):services.index("// ---- the hull family's entry points")]
+    assert "strict_moored_integrate(gi, o->stream, a)" in launch and "hull_step_launch(o, p, c)" in launch
+    rig = open(os.path.join(csrc, "rigging.h")).read()
+    add = rig[rig.index("MW_HD float rig_add("):rig.index("// what rig_wrench and rigged_integrate report")]
+    assert "if (kind != MW_RIG_SLOT_TOW) {" in add and "return mooring_add(&r->m, body, R, s);" in add
+    rigk = rig[rig.index("void k_rigged_integrate"):]
+    assert "rig_add(&r, body, R, slot, kind, other)" in rigk and "rig_push(body, row, mass" in rigk
     bodies = open(os.path.join(csrc, "rigid_bodies.h")).read()
     assert "moor" not in bodies  # k_bodies_step took no parameter for this
     code = re.sub(r"//[^\n]*", "", src)

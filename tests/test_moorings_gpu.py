@@ -6,7 +6,8 @@ OceanRenderer resolution 8; the hulls are hull_ref.box (12 triangles) and icosph
   1, 255, 256 and 257 bodies (the last lane of k_moored_integrate's first workgroup and the first of its second), K = 1 and 8;
 * the two plans give the same bits; every line slack or empty gives mw_ocean_step_bodies' bits (periodic, and non-periodic with
   draught); one substep equals mw_ocean_step_fleet_device given the shim's wrench; the first substep's out is
-  mw_ocean_hull_forces_device's;
+  mw_ocean_hull_forces_device's; 257 bodies, slack, taut and one invalid, through both plans, the one-launch plan being the
+  fleets' k_fleet_step on a one-hull table;
 * a moored box on flat water surges with the period of its lines; invalid slots and NaN rows stay local; the argument, frame and state
   rules; the handle's state is untouched;
 * the one footprint without draught, whose rows come from kernels built with contraction, against the float64 composition.
@@ -233,6 +234,44 @@ def test_all_slack_equals_step_bodies(mw):
                 change = np.linalg.norm(free[:, sl].astype(np.float64) - start[:, sl], axis=1)
                 err = np.abs(got[:, sl].astype(np.float64) - free[:, sl]).max(1)
                 assert (err <= FOOT[key] * change).all(), (name, key, (err / change).max())
+
+
+def test_moored_calls_ride_the_fleet_table(mw):
+    """The one-launch plan of a moored call is the fleets' strict k_fleet_step on a one-hull table, with the lines; the per-substep plan
+    is k_moored_integrate.  257 boxes, K = 8, 3 substeps: the last body sits in the second 256-lane workgroup of the per-substep kernel.
+    Every third body's lines are all slack or empty, body 130 has an invalid slot, the rest are taut.  The two plans give equal states,
+    out and tension to the bit, the NaN pattern included, and the slack bodies are mw_ocean_step_bodies_device's to the bit."""
+    import torch
+    n, K, bad = 257, 8, 130
+    with _ocean(mw, periodic=True) as o:
+        # the same draws twice: the two scenes differ in the rest lengths alone
+        hull, tris, bodies, mass, taut = _scene(mw, o, np.random.default_rng(24), n, K, 96.0)
+        slack = _scene(mw, o, np.random.default_rng(24), n, K, 96.0, slack=True)
+        assert _same(bodies, slack[2])
+        loose = np.arange(n) % 3 == 0
+        lines = np.where(loose[:, None, None], slack[4], taut).astype(np.float32)
+        assert not loose[bad] and not loose[n - 1]
+        lines[bad, 3, 7] = -1.0  # a negative stiffness
+        hauled = ~loose & (np.arange(n) != bad)
+        got = {}
+        for plan in (1, 0):
+            got[plan] = _run_plan(mw, plan, lambda: _moored_device(o, hull, tris, bodies, mass, lines, 0.06, 3))
+            d_h, d_t, d_b, d_m = _up(hull, tris, bodies.copy(), mass)
+            d_o = torch.full((n, 8), 7.0, dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()
+            _run_plan(mw, plan, lambda: o.step_bodies_device(d_h.data_ptr(), len(hull), d_t.data_ptr(), len(tris), d_b.data_ptr(), d_m.data_ptr(), n,
+                                                             0.06, 3, d_o.data_ptr()))
+            o.synchronize()
+            state, out, tens = got[plan]
+            free, frows = d_b.cpu().numpy(), d_o.cpu().numpy()
+            assert _same(state[loose], free[loose]) and _same(out[loose], frows[loose]) and (tens[loose] == 0).all(), plan
+            assert not _same(free[loose], bodies[loose])
+            assert _same(state[bad], bodies[bad]) and np.isnan(out[bad]).all() and np.isnan(tens[bad]).all(), plan
+            assert np.isfinite(state[hauled]).all() and np.isfinite(out[hauled]).all() and (tens[hauled] >= 0).all(), plan
+            # the lines pull: slot 0 is taut by its length, and only a fast approach can clamp its tension to 0
+            assert (tens[hauled, 0] > 0).mean() > 0.9 and ((_bits(state[hauled]) != _bits(free[hauled])).any(1)).mean() > 0.9, plan
+        for a, b, what in zip(got[1], got[0], ("state", "out", "tension")):
+            assert _same(a, b), what  # equal bits: a NaN in one plan is the same NaN in the other
 
 
 @pytest.mark.parametrize("plan", [0, 1], ids=["per_substep", "one_launch"])
